@@ -7,7 +7,9 @@ One *timestep* of the metric = one INSTANCE (all 8 agents) advanced by DT = 0.2 
 
 The workload is ONE batch of `--batch` (4096) instances whatever --gpus is: rank r owns instances
 shard_instances(4096, r, N) -- strong scaling, no data-path collective (all agents of an instance are rank-local).
-value = 4096 * steps / max-over-ranks time.  Extra keys of the same JSON line (each measured after the headline region):
+value = 4096 * steps / max-over-ranks time.  A plain run sets up, warms up, times the steps, writes the outputs of the last timed step
+(--dump-outputs DIR) and prints the line.  With --full the same JSON line also carries these extra keys (each measured after the headline
+region; --no-extras / --no-cpu leave out the GPU extras / the CPU baseline):
   steady_state   the same measurement after >= 100 closed-loop steps (traffic has built up; different iteration mix)
   expand         motion-primitive expansion of a 2^20-node Prius frontier, HIP-event timed
   agent_sharded  (N > 1) the layout with a real exchange step: agents sharded over ranks, one RCCL all-gather per step
@@ -17,7 +19,7 @@ value = 4096 * steps / max-over-ranks time.  Extra keys of the same JSON line (e
   shard_proxy    (N = 1) the per-rank shares of the headline batch at N = 2 / 4 / 8 (2048 / 1024 / 512 instances) timed on this GPU
   cpu_baseline   the oracle on this host: one thread, and all cores (threads over agents in C)
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -160,6 +162,35 @@ def cpu_baseline(sim, snap, n_agents: int):
                 sample_1thread='%d agent-steps on one thread, %.1f s' % (n1, t1))
 
 
+DUMP_BYTES = 63 << 20          # --dump-outputs: 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(sim, out_dir, world, rank):
+    """--dump-outputs: what the last timed step handed its caller, per agent (plant state and applied input, path indices and conflict
+    search results, QP solution and statistics), one float64 DIR/<name>.npy per array, rows in (instance, agent) order of the WHOLE batch
+    (the ranks' instance slices are gathered on rank 0), so the files do not depend on --gpus.  Beyond DUMP_BYTES the rows are a seeded
+    sample whose indices go to DIR/agent_index.npy."""
+    import torch.distributed as dist
+    bufs = dict(state=sim.state, applied=sim.applied, traj_idx=sim.traj_idx, target_ind=sim.target_ind,
+                hit_idx=sim.inter['hit_idx'], hit_xy=sim.inter['hit_xy'], cut_len=sim.inter['cut_len'], **sim.sol)
+    out = {k: v.cpu().numpy().astype(np.float64) for k, v in bufs.items()}
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, out)
+        out = {k: np.concatenate([p[k] for p in parts]) for k in out}
+    if rank != 0:
+        return
+    P = len(out['state'])
+    row_bytes = sum(v[0].nbytes for v in out.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if P * row_bytes > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(P, DUMP_BYTES // (row_bytes + 8), replace=False))
+        out = {k: v[keep] for k, v in out.items()}
+        out['agent_index'] = keep.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -168,13 +199,20 @@ def main():
     ap.add_argument('--batch', type=int, default=4096, help='scenario instances of the WHOLE job (sharded over the GPUs)')
     ap.add_argument('--agents', type=int, default=8)
     ap.add_argument('--horizon', type=int, default=20)
+    ap.add_argument('--full', action='store_true', help='also the extra keys (other configurations, sizes and controllers, expansion, '
+                                                        'device search, multi-rank layouts) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the per-agent outputs of the last timed step to DIR/<name>.npy (float64)')
     ap.add_argument('--cpu-agents', type=int, default=1 << 20, help='cap of the CPU baseline sample (it is sized for ~10 s per leg)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='headline measurement only')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: no CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: no GPU extras')
     ap.add_argument('--steady-steps', type=int, default=100, help='closed-loop steps before the steady-state measurement')
     ap.add_argument('--burn-in', type=int, default=3, help='closed-loop steps taken while the workload is built (SURVEY 8d config 2: "run 3 burn-in steps"), '
                                                             'so that every timed step starts from a previous solution whatever --warmup is')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    extras = args.full and not args.no_extras
+    cpu = args.full and not args.no_cpu
 
     import torch
     import torch.distributed as dist
@@ -272,7 +310,7 @@ def main():
         iters_sum += sim.sol['iters'].sum()
         fail_sum += (sim.sol['status'] != 0).sum()
     torch.cuda.synchronize()
-    snap = sim.snapshot() if (rank == 0 and not args.no_cpu) else None
+    snap = sim.snapshot() if (rank == 0 and cpu) else None
 
     elapsed, it_total, failures, qp_ms, qp_launches = timed(sim, args.steps)
     max_iters = timed.max_iterations
@@ -340,7 +378,10 @@ def main():
                                             'note': 'lane-flops the kernel executes (committed PMC passes: SQ_INSTS_VALU_FLOPS_FP64 x mean active lanes) / live kernel time; includes '
                                                     'recomputation, padded slots and masked work'}
 
-    if not args.no_extras:
+    if args.dump_outputs:                            # before the extras: the steady-state leg runs this batch on
+        dump_outputs(sim, args.dump_outputs, world, rank)
+
+    if extras:
         # -------------------------------------------------------------- steady state: the same batch after >= 100 closed-loop steps
         try:
             more = args.steady_steps - sim.steps_done
