@@ -261,6 +261,10 @@ int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const d
     if (hipEventRecord(ctx->ev_fork, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "mpc_prepare_batch: cannot fork the side stream");
     hipLaunchKernelGGL(mpcx::rollout_kernel, dim3((B + 63) / 64), dim3(64), 64 * (4 * (size_t)(ctx->mpc.T + 1) + 1) * sizeof(double), ctx->side, ro);
+    // a refused launch is the rollout's failure, not that of whichever call checks the error state next (the staging buffer is above
+    // 64 KB for T >= 31: gfx950 grants up to 160 KB of LDS per workgroup without hipFuncAttributeMaxDynamicSharedMemorySize)
+    const int32_t rc = mpcx_check_launch(ctx, "rollout_kernel");
+    if (rc != MPCX_OK) return rc;
     // the join event right behind the rollout: by the time the context's stream waits for it (in front of the solve) the marker has long
     // been processed -- recorded there, the wait paid for the side queue's marker AND its own barrier
     if (hipEventRecord(ctx->ev_join, ctx->side) != hipSuccess)

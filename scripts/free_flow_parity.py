@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from mpc_for_av_at_intersection_amd.batch import config2_batch
 from mpc_for_av_at_intersection_amd.runtime import Context
-from tests.test_gpu_fullsize import _replay_all_on_oracle
+from tests.helpers import replay_all_on_oracle as _replay_all_on_oracle
 ctx = Context(0)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
 sim = config2_batch(ctx, B=B, T=20, seed=0)

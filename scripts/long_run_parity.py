@@ -1,12 +1,12 @@
 """GPU box: the benchmark's closed loop (4096 instances x 8 agents, T = 20) for 200 steps, EVERY agent of every 10th step replayed on the
-oracle from the device state of the step before (tests/test_gpu_fullsize.py::_replay_all_on_oracle: path indices, cut lengths, conflict
+oracle from the device state of the step before (tests/helpers.py::replay_all_on_oracle: path indices, cut lengths, conflict
 indices, statuses identical for every agent; solutions within 2e-7).  Summary for profiles/."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from mpc_for_av_at_intersection_amd.batch import synthetic_batch
 from mpc_for_av_at_intersection_amd.runtime import Context
-from tests.test_gpu_fullsize import _replay_all_on_oracle
+from tests.helpers import replay_all_on_oracle as _replay_all_on_oracle
 ctx = Context(0)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 sim = synthetic_batch(ctx, B=B, A=8, T=20, seed=1000)

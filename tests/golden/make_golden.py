@@ -15,7 +15,7 @@ by KKT residuals, see DESIGN.md "parity").
 
 Only DATA is written (npz/json): no reference source, bytecode or pickle is copied.
 
-usage:  python tests/golden/make_golden.py [--stage numpy|closedloop|all]
+usage:  python tests/golden/make_golden.py [--stage numpy|closedloop|...|horizons|all]
 """
 import argparse
 import json
@@ -41,6 +41,24 @@ def _savez(name, **arrays):
     import numpy as np
     path = os.path.join(HERE, name)
     np.savez_compressed(path, **arrays)
+    print('wrote', path, '%.1f KiB' % (os.path.getsize(path) / 1024))
+
+
+def _savez_stable(name, **arrays):
+    """as _savez, but byte-reproducible: np.savez_compressed stamps every member with the wall-clock time, this writes a fixed
+    timestamp (np.load reads both alike)"""
+    import io
+    import zipfile
+    import numpy as np
+    path = os.path.join(HERE, name)
+    with zipfile.ZipFile(path, 'w', compression=zipfile.ZIP_DEFLATED) as z:
+        for key, val in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            info = zipfile.ZipInfo(key + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o600 << 16
+            z.writestr(info, buf.getvalue())
     print('wrote', path, '%.1f KiB' % (os.path.getsize(path) / 1024))
 
 
@@ -408,7 +426,7 @@ def stage_numpy():
     _savez('moving.npz', **mov)
 
 
-def stage_closedloop(max_iter=1, horizons=(10, 13, 20), name='closedloop.npz', max_steps=400):
+def stage_closedloop(max_iter=1, horizons=(10, 13, 20), name='closedloop.npz', max_steps=400, save=_savez):
     """G9: reference closed loop (mpc_intersection.py:95-159 sequence) with the oracle QP in place of ECOS.
     max_iter > 1 (closedloop_iter2.npz): the reference's successive linearisation, mpc.py:226-237 -- MAX_ITER passes per step, the
     reference window of every pass after the first spaced by the previous pass's speeds (`ov`), its rollout made with the previous
@@ -499,7 +517,88 @@ def stage_closedloop(max_iter=1, horizons=(10, 13, 20), name='closedloop.npz', m
         out['T%d/full' % T] = full  # yaw column already smoothed in place by MPC.__init__
         out['T%d/steps' % T] = np.array(i)
     rmpc.MAX_ITER = 1
-    _savez(name, **out)
+    save(name, **out)
+
+
+HORIZONS = (1, 2, 9, 11, 14, 16, 17, 21, 24, 25, 30, 31, 32)
+
+
+def stage_horizons():
+    """mpc_pre_horizons.npz: the T%d/* window / rollout cases of mpc_pre.npz (same recipe and case mix: cut paths, starts near the
+    end, v = 0, zero-steer warm starts) at the horizons the stock configuration does not use, 1 .. MPCX_T_MAX, plus the speed-reference
+    window at T = 24 / 32; closedloop_horizons.npz: the stock closed loop of stage_closedloop at T = 16 / 24 / 32.  Own RNG seed; the
+    A* paths are those recorded in mpc_pre.npz (path_%d_%d), so no search is rerun."""
+    import numpy as np
+    from lib.car_dimensions import BicycleModelDimensions
+    from lib.simulation import State
+    import lib.mpc as rmpc
+    import lib.mpc_with_speed as rmpcs
+
+    rng = np.random.default_rng(20261016)
+    bic = BicycleModelDimensions()
+    g = np.load(os.path.join(HERE, 'mpc_pre.npz'))
+    paths = {(int(k.split('_')[1]), int(k.split('_')[2])): g[k] for k in g.files if k.startswith('path_')}
+    pre = {}
+    keys = sorted(paths.keys())
+    for T in HORIZONS:
+        rmpc.T = T
+        rmpc.Qf = np.diag([1.0, 1.0, 0.0, 0.5]) * T
+        c_state, c_path, c_start, c_xref, c_tind, c_re, c_oa, c_od, c_xbar = [], [], [], [], [], [], [], [], []
+        for case in range(48):
+            sp, ti = keys[case % len(keys)]
+            full = paths[(sp, ti)].copy()
+            rmpc.smooth_yaw(full[:, 2])
+            n = len(full)
+            cut = n if case % 3 else int(rng.integers(40, n))
+            path = full[:cut]
+            i0 = int(rng.integers(0, max(1, cut - 3)))
+            if case % 7 == 0:
+                i0 = max(0, cut - int(rng.integers(1, 30)))  # near the end: reaches_end rows
+            lat = rng.normal(0, 0.3)
+            yaw = path[i0, 2]
+            st = State(x=path[i0, 0] - lat * np.sin(yaw), y=path[i0, 1] + lat * np.cos(yaw),
+                       yaw=yaw + rng.normal(0, 0.05), v=float(rng.uniform(0, 30 / 3.6)) if case % 5 else 0.0)
+            start = max(0, i0 - int(rng.integers(0, 4)))
+            dl = float(np.linalg.norm(full[0, :2] - full[1, :2]))
+            xref, tind, dref, re = rmpc._calc_ref_trajectory(st, path[:, 0], path[:, 1], path[:, 2], dl, 0.2, start, None)
+            oa = rng.uniform(-3, 2, T); od = rng.uniform(-0.9, 0.9, T) * (rng.random() < 0.8)
+            xbar = rmpc._predict_motion([st.x, st.y, st.v, st.yaw], oa, od, xref, bic, 0.2)
+            c_state.append([st.x, st.y, st.v, st.yaw]); c_path.append((sp, ti, cut)); c_start.append(start)
+            c_xref.append(xref); c_tind.append(tind); c_re.append(re); c_oa.append(oa); c_od.append(od); c_xbar.append(xbar)
+        pre['T%d/state' % T] = np.array(c_state); pre['T%d/path' % T] = np.array(c_path, dtype=np.int32)
+        pre['T%d/start' % T] = np.array(c_start, dtype=np.int32); pre['T%d/xref' % T] = np.array(c_xref)
+        pre['T%d/target_ind' % T] = np.array(c_tind, dtype=np.int32)
+        pre['T%d/reaches_end' % T] = np.array(c_re, dtype=np.uint8)
+        pre['T%d/oa' % T] = np.array(c_oa); pre['T%d/od' % T] = np.array(c_od); pre['T%d/xbar' % T] = np.array(c_xbar)
+    rmpc.T = 13
+    rmpc.Qf = np.diag([1.0, 1.0, 0.0, 0.5]) * 13
+    for T in (24, 32):
+        rmpcs.T = T
+        ws_state, ws_cut, ws_start, ws_xref, ws_tind, ws_re, ws_cutoff = [], [], [], [], [], [], []
+        full = paths[(4, 1)].copy()
+        rmpc.smooth_yaw(full[:, 2])
+        for case in range(24):
+            cut = len(full) if case % 2 else int(rng.integers(100, len(full)))
+            path = full[:cut]
+            i0 = int(rng.integers(0, cut - 3))
+            cutoff = 999 if case % 3 else int(rng.integers(i0, cut))
+            cv = np.full(cut, rmpcs.MAX_SPEED)
+            if cutoff != 999:
+                cv[cutoff:] = 0
+            st = State(x=path[i0, 0] + rng.normal(0, 0.2), y=path[i0, 1] + rng.normal(0, 0.2), yaw=path[i0, 2], v=float(rng.uniform(0, 8)))
+            start = max(0, i0 - 2)
+            dl = float(np.linalg.norm(full[0, :2] - full[1, :2]))
+            xref, tind, dref, re = rmpcs._calc_ref_trajectory(st, path[:, 0], path[:, 1], cv, path[:, 2], dl, 0.2, start, None)
+            ws_state.append([st.x, st.y, st.v, st.yaw]); ws_cut.append(cut); ws_start.append(start); ws_xref.append(xref)
+            ws_tind.append(tind); ws_re.append(re); ws_cutoff.append(cutoff)
+        pre['ws%d/state' % T] = np.array(ws_state); pre['ws%d/cut' % T] = np.array(ws_cut, dtype=np.int32)
+        pre['ws%d/start' % T] = np.array(ws_start, dtype=np.int32); pre['ws%d/xref' % T] = np.array(ws_xref)
+        pre['ws%d/target_ind' % T] = np.array(ws_tind, dtype=np.int32); pre['ws%d/reaches_end' % T] = np.array(ws_re, dtype=np.uint8)
+        pre['ws%d/cutoff' % T] = np.array(ws_cutoff, dtype=np.int32)
+    pre['ws/MAX_SPEED'] = np.array(rmpcs.MAX_SPEED)
+    rmpcs.T = 13
+    _savez_stable('mpc_pre_horizons.npz', **pre)
+    stage_closedloop(horizons=(16, 24, 32), name='closedloop_horizons.npz', save=_savez_stable)
 
 
 def stage_onedisc():
@@ -695,7 +794,7 @@ def stage_worlds():
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
-    ap.add_argument('--stage', default='numpy', choices=['numpy', 'closedloop', 'closedloop_iter2', 'onedisc', 'traffic', 'worlds', 'all'])
+    ap.add_argument('--stage', default='numpy', choices=['numpy', 'closedloop', 'closedloop_iter2', 'onedisc', 'traffic', 'worlds', 'horizons', 'all'])
     a = ap.parse_args()
     _enter_reference()
     if a.stage in ('numpy', 'all'):
@@ -710,3 +809,5 @@ if __name__ == '__main__':
         stage_traffic()
     if a.stage in ('worlds', 'all'):
         stage_worlds()
+    if a.stage in ('horizons', 'all'):          # reads the paths of mpc_pre.npz: after stage_numpy
+        stage_horizons()

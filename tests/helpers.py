@@ -88,3 +88,90 @@ def harvest_closed_loop_qps(ctx, B=4096, A=8, T=20, seed=1000, windows=((3, 6), 
     r = {k: cat(rest, k) for k in rest[0]}
     keep = rng.choice(len(r['iters']), min(n_rest, len(r['iters'])), replace=False)
     return {k: np.concatenate([out[k], r[k][keep]]) for k in out}
+
+
+HORIZON_FIXTURE_TS = (1, 2, 9, 11, 14, 16, 17, 21, 24, 25, 30, 31, 32)     # mpc_pre_horizons.npz (make_golden.py --stage horizons)
+
+
+def pre_gold(T):
+    """the T%d/* window / rollout block for horizon T: mpc_pre.npz holds T = 10 / 13 / 20, mpc_pre_horizons.npz the others"""
+    return gold('mpc_pre.npz') if T in (10, 13, 20) else gold('mpc_pre_horizons.npz')
+
+
+def _fit(a, T):
+    """a control sequence cut or extended (last value held) to T entries"""
+    return a[:T] if len(a) >= T else np.concatenate([a, np.full(T - len(a), a[-1])])
+
+
+def horizon_problems(T, n=12, every=1):
+    """QP inputs at horizon T built by the oracle from golden cases (those of T itself where a fixture has them, else those of the
+    nearest fixture horizon): states, cut paths and starts of the fixture, reference window and rollout made at T.  Each case gives two
+    problems, as two steps of a closed loop: (1) the rollout of the fixture's random controls, those controls as warm start; (2) the state
+    the plant reaches under (1)'s solution, its window from (1)'s target index, its rollout made with (1)'s solution and that solution as
+    warm start.  Returns a list of (x0, xref, xbar, re, u_warm)."""
+    from oracle import oracle_py as orc
+    have = (10, 13, 20) + HORIZON_FIXTURE_TS
+    src = min(have, key=lambda t: (abs(t - T), t))
+    g = pre_gold(src)
+    p = orc.MpcParams(T=T)
+    out = []
+    for k in range(0, min(n * every, len(g['T%d/state' % src])), every):
+        sp, ti, cut = g['T%d/path' % src][k]
+        full = smoothed_path(sp, ti)
+        path = full[:cut]
+        dl = float(np.linalg.norm(full[0, :2] - full[1, :2]))
+        st = g['T%d/state' % src][k]
+        xref, s, re = orc.calc_ref_trajectory(p, st, path[:, 0], path[:, 1], path[:, 2], dl, int(g['T%d/start' % src][k]))
+        if s < 0:
+            continue
+        uw = np.stack([_fit(g['T%d/oa' % src][k], T), _fit(g['T%d/od' % src][k], T)])
+        xbar = orc.predict_motion(p, st, uw[0], uw[1])
+        out.append((st, xref, xbar, re, uw))
+        sol = orc.qp_solve(p, st, xref, xbar, re, uw)
+        if sol.status != 0:
+            continue
+        st2 = orc.plant_step(p, st, sol.u[0, 0], sol.u[1, 0])
+        xref2, s2, re2 = orc.calc_ref_trajectory(p, st2, path[:, 0], path[:, 1], path[:, 2], dl, s)
+        if s2 < 0:
+            continue
+        out.append((st2, xref2, orc.predict_motion(p, st2, sol.u[0], sol.u[1]), re2, sol.u.copy()))
+    return out
+
+
+def stack_problems(probs):
+    """list of (x0, xref, xbar, re, u_warm) -> five stacked arrays (re as uint8)"""
+    return [np.stack([q[i] for q in probs]).astype(np.uint8 if i == 3 else np.float64) for i in range(5)]
+
+
+def replay_all_on_oracle(sim, before, after, threads=16, tol=2e-7, dead=None):
+    """EVERY agent of the step before -> after replayed on the oracle (orc_agent_steps_mt: the whole per-agent step in C, pthreads
+    over agents) from the device state `before`: integer decisions and solver status must be identical for every agent, solutions
+    within tol -- ONE tolerance for every agent, whatever its iteration count: since the active-set polish of round 3 both sides end
+    on the same KKT point even where an exit test on the edge of its tolerance sends them there by different routes.  Returns (worst
+    |solution difference|, agents whose iteration count differs, failed solves)."""
+    from oracle import oracle_py as orc
+    import dataclasses
+    po = orc.MpcParams(**{f.name: getattr(sim.params, f.name) for f in dataclasses.fields(orc.MpcParams)})
+    tab = sim.path.cpu().numpy(); off = sim.path_off.cpu().numpy(); ln = sim.path_len.cpu().numpy()
+    r = orc.agent_steps_batch(po, threads, sim.A, tab, off, ln, sim.dl, before['state'], before['applied'], before['u'],
+                              before['traj_idx'], before['prev_cut'], before['target_ind'],
+                              np.asarray(sim.ip.circle_centers).reshape(2, 2), sim.ip.radius, sim.ip.cutoff_margin,
+                              pred_steps=sim.ip.pred_steps, frame_window=sim.ip.frame_window, max_accel=sim.ip.max_accel)
+    o = r['out6']
+    # where the reference raises Exception('something wrong') (trajectories.py:120: the three nearest path points are not
+    # contiguous) the oracle stops (index -1) and the kernels flag the agent: hit_idx -3 (conflict search) / target_ind -1
+    # (agents in `dead` raised on an earlier step: the reference's run ended there, they are not followed any further)
+    dead = np.zeros(len(o), bool) if dead is None else dead
+    raised_a, raised_b = (o[:, 0] < 0) & ~dead, (o[:, 0] >= 0) & (o[:, 2] < 0) & ~dead
+    assert np.array_equal((after['hit_idx'] == -3) & ~dead, raised_a) and np.array_equal((after['target_ind'] < 0) & ~raised_a & ~dead, raised_b)
+    live = ~(raised_a | raised_b | dead)
+    sim.raised = raised_a | raised_b
+    for col, name in ((0, 'traj_idx'), (1, 'cut_len'), (2, 'target_ind'), (3, 'hit_idx'), (4, 'status')):
+        bad = np.nonzero((o[:, col] != after[name]) & live)[0]
+        assert len(bad) == 0, '%s differs from the oracle for %d agents, first %s: %s vs %s' % (name, len(bad), bad[:5], after[name][bad[:5]], o[bad[:5], col])
+    ok = (after['status'] == 0) & live
+    diff = np.maximum(np.abs(r['u'] - after['u']).max((1, 2)), np.abs(r['x'] - after['x']).max((1, 2)))
+    same_count = o[:, 5] == after['iters']
+    worst = float(diff[ok].max()) if ok.any() else 0.0
+    assert worst < tol, (worst, int(diff[ok].argmax()))
+    return worst, int((~same_count).sum()), int((~ok).sum())

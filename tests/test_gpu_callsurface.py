@@ -128,19 +128,20 @@ def test_check_collision_and_linalg_functions():
         check_collision(hp[:4, :2], pts[:, :2].T)                                    # shape assertions of obstacles.py:166-170
 
 
-@pytest.mark.parametrize('T,max_iter', [(10, 1), (13, 1), (20, 1), (13, 2)])
+@pytest.mark.parametrize('T,max_iter', [(10, 1), (13, 1), (20, 1), (13, 2), (16, 1), (24, 1), (32, 1)])
 def test_stock_closed_loop_matches_reference_run(T, max_iter):
     """main/scenarios/mpc_intersection.py:95-159 driven with the product classes; golden = the reference's own loop with
     the oracle QP substituted for ECOS (tests/golden/make_golden.py --stage closedloop).
     max_iter = 2 (closedloop_iter2.npz, 60 steps): the reference's successive linearisation (lib/mpc.py:226-237, MAX_ITER passes per
-    step, the second one's reference window spaced by the first one's speeds) -- the stock mpc_config.json has MAX_ITER = 1."""
+    step, the second one's reference window spaced by the first one's speeds) -- the stock mpc_config.json has MAX_ITER = 1.
+    T = 16 / 24 / 32 (closedloop_horizons.npz): the same loop at horizons of both long-horizon stage-solver widths and the largest."""
     import mpc_for_av_at_intersection_amd.lib.mpc as pmpc
     from mpc_for_av_at_intersection_amd.lib.car_dimensions import BicycleModelDimensions
     from mpc_for_av_at_intersection_amd.lib.collision_avoidance import check_collision_moving_cars, get_cutoff_curve_by_position_idx
     from mpc_for_av_at_intersection_amd.lib.moving_obstacles_prediction import MovingObstaclesPrediction
     from mpc_for_av_at_intersection_amd.lib.simulation import HistorySimulation, Simulation, State
     from mpc_for_av_at_intersection_amd.lib.trajectories import calc_nearest_index_in_direction, resample_curve
-    g = H.gold('closedloop.npz' if max_iter == 1 else 'closedloop_iter%d.npz' % max_iter)
+    g = H.gold('closedloop_iter%d.npz' % max_iter if max_iter > 1 else 'closedloop_horizons.npz' if T in (16, 24, 32) else 'closedloop.npz')
     tape = H.gold('moving.npz')['traffic/tape']
     pmpc.T = T
     pmpc.Qf = np.diag([1.0, 1.0, 0.0, 0.5]) * T

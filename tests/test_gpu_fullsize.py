@@ -17,40 +17,6 @@ def ctx():
     c.close()
 
 
-def _replay_all_on_oracle(sim, before, after, threads=16, tol=2e-7, dead=None):
-    """EVERY agent of the step before -> after replayed on the oracle (orc_agent_steps_mt: the whole per-agent step in C, pthreads
-    over agents) from the device state `before`: integer decisions and solver status must be identical for every agent, solutions
-    within tol -- ONE tolerance for every agent, whatever its iteration count: since the active-set polish of round 3 both sides end
-    on the same KKT point even where an exit test on the edge of its tolerance sends them there by different routes.  Returns (worst
-    |solution difference|, agents whose iteration count differs, failed solves)."""
-    from oracle import oracle_py as orc
-    import dataclasses
-    po = orc.MpcParams(**{f.name: getattr(sim.params, f.name) for f in dataclasses.fields(orc.MpcParams)})
-    tab = sim.path.cpu().numpy(); off = sim.path_off.cpu().numpy(); ln = sim.path_len.cpu().numpy()
-    r = orc.agent_steps_batch(po, threads, sim.A, tab, off, ln, sim.dl, before['state'], before['applied'], before['u'],
-                              before['traj_idx'], before['prev_cut'], before['target_ind'],
-                              np.asarray(sim.ip.circle_centers).reshape(2, 2), sim.ip.radius, sim.ip.cutoff_margin,
-                              pred_steps=sim.ip.pred_steps, frame_window=sim.ip.frame_window, max_accel=sim.ip.max_accel)
-    o = r['out6']
-    # where the reference raises Exception('something wrong') (trajectories.py:120: the three nearest path points are not
-    # contiguous) the oracle stops (index -1) and the kernels flag the agent: hit_idx -3 (conflict search) / target_ind -1
-    # (agents in `dead` raised on an earlier step: the reference's run ended there, they are not followed any further)
-    dead = np.zeros(len(o), bool) if dead is None else dead
-    raised_a, raised_b = (o[:, 0] < 0) & ~dead, (o[:, 0] >= 0) & (o[:, 2] < 0) & ~dead
-    assert np.array_equal((after['hit_idx'] == -3) & ~dead, raised_a) and np.array_equal((after['target_ind'] < 0) & ~raised_a & ~dead, raised_b)
-    live = ~(raised_a | raised_b | dead)
-    sim.raised = raised_a | raised_b
-    for col, name in ((0, 'traj_idx'), (1, 'cut_len'), (2, 'target_ind'), (3, 'hit_idx'), (4, 'status')):
-        bad = np.nonzero((o[:, col] != after[name]) & live)[0]
-        assert len(bad) == 0, '%s differs from the oracle for %d agents, first %s: %s vs %s' % (name, len(bad), bad[:5], after[name][bad[:5]], o[bad[:5], col])
-    ok = (after['status'] == 0) & live
-    diff = np.maximum(np.abs(r['u'] - after['u']).max((1, 2)), np.abs(r['x'] - after['x']).max((1, 2)))
-    same_count = o[:, 5] == after['iters']
-    worst = float(diff[ok].max()) if ok.any() else 0.0
-    assert worst < tol, (worst, int(diff[ok].argmax()))
-    return worst, int((~same_count).sum()), int((~ok).sum())
-
-
 def test_full_batch_closed_loop_properties(ctx):
     from mpc_for_av_at_intersection_amd.batch import stock_routes, synthetic_batch
     from oracle import oracle_py as orc
@@ -97,7 +63,7 @@ def test_full_batch_closed_loop_properties(ctx):
     late = conflict & ~cut
     assert (after['traj_idx'][late] + 1 >= ln[late]).all(), int(late.sum())
     # 6. ALL 32768 agents replayed on the oracle from the same inputs: identical decisions and statuses, solutions <= 2e-7
-    worst, it_diff, failed = _replay_all_on_oracle(sim, before, after)
+    worst, it_diff, failed = H.replay_all_on_oracle(sim, before, after)
     print('4096 x 8 agents vs oracle: worst %.2e, %d agents with a different iteration count, %d failed solves (same on both sides)' % (worst, it_diff, failed))
     assert it_diff <= P // 1000, it_diff       # (observed since the polish: 0)
 
@@ -114,7 +80,7 @@ def test_config3_1024_instances_8_agents(ctx):
     for _ in range(4):
         sim.step()
         after = sim.snapshot()
-        w, it_diff, failed = _replay_all_on_oracle(sim, before, after)
+        w, it_diff, failed = H.replay_all_on_oracle(sim, before, after)
         worst = max(worst, w)
         assert it_diff <= 8
         before = after
@@ -163,7 +129,7 @@ def test_prius_mpc_refinement_of_prius_paths(ctx):
     for step in range(40):
         sim.step()
         after = sim.snapshot()
-        w, it_diff, failed = _replay_all_on_oracle(sim, before, after, threads=4, dead=dead)
+        w, it_diff, failed = H.replay_all_on_oracle(sim, before, after, threads=4, dead=dead)
         worst = max(worst, w)
         raised_total += int(sim.raised.sum())
         dead |= sim.raised
@@ -201,7 +167,7 @@ def test_long_closed_loop_stays_exact_against_the_oracle(ctx):
         before = sim.snapshot()
         sim.step(); done += 1
         after = sim.snapshot()
-        w, it_diff, failed = _replay_all_on_oracle(sim, before, after, threads=8)
+        w, it_diff, failed = H.replay_all_on_oracle(sim, before, after, threads=8)
         assert failed == 0 and it_diff <= 4
         worst = max(worst, w)
         seen['cut'] += int((after['cut_len'] < sim.path_len.cpu().numpy()).sum())
@@ -317,7 +283,7 @@ def test_config2_256_independent_instances_closed_loop(ctx):
         sim.step()
         after = sim.snapshot()
         assert (after['status'] == 0).all()
-        w, it_diff, failed = _replay_all_on_oracle(sim, before, after, threads=8)
+        w, it_diff, failed = H.replay_all_on_oracle(sim, before, after, threads=8)
         assert it_diff == 0 and failed == 0
         worst = max(worst, w)
         for q in range(0, B, 8):                         # plant: the oracle's Euler step from the same control reproduces the device state

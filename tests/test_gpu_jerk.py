@@ -145,7 +145,7 @@ def test_jerk_batched_closed_loop_vs_oracle(ctx):
     """256 instances x 8 agents with the jerk controller in the coupled closed loop; every agent of four steps replayed on the oracle"""
     from mpc_for_av_at_intersection_amd.batch import stock_routes, synthetic_batch
     from mpc_for_av_at_intersection_amd.runtime import MpcParams
-    from tests.test_gpu_fullsize import _replay_all_on_oracle
+    from tests.helpers import replay_all_on_oracle as _replay_all_on_oracle
     routes, dl, cd = stock_routes(ctx)
     sim = synthetic_batch(ctx, B=256, A=8, seed=5, routes=routes, dl=dl, cd=cd, mpc=MpcParams.jerk())
     assert sim.params.T == 13 and sim.params.model == 1
