@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mpcx.h"
+#include "mpcx_qp_consts.h"
 #include <vector>
 
 struct mpcx_ctx {
@@ -70,9 +71,7 @@ int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const d
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                      // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).
-#ifndef MPCX_JUMP_BONUS
 #define MPCX_JUMP_BONUS 11
-#endif
 #define MPCX_ORDER_BINS 64
 #define MPCX_TICKET_WORDS 8      /* ctx->ticket: the queue head and the other per-launch counters, zeroed together */
 #define MPCX_ORDER_COPIES 16
@@ -85,43 +84,6 @@ __device__ __forceinline__ int order_key_of(int hint, bool moved) {
 }
 int32_t mpcx_ensure_order(mpcx_ctx *ctx, size_t B);             // work-queue order scratch (mpcx_qp.hip)
 int32_t mpcx_qp_build_order(mpcx_ctx *ctx, int32_t B, hipStream_t st);   // counting sort of the work queue on stream st; also zeroes the ticket (mpcx_qp.hip)
-
-// fraction of the step to the boundary the interior-point iteration takes (both solvers must agree, and the tests' CPU checker
-// uses the same value).  0.995 in round 1; 0.999 saves 0.8 of 6.1 iterations on the closed-loop workload (numpy replica of the iteration over
-// 1280 harvested QPs: mean 6.09 -> 5.27, 99th percentile 13 -> 13, max 15 -> 15; 0.9999 is worse again)
-#ifndef MPCX_STEP_FRACTION
-#define MPCX_STEP_FRACTION 0.999
-#endif
-#ifndef MPCX_SLACK_FLOOR
-#define MPCX_SLACK_FLOOR 0.5    /* starting point of the iteration: s = max(slack, floor), lam = MPCX_LAM0 (same in mpcx_qp_stage.h) */
-#endif
-#ifndef MPCX_LAM0
-#define MPCX_LAM0 3.0              /* 1 until round 2; with separate step lengths 3 takes the hardest problems of a launch from 23 to 18 iterations (2 / 5: 18 / 17, slower on average) */
-#endif
-#ifndef MPCX_TRIAL_STEP
-#define MPCX_TRIAL_STEP 1      /* unconstrained trial step before the interior-point iteration: mpcx_qp_stage.h, mpcx_qp.hip (the tests' CPU checker follows the same rule) */
-#endif
-
-/* active-set polish at the end of the interior-point iteration: the rule and the constants are those of mpcx_qp_stage.h (the host
-   build of that header has no other source; the tests' CPU checker carries the same values) */
-#ifndef MPCX_POLISH
-#define MPCX_POLISH 1
-#endif
-#ifndef MPCX_POLISH_MU
-#define MPCX_POLISH_MU 1e-5
-#endif
-#ifndef MPCX_POLISH_RP
-#define MPCX_POLISH_RP 1e-6
-#endif
-#ifndef MPCX_POLISH_RD
-#define MPCX_POLISH_RD 1e-3
-#endif
-#ifndef MPCX_POLISH_RHO
-#define MPCX_POLISH_RHO 1e8
-#define MPCX_POLISH_TRIES 3
-#define MPCX_POLISH_EPS_L 1e-9
-#define MPCX_POLISH_EPS_G 1e-9
-#endif
 
 namespace mpcx {
 

@@ -16,10 +16,7 @@
 
 namespace mpcx {
 
-#ifndef MPCX_EXP_CHUNKS
-#define MPCX_EXP_CHUNKS 1
-#endif
-constexpr int EXP_CHUNKS = MPCX_EXP_CHUNKS;
+constexpr int EXP_CHUNKS = 1;       // node groups per block of expand_coop_kernel
 
 __device__ __forceinline__ void expand_block(const ExpandArgs &a, unsigned block_in_segment) {
     __shared__ ExpandTables t;
@@ -32,10 +29,7 @@ __global__ __launch_bounds__(256) void expand_kernel(ExpandArgs a) { expand_bloc
 
 // bulk launches: floor(256 / n_prim) nodes per block, the (record, obstacle) pairs of a wavefront worked off together
 // (expand_records_coop), tables in dynamic LDS at the model's sizes
-#ifndef MPCX_EXP_WAVES
-#define MPCX_EXP_WAVES 6
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MPCX_EXP_WAVES, 8))) void expand_coop_kernel(ExpandArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void expand_coop_kernel(ExpandArgs a) {
     extern __shared__ double s_dyn[];
     ExpandCoop &co = *reinterpret_cast<ExpandCoop *>(s_dyn);
     ExpandTablesView t = expand_view(a, s_dyn + sizeof(ExpandCoop) / sizeof(double));

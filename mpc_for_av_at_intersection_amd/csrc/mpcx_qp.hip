@@ -19,27 +19,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#ifndef MPCX_CHUNK
-#define MPCX_CHUNK 40
-#endif
-#ifndef MPCX_SPLIT
-#define MPCX_SPLIT 1
-#endif
-#ifndef MPCX_PRE
-#define MPCX_PRE 8
-#endif
-#ifndef MPCX_BCH
-#define MPCX_BCH 5
-#endif
-#ifndef MPCX_OCC
-#define MPCX_OCC 1
-#endif
-#ifdef MPCX_STAGE_BARRIER
-#define STAGE_BARRIER __builtin_amdgcn_sched_barrier(0)
-#else
-#define STAGE_BARRIER
-#endif
-
 // automatic choice: the stage-structured solver wins on throughput (8 problems per wavefront, O(T) work) once the batch fills
 // the chip, the condensed solver on latency (one problem per wavefront: 0.08-0.26 ms per launch up to ~1000 problems against a
 // 0.37-0.78 ms floor); measured crossover on the closed-loop benchmark workload (warm starts, mean 6.2 iterations with a tail to ~20: a small batch is bound by its
@@ -47,9 +26,7 @@
 // (three quarters of the problems need one pass only) and the hardest-first queue the condensed kernel's work fell more than the
 // stage solver's tail; launch times condensed / stage: 4096 problems 0.33 / 0.64 ms, 8192 0.51 / 0.68, 10240 0.61 / 0.68,
 // 12288 0.71 / 0.68, 14336 0.83 / 0.70, 16384 0.92 / 0.71.  Beyond T = 20 the condensed kernel spills and is never competitive.
-#ifndef MPCX_STAGE_MIN_BATCH
 #define MPCX_STAGE_MIN_BATCH 11264
-#endif
 
 namespace mpcx {
 
@@ -108,35 +85,12 @@ __device__ __forceinline__ double ldl_solve(const double (&Rlo)[N], const double
     return fma(-dinv, sum, w);
 }
 
-// Single-array variant (MPCX_SPLIT=0): lane i keeps L~(i,k) for k<i and the unscaled Schur entries for k>i in ONE array (80
-// VGPRs less); a finished lane's accumulators are then disturbed by later steps, so each sweep captures its result.
-template <int N>
-__device__ __forceinline__ double ldl_solve1(const double (&R)[N], double dinv, double b, int lane) {
-    double acc = b, z = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        const double zj = rdlane(acc, j);
-        z = (lane == j) ? acc : z;
-        acc = fma(-R[j], zj, acc);
-    }
-    const double w = z * dinv;
-    double sum = 0.0, x = 0.0;
-#pragma unroll
-    for (int j = N - 1; j >= 0; j--) {
-        const double tmp = fma(-dinv, sum, w);
-        const double xj = rdlane(tmp, j);
-        x = (lane == j) ? tmp : x;
-        sum = fma(R[j], xj, sum);
-    }
-    return x;
-}
-
 template <int NT>
-__global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
+__global__ __launch_bounds__(64, 1) void qp_kernel(QpArgs a) {
     constexpr int N = 2 * NT;
-    constexpr int CHUNK = MPCX_CHUNK;      // LDS values staged per batch in the unrolled loops
-    constexpr int PRE = (N - 1 < MPCX_PRE) ? N - 1 : MPCX_PRE;   // column entries prefetched one column ahead in the factorisation
-    constexpr int BCH = MPCX_BCH;          // same, stage pairs in the Hessian build (8 doubles each)
+    constexpr int CHUNK = 40;              // LDS values staged per batch in the unrolled loops
+    constexpr int PRE = (N - 1 < 8) ? N - 1 : 8;   // column entries prefetched one column ahead in the factorisation
+    constexpr int BCH = 5;                 // same, stage pairs in the Hessian build (8 doubles each)
     __shared__ QpShared<NT> sh;
   for (int guard = 0; guard <= a.B; guard++) {      // every wavefront leaves after at most B+1 tickets (bounded by construction)
     // the lane index is made opaque once per problem: everything derived from it (table indices, row masks, tile maps: ~40 values) is
@@ -389,8 +343,8 @@ __global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
     const double rowm = inrow ? 1.0 : 0.0;
     // trial step (see mpcx_qp_stage.h): the first pass runs with every multiplier taken as zero, so that M = H and the
     // predictor direction leads to the unconstrained minimiser; if that point violates no row it is the solution (0 iterations)
-    bool trial = feasible0 && MPCX_TRIAL_STEP != 0, accepted = false;
-    // active-set polish (see MPCX_POLISH in mpcx_qp_stage.h): a pass like the trial pass, with weight rho on the rows of the active set
+    bool trial = feasible0, accepted = false;
+    // active-set polish (see mpcx_qp_consts.h): a pass like the trial pass, with weight rho on the rows of the active set
     // (pm0..pm3: this lane's four rows) and lam_e + rho gap as their linear term; accepted if its end point is a KKT point
     bool polish = false, pol_pred = false, pm0 = false, pm1 = false, pm2 = false, pm3 = false;
     int ptries = 0, pend = 0, ptested = -1;
@@ -419,7 +373,7 @@ __global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
         // reduced-accuracy acceptance when the iteration cannot continue (the reference accepts ECOS's OPTIMAL_INACCURATE, mpc.py:196)
         const bool loose = !trial && resn <= tol_loose && mu <= tol_loose;
         if (!trial && !polish) {
-            if (MPCX_POLISH != 0 && pol_pred && ptested != it) {     // the step that led here predicted a point close enough to polish
+            if (pol_pred && ptested != it) {     // the step that led here predicted a point close enough to polish
                 polish = true; ptries = 0; pend = 0;
             } else {                                 // the exit tests, once per iterate
                 const bool conv = resn <= P.tol && mu <= P.tol;
@@ -428,7 +382,7 @@ __global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
                 loose_run = loose ? loose_run + 1 : 0;
                 const bool stop_ok = conv || loose_run >= 4 || (it == max_iter && loose);
                 const bool stop_fail = it == max_iter && !loose;
-                if (MPCX_POLISH != 0 && (stop_ok || stop_fail) && ptested != it) { polish = true; ptries = 0; pend = stop_ok ? 1 : 2; }
+                if ((stop_ok || stop_fail) && ptested != it) { polish = true; ptries = 0; pend = stop_ok ? 1 : 2; }
                 else if (stop_ok) { status = MPCX_QP_OPTIMAL; break; }
                 else if (stop_fail) break;
             }
@@ -468,12 +422,7 @@ __global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
         double dinv = 1.0;
         bool bad = false;
         double pre[2][PRE];
-#if MPCX_SPLIT
         double Rlo[N];
-#define SOLVE(b_) ldl_solve<N>(Rlo, R, dinv, b_, lane)
-#else
-#define SOLVE(b_) ldl_solve1<N>(R, dinv, b_, lane)
-#endif
         sh.cb[0][lane] = R[0];
         lds_order();
 #pragma unroll
@@ -511,12 +460,8 @@ __global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
 #pragma unroll
                 for (int kk = j + 2; kk < N; kk++) pin(R[kk]);
             }
-#if MPCX_SPLIT
             Rlo[j] = tj;                                                // unit lower factor entry (0 for lanes <= j)
             R[j] = (lane < j) ? R[j] : 0.0;                             // lanes < j keep their unscaled Schur entry
-#else
-            R[j] = (lane < j) ? R[j] : tj;                              // lanes < j keep their unscaled Schur entry, lane j gets 0
-#endif
             dinv = (lane == j) ? rinv : dinv;
             rinv = rinv_n;
             __builtin_amdgcn_sched_barrier(0);
@@ -554,7 +499,7 @@ __global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
             w2 = -m23 * l2 + (pm2 ? e2l + MPCX_POLISH_RHO * (rp2 - s2) : 0.0); w3 = -m23 * l3 + (pm3 ? e3 + MPCX_POLISH_RHO * (rp3 - s3) : 0.0);
         }
         double rhs = m01 * (-rd - gt_apply(w0, w1, w2, w3));
-        double du = m01 * SOLVE(rhs);
+        double du = m01 * ldl_solve<N>(Rlo, R, dinv, rhs, lane);
         double f2 = second_rows(du);
         if (polish) {
             const double un = u + du, en = e2u + f2;
@@ -617,7 +562,7 @@ __global__ __launch_bounds__(64, MPCX_OCC) void qp_kernel(QpArgs a) {
         w0 = m01 * (-rc0 + l0 * rp0) * is0; w1 = m01 * (-rc1 + l1 * rp1) * is1;
         w2 = m23 * (-rc2 + l2 * rp2) * is2; w3 = m23 * (-rc3 + l3 * rp3) * is3;
         rhs = m01 * (-rd - gt_apply(w0, w1, w2, w3));
-        du = m01 * SOLVE(rhs);
+        du = m01 * ldl_solve<N>(Rlo, R, dinv, rhs, lane);
         f2 = second_rows(du);
         const double ds0 = -rp0 - m01 * du, ds1 = -rp1 + m01 * du, ds2 = -rp2 - f2, ds3 = -rp3 + f2;
         const double dl0 = -m01 * (rc0 + l0 * ds0) * is0, dl1 = -m01 * (rc1 + l1 * ds1) * is1;
@@ -794,7 +739,6 @@ extern "C" int32_t mpcx_qp_solve_batch(mpcx_ctx *ctx, int32_t B, const double *x
     if (B == 0) return MPCX_OK;       // empty batch: nothing to do (zero-size tensors have null data pointers)
     if (B < 0 || !x0 || !xref || !xbar || !reaches_end || !x_out || !u_out || !status || !iters || !kkt)
         return mpcx_fail(ctx, MPCX_E_INVALID, "qp_solve_batch: null pointer or negative batch");
-    if (B == 0) return MPCX_OK;
     { int32_t rc = mpcx_ensure_ticket(ctx); if (rc != MPCX_OK) return rc; }
     if (!ctx->order_ready) ctx->bins_clean = false;      // this solve draws tickets outside the closed loop's bookkeeping
     // persistent wavefronts: one per SIMD slot the kernel can occupy (1 wave/SIMD, 4 SIMDs/CU), never more than B

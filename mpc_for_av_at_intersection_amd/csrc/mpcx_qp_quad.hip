@@ -1,43 +1,42 @@
 // mpcx_qp_quad.hip -- device build of the stage-structured QP solver (mpcx_qp_stage.h): EIGHT lanes per problem, eight
-// problems per wavefront (a four-lane geometry is kept for experiments).  Lane q of a group owns stages q*SPL ..
+// problems per wavefront.  Lane q of a group owns stages q*SPL ..
 // q*SPL+SPL-1; the Riccati / costate / rollout sweeps hand their carry to the neighbour lane with row_shl:1 / row_shr:1 DPP
 // moves (full rate, no LDS), group reductions are three DPP butterflies, slacks / multipliers / the state block of the gains
 // live in LDS as [row][lane] (conflict-free, 36 KB per workgroup at SPL = 3 = four workgroups per CU), everything else in
 // registers.  Wavefronts are persistent: groups draw problems from a global ticket (QueueSrc).
 #include "mpcx_common.h"
-#include <cstdlib>
 #include "mpcx_qp_stage.h"
 
 namespace mpcx {
 
 typedef __attribute__((address_space(3))) double lds_double;
 
-// group geometry: LQ_ = 4 (quad_perm selectors) or 8 (row shifts + half-row mirror), both inside one DPP row of 16 lanes
+// group geometry: 8 lanes (row shifts + half-row mirror) inside one DPP row of 16 lanes
 template <int LQ_, int SPL_, bool JERK_ = false>
 struct GroupCx {
     static constexpr int LQ = LQ_, SPL = SPL_;
     static constexpr bool JERK = JERK_;       // the five-state problem of lib/mpc_jerk.py (mpcx_mpc_params.model)
-    static_assert(LQ == 4 || LQ == 8, "groups of 4 or 8 lanes");
+    static_assert(LQ == 8, "groups of 8 lanes");
     int q, lane;
     lds_double *sh;                       // s [SPL*8][64], lam [SPL*8][64], gains [SPL*8][64], spare [2*SPL][64]
-    // quad_perm [1,2,3,3] / [0,0,1,2] = value of lane q+1 / q-1; row_shl:1 / row_shr:1 do the same across a whole row.
+    // row_shl:1 / row_shr:1 = value of lane q+1 / q-1.
     // The value arriving at a group's edge lane comes from the neighbouring group and is never used.
-    __device__ __forceinline__ double nxt(double v) const { return LQ == 4 ? dpp_mov<0xF9>(v, v) : dpp_mov<0x101>(v, v); }
-    __device__ __forceinline__ double prv(double v) const { return LQ == 4 ? dpp_mov<0x90>(v, v) : dpp_mov<0x111>(v, v); }
+    __device__ __forceinline__ double nxt(double v) const { return dpp_mov<0x101>(v, v); }
+    __device__ __forceinline__ double prv(double v) const { return dpp_mov<0x111>(v, v); }
     // butterflies: quad_perm [1,0,3,2] (xor 1), [2,3,0,1] (xor 2), row_half_mirror (lane i <-> 7-i of each half row)
     __device__ __forceinline__ double gsum(double v) const {
         v += dpp_mov<0xB1>(v, v); v += dpp_mov<0x4E>(v, v);
-        if (LQ == 8) v += dpp_mov<0x141>(v, v);
+        v += dpp_mov<0x141>(v, v);
         return v;
     }
     __device__ __forceinline__ double gmax(double v) const {
         v = fmax(v, dpp_mov<0xB1>(v, v)); v = fmax(v, dpp_mov<0x4E>(v, v));
-        if (LQ == 8) v = fmax(v, dpp_mov<0x141>(v, v));
+        v = fmax(v, dpp_mov<0x141>(v, v));
         return v;
     }
     __device__ __forceinline__ double gmin(double v) const {
         v = fmin(v, dpp_mov<0xB1>(v, v)); v = fmin(v, dpp_mov<0x4E>(v, v));
-        if (LQ == 8) v = fmin(v, dpp_mov<0x141>(v, v));
+        v = fmin(v, dpp_mov<0x141>(v, v));
         return v;
     }
     __device__ __forceinline__ bool gany(bool b) const {
@@ -63,12 +62,6 @@ struct GroupCx {
 #else
     __device__ __forceinline__ void stamp(int) const {}
 #endif
-#ifdef MPCX_STAGE_TRACE
-    double *trace_buf = nullptr;          // dev build: 8 doubles per iteration of the problem in group 0 (needs room behind kkt)
-    __device__ __forceinline__ void trace(int it, double a, double b, double c, double d, double e, double f) {
-        if (lane == 0 && trace_buf && it < 64) { double *t = trace_buf + 8 * it; t[0] = a; t[1] = b; t[2] = c; t[3] = d; t[4] = e; t[5] = f; t[6] = 1.0; }
-    }
-#endif
     __device__ __forceinline__ double ld_s(int k) const { return sh[(0 * SPL * 8 + k) * 64 + lane]; }
     __device__ __forceinline__ double ld_l(int k) const { return sh[(1 * SPL * 8 + k) * 64 + lane]; }
     __device__ __forceinline__ double ld_k(int k) const { return sh[(2 * SPL * 8 + k) * 64 + lane]; }
@@ -79,7 +72,9 @@ struct GroupCx {
     __device__ __forceinline__ void st_w(int k, double v) { sh[(3 * SPL * 8 + k) * 64 + lane] = v; }
 };
 
-// work queue: group leaders draw problem indices from a global ticket until the batch is exhausted
+// work queue: group leaders draw problem indices from a global ticket until the batch is exhausted; idle groups are refilled
+// once REFILL_GROUPS of them are waiting (or nobody is running any more)
+constexpr int REFILL_GROUPS = 2;
 template <int LQ, int SPL, bool TUNED>
 struct QueueSrc {
     const QpArgs &a;
@@ -92,10 +87,7 @@ struct QueueSrc {
                                    a.status + b, a.iters + b};
     }
     // every round either advances some group's iteration counter or consumes a ticket
-#ifndef MPCX_REFILL_GROUPS
-#define MPCX_REFILL_GROUPS 2
-#endif
-    __device__ __forceinline__ int refill_min() const { return MPCX_REFILL_GROUPS * LQ; }   // in lanes
+    __device__ __forceinline__ int refill_min() const { return REFILL_GROUPS * LQ; }   // in lanes
     __device__ __forceinline__ long max_rounds() const { return ((long)a.B + 2) * (long)(a.p.max_iter + 6) * (MPCX_POLISH_TRIES + 1); }
     template <class Cx>
     __device__ __forceinline__ bool fetch(Cx &cx, mpcx_mpc_params &P, int &pbi) const {
@@ -126,9 +118,6 @@ __global__ __launch_bounds__(64, 1) void qp_quad_kernel(QpArgs a) {
     const int lane = threadIdx.x;
     GroupCx<LQ, SPL, JERK> cx{lane & (LQ - 1), lane, (lds_double *)sh};
     QueueSrc<LQ, SPL, TUNED> src{a};
-#ifdef MPCX_STAGE_TRACE
-    if (blockIdx.x == 0) cx.trace_buf = a.kkt + 4 * (size_t)a.B;
-#endif
 #ifdef MPCX_STAGE_PROFILE
     cx.occ = (unsigned char *)(a.kkt + 4 * (size_t)a.B + 16) + 128 * (size_t)blockIdx.x;      // dev build only: needs 16 + 16 * grid spare doubles behind kkt
     cx.life = (unsigned char *)(a.kkt + 4 * (size_t)a.B + 16 + 16 * 1024);                   // ... and B / 4 more behind those (grid <= 1024)
@@ -141,9 +130,7 @@ __global__ __launch_bounds__(64, 1) void qp_quad_kernel(QpArgs a) {
 
 int qp_stage_grid(int B, int n_cu) {
     const int need = (B + 7) / 8;       // eight lane groups per wavefront
-    // one wavefront per SIMD; MPCX_QP_GRID_DIV=d (dev aid: several shards in flight on separate streams, each on 1/d of the chip)
-    static const int grid_div = [] { const char *e = getenv("MPCX_QP_GRID_DIV"); const int d = e ? atoi(e) : 1; return d >= 1 && d <= 16 ? d : 1; }();
-    const int resident = n_cu * 4 / grid_div;
+    const int resident = n_cu * 4;      // one wavefront per SIMD
     return need < resident ? need : resident;
 }
 

@@ -23,45 +23,12 @@
 #include <math.h>
 #include <stdint.h>
 #include "mpcx.h"
+#include "mpcx_qp_consts.h"
 
 #if defined(__HIPCC__)
 #define MPCX_HD __host__ __device__ __forceinline__
 #else
 #define MPCX_HD inline
-#endif
-#ifndef MPCX_STEP_FRACTION
-#define MPCX_STEP_FRACTION 0.999     /* fraction of the step to the boundary; see mpcx_common.h (the host build of this header has no other source) */
-#endif
-#ifndef MPCX_SLACK_FLOOR
-#define MPCX_SLACK_FLOOR 0.5        /* starting point of the iteration: s = max(slack, floor), lam = MPCX_LAM0 */
-#endif
-#ifndef MPCX_LAM0
-#define MPCX_LAM0 3.0
-#endif
-#ifndef MPCX_TRIAL_STEP
-#define MPCX_TRIAL_STEP 1            /* try the unconstrained minimiser before the interior-point iteration (see `trial` below) */
-#endif
-/* Active-set polish (round 3; same rule in the condensed solver and in the tests' CPU checker): an interior-point iterate sits ~sqrt(mu) from the optimum
-   on weakly active rows, and the low curvature of the input cost (2R = 0.02) amplifies that -- up to 1e-3 on the hard closed-loop
-   problems at the reduced-accuracy exit.  Once the iterate is close (mu <= MPCX_POLISH_MU with small residuals, or at any exit) the
-   rows with s < lam are taken as the active set and ONE augmented-Lagrangian solve is made on it -- a round whose barrier weights
-   are rho on the active rows and 0 elsewhere, with lam_a + rho gap_a as the rows' linear term: the trial pass below is the special
-   case "no active row".  "Close" is decided at the END of the step that produces the iterate (the new mu is known exactly there, the
-   residuals shrink by one minus the step lengths), so that the polish round takes the place of the iterate's first row pass.  The end point is accepted only if it is a KKT point (new multipliers lam_a + rho gap_a' >= 0, no other
-   row violated): then it is the minimiser up to |lam - lam*| / rho.  Otherwise rows with a negative multiplier leave the set,
-   violated rows enter it, and the round is repeated, MPCX_POLISH_TRIES times in all; after that nothing is kept and the iteration goes on
-   (or ends with its own iterate).  Polish rounds are not counted as iterations. */
-#ifndef MPCX_POLISH
-#define MPCX_POLISH 1
-#endif
-#ifndef MPCX_POLISH_MU
-#define MPCX_POLISH_MU 1e-5         /* entry: mu, primal residual / hnorm, dual residual / gnorm predicted below these (or any exit) */
-#define MPCX_POLISH_RP 1e-6
-#define MPCX_POLISH_RD 1e-3
-#define MPCX_POLISH_RHO 1e8         /* penalty of the augmented-Lagrangian solve */
-#define MPCX_POLISH_TRIES 3
-#define MPCX_POLISH_EPS_L 1e-9      /* a new multiplier below -EPS_L / a gap above EPS_G rejects the point */
-#define MPCX_POLISH_EPS_G 1e-9
 #endif
 #define MPCX_UNROLL _Pragma("unroll")
 #define MPCX_NOUNROLL _Pragma("nounroll")
@@ -122,17 +89,13 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
     // step, reports 0 iterations and is done; about two thirds of the closed-loop problems end this way instead of spending four
     // interior-point iterations walking lam from 1 to 1e-10.  Otherwise nothing is kept and the iteration starts as before.
     bool trial = false, accepted = false;
-    // polish rounds (see MPCX_POLISH above): the current active set, one byte of row bits per slot; rounds tried; what the group does
+    // polish rounds (see mpcx_qp_consts.h): the current active set, one byte of row bits per slot; rounds tried; what the group does
     // if no round is accepted (0: the iteration goes on, 1: it ends OPTIMAL with its own iterate, 2: it ends as it is -- MAXITER)
     // The active set of a polishing group is kept in the SIGN of the stored slacks (an iterate's slacks are positive): a row is in the
     // set iff the group is polishing and its stored s is negative.  Every pass takes |s| (a free source modifier) and the set costs no
     // registers.  The signs go away with the next step (of an accepted round, or of the iteration after the group gave up).
     bool polish = false, pinit = false;     // pinit: the set is still to be taken from the iterate (rows with s < lam)
     int ptries = 0, pend = 0, ptested = -1; // ptested: the iterate (by its count) that has had its polish rounds
-#ifdef MPCX_STAGE_TRACE
-    double trace_alpha = 0.0, trace_aff = 0.0, trace_sigma = 0.0;       // dev build: per-iteration history of one problem
-    int trace_n = 0;
-#endif
 
 #define WV(ls) (act[ls] ? (ended[ls] ? wv_end : wv_run) : 0.0)
 #define WP(ls) (act[ls] ? (ended[ls] ? wp_end : wp_run) : 0.0)
@@ -375,7 +338,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         max_iter = (valid && feasible0) ? P.max_iter : -1;
         if (!feasible0) status = MPCX_QP_INFEASIBLE;
         running = valid && feasible0;
-        trial = running && MPCX_TRIAL_STEP != 0;
+        trial = running;
         accepted = false;
         polish = false; pinit = false; ptries = 0; pend = 0; ptested = -1;
     };
@@ -494,9 +457,6 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             if (running && !polish) { res_d = n_rd; res_p = n_rp; mu = n_mu; }
             const bool test = running && !trial && !polish && (pass == 0 || fresh);      // a group takes the exit tests once per iterate
             if (test && accepted) { status = MPCX_QP_OPTIMAL; running = false; }     // residuals of the accepted trial point: measured above, for the report
-#ifdef MPCX_STAGE_TRACE
-            if (test) cx.trace(it, res_d, res_p, mu, trace_alpha, trace_aff, trace_sigma);
-#endif
             cx.stamp(2);                    // [costate sweep]
             // ---- exit tests (uniform per group)
             // a group that reaches an exit without having polished this iterate polishes it now: its row pass is redone with the polish
@@ -508,7 +468,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 loose_run = loose ? loose_run + 1 : 0;
                 const bool stop_ok = conv || loose_run >= 4 || (it == max_iter && loose);
                 const bool stop_fail = it == max_iter && !loose;
-                if (MPCX_POLISH != 0 && (stop_ok || stop_fail) && ptested != it) {
+                if ((stop_ok || stop_fail) && ptested != it) {
                     polish = true; pinit = true; entered = true; ptries = 0; pend = stop_ok ? 1 : 2;
                 } else if (stop_ok) { status = MPCX_QP_OPTIMAL; running = false; }
                 else if (stop_fail) running = false;
@@ -845,9 +805,6 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         if (polish) {
             const bool rej = cx.gany(viol) || any_bad;
             accepted = running && !rej;
-#ifdef MPCX_STAGE_TRACE
-            cx.trace(24 + trace_n++, (double)it, (double)ptries, rej ? 1.0 : 0.0, 0.0, 0.0, (any_bad ? 100.0 : 0.0) + (double)guard);
-#endif
             if (cx.any(rej && !any_bad && ptries + 1 < MPCX_POLISH_TRIES)) {
                 // rare: the active set of the next polish round -- rows with a negative multiplier leave, violated rows enter.  Rolled loop
                 // over the rows of a slot: small code, few registers.
@@ -889,9 +846,6 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         // a clipped reference (tests/golden/qp_hard2.npz) lost its fourth consecutive reduced-accuracy iterate that way and ran on
         // into garbage
         const double smu = fmax(sigma * n_mu, 0.1 * P.tol);
-#ifdef MPCX_STAGE_TRACE
-        trace_aff = alpha_aff; trace_sigma = sigma;
-#endif
 
         cx.fence();
         cx.stamp(5);                    // [local pass C]
@@ -1030,16 +984,13 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             if (!cx.any(running && !was_trial && !was_polish && !ok)) break;
             if (!ok && !was_trial && !was_polish) { alpha *= 0.7; alpha_d *= 0.7; }      // (a trial / polish group takes the full step or none)
         }
-#ifdef MPCX_STAGE_TRACE
-        trace_alpha = alpha;
-#endif
         cx.stamp(8);                    // [local pass E + safeguard]
         // ---- step
         if (running && (!(was_trial || was_polish) || accepted)) {
             // is the new iterate close enough to polish?  (same rule in the condensed solver: mu of the new point, the primal residual shrinks by
             // 1 - alpha, the dual one by about the smaller of the two step lengths.)  If so the group polishes from the next round on,
             // and the step itself marks the rows the new iterate holds active (s < lam) by the sign of the stored slack.
-            const bool pnext = MPCX_POLISH != 0 && !was_trial && !was_polish && mu_next <= MPCX_POLISH_MU &&
+            const bool pnext = !was_trial && !was_polish && mu_next <= MPCX_POLISH_MU &&
                                (1.0 - alpha) * res_p <= MPCX_POLISH_RP * hnorm &&
                                (1.0 - (alpha < alpha_d ? alpha : alpha_d)) * res_d <= MPCX_POLISH_RD * gnorm;
             {

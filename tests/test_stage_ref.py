@@ -1,5 +1,5 @@
 """Host build of the stage-structured QP solver (csrc/mpcx_qp_stage.h, one lane per problem) against the oracle, and the same
-source under AddressSanitizer + UBSan.  The GPU kernels (csrc/mpcx_qp_quad.hip) compile this very header with four or eight
+source under AddressSanitizer + UBSan.  The GPU kernels (csrc/mpcx_qp_quad.hip) compile this very header with eight
 lanes per problem; their parity tests are in tests/test_gpu_*.py.  Nothing here is a product path."""
 import ctypes as C
 import os
