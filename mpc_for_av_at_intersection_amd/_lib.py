@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# MPCX_LIB: developer override (instrumented builds of the same sources, scripts/*_phase_profile.py); the product is libmpcx.so
+# MPCX_LIB: developer override (another build of the same sources, such as the MPCX_INTER_FORCE_EXACT one); the product is libmpcx.so
 LIB_PATH = os.environ.get('MPCX_LIB') or os.path.join(_HERE, 'libmpcx.so')
 _lib = None
 

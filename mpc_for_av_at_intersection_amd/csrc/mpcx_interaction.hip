@@ -138,17 +138,7 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
                               double (*s_box)[4], int lane, double &hx, double &hy,
                               bool boxes_ready = false,          // s_box already holds the runs' boxes (mpcx_interaction_params.plan_box)
                               const double *pdisc = nullptr      // disc centres of the poses of `rem` (mpcx_interaction_params.path_disc + 4 * row of rem[0]) or nullptr
-#ifdef MPCX_INTER_PROFILE
-                              , unsigned long long *fc_prof = nullptr
-#endif
                               ) {
-#ifdef MPCX_INTER_PROFILE
-    unsigned long long fc_t = __builtin_amdgcn_s_memtime();
-#define FCSTAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0 && fc_prof) fc_prof[k] += t_ - fc_t; fc_t = t_; } while (0)
-    int dbg_queued = 0;      // dev build: candidates that reached a run's queue (returned in hx when there is no conflict)
-#else
-#define FCSTAMP(k) do {} while (0)
-#endif
     const double md = 2.0 * ip.radius;
     const double md2lo = md * md * (1.0 - 1e-12), md2hi = md * md * (1.0 + 1e-12);
     const int steps = ip.pred_steps, w = ip.frame_window;
@@ -175,7 +165,6 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
         if (j == 0) { s_box[sg][0] = x0 - slack; s_box[sg][1] = x1 + slack; s_box[sg][2] = y0 - slack; s_box[sg][3] = y1 + slack; }
     }
     __syncthreads();
-    FCSTAMP(8);      // run boxes
     const long long NOKEY = 0x7fffffffffffffffLL;
     long long best = NOKEY;
     long long lbest = NOKEY;                               // this lane's own smallest key and the obstacle disc position it belongs to
@@ -201,7 +190,6 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
 #pragma unroll
         for (int u = 0; u < 8; u++)
             if (cb + u * WAVE + lane >= ncand_all) { ox[u] = INFINITY; oy[u] = INFINITY; }       // fails every box test
-        FCSTAMP(9);      // candidate loads
         for (int sg = 0; sg < sg_limit; sg++) {             // wave-uniform
             const double b0 = s_box[sg][0], b1 = s_box[sg][1], b2 = s_box[sg][2], b3 = s_box[sg][3];
             // Round 4: no queue.  Which of the lane's eight positions lie in the run's box is a bit mask, and every lane works its OWN set bits
@@ -213,10 +201,6 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
 #pragma unroll
             for (int u = 0; u < 8; u++)
                 mask |= (unsigned)((ox[u] >= b0) & (ox[u] <= b1) & (oy[u] >= b2) & (oy[u] <= b3)) << u;
-            FCSTAMP(10);     // box tests of one run
-#ifdef MPCX_INTER_PROFILE
-            dbg_queued += (int)wave_sum((double)__popc(mask));
-#endif
             if (!__ballot(mask != 0u)) continue;
             const int f0 = sg * SL;
             int f1 = (sg + 1) * SL < F ? (sg + 1) * SL : F;
@@ -253,7 +237,6 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
                     if (__ballot(hit)) { found = true; f1 = f + 1; break; }
                 }
             }
-            FCSTAMP(11);     // distance tests of one run
             if (__ballot(found)) {                         // rows of later runs come later in the reference's order
                 sg_limit = sg + 1;                         // later chunks: only runs up to this one can still win
                 break;
@@ -261,9 +244,6 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
         }
     }
     best = wave_min_ll(lbest);
-#ifdef MPCX_INTER_PROFILE
-    if (best == NOKEY) hx = (double)dbg_queued;
-#endif
     if (best == NOKEY) return -1;
     // the obstacle disc of the first row: the lane that found the key still holds its position (a key belongs to one candidate, a
     // candidate to one lane) -- no decode, no load
@@ -298,7 +278,6 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
             }
         }
     }
-    FCSTAMP(12);     // earliest pose
     first = (first == 0x7fffffff) ? 0 : first % n;      // argmax of an all-False mask is 0
     hx = rem[3 * first]; hy = rem[3 * first + 1];
     return first;
@@ -306,11 +285,6 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
 
 constexpr int MAXF_STATIC = MPCX_EGO_FRAMES_MAX;      // moving_collision_kernel (explicit trajectories)
 
-#ifdef MPCX_INTER_PROFILE
-#define ISTAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) ((unsigned long long *)(a.hit_xy + 2 * (size_t)a.P))[16 * (size_t)p + (k)] = t_ - t_last; t_last = t_; } while (0)   /* dev build: needs 16 slots per ego behind hit_xy */
-#else
-#define ISTAMP(k) do {} while (0)
-#endif
 __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     // dynamic LDS, sized by the host from the longest path of the call (mpcx_interaction_params.max_path_len):
     //   s_cum [max_rem] doubles   step / cumulative lengths of the remaining path; once the resampling has consumed them the
@@ -326,9 +300,6 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     double (*s_box)[4] = reinterpret_cast<double (*)[4]>(s_cum + (size_t)MAXF * 4);           // bounding boxes of the ego discs per run of frames (256 B behind s_ego)
 
     const int p = blockIdx.x, lane = threadIdx.x;
-#ifdef MPCX_INTER_PROFILE
-    unsigned long long t_last = __builtin_amdgcn_s_memtime();
-#endif
     const mpcx_interaction_params &ip = a.ip;
     const double *path = a.path + 3 * (size_t)a.path_off[p];
     const double *pcs = a.path_cs + 2 * (size_t)a.path_off[p];
@@ -428,7 +399,6 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
             for (int k = 0; k < DEPTH; k++) { bx[k] = nbx[k]; by[k] = nby[k]; }
         }
     }
-    ISTAMP(0);      // distance / step-length pass
     if (advance) {
         if (n_old <= 1) tidx = t_old;
         else if (n_old == 2) tidx = t_old + 1;
@@ -461,7 +431,6 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
         return;
     }
     __syncthreads();
-    ISTAMP(1);      // three-smallest selection
     // ---- mpc_intersection.py:110-116 + trajectories.py:72-86: ego prediction = resample_curve(trajectory, dl_k).
     // np.cumsum adds strictly left to right.  Replaying that on one lane cost a third of this kernel, so the cumulative
     // lengths first come from a PARALLEL scan (all terms >= 0: it differs from the sequential sum by <= 2.4e-11 for 1024
@@ -697,24 +666,22 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
         }
     }
 #endif
-    if (plan_ok) {
-        ISTAMP(2);
-    } else if (search_ok) {
-        ISTAMP(2);
-        na = resample_search(unsure);
-    } else {
-        if (tab) {      // running sums from the table, four batches of loads in flight (one by one the pass waited a memory round trip per 64 points)
-            for (int i0 = 0; i0 < n; i0 += 4 * WAVE) {
-                double t[4];
+    if (!plan_ok) {      // else: poses, discs and boxes came from the table
+        if (search_ok) {
+            na = resample_search(unsure);
+        } else {
+            if (tab) {      // running sums from the table, four batches of loads in flight (one by one the pass waited a memory round trip per 64 points)
+                for (int i0 = 0; i0 < n; i0 += 4 * WAVE) {
+                    double t[4];
 #pragma unroll
-                for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + lane; t[k] = cumtab[tidx + (i < n ? i : 0)]; }
+                    for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + lane; t[k] = cumtab[tidx + (i < n ? i : 0)]; }
 #pragma unroll
-                for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + lane; if (i < n) s_cum[shift + i] = t[k] - cum0; }
-            }
-        } else prefix_fast();
-        __syncthreads();
-        ISTAMP(2);      // cumulative lengths
-        na = resample(std::true_type{}, unsure);
+                    for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + lane; if (i < n) s_cum[shift + i] = t[k] - cum0; }
+                }
+            } else prefix_fast();
+            __syncthreads();
+            na = resample(std::true_type{}, unsure);
+        }
     }
 #ifdef MPCX_INTER_FORCE_EXACT
     unsure = true;                            // dev build: every ego takes the sequential path (tests run both builds)
@@ -729,7 +696,6 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
         return;
     }
     __syncthreads();
-    ISTAMP(3);      // resample
     // ego disc centres per kept pose
     if (!plan_ok)
     for (int f = lane; f < na; f += WAVE) {
@@ -743,24 +709,13 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
         }
     }
     __syncthreads();
-    ISTAMP(4);      // ego discs
     const int ooff = a.obs_off[p], oskip = a.obs_skip ? a.obs_skip[p] : -1;
+    // conflict search (+ scan of the detailed path on a hit)
     double hx, hy;
-#ifdef MPCX_INTER_PROFILE
-    const double *pdisc = ip.plan_cnt ? ip.path_disc + 4 * prow : nullptr;     // disc centres of trajectory_full[tidx:] from the host's table
-    const int first = first_conflict(ip, s_ego, na, a.pred, ooff, nobs, oskip, rem, rcs, n, s_box, lane, hx, hy, plan_ok, pdisc,
-                                     (unsigned long long *)(a.hit_xy + 2 * (size_t)a.P) + 16 * (size_t)p);
-#else
     const double *pdisc = ip.plan_cnt ? ip.path_disc + 4 * prow : nullptr;     // disc centres of trajectory_full[tidx:] from the host's table
     const int first = first_conflict(ip, s_ego, na, a.pred, ooff, nobs, oskip, rem, rcs, n, s_box, lane, hx, hy, plan_ok, pdisc);
-#endif
-    ISTAMP(5);      // conflict search (+ path scan on a hit)
     if (first < 0) {
-#ifdef MPCX_INTER_PROFILE
-        if (lane == 0) { a.hit_idx[p] = -1; a.cut_len[p] = len; file_key(len); a.hit_xy[2 * p] = hx; a.hit_xy[2 * p + 1] = 0; }
-#else
         if (lane == 0) { a.hit_idx[p] = -1; a.cut_len[p] = len; file_key(len); a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; }
-#endif
         return;
     }
     // ---- collision_avoidance.py:107-119 on trajectory_full, then mpc_intersection.py:130-134
@@ -780,7 +735,6 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     int cl = len;
     if (cut != 0x7fffffff) { cl = cut - ip.cutoff_margin; cl = cl > tidx + 1 ? cl : tidx + 1; }
     if (lane == 0) { a.hit_idx[p] = first; a.hit_xy[2 * p] = hx; a.hit_xy[2 * p + 1] = hy; a.cut_len[p] = cl; file_key(cl); }
-    ISTAMP(6);      // cut index
 }
 
 // ------------------------------------------------------------------------------------------------------------

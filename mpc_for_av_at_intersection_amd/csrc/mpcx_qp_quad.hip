@@ -51,17 +51,9 @@ struct GroupCx {
     __device__ __forceinline__ double rcp_seed(double v) const { return __builtin_amdgcn_rcp(v); }
     // phase boundary: LDS values are re-read afterwards instead of being carried in registers across the phase
     __device__ __forceinline__ void fence() const { asm volatile("" ::: "memory"); }
-#ifdef MPCX_STAGE_PROFILE
-    // dev build: shader-clock time per phase, summed per wavefront (lane 0 adds to prof[phase] at the end)
-    unsigned long long t_last = 0, t_acc[10] = {};
-    __device__ __forceinline__ void stamp(int k) { const unsigned long long t = __builtin_amdgcn_s_memtime(); if (t_last) t_acc[k] += t - t_last; t_last = t; }
-    unsigned char *occ = nullptr;        // dev build: per wavefront 64 rounds x (groups at work, of which in a trial / polish round)
-    unsigned char *life = nullptr;       // dev build: per problem (round it was drawn in, round it was handed in: + 100 = handed over)
-    __device__ __forceinline__ void lifetime(int b, int which, int round) { if (q == 0 && life) life[2 * b + which] = (unsigned char)round; }
-    __device__ __forceinline__ void occupancy(int round, int groups, int special) { if (lane == 0 && occ && round < 64) { occ[2 * round] = (unsigned char)groups; occ[2 * round + 1] = (unsigned char)special; } }
-#else
+    // phase-boundary marker of solve_queue: empty in every build.  The calls stay because the compiled stage kernel changes without them
+    // (registers, spills and scratch of the SPL = 3 and 4 instances move) although they emit no instruction themselves.
     __device__ __forceinline__ void stamp(int) const {}
-#endif
     __device__ __forceinline__ double ld_s(int k) const { return sh[(0 * SPL * 8 + k) * 64 + lane]; }
     __device__ __forceinline__ double ld_l(int k) const { return sh[(1 * SPL * 8 + k) * 64 + lane]; }
     __device__ __forceinline__ double ld_k(int k) const { return sh[(2 * SPL * 8 + k) * 64 + lane]; }
@@ -118,14 +110,7 @@ __global__ __launch_bounds__(64, 1) void qp_quad_kernel(QpArgs a) {
     const int lane = threadIdx.x;
     GroupCx<LQ, SPL, JERK> cx{lane & (LQ - 1), lane, (lds_double *)sh};
     QueueSrc<LQ, SPL, TUNED> src{a};
-#ifdef MPCX_STAGE_PROFILE
-    cx.occ = (unsigned char *)(a.kkt + 4 * (size_t)a.B + 16) + 128 * (size_t)blockIdx.x;      // dev build only: needs 16 + 16 * grid spare doubles behind kkt
-    cx.life = (unsigned char *)(a.kkt + 4 * (size_t)a.B + 16 + 16 * 1024);                   // ... and B / 4 more behind those (grid <= 1024)
-#endif
     mpcx_stage::solve_queue(cx, src);
-#ifdef MPCX_STAGE_PROFILE
-    if (lane == 0) for (int k = 0; k < 10; k++) atomicAdd((unsigned long long *)(a.kkt + 4 * (size_t)a.B) + k, cx.t_acc[k]);   // dev build only: needs 10 spare slots behind kkt
-#endif
 }
 
 int qp_stage_grid(int B, int n_cu) {

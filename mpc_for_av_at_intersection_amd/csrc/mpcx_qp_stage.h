@@ -480,14 +480,8 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             if (!(cx.count(need) >= src.refill_min() || (cx.any(need) && !cx.any(running)) || cx.any(entered))) break;
             fresh = false;
             if (need) {                  // uniform within a group: the DPP operations inside stay inside the group
-#ifdef MPCX_STAGE_PROFILE
-                if (have) cx.lifetime(pbi, 1, (int)guard);
-#endif
                 if (have) emit();
                 have = src.fetch(cx, P, pbi);
-#ifdef MPCX_STAGE_PROFILE
-                if (have) cx.lifetime(pbi, 0, (int)guard);
-#endif
                 drained = !have;         // the queue is empty: zero the group's data once and idle from now on
                 setup();
                 fresh = true;
@@ -495,9 +489,6 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             cx.stamp(0);                    // [refill / set-up]
         }
         if (!cx.any(have)) break;
-#ifdef MPCX_STAGE_PROFILE
-        cx.occupancy((int)guard, cx.count(running) / Cx::LQ, cx.count(running && (trial || polish)) / Cx::LQ);      // dev build: groups at work in this round
-#endif
 
         cx.fence();
         // ---- backward sweep: Riccati factorisation + predictor gains.  Carry: cost-to-go Hessian Pm (6x6 symmetric, 21
@@ -1028,9 +1019,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
 #undef RA_
 #undef RS_
 #undef JW_
-#ifdef PX7
 #undef PX7
-#endif
 }
 
 }  // namespace mpcx_stage

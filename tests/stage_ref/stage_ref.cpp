@@ -28,7 +28,7 @@ struct HostCx {
 #endif
     double rcp_seed(double v) const { return 1.0 / v; }
     void fence() const {}
-    void stamp(int) const {}
+    void stamp(int) const {}      // phase-boundary marker, empty in every build (kept for the GPU kernel's code generation, see GroupCx)
     double ld_s(int k) const { return s[k]; }
     double ld_l(int k) const { return l[k]; }
     double ld_k(int j) const { return k[j]; }
