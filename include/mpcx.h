@@ -276,12 +276,49 @@ int32_t mpcx_selftest_mfma(mpcx_ctx *ctx, const double *A64, const double *B64, 
 int32_t mpcx_plant_step_batch(mpcx_ctx *ctx, int32_t B, double *state /*B,4 in-out*/, double *u /*B,2,T in-out*/,
                               const int32_t *status /*B or NULL*/, double *applied /*B,2 in-out: (steer, accel)*/);
 
+/* ---- scripted traffic: lib/moving_obstacles.py:16-231 (MovingObstacleTIntersection / MovingObstacleRoundabout /
+ * MovingObstacleArterial) + bicycle/main.py:28-41, the cars of the reference's scenarios that never yield
+ * (scenarios/mpc_intersection.py:42-45,118-122,155-156; mpc_roundabout.py:45-46; overtaking_cyclist_bidirectional_road.py:82).
+ * One call = for every actor get() -- its 6-tuple (x, y, v, yaw, a = 0, steer) written to row pool_row[i] of obs6 -- followed by
+ * step().  The step rule is csrc/mpcx_traffic_core.h: un-fused arithmetic in the reference's operation order, so the decision
+ * columns (v, a, steer) are the host classes' bit for bit and the poses differ only by what the device's sincos / tan differ from
+ * the host's libm.  MPCX_TRAFFIC_TAPE actors do no arithmetic: they copy row tape_off + cursor * tape_stride of the uploaded table
+ * tape[rows][6] (cursor = 0, 1, ..., holding the last of its tape_rows rows) -- bit-exact replay of rows the host computed or recorded.
+ * ALL mutable state is in actor_state (device, 4 doubles per actor: x, y, theta, counter -- the step counter, or the cursor of a
+ * TAPE actor, as an integer-valued double): no call argument counts steps, a replayed hipGraph keeps advancing.
+ * UNLIKE the other per-stage entry points this one is not asynchronous: the actor table and pool_row are device memory, so each call
+ * first synchronises the stream and reads both back (80 bytes + 4 per actor) to check them -- kinds, TAPE actors inside the table, rows
+ * inside the pool -- before it launches.  mpcx_closed_loop_run with traffic does the same (+ ego_row) ONCE PER CALL, before its first
+ * launch: n_steps in one call pay it once, a caller that steps with n_steps = 1 pays it every step (and a graph replay likewise,
+ * per call).  The kernels clamp every index all the same. */
+enum { MPCX_TRAFFIC_TINTERSECTION = 0, MPCX_TRAFFIC_ROUNDABOUT = 1, MPCX_TRAFFIC_ARTERIAL = 2, MPCX_TRAFFIC_TAPE = 3 };
+typedef struct {
+    int32_t kind;        /* MPCX_TRAFFIC_* */
+    int32_t direction;   /* +1: enters from the left (lane y = -3), -1: from the right (moving_obstacles.py:176-187) */
+    int32_t turning;     /* `turning is True` of the constructor */
+    int32_t tape_rows, tape_off, tape_stride;   /* TAPE: rows of this actor, its first row and the row distance between its steps */
+    double speed;        /* m/s once the start delay is over */
+    double offset;       /* start delay [s]: standing until counter > offset / counter_dt; <= 0 = none */
+    double counter_dt;   /* what the delay is counted in: the constructor's dt, but always 0.2 for the roundabout class (:45) */
+    double model_dt;     /* sample time of the plant */
+    double L;            /* wheelbase of the plant */
+    double x_turn;       /* TINTERSECTION: -10 / 12 */
+    double arc;          /* ROUNDABOUT: arctan(2.86 / 5) as the host's libm gives it (moving_obstacles.py:16-25) */
+} mpcx_traffic_actor;    /* 6 int32 + 7 doubles */
+int32_t mpcx_traffic_step_batch(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffic_actor *actors, double *actor_state /*n,4 in-out*/,
+                                const double *tape /*rows,6 or NULL without TAPE actors*/, int64_t tape_rows,
+                                const int32_t *pool_row /*n*/, int32_t n_obs_pool, double *obs6 /*NOBS,6 out*/);
+
 /* ---- the closed loop itself: scenarios/mpc_intersection.py:95-159 for P agents, n_steps times, with no host work
- * between steps.  One step = [pool row q <- (x, y, v, yaw, accel, steer) of agent q, what MovingObstacle*.get()
- * returns] -> mpcx_interaction_batch (prev_cut_len = the cut_len of the previous step; zero = none yet) ->
- * mpcx_mpc_prepare_batch (path_len = cut_len, warm start = u_sol) -> mpcx_qp_solve_batch (warm start = u_sol, in
- * place) -> mpcx_plant_step_batch.  Every agent is a moving obstacle for the agents whose obs_off/obs_cnt window
- * covers it, so the pool has exactly P rows.  All pointers are device pointers owned by the caller; the buffers
+ * between steps.  One step = [pool row of agent q <- (x, y, v, yaw, accel, steer) of agent q, what MovingObstacle*.get()
+ * returns; pool rows of the scripted actors <- their get(), mpcx_traffic_step_batch] -> mpcx_interaction_batch (prev_cut_len =
+ * the cut_len of the previous step; zero = none yet) -> mpcx_mpc_prepare_batch (path_len = cut_len, warm start = u_sol) ->
+ * mpcx_qp_solve_batch (warm start = u_sol, in place) -> mpcx_plant_step_batch.  Every agent is a moving obstacle for the agents
+ * whose obs_off/obs_cnt window covers it.  Without traffic (n_actors = 0) the pool has exactly P rows and row q is agent q.  With
+ * traffic the pool has pool_rows rows, agent q sits in row ego_row[q] and actor i in row actor_row[i] (the batch of this package
+ * lays an instance out as [its A agents | its actors], so every window stays one contiguous run); the actors' step() takes
+ * effect for the NEXT step, as o.step() at the end of the reference's loop body does (mpc_intersection.py:155-156).
+ * All pointers are device pointers owned by the caller; the buffers
  * are the same ones the per-stage entry points take and hold the same values afterwards.
  * use_graph != 0 captures one step into a hipGraph on the context's stream (which must then not be the null
  * stream) and replays it n_steps times; the instantiated graph is cached in the context per descriptor. */
@@ -289,7 +326,7 @@ typedef struct {
     int32_t P;
     int32_t exchange;   /* 0: the pool obs6 is this rank's own P agents; MPCX_SHARD_AGENTS: agent-sharded multi-GPU layout, see below */
     double dl;
-    double *state /*P,4*/, *applied /*P,2: (steer, accel)*/, *obs6 /*P,6 scratch*/;
+    double *state /*P,4*/, *applied /*P,2: (steer, accel)*/, *obs6 /*P,6 scratch (pool_rows,6 with traffic)*/;
     const double *path_xyyaw, *path_cs, *path_v /*or NULL*/;
     const int32_t *path_off /*P*/, *path_len /*P*/, *obs_off /*P*/, *obs_cnt /*P*/, *obs_skip /*P or NULL*/;
     int32_t *traj_idx /*P*/, *target_ind /*P*/, *hit_idx /*P*/, *cut_len /*P, zero-initialised*/;
@@ -303,6 +340,14 @@ typedef struct {
      * [n_inst][world * agents_local][6] and is filled every step by mpcx_allgather_states from obs_local. */
     int32_t n_inst, agents_local;
     double *obs_local /*P,6 scratch*/;
+    /* scripted traffic (n_actors = 0: none, the fields below are not read).  Refused together with exchange == MPCX_SHARD_AGENTS:
+     * traffic is instance-local, the instance-sharded layout needs nothing. */
+    int32_t n_actors, pool_rows /* rows of obs6: at least P + n_actors */;
+    const mpcx_traffic_actor *actors /*n_actors*/;
+    double *actor_state /*n_actors,4*/;
+    const double *tape /*tape_rows,6 or NULL*/;
+    const int32_t *actor_row /*n_actors*/, *ego_row /*P*/;
+    int64_t tape_rows;
 } mpcx_closed_loop;
 int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
                              int32_t n_steps, int32_t use_graph);

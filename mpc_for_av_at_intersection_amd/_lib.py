@@ -40,7 +40,16 @@ class ClosedLoopC(C.Structure):
              'obs_skip', 'traj_idx', 'target_ind', 'hit_idx', 'cut_len', 'hit_xy', 'xref', 'xbar', 'reaches_end',
              'x_sol', 'u_sol', 'status', 'iters', 'kkt']
     _fields_ = ([('P', C.c_int32), ('exchange', C.c_int32), ('dl', C.c_double)] + [(n, C.c_void_p) for n in _PTRS] +
-                [('n_inst', C.c_int32), ('agents_local', C.c_int32), ('obs_local', C.c_void_p)])
+                [('n_inst', C.c_int32), ('agents_local', C.c_int32), ('obs_local', C.c_void_p)] +
+                # scripted traffic (n_actors = 0: none)
+                [('n_actors', C.c_int32), ('pool_rows', C.c_int32), ('actors', C.c_void_p), ('actor_state', C.c_void_p), ('tape', C.c_void_p),
+                 ('actor_row', C.c_void_p), ('ego_row', C.c_void_p), ('tape_rows', C.c_int64)])
+
+
+class TrafficActorC(C.Structure):
+    """mirror of mpcx_traffic_actor (include/mpcx.h): the constants of one scripted vehicle"""
+    _fields_ = ([(n, C.c_int32) for n in ('kind', 'direction', 'turning', 'tape_rows', 'tape_off', 'tape_stride')] +
+                [(n, C.c_double) for n in ('speed', 'offset', 'counter_dt', 'model_dt', 'L', 'x_turn', 'arc')])
 
 
 class AstarSearchC(C.Structure):
@@ -62,6 +71,12 @@ ASTAR_SEARCH_DTYPE = _np.dtype([('start', '<f8', 3), ('goal_box', '<f8', 4), ('g
                                 ('wh', '<f8', 5), ('wc', '<f8', 4), ('hp_norm', '<u8'), ('variant', '<i4'), ('max_expansions', '<i4'),
                                 ('ov_off', '<i4'), ('ov_cnt', '<i4')])
 assert ASTAR_SEARCH_DTYPE.itemsize == C.sizeof(AstarSearchC)
+# mpcx_traffic_actor as a numpy record (actor tables of thousands of rows are filled column by column)
+TRAFFIC_ACTOR_DTYPE = _np.dtype([(n, '<i4') for n in ('kind', 'direction', 'turning', 'tape_rows', 'tape_off', 'tape_stride')] +
+                                [(n, '<f8') for n in ('speed', 'offset', 'counter_dt', 'model_dt', 'L', 'x_turn', 'arc')])
+assert TRAFFIC_ACTOR_DTYPE.itemsize == C.sizeof(TrafficActorC)
+TRAFFIC_TINTERSECTION, TRAFFIC_ROUNDABOUT, TRAFFIC_ARTERIAL, TRAFFIC_TAPE = 0, 1, 2, 3
+MAX_OBS = 16        # MPCX_MAX_OBS: moving obstacles seen by one ego
 ASTAR_BASE, ASTAR_MODIFIED, ASTAR_MULTI_LANE, ASTAR_ROUNDABOUT, ASTAR_SINGLE_LANE = 0, 1, 2, 3, 4
 ASTAR_VARIANTS = {'base': ASTAR_BASE, 'modified': ASTAR_MODIFIED, 'multi_lane': ASTAR_MULTI_LANE, 'roundabout': ASTAR_ROUNDABOUT,
                   'single_lane': ASTAR_SINGLE_LANE}
@@ -76,7 +91,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_transform_batch', 'mpcx_cutoff_index_batch', 'mpcx_predict_obstacles_batch', 'mpcx_selftest_wave_ops', 'mpcx_selftest_mfma',
            'mpcx_closed_loop_run', 'mpcx_profile_qp', 'mpcx_profile_qp_read', 'mpcx_set_instance_tuning', 'mpcx_set_qp_solver', 'mpcx_qp_set_order_hint', 'mpcx_expand_multi_batch',
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
-           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch']
+           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch']
 
 
 def load():
@@ -134,5 +149,6 @@ def load():
     lib.mpcx_comm_destroy.restype = i32; lib.mpcx_comm_destroy.argtypes = [vp]
     lib.mpcx_allgather_states.restype = i32; lib.mpcx_allgather_states.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.mpcx_closed_loop_stats.restype = i32; lib.mpcx_closed_loop_stats.argtypes = [vp, C.POINTER(C.c_int64), i32]
+    lib.mpcx_traffic_step_batch.restype = i32; lib.mpcx_traffic_step_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int64, vp, i32, vp]
     _lib = lib
     return lib

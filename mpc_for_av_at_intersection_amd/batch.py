@@ -5,7 +5,9 @@ One `step()` is the body of the reference's scenario loop (main/scenarios/mpc_in
 search and path cut (mpcx_interaction_batch), reference window + warm-start rollout (mpcx_mpc_prepare_batch), the
 QP (mpcx_qp_solve_batch) and the plant update (mpcx_plant_step_batch). Every other agent of the same instance plays
 the role of the reference's `moving_obstacles`: it is described by (x, y, v, yaw, a, steer) exactly like
-`MovingObstacle*.get()` (a, steer = the controls it applied last step). All state lives on the device.
+`MovingObstacle*.get()` (a, steer = the controls it applied last step). An instance may also carry the reference's own
+SCRIPTED cars (lib/moving_obstacles.py; `traffic=`): they are stepped on the device too (mpcx_traffic_step_batch) and share
+the instance's rows of the obstacle pool with its agents. All state lives on the device.
 `run(n)` hands the whole loop to mpcx_closed_loop_run (n steps enqueued back to back, optionally as a replayed
 hipGraph); `step_staged()` drives the same kernels stage by stage through the per-stage entry points.
 """
@@ -16,14 +18,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from .runtime import path_first_within, path_plan, path_tables, Context, InteractionParams, MpcParams, MpcxError
+from .runtime import (path_first_within, path_plan, path_tables, traffic_pool_layout, Context, InteractionParams, MpcParams, MpcxError,
+                      Traffic)
 
 
 class IntersectionBatch:
     def __init__(self, ctx: Context, params: MpcParams, ip: InteractionParams, routes: Sequence[np.ndarray], dl: float,
                  route_of_agent: np.ndarray, start_index: np.ndarray, v0: Optional[np.ndarray] = None,
                  tuning: Optional[np.ndarray] = None, agent_shard: Optional[tuple] = None, exchange=None,
-                 pose_offset: Optional[np.ndarray] = None):
+                 pose_offset: Optional[np.ndarray] = None, traffic: Optional[Traffic] = None):
         """routes: list of (n_r, 3) paths whose yaw column is already unwrapped (MPC.__init__, mpc.py:257);
         route_of_agent, start_index: integer arrays of shape (B, A); tuning: optional (B, 16) or (B*A, 16) array of
         MpcParams.tuning_row()s -- one cost/limit set per instance (or agent), the batched form of the reference's
@@ -35,7 +38,9 @@ class IntersectionBatch:
         on the context's communicator, inside mpcx_closed_loop_run) or a callable local(B, A_loc, 6) -> pool(B, A, 6)
         (sharding.torch_exchange: torch.distributed, used for gloo rehearsals).
         pose_offset: optional (B, A, 2) array (lateral offset [m] to the left of the path, heading error [rad]) added to the start
-        poses, which otherwise sit exactly on the path (config2_batch)."""
+        poses, which otherwise sit exactly on the path (config2_batch).
+        traffic: optional runtime.Traffic -- scripted cars per instance (scenarios/mpc_intersection.py:42-45), stepped on the device; the
+        pool then holds [A agents | K actors] per instance (runtime.traffic_pool_layout).  None: exactly the ego-only batch."""
         # (a copy: the arc-length table below belongs to THIS batch's paths)
         ip = dataclasses.replace(ip, max_path_len=max(int(ip.max_path_len), max(len(r) for r in routes)))     # sizes the interaction kernel's LDS
         self.ctx, self.params, self.ip, self.dl = ctx, params, ip, float(dl)
@@ -112,6 +117,19 @@ class IntersectionBatch:
         self.obs_skip = ctx.i32((np.arange(self.B)[:, None] * self.A_total + a_lo + np.arange(self.A)[None, :]).reshape(-1))
         f = torch.float64
         self.obs6 = torch.zeros((self.B * self.A_total, 6), dtype=f, device=dev)
+        self.traffic = traffic
+        if traffic is not None:
+            # ... and, behind them, the instance's scripted actors: [A agents | K_b actors | unused up to max K]
+            if self.shard_world > 1:
+                raise ValueError('scripted traffic is instance-local: shard a batch that has it by instances, not by agents')
+            lay = traffic_pool_layout(self.B, self.A, traffic.k_of_instance, a_lo, self.A_total)      # ValueError beyond MPCX_MAX_OBS
+            self.obs_off, self.obs_cnt, self.obs_skip = ctx.i32(lay['obs_off']), ctx.i32(lay['obs_cnt']), ctx.i32(lay['obs_skip'])
+            self.ego_row, self.actor_row = ctx.i32(lay['ego_row']), ctx.i32(lay['actor_row'])
+            self.ego_row64 = self.ego_row.long()
+            self.obs6 = torch.zeros((lay['pool_rows'], 6), dtype=f, device=dev)
+            self.actors = torch.as_tensor(np.frombuffer(traffic.actors.tobytes(), dtype=np.uint8).copy()).to(dev)
+            self.traffic_state = ctx.f64(traffic.state)
+            self.tape = ctx.f64(traffic.tape) if traffic.tape is not None and len(traffic.tape) else None
         self.obs_local = torch.zeros((P, 6), dtype=f, device=dev) if agent_shard is not None else None
         # cut_len doubles as "length of the previous tmp_trajectory" (0 = none yet) for the next step
         self.inter = dict(hit_idx=torch.empty(P, dtype=torch.int32, device=dev), hit_xy=torch.empty((P, 2), dtype=f, device=dev),
@@ -151,6 +169,10 @@ class IntersectionBatch:
                     kkt=self.sol['kkt'])
         for k, t in bufs.items():
             setattr(d, k, None if t is None else t.data_ptr())
+        if self.traffic is not None and self.traffic.n_actors:
+            d.n_actors, d.pool_rows = self.traffic.n_actors, int(self.obs6.shape[0])
+            d.actors, d.actor_state, d.actor_row, d.ego_row = (t.data_ptr() for t in (self.actors, self.traffic_state, self.actor_row, self.ego_row))
+            d.tape, d.tape_rows = (None, 0) if self.tape is None else (self.tape.data_ptr(), int(self.tape.shape[0]))
         return d
 
     def _claim_context(self):
@@ -193,11 +215,18 @@ class IntersectionBatch:
         self._claim_context()
         # what MovingObstacle*.get() would return for every agent: (x, y, v, yaw, a, steer)
         rows = self.obs6 if self.obs_local is None else self.obs_local
-        rows[:, 0:2] = self.state[:, 0:2]
-        rows[:, 2] = self.state[:, 2]
-        rows[:, 3] = self.state[:, 3]
-        rows[:, 4] = self.applied[:, 1]
-        rows[:, 5] = self.applied[:, 0]
+        if self.traffic is not None and self.traffic.n_actors:
+            if self.obs_local is not None:
+                raise MpcxError('scripted traffic is not supported in the agent-sharded layout')
+            # agents into their pool rows, then the scripted cars: get() into theirs and step() (mpc_intersection.py:118-122, 155-156)
+            self.obs6[self.ego_row64] = torch.cat([self.state, self.applied[:, 1:2], self.applied[:, 0:1]], dim=1)
+            c.traffic_step(self.actors, self.traffic_state, self.actor_row, self.obs6, tape=self.tape)
+        else:
+            rows[:, 0:2] = self.state[:, 0:2]
+            rows[:, 2] = self.state[:, 2]
+            rows[:, 3] = self.state[:, 3]
+            rows[:, 4] = self.applied[:, 1]
+            rows[:, 5] = self.applied[:, 0]
         if self.obs_local is not None:       # agent-sharded: every rank assembles the whole pool
             loc = self.obs_local.view(self.B, self.A, 6)
             if callable(self.exchange):
@@ -224,6 +253,9 @@ class IntersectionBatch:
         out.update({k: v.cpu().numpy().copy() for k, v in self.sol.items()})
         out.update({k: v.cpu().numpy().copy() for k, v in self.inter.items()})
         out.update({k: v.cpu().numpy().copy() for k, v in self.pre.items()})
+        if self.traffic is not None:         # the actors' states (x, y, theta, counter / cursor) and the pool as the last step saw it
+            out['traffic_state'] = self.traffic_state.cpu().numpy().copy()
+            out['obs6'] = self.obs6.cpu().numpy().copy()
         return out
 
 
@@ -276,6 +308,67 @@ def synthetic_batch(ctx: Context, B: int, A: int = 8, T: int = 20, seed: int = 0
     ip = InteractionParams(cutoff_margin=4 * int(np.ceil(cd.radius / dl)), L=cd.distance_back_to_front_wheel, radius=cd.radius,
                            circle_centers=np.asarray(cd.circle_centers).ravel())
     return IntersectionBatch(ctx, params, ip, routes, dl, route_of_agent, start, agent_shard=agent_shard, exchange=exchange)
+
+
+def scripted_traffic_specs(B: int, K: int, seed: int, L: float, dt: float = 0.2):
+    """the scripted cars of scripted_traffic_batch as a runtime.Traffic (host tables only, no GPU needed): K
+    MovingObstacleTIntersection per instance, direction +-1, turning or not, speed ~ U[15, 35] / 3.6 m/s, start delay ~ U[0, 6] s,
+    drawn with numpy.random.default_rng([seed, 1]); instance 0 carries the stock pair of scenarios/mpc_intersection.py:42-45 in its
+    first two places (direction 1, offset 2, straight on / direction -1, offset 4, turning; 25 / 3.6 m/s)."""
+    from .lib.moving_obstacles import calculate_steering_angle_for_radius
+    rng = np.random.default_rng([seed, 1])
+    direction = np.where(rng.random((B, K)) < 0.5, 1, -1)
+    turning = rng.random((B, K)) < 0.5
+    speed = rng.uniform(15.0, 35.0, (B, K)) / 3.6
+    offset = rng.uniform(0.0, 6.0, (B, K))
+    if B and K:
+        stock = [(1, False, 25 / 3.6, 2.0), (-1, True, 25 / 3.6, 4.0)][:K]
+        for k, (d, t, v, o) in enumerate(stock):
+            direction[0, k], turning[0, k], speed[0, k], offset[0, k] = d, t, v, o
+    actors = np.zeros(B * K, _lib.TRAFFIC_ACTOR_DTYPE)
+    d = direction.reshape(-1)
+    actors['kind'] = _lib.TRAFFIC_TINTERSECTION
+    actors['direction'], actors['turning'] = d, turning.reshape(-1)
+    actors['speed'], actors['offset'] = speed.reshape(-1), offset.reshape(-1)
+    actors['counter_dt'] = actors['model_dt'] = dt
+    actors['L'] = L
+    actors['x_turn'] = np.where(d == 1, -10.0, 12.0)
+    actors['arc'] = float(calculate_steering_angle_for_radius(5))
+    state = np.zeros((B * K, 4))
+    state[:, 0], state[:, 1], state[:, 2] = np.where(d == 1, -30.0, 30.0), np.where(d == 1, -3.0, 3.0), np.where(d == 1, 0.0, np.pi)
+    return Traffic(actors, state, np.full(B, K, dtype=np.int64))
+
+
+def scripted_traffic_batch(ctx: Context, B: int, T: int = 20, seed: int = 0, A: int = 1, K: int = 2, routes=None, dl=None, cd=None,
+                           max_start_frac: float = 0.35, instance_slice: Optional[tuple] = None, mpc: Optional[MpcParams] = None,
+                           stock_route: int = 6):
+    """The reference's stock scenario (scenarios/mpc_intersection.py: one ego + two scripted cars that never yield) as a seeded family of
+    B instances: the ego's route uniform over the stock routes, A - 1 further egos on the other arms (every ego yields to every other, as
+    in synthetic_batch: start positions staggered along the approach, v0 = 0), K scripted T-intersection cars per instance
+    (scripted_traffic_specs).  Instance 0 is ALWAYS the stock set: route `stock_route` of `routes` ((4, 1) of stock_routes), started at
+    the first path point, with the stock pair of cars.  A function of (B, seed) only (for given A, K), so a rank takes its part with
+    instance_slice = (lo, hi)."""
+    if routes is None:
+        routes, dl, cd = stock_routes(ctx)
+    R = len(routes)
+    rng = np.random.default_rng([seed, 0])
+    first = rng.integers(0, R, size=B)
+    if B:
+        first[0] = min(stock_route, R - 1)
+    a = np.arange(A)
+    route_of_agent = (first[:, None] + 2 * a[None, :] + (2 * a[None, :]) // R) % R        # the next arm first, then the other manoeuvre
+    lens = np.array([len(r) for r in routes])[route_of_agent]
+    start = (rng.random((B, A)) * max_start_frac * lens).astype(np.int64)
+    if B:
+        start[0, 0] = 0
+    params = MpcParams(T=T, L=cd.distance_back_to_front_wheel) if mpc is None else dataclasses.replace(mpc, L=cd.distance_back_to_front_wheel)
+    traffic = scripted_traffic_specs(B, K, seed, cd.distance_back_to_front_wheel, dt=params.dt)
+    if instance_slice is not None:
+        lo, hi = instance_slice
+        route_of_agent, start, traffic = route_of_agent[lo:hi], start[lo:hi], traffic.slice(lo, hi)
+    ip = InteractionParams(cutoff_margin=4 * int(np.ceil(cd.radius / dl)), L=cd.distance_back_to_front_wheel, radius=cd.radius,
+                           circle_centers=np.asarray(cd.circle_centers).ravel())
+    return IntersectionBatch(ctx, params, ip, routes, dl, route_of_agent, start, traffic=traffic)
 
 
 _PLAN_CACHE = {}

@@ -36,6 +36,10 @@ struct mpcx_ctx {
     bool bin_scatter = false;             // set around the window selection: write `order`
     bool bin_reset = false;               // set around the plant step: zero bins and ticket
     const double *pack_state = nullptr, *pack_applied = nullptr;   // mpcx_closed_loop_run, local pool: the prediction kernel packs the pool rows itself
+    // ... with scripted traffic in the pool: agent q is packed into row pack_ego_row[q], and the pack_n_actors rows pack_actor_row[] (written by
+    // traffic_kernel just before) are predicted as they stand; nullptr: row q is agent q
+    const int32_t *pack_ego_row = nullptr, *pack_actor_row = nullptr;
+    int32_t pack_n_ego = 0, pack_n_actors = 0;
     int32_t *inter_prev_save = nullptr;   // mpcx_closed_loop_run: where the conflict search leaves the cut lengths it read (the queue order's `moved` test)
     // mpcx_closed_loop_run: the conflict search and the window selection both run calc_nearest_index_in_direction for the same agent, state
     // and path, mostly from the same start index.  The conflict search leaves (its start index, the largest of its three nearest indices
@@ -68,6 +72,10 @@ int32_t mpcx_fail(mpcx_ctx *ctx, int32_t code, const char *fmt, ...);
 int32_t mpcx_check_launch(mpcx_ctx *ctx, const char *what);
 int32_t mpcx_ensure_pred(mpcx_ctx *ctx, size_t need_doubles);   // prediction scratch (mpcx_interaction.hip)
 int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, double *xbar);   // mpcx_prepare.hip
+int32_t mpcx_traffic_validate(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffic_actor *actors, const double *tape, int64_t tape_rows,
+                              const int32_t *pool_row, int32_t n_obs_pool);                                      // mpcx_traffic.hip
+int32_t mpcx_traffic_enqueue(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffic_actor *actors, double *actor_state, const double *tape,
+                             int64_t tape_rows, const int32_t *pool_row, int32_t n_obs_pool, double *obs6);       // mpcx_traffic.hip
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                      // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

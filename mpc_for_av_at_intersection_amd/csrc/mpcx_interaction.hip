@@ -19,23 +19,35 @@ namespace mpcx {
 
 struct PredArgs {
     mpcx_interaction_params ip;
-    int n;
+    int n, n_pool;   // lanes, rows of the pool
     const double *obs6;
-    double *pred;    // [n][steps][2][2]
+    double *pred;    // [n_pool][steps][2][2]
     // closed loop, local pool: the pool row of agent o is packed here from its state and applied inputs (MovingObstacle*.get():
     // x, y, v, yaw, a, steer) instead of by a launch of its own; nullptr: obs6 is read as it is
     const double *pack_state, *pack_applied;
     double *pack_out;
+    // closed loop with scripted traffic in the pool (MAPPED instantiation only): lane o < n_ego packs agent o into pool row ego_row[o], lane
+    // n_ego + i predicts the row actor_row[i] that traffic_kernel has just written; n = n_ego + n_actors lanes
+    const int32_t *ego_row, *actor_row;
+    int n_ego;
 };
 
 // moving_obstacles_prediction.py:21-28: v is updated BEFORE yaw; disc centres as trajectories.py:11-37
+template <bool MAPPED>
 __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
-    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= a.n) return;
     double x, y, v, yaw, acc, steer;
-    if (a.pack_state) {
-        const double *st = a.pack_state + 4 * (size_t)o;
-        x = st[0]; y = st[1]; v = st[2]; yaw = st[3]; acc = a.pack_applied[2 * o + 1]; steer = a.pack_applied[2 * o];
+    bool pack = a.pack_state != nullptr;
+    int src = o;
+    if constexpr (MAPPED) {
+        pack = o < a.n_ego;
+        o = pack ? a.ego_row[o] : a.actor_row[o - a.n_ego];
+        if (o < 0 || o >= a.n_pool) return;      // (checked by the host; never written outside the pool)
+    }
+    if (pack) {
+        const double *st = a.pack_state + 4 * (size_t)src;
+        x = st[0]; y = st[1]; v = st[2]; yaw = st[3]; acc = a.pack_applied[2 * src + 1]; steer = a.pack_applied[2 * src];
         double *row = a.pack_out + 6 * (size_t)o;
         row[0] = x; row[1] = y; row[2] = v; row[3] = yaw; row[4] = acc; row[5] = steer;
     } else {
@@ -815,9 +827,16 @@ extern "C" int32_t mpcx_interaction_batch(mpcx_ctx *ctx, const mpcx_interaction_
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: pred_steps outside 1..%d or bad dt/L/frame_window", MPCX_PRED_STEPS_MAX);
     if (P == 0) return MPCX_OK;
     { int32_t rc = mpcx_ensure_pred(ctx, (size_t)(n_obs_pool > 0 ? n_obs_pool : 1) * ip->pred_steps * 4); if (rc != MPCX_OK) return rc; }
-    if (n_obs_pool > 0) {
-        mpcx::PredArgs pa{*ip, n_obs_pool, obs6, ctx->pred, ctx->pack_state, ctx->pack_applied, ctx->pack_state ? const_cast<double *>(obs6) : nullptr};
-        hipLaunchKernelGGL(mpcx::predict_kernel, dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
+    if (n_obs_pool > 0 && ctx->pack_state && ctx->pack_ego_row) {
+        // closed loop with scripted traffic: only the rows that hold an agent or an actor are predicted (the others are outside every window)
+        const int lanes = ctx->pack_n_ego + ctx->pack_n_actors;
+        mpcx::PredArgs pa{*ip, lanes, n_obs_pool, obs6, ctx->pred, ctx->pack_state, ctx->pack_applied, const_cast<double *>(obs6),
+                          ctx->pack_ego_row, ctx->pack_actor_row, ctx->pack_n_ego};
+        hipLaunchKernelGGL(mpcx::predict_kernel<true>, dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
+    } else if (n_obs_pool > 0) {
+        mpcx::PredArgs pa{*ip, n_obs_pool, n_obs_pool, obs6, ctx->pred, ctx->pack_state, ctx->pack_applied, ctx->pack_state ? const_cast<double *>(obs6) : nullptr,
+                          nullptr, nullptr, 0};
+        hipLaunchKernelGGL(mpcx::predict_kernel<false>, dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
     }
     // capacity: max_path_len path points (0 = MPCX_MAX_REMAINING; never below 512), rounded up to whole wavefronts; the LDS that
     // holds their cumulative lengths later holds the ego discs of max_rem / 4 - 32 resampled poses and the runs' boxes.

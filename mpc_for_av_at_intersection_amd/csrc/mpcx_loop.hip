@@ -1,5 +1,5 @@
 // mpcx_loop.hip -- the reference's scenario loop body (main/scenarios/mpc_intersection.py:95-159) for P agents as a
-// device-resident pipeline: n_steps x [pool pack -> predict -> conflict search + path cut -> reference window ->
+// device-resident pipeline: n_steps x [scripted traffic rows -> pool pack -> predict -> conflict search + path cut -> reference window ->
 // rollout -> QP -> plant], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
 // host synchronisation or host arithmetic in between.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
@@ -28,6 +28,17 @@ __global__ __launch_bounds__(256) void pack_pool_kernel(PackArgs a) {
 
 }  // namespace mpcx
 
+// the agents' pool rows (device) lie inside the pool
+static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego_row, int32_t pool_rows) {
+    std::vector<int32_t> rows((size_t)P);
+    if (hipMemcpy(rows.data(), ego_row, rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: cannot read ego_row back for its check");
+    for (int32_t q = 0; q < P; q++)
+        if (rows[q] < 0 || rows[q] >= pool_rows)
+            return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: agent %d sits in pool row %d of %d", q, rows[q], pool_rows);
+    return MPCX_OK;
+}
+
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c) {
     const int P = c->P;
     ctx->bins_clean = false;        // until the plant kernel of this step is enqueued
@@ -47,6 +58,15 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     } else {
         // local pool: row q is agent q, and the prediction kernel (inside mpcx_interaction_batch) packs it on its way -- no launch of its own
         ctx->pack_state = c->state; ctx->pack_applied = c->applied;
+        if (c->n_actors > 0) {
+            // scripted traffic (mpc_intersection.py:118-122): the actors' get() rows go into their pool rows and their step() is taken at once --
+            // it shows in the NEXT step's rows, as o.step() at the end of the reference's loop body does (:155-156).  Agent q sits in row ego_row[q].
+            rc = mpcx_traffic_enqueue(ctx, c->n_actors, c->actors, c->actor_state, c->tape, c->tape_rows, c->actor_row, c->pool_rows, c->obs6);
+            if (rc != MPCX_OK) { ctx->pack_state = nullptr; ctx->pack_applied = nullptr; return rc; }
+            ctx->pack_ego_row = c->ego_row; ctx->pack_actor_row = c->actor_row;
+            ctx->pack_n_ego = P; ctx->pack_n_actors = c->n_actors;
+            pool_rows = c->pool_rows;
+        }
     }
     // the conflict search leaves the cut lengths of the previous step in ctx->prev_cut (the queue of the QP kernel puts the agents whose
     // cut moved at the front) and files every agent under its work-queue key (previous iteration count + "the cut moved"): hard problems first.  The window
@@ -62,6 +82,8 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     ctx->inter_near = nullptr;
     ctx->bin_hint = nullptr;
     ctx->pack_state = nullptr; ctx->pack_applied = nullptr;
+    ctx->pack_ego_row = nullptr; ctx->pack_actor_row = nullptr;
+    ctx->pack_n_ego = ctx->pack_n_actors = 0;
     if (rc != MPCX_OK) return rc;
     // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
     // previous pass's speeds (row 2 of its x) and the rollout uses its inputs.  (Where a pass fails the reference crashes in the next
@@ -111,10 +133,23 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
             return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: agent-sharded layout needs obs_local and P = n_inst * agents_local");
         if (use_graph) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: the agent-sharded layout (RCCL exchange) is not captured into a graph");
     }
-    // everything that allocates happens before the first launch (and outside any capture)
-    const size_t pool_rows = (size_t)c->P * (c->exchange == MPCX_SHARD_AGENTS ? (size_t)ctx->comm_world : 1);
+    if (c->n_actors < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: negative number of scripted actors");
+    if (c->n_actors > 0) {
+        if (c->exchange == MPCX_SHARD_AGENTS)
+            return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: scripted traffic is not supported in the agent-sharded layout (it is instance-local: shard by instances)");
+        if (!c->actors || !c->actor_state || !c->actor_row || !c->ego_row || c->tape_rows < 0 || (long)c->pool_rows < (long)c->P + c->n_actors)
+            return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: scripted traffic needs actors, actor_state, actor_row, ego_row and pool_rows >= P + n_actors");
+    }
+    // everything that allocates (or reads back) happens before the first launch (and outside any capture)
+    const size_t pool_rows = c->n_actors > 0 ? (size_t)c->pool_rows : (size_t)c->P * (c->exchange == MPCX_SHARD_AGENTS ? (size_t)ctx->comm_world : 1);
     int32_t rc = mpcx_ensure_pred(ctx, pool_rows * ip->pred_steps * 4);
     if (rc != MPCX_OK) return rc;
+    if (c->n_actors > 0) {
+        rc = mpcx_traffic_validate(ctx, c->n_actors, c->actors, c->tape, c->tape_rows, c->actor_row, c->pool_rows);
+        if (rc != MPCX_OK) return rc;
+        rc = mpcx_loop_check_rows(ctx, c->P, c->ego_row, c->pool_rows);
+        if (rc != MPCX_OK) return rc;
+    }
     rc = mpcx_ensure_ticket(ctx);
     if (rc != MPCX_OK) return rc;
     {

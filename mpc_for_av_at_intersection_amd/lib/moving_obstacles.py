@@ -4,13 +4,16 @@ main/bicycle/main.py:14-41): vehicles that follow a hard-wired steering rule at 
 Each class keeps the reference's constructor, `.step()`, `.get()` -> (x, y, v, yaw, a, steer), the `steering_angle`
 / `forward_velocity` properties and the `model.xc / yc / theta` attributes the scenario scripts read.  `get()` is the
 6-tuple the conflict search consumes (mpcx_interaction_batch's obs6 rows); `tape(n)` returns n consecutive
-get()/step() pairs as an (n, 6) array ready to be uploaded as a device-side traffic table.  Pure host scalar code --
+get()/step() pairs as an (n, 6) array ready to be uploaded as a device-side traffic table (runtime.Traffic.from_tapes: TAPE
+actors of mpcx_traffic_step_batch); `device_spec()` describes the vehicle in its CURRENT state as one actor of that entry point,
+which then steps it on the device (csrc/mpcx_traffic_core.h restates the rules below).  Pure host scalar code --
 one multiply-add per vehicle and step -- with numpy's libm so the poses match the reference bit for bit.
 """
 from typing import Tuple
 
 import numpy as np
 
+from .. import _lib
 from .car_dimensions import BicycleModelDimensions, CarDimensions  # noqa: F401
 
 
@@ -71,6 +74,19 @@ class _ScriptedVehicle:
             self.step()
         return out
 
+    _KIND = None
+
+    def device_spec(self) -> dict:
+        """this vehicle, as it stands now, as one row of the device's actor table: the fields of mpcx_traffic_actor (include/mpcx.h)
+        plus 'state' = (x, y, theta, counter), the actor's mutable part.  An object that has been stepped k times gives the spec the
+        device reaches after k steps from the fresh one."""
+        m = self.model
+        return dict(kind=self._KIND, direction=int(getattr(self, 'direction', 1)), turning=int(getattr(self, 'turning', False) is True),
+                    tape_rows=0, tape_off=0, tape_stride=0, speed=float(self.speed), offset=0.0 if self.offset is None else float(self.offset),
+                    counter_dt=float(self.dt), model_dt=float(m.sample_time), L=float(m.L), x_turn=float(getattr(self, 'x_turn', 0.0)),
+                    arc=float(calculate_steering_angle_for_radius(5)),
+                    state=(float(m.xc), float(m.yc), float(m.theta), float(self.counter)))
+
     def _place_on_main_road(self, direction):
         self.direction = 1 if direction >= 0 else -1
         if self.direction == 1:
@@ -83,6 +99,7 @@ class MovingObstacleTIntersection(_ScriptedVehicle):
     """cross traffic of the (T-)intersection scenarios (moving_obstacles.py:165-231): enters on the main road from the
     left (direction >= 0, lane y = -3) or right (lane y = +3); a turning vehicle steers -0.38 rad (short right turn)
     or +0.19 rad (long left turn) from x_turn on until its heading has swept a quarter turn"""
+    _KIND = _lib.TRAFFIC_TINTERSECTION
 
     def __init__(self, car_dimensions, direction: int, turning: bool, speed: float, offset=None, dt=10e-3):
         self.turning = turning
@@ -101,6 +118,7 @@ class MovingObstacleTIntersection(_ScriptedVehicle):
 
 class MovingObstacleArterial(_ScriptedVehicle):
     """vehicle driving straight up (+y) from (x_init, y_init) (moving_obstacles.py:128-163)"""
+    _KIND = _lib.TRAFFIC_ARTERIAL
 
     def __init__(self, car_dimensions, x_init: float, y_init: float, speed: float, offset=None, dt=10e-3):
         self._init_common(car_dimensions, speed, offset, dt, dt)
@@ -116,6 +134,7 @@ class MovingObstacleRoundabout(_ScriptedVehicle):
     start-delay counter always uses 0.2 s whatever `dt` drives the plant (:45), and reading `steering_angle` may SNAP the
     heading to -pi / 0 once the vehicle has come around (:81-83, :103-105) -- get() and step() both read it, as in the
     reference"""
+    _KIND = _lib.TRAFFIC_ROUNDABOUT
 
     def __init__(self, car_dimensions, direction: int, turning: bool, speed: float, offset=None, dt=10e-3, start_pos=2, end_pos=4):
         self.turning = turning

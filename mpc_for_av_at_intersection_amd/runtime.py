@@ -201,6 +201,103 @@ def path_plan(table: np.ndarray, cs: np.ndarray, offs, dt: float, max_speed: flo
     return dict(cnt=cnt, disc=disc, box=box, path_disc=path_disc, cap=cap, steps=int(pred_steps), dl=dl, radius=float(radius))
 
 
+def traffic_pool_layout(B: int, A: int, k_of_instance, a_lo: int = 0, a_total: Optional[int] = None) -> dict:
+    """The obstacle pool of a batch of B instances x A agents with k_of_instance[b] scripted actors in instance b: every instance owns
+    stride = a_total + max(K) consecutive rows, [its agents | its actors | unused], so that the window of each of its agents --
+    obs_off = b * stride, obs_cnt = a_total + K_b, obs_skip = the agent's own row -- stays ONE contiguous run (what
+    mpcx_interaction_batch takes).  Returns int32 arrays obs_off / obs_cnt / obs_skip / ego_row (per agent, (instance, agent) order),
+    actor_row (per actor, (instance, actor) order) + stride, pool_rows.  Raises ValueError where an agent would see more than
+    MPCX_MAX_OBS moving obstacles.  (a_lo, a_total: the agent-sharded layout's part of the agents; without traffic only.)"""
+    k = np.asarray(k_of_instance, dtype=np.int64).reshape(-1)
+    a_total = A if a_total is None else int(a_total)
+    if len(k) != B or (k < 0).any():
+        raise ValueError('traffic: one non-negative actor count per instance expected, got %d for %d instances' % (len(k), B))
+    kmax = int(k.max()) if B else 0
+    if B and a_total - 1 + kmax > _lib.MAX_OBS:
+        raise ValueError('an agent would see %d other agents + %d scripted actors: more than MPCX_MAX_OBS = %d moving obstacles'
+                         % (a_total - 1, kmax, _lib.MAX_OBS))
+    stride = a_total + kmax
+    inst = np.repeat(np.arange(B), A)
+    agent = np.tile(np.arange(A), B) + a_lo
+    ego_row = inst * stride + agent
+    actor_inst = np.repeat(np.arange(B), k)
+    actor_k = np.arange(int(k.sum())) - np.repeat(np.cumsum(k) - k, k)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return dict(stride=stride, pool_rows=B * stride, obs_off=i32(inst * stride), obs_cnt=i32(a_total + k[inst]), obs_skip=i32(ego_row),
+                ego_row=i32(ego_row), actor_row=i32(actor_inst * stride + a_total + actor_k))
+
+
+class Traffic:
+    """Scripted traffic of a batch (host side): the actor table (records of _lib.TRAFFIC_ACTOR_DTYPE = mpcx_traffic_actor, ordered by
+    instance, then actor), the actors' start states (n, 4: x, y, theta, counter / cursor), how many actors each instance has, and the
+    uploaded table TAPE actors read.  batch.IntersectionBatch(traffic=...) uploads it and steps it on the device."""
+
+    def __init__(self, actors: np.ndarray, state: np.ndarray, k_of_instance, tape: Optional[np.ndarray] = None):
+        self.actors = np.ascontiguousarray(actors, dtype=_lib.TRAFFIC_ACTOR_DTYPE).reshape(-1)
+        self.state = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, 4)
+        self.k_of_instance = np.asarray(k_of_instance, dtype=np.int64).reshape(-1)
+        self.tape = None if tape is None else np.ascontiguousarray(tape, dtype=np.float64).reshape(-1, 6)
+        if len(self.actors) != len(self.state) or int(self.k_of_instance.sum()) != len(self.actors):
+            raise ValueError('traffic: %d actors, %d states, %d actors counted over the instances'
+                             % (len(self.actors), len(self.state), int(self.k_of_instance.sum())))
+
+    @property
+    def n_actors(self) -> int:
+        return len(self.actors)
+
+    @classmethod
+    def empty(cls, B: int) -> 'Traffic':
+        return cls(np.zeros(0, _lib.TRAFFIC_ACTOR_DTYPE), np.zeros((0, 4)), np.zeros(B, np.int64))
+
+    @classmethod
+    def from_specs(cls, specs_of_instance) -> 'Traffic':
+        """specs_of_instance: per instance a list of `device_spec()` dicts (lib/moving_obstacles.py)"""
+        flat = [s for inst in specs_of_instance for s in inst]
+        actors = np.zeros(len(flat), _lib.TRAFFIC_ACTOR_DTYPE)
+        for name in _lib.TRAFFIC_ACTOR_DTYPE.names:
+            actors[name] = [s[name] for s in flat]
+        state = np.array([s['state'] for s in flat], dtype=np.float64).reshape(-1, 4)
+        return cls(actors, state, [len(inst) for inst in specs_of_instance])
+
+    @classmethod
+    def from_objects(cls, vehicles_of_instance) -> 'Traffic':
+        """per instance a list of scripted vehicles (lib.moving_obstacles.MovingObstacle*), taken in their CURRENT state"""
+        return cls.from_specs([[o.device_spec() for o in inst] for inst in vehicles_of_instance])
+
+    @classmethod
+    def from_tapes(cls, tapes, track_of_instance) -> 'Traffic':
+        """TAPE actors: tapes = list of (n_t, K_t, 6) arrays (track t: n_t steps of K_t vehicles, rows as get() returns them -- e.g.
+        np.stack([o.tape(n) for o in vehicles], axis=1) or recorded traffic); instance b replays track track_of_instance[b] with one actor
+        per vehicle, from row 0, holding the last row once the track has ended.  Tracks are uploaded once, whatever the number of
+        instances that play them."""
+        tapes = [np.ascontiguousarray(t, dtype=np.float64) for t in tapes]
+        for t in tapes:
+            if t.ndim != 3 or t.shape[2] != 6 or t.shape[0] < 1:
+                raise ValueError('traffic: a tape track has shape (steps >= 1, vehicles, 6), got %s' % (t.shape,))
+        off = np.cumsum([0] + [t.shape[0] * t.shape[1] for t in tapes])
+        track = np.asarray(track_of_instance, dtype=np.int64).reshape(-1)
+        k = np.array([tapes[t].shape[1] for t in track], dtype=np.int64)
+        actors = np.zeros(int(k.sum()), _lib.TRAFFIC_ACTOR_DTYPE)
+        which = np.repeat(track, k)
+        lane = np.arange(len(actors)) - np.repeat(np.cumsum(k) - k, k)
+        actors['kind'] = _lib.TRAFFIC_TAPE
+        actors['direction'] = 1
+        actors['tape_rows'] = [tapes[t].shape[0] for t in which]
+        actors['tape_off'] = off[which] + lane
+        actors['tape_stride'] = [tapes[t].shape[1] for t in which]
+        table = np.concatenate([t.reshape(-1, 6) for t in tapes]) if tapes else np.zeros((0, 6))
+        state = np.zeros((len(actors), 4))
+        if len(actors):
+            state[:, :3] = table[actors['tape_off']][:, [0, 1, 3]]
+        return cls(actors, state, k, tape=table)
+
+    def slice(self, lo: int, hi: int) -> 'Traffic':
+        """the traffic of instances lo .. hi-1 (instance-sharded runs)"""
+        first = np.concatenate([[0], np.cumsum(self.k_of_instance)])
+        a, b = int(first[lo]), int(first[hi])
+        return Traffic(self.actors[a:b], self.state[a:b], self.k_of_instance[lo:hi], tape=self.tape)
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -486,6 +583,20 @@ class Context:
         out = torch.empty((n, steps, 3), dtype=torch.float64, device=self.device)
         self._chk(self.lib.mpcx_predict_obstacles_batch(self._ctx, n, int(steps), C.c_double(dt), C.c_double(L), _ptr(obs6), _ptr(out)))
         return out
+
+    @_ordered
+    def traffic_step(self, actors, actor_state, pool_row, obs6, tape=None):
+        """mpcx_traffic_step_batch: every scripted actor writes its get() row (x, y, v, yaw, a, steer) into row pool_row[i] of obs6 and
+        takes its step().  actors: uint8 device tensor holding n records of _lib.TRAFFIC_ACTOR_DTYPE; actor_state (n, 4) float64, updated in
+        place; tape (rows, 6) float64 or None."""
+        n = int(actor_state.shape[0])
+        self._want(actors, torch.uint8, (n * _lib.TRAFFIC_ACTOR_DTYPE.itemsize,), 'actors')
+        self._want(actor_state, torch.float64, (n, 4), 'actor_state'); self._want(pool_row, torch.int32, (n,), 'pool_row')
+        self._want(obs6, torch.float64, (obs6.shape[0], 6), 'obs6')
+        if tape is not None:
+            self._want(tape, torch.float64, (tape.shape[0], 6), 'tape')
+        self._chk(self.lib.mpcx_traffic_step_batch(self._ctx, n, _ptr(actors), _ptr(actor_state), _ptr(tape), 0 if tape is None else int(tape.shape[0]),
+                                                   _ptr(pool_row), int(obs6.shape[0]), _ptr(obs6)))
 
     @_ordered
     def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False):
