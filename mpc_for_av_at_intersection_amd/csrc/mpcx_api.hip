@@ -2,7 +2,6 @@
 #include "mpcx_common.h"
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
 #include <new>
 
 int32_t mpcx_fail(mpcx_ctx *ctx, int32_t code, const char *fmt, ...) {
@@ -21,6 +20,15 @@ int32_t mpcx_check_launch(mpcx_ctx *ctx, const char *what) {
     return MPCX_OK;
 }
 
+int32_t mpcx_grow(mpcx_ctx *ctx, void **p, size_t *cap_bytes, size_t need_bytes, const char *what) {
+    if (need_bytes <= *cap_bytes) return MPCX_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap_bytes = 0;
+    if (hipMalloc(p, need_bytes) != hipSuccess) return mpcx_fail(ctx, MPCX_E_LAUNCH, "cannot allocate %zu bytes for %s", need_bytes, what);
+    *cap_bytes = need_bytes;
+    return MPCX_OK;
+}
+
 extern "C" {
 
 const char *mpcx_version(void) { return "mpcx 0.1 (gfx950)"; }
@@ -33,29 +41,8 @@ mpcx_ctx *mpcx_create(int32_t device, void *hip_stream) {
     if (!c) return nullptr;
     c->device = device;
     c->stream = (hipStream_t)hip_stream;
-    c->have_mpc = false;
-    c->pred = nullptr;
-    c->ticket = nullptr;
-    {
-        hipDeviceProp_t prop;
-        c->n_cu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    c->pred_cap = 0;
-    c->loop_exec = nullptr;
-    c->prof_qp = false;
-    c->qp_solver = 0;
-    c->multi = nullptr;
-    c->multi_cap = 0;
-    c->order_hint = nullptr;
-    c->order_now = c->order_prev = nullptr;
-    c->prev_cut = nullptr;
-    c->prev_cut_cap = 0;
-    c->order = nullptr;
-    c->order_cap = 0;
-    c->tune = nullptr;
-    c->tune_rows = 0;
-    memset(c->loop_key, 0, sizeof c->loop_key);
-    c->err[0] = 0;
+    hipDeviceProp_t prop;
+    c->n_cu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { mpcx_destroy(c); return nullptr; }

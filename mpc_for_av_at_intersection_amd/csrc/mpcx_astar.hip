@@ -439,12 +439,9 @@ extern "C" int32_t mpcx_astar_batch(mpcx_ctx *ctx, int32_t n_search, const mpcx_
     }
     if (max_obst_rows > 1024) return mpcx_fail(ctx, MPCX_E_INVALID, "astar_batch: %d half-plane rows exceed the 1024 the obstacle-distance term stages in LDS", max_obst_rows);
     const size_t need = host.size() * sizeof(mpcx::AstarArgs);
-    if (need > ctx->multi_cap) {
-        if (ctx->multi) (void)hipFree(ctx->multi);
-        ctx->multi = nullptr; ctx->multi_cap = 0;
-        if (hipMalloc((void **)&ctx->multi, need * 2) != hipSuccess) return mpcx_fail(ctx, MPCX_E_LAUNCH, "astar_batch: cannot allocate %zu bytes", need * 2);
-        ctx->multi_cap = need * 2;
-    }
+    // (a buffer that has to grow grows to twice the need)
+    int32_t rc = mpcx_grow(ctx, &ctx->multi, &ctx->multi_cap, need > ctx->multi_cap ? need * 2 : need, "the search descriptors of astar_batch");
+    if (rc != MPCX_OK) return rc;
     if (hipMemcpyAsync(ctx->multi, host.data(), need, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess)      // `host` goes out of scope
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "astar_batch: descriptor upload failed");

@@ -80,14 +80,10 @@ extern "C" int32_t mpcx_allgather_states(mpcx_ctx *ctx, int32_t layout, int32_t 
     }
     double *dst = all;
     if (layout == MPCX_SHARD_AGENTS && world > 1 && agents_local != 0) {
-        const size_t need = rows * 6 * world;
-        if (need > ctx->xchg_cap) {
-            if (ctx->xchg) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->xchg); }
-            ctx->xchg = nullptr; ctx->xchg_cap = 0;
-            if (hipMalloc((void **)&ctx->xchg, need * sizeof(double)) != hipSuccess)
-                return mpcx_fail(ctx, MPCX_E_LAUNCH, "allgather_states: cannot allocate %zu bytes", need * sizeof(double));
-            ctx->xchg_cap = need;
-        }
+        const size_t need = rows * 6 * world * sizeof(double);
+        if (ctx->xchg && need > ctx->xchg_cap) (void)hipStreamSynchronize(ctx->stream);     // before the buffer in use is freed
+        const int32_t rc = mpcx_grow(ctx, (void **)&ctx->xchg, &ctx->xchg_cap, need, "the all-gather landing buffer");
+        if (rc != MPCX_OK) return rc;
         dst = ctx->xchg;
     }
     const ncclResult_t r = ncclAllGather(local, dst, rows * 6, ncclDouble, (ncclComm_t)ctx->comm, ctx->stream);

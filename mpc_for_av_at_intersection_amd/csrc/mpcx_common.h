@@ -7,69 +7,97 @@
 #include <vector>
 
 struct mpcx_ctx {
-    int device;
-    hipStream_t stream;
-    mpcx_mpc_params mpc;
-    bool have_mpc;
-    int32_t *ticket;     // device words: [0] work-queue head of the persistent QP kernel, [4] the list of problems the condensed solver gives up on, [5] the head of the launch that works that list off; 8 allocated
-    int n_cu;            // compute units of the device
-    double *pred;        // scratch: predicted obstacle disc centres [NOBS][steps][2 discs][2]
-    size_t pred_cap;     // capacity of pred in doubles
-    hipGraphExec_t loop_exec;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[768]; // descriptor + parameters the cached graph was captured for
-    const mpcx_qp_tuning *tune; // per-instance tuning rows (device) or nullptr
-    int32_t tune_rows;
-    const int32_t *order_hint;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
-    const int32_t *order_now, *order_prev;   // optional pair: entries that differ mark a discontinuous change of the reference
-    int32_t *prev_cut;          // scratch of mpcx_closed_loop_run: cut lengths of the previous step
-    size_t prev_cut_cap;
-    int32_t *order;             // scratch: work-queue order built from the hint | per-block key histograms | list of given-up problems | 2 counters
-    size_t order_cap;
-    bool order_ready = false;   // mpcx_closed_loop_run: the order of this step's first solve is in `order` already and the ticket is zero
+    int device = 0;
+    hipStream_t stream = nullptr;
+    mpcx_mpc_params mpc = {};
+    bool have_mpc = false;
+    int32_t *ticket = nullptr;  // device words: [0] work-queue head of the persistent QP kernel, [4] the list of problems the condensed solver gives up on, [5] the head of the launch that works that list off; 8 allocated
+    int n_cu = 0;               // compute units of the device
+    // device scratch that grows on demand (mpcx_grow); every capacity is in bytes
+    double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
+    size_t pred_cap = 0;
+    hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
+    unsigned char loop_key[768] = {};     // descriptor + parameters the cached graph was captured for
+    const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
+    int32_t tune_rows = 0;
+    const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
+    const int32_t *order_now = nullptr, *order_prev = nullptr;   // optional pair: entries that differ mark a discontinuous change of the reference
+    // scratch of mpcx_closed_loop_run for P agents: [P] cut lengths of the previous step | [3 P] what the conflict search's nearest-index
+    // scan found, for the window selection (mpcx_window_extras::near)
+    int32_t *prev_cut = nullptr;
+    size_t prev_cut_cap = 0;
+    int32_t *order = nullptr;   // scratch: work-queue order built from the hint | per-block key histograms | list of given-up problems | 2 counters
+    size_t order_cap = 0;
     // closed loop: the counting sort of the work queue rides in the kernels of the step instead of two launches and two fills of its own.
     // The conflict search files every agent under its queue key (bins[key]++ -> slot), the window selection turns (key, slot) into the
     // agent's place in `order`, the plant kernel zeroes the bins and the ticket for the next step.
     int32_t *bins = nullptr;    // [MPCX_ORDER_COPIES][MPCX_ORDER_BINS] counters (agent p counts in copy p % COPIES: 32 k atomics on 64 words are slow) | [P] (key << 24 | slot)
     size_t bins_cap = 0;
     bool bins_clean = false;    // host's knowledge: the counters and the ticket are zero (the last closed-loop step ran through and nothing has drawn tickets since)
-    const int32_t *bin_hint = nullptr;    // set around the conflict search: iteration counts of the previous step (queue key)
-    bool bin_scatter = false;             // set around the window selection: write `order`
-    bool bin_reset = false;               // set around the plant step: zero bins and ticket
-    const double *pack_state = nullptr, *pack_applied = nullptr;   // mpcx_closed_loop_run, local pool: the prediction kernel packs the pool rows itself
-    // ... with scripted traffic in the pool: agent q is packed into row pack_ego_row[q], and the pack_n_actors rows pack_actor_row[] (written by
-    // traffic_kernel just before) are predicted as they stand; nullptr: row q is agent q
-    const int32_t *pack_ego_row = nullptr, *pack_actor_row = nullptr;
-    int32_t pack_n_ego = 0, pack_n_actors = 0;
-    int32_t *inter_prev_save = nullptr;   // mpcx_closed_loop_run: where the conflict search leaves the cut lengths it read (the queue order's `moved` test)
-    // mpcx_closed_loop_run: the conflict search and the window selection both run calc_nearest_index_in_direction for the same agent, state
-    // and path, mostly from the same start index.  The conflict search leaves (its start index, the largest of its three nearest indices
-    // or -1) per agent here (behind prev_cut), and the window selection takes the conflict search's answer where that is provably its own.
-    int32_t *inter_near = nullptr;        // set around the conflict search (2 ints per agent) ...
-    const int32_t *window_near = nullptr, *window_tidx = nullptr;   // ... and around the window selection (+ the conflict search's updated traj_idx)
     hipStream_t side = nullptr; // side stream of mpcx_mpc_prepare_batch: the warm-start rollout runs beside the window selection (fork / join by events)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool rollout_forked = false; // mpcx_closed_loop_run has the rollout of this step in flight on the side stream (mpcx_rollout_fork)
     double *cs = nullptr;       // scratch of mpcx_expand_batch: (cos, sin) of the nodes' headings
     size_t cs_cap = 0;
-    void *multi;                // scratch of mpcx_expand_multi_batch (segment descriptors + block tables)
-    size_t multi_cap;
-    int qp_solver;              // 0 = automatic, 1 = condensed (one wavefront per QP), 2 = stage-structured (mpcx_set_qp_solver)
+    void *multi = nullptr;      // scratch of mpcx_expand_multi_batch and mpcx_astar_batch (segment descriptors + block tables)
+    size_t multi_cap = 0;
+    int qp_solver = 0;          // 0 = automatic, 1 = condensed (one wavefront per QP), 2 = stage-structured (mpcx_set_qp_solver)
     int lin_passes = 1;         // linearisation passes per step of mpcx_closed_loop_run (lib/mpc.py MAX_ITER; mpcx_set_linearisation_passes)
-    bool prof_qp;               // bracket qp_kernel launches with events (mpcx_profile_qp)
+    bool prof_qp = false;       // bracket qp_kernel launches with events (mpcx_profile_qp)
     std::vector<hipEvent_t> prof_ev;   // start/stop pairs recorded so far
     std::vector<hipEvent_t> prof_free; // recycled events
     unsigned long long *stats = nullptr;    // run statistics of mpcx_closed_loop_run: per wavefront of the plant kernel (agent-steps, iterations, failures, max iterations)
     size_t stats_slots = 0;                 // wavefront slots allocated
-    const int32_t *stats_iters = nullptr;   // set by mpcx_closed_loop_run around its plant step
     void *comm = nullptr;       // ncclComm_t (mpcx_comm_init) or nullptr = single rank
     int comm_world = 1, comm_rank = 0;
     double *xchg = nullptr;     // all-gather landing buffer of the agent-sharded layout
     size_t xchg_cap = 0;
-    char err[256];
+    char err[256] = {};
 };
+
+// The stages of a step.  Each is the whole of the C entry point of the same name (checks included) plus one struct of what only
+// mpcx_closed_loop_run passes: default-constructed = the stand-alone call.
+struct mpcx_interaction_extras {
+    // local pool: the prediction kernel packs the pool rows from the agents' states and applied inputs itself (no launch of its own)
+    const double *pack_state = nullptr, *pack_applied = nullptr;
+    // ... with scripted traffic in the pool: agent q is packed into row ego_row[q], and the n_actors rows actor_row[] (written by
+    // traffic_kernel just before) are predicted as they stand; nullptr: row q is agent q
+    const int32_t *ego_row = nullptr, *actor_row = nullptr;
+    int32_t n_ego = 0, n_actors = 0;
+    int32_t *prev_save = nullptr;       // where the cut lengths as read are left (the queue order's `moved` test)
+    // the conflict search and the window selection both run calc_nearest_index_in_direction for the same agent, state and path, mostly
+    // from the same start index.  The conflict search leaves (its start index, the largest, the smallest of its three nearest indices
+    // or -1) here, 3 ints per agent, and the window selection takes the conflict search's answer where that is provably its own.
+    int32_t *near = nullptr;
+    const int32_t *bin_hint = nullptr;  // iteration counts of the previous step: every agent is filed in ctx->bins under its queue key
+};
+struct mpcx_window_extras {
+    bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
+    const int32_t *near = nullptr, *tidx = nullptr;   // mpcx_interaction_extras::near and the conflict search's updated traj_idx
+    bool rollout_forked = false;        // the rollout of this step is in flight on the side stream already (mpcx_rollout_fork)
+};
+struct mpcx_qp_order {                  // where the work-queue order of a solve comes from
+    bool ready = false;                 // it is in ctx->order already and the ticket is zero (mpcx_window_extras::scatter)
+    const int32_t *hint = nullptr, *now = nullptr, *prev = nullptr;   // else built from these as mpcx_qp_set_order_hint describes; all nullptr: no order
+};
+struct mpcx_plant_extras {
+    const int32_t *stats_iters = nullptr;   // the step's iteration counts: the step feeds the run statistics (ctx->stats)
+    bool reset_bins = false;                // zero the queue bins and the ticket for the next step
+};
+int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const double *path_xyyaw,
+                               const double *path_cs, const int32_t *path_off, const int32_t *path_len, const int32_t *prev_cut_len,
+                               int32_t n_obs_pool, const double *obs6, const int32_t *obs_off, const int32_t *obs_cnt, const int32_t *obs_skip,
+                               int32_t *traj_idx, int32_t *hit_idx, double *hit_xy, int32_t *cut_len, const mpcx_interaction_extras &x);   // mpcx_interaction.hip
+int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, const double *path_xyyaw, const double *path_v,
+                          const int32_t *path_off, const int32_t *path_len, double dl, int32_t *target_ind, const double *ov, int64_t ov_stride,
+                          double *xref, uint8_t *reaches_end, double *xbar, const mpcx_window_extras &x);                                   // mpcx_prepare.hip
+int32_t mpcx_qp_enqueue(mpcx_ctx *ctx, int32_t B, const double *x0, const double *xref, const double *xbar, const uint8_t *reaches_end,
+                      const double *u_warm, double *x_out, double *u_out, int32_t *status, int32_t *iters, double *kkt, const mpcx_qp_order &ord);   // mpcx_qp.hip
+int32_t mpcx_plant_enqueue(mpcx_ctx *ctx, int32_t B, double *state, double *u, const int32_t *status, double *applied, const mpcx_plant_extras &x);   // mpcx_prepare.hip
 
 int32_t mpcx_fail(mpcx_ctx *ctx, int32_t code, const char *fmt, ...);
 int32_t mpcx_check_launch(mpcx_ctx *ctx, const char *what);
+// grow-on-demand device scratch: *p holds at least need_bytes afterwards (contents are not kept); `what` names it in the error text (mpcx_api.hip)
+int32_t mpcx_grow(mpcx_ctx *ctx, void **p, size_t *cap_bytes, size_t need_bytes, const char *what);
 int32_t mpcx_ensure_pred(mpcx_ctx *ctx, size_t need_doubles);   // prediction scratch (mpcx_interaction.hip)
 int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, double *xbar);   // mpcx_prepare.hip
 int32_t mpcx_traffic_validate(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffic_actor *actors, const double *tape, int64_t tape_rows,
@@ -91,7 +119,8 @@ __device__ __forceinline__ int order_key_of(int hint, bool moved) {
 }
 }
 int32_t mpcx_ensure_order(mpcx_ctx *ctx, size_t B);             // work-queue order scratch (mpcx_qp.hip)
-int32_t mpcx_qp_build_order(mpcx_ctx *ctx, int32_t B, hipStream_t st);   // counting sort of the work queue on stream st; also zeroes the ticket (mpcx_qp.hip)
+// counting sort of the work queue on stream st from (hint, now, prev) into ctx->order; also zeroes the ticket (mpcx_qp.hip)
+int32_t mpcx_qp_build_order(mpcx_ctx *ctx, int32_t B, const int32_t *hint, const int32_t *now, const int32_t *prev, hipStream_t st);
 
 namespace mpcx {
 

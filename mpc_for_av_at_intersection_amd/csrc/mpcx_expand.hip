@@ -177,12 +177,9 @@ extern "C" int32_t mpcx_expand_multi_batch(mpcx_ctx *ctx, int32_t n_seg, const m
     // one upload: [segment descriptors | block -> segment | first block of each segment]
     const size_t b0 = segs.size() * sizeof(mpcx::ExpandArgs), b1 = blk_seg.size() * sizeof(int32_t), b2 = blk_first.size() * sizeof(int32_t);
     const size_t need = b0 + b1 + b2;
-    if (need > ctx->multi_cap) {
-        if (ctx->multi) (void)hipFree(ctx->multi);
-        ctx->multi = nullptr; ctx->multi_cap = 0;
-        if (hipMalloc((void **)&ctx->multi, need * 2) != hipSuccess) return mpcx_fail(ctx, MPCX_E_LAUNCH, "expand_multi_batch: cannot allocate %zu bytes", need * 2);
-        ctx->multi_cap = need * 2;
-    }
+    // (a buffer that has to grow grows to twice the need)
+    int32_t rc = mpcx_grow(ctx, &ctx->multi, &ctx->multi_cap, need > ctx->multi_cap ? need * 2 : need, "the segment descriptors of expand_multi_batch");
+    if (rc != MPCX_OK) return rc;
     std::vector<unsigned char> host(need);
     memcpy(host.data(), segs.data(), b0); memcpy(host.data() + b0, blk_seg.data(), b1); memcpy(host.data() + b0 + b1, blk_first.data(), b2);
     if (hipMemcpyAsync(ctx->multi, host.data(), need, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
@@ -210,13 +207,8 @@ extern "C" int32_t mpcx_expand_batch(mpcx_ctx *ctx, const mpcx_search_model *m, 
         return mpcx_fail(ctx, MPCX_E_INVALID, "expand_batch: null pointer or negative node count");
     if (n_nodes == 0) return MPCX_OK;
     if (!nodes_cs && n_nodes >= 4096) {        // bulk expansion with device trigonometry: one sincos per node in front of the records
-        const size_t need = (size_t)n_nodes * 2 * sizeof(double);
-        if (need > ctx->cs_cap) {
-            if (ctx->cs) (void)hipFree(ctx->cs);
-            ctx->cs = nullptr; ctx->cs_cap = 0;
-            if (hipMalloc((void **)&ctx->cs, need) != hipSuccess) return mpcx_fail(ctx, MPCX_E_LAUNCH, "expand_batch: cannot allocate %zu bytes", need);
-            ctx->cs_cap = need;
-        }
+        int32_t rc = mpcx_grow(ctx, (void **)&ctx->cs, &ctx->cs_cap, (size_t)n_nodes * 2 * sizeof(double), "the node headings of expand_batch");
+        if (rc != MPCX_OK) return rc;
         hipLaunchKernelGGL(mpcx::node_cs_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, ctx->stream, n_nodes, nodes, ctx->cs);
         nodes_cs = ctx->cs;
     }

@@ -818,6 +818,14 @@ extern "C" int32_t mpcx_interaction_batch(mpcx_ctx *ctx, const mpcx_interaction_
                                           int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
                                           const int32_t *obs_cnt, const int32_t *obs_skip,
                                           int32_t *traj_idx, int32_t *hit_idx, double *hit_xy, int32_t *cut_len) {
+    return mpcx_interaction_enqueue(ctx, ip, P, state, path_xyyaw, path_cs, path_off, path_len, prev_cut_len, n_obs_pool, obs6, obs_off,
+                                    obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, {});
+}
+
+int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const double *path_xyyaw,
+                                 const double *path_cs, const int32_t *path_off, const int32_t *path_len, const int32_t *prev_cut_len,
+                                 int32_t n_obs_pool, const double *obs6, const int32_t *obs_off, const int32_t *obs_cnt, const int32_t *obs_skip,
+                                 int32_t *traj_idx, int32_t *hit_idx, double *hit_xy, int32_t *cut_len, const mpcx_interaction_extras &x) {
     if (!ctx) return MPCX_E_INVALID;
     if (P == 0) return MPCX_OK;
     if (!ip || P < 0 || n_obs_pool < 0 || !state || !path_xyyaw || !path_cs || !path_off || !path_len || !obs_off ||
@@ -825,16 +833,15 @@ extern "C" int32_t mpcx_interaction_batch(mpcx_ctx *ctx, const mpcx_interaction_
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: null pointer or negative size");
     if (ip->pred_steps < 1 || ip->pred_steps > MPCX_PRED_STEPS_MAX || ip->frame_window < 0 || !(ip->dt > 0) || !(ip->L > 0))
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: pred_steps outside 1..%d or bad dt/L/frame_window", MPCX_PRED_STEPS_MAX);
-    if (P == 0) return MPCX_OK;
     { int32_t rc = mpcx_ensure_pred(ctx, (size_t)(n_obs_pool > 0 ? n_obs_pool : 1) * ip->pred_steps * 4); if (rc != MPCX_OK) return rc; }
-    if (n_obs_pool > 0 && ctx->pack_state && ctx->pack_ego_row) {
+    if (n_obs_pool > 0 && x.pack_state && x.ego_row) {
         // closed loop with scripted traffic: only the rows that hold an agent or an actor are predicted (the others are outside every window)
-        const int lanes = ctx->pack_n_ego + ctx->pack_n_actors;
-        mpcx::PredArgs pa{*ip, lanes, n_obs_pool, obs6, ctx->pred, ctx->pack_state, ctx->pack_applied, const_cast<double *>(obs6),
-                          ctx->pack_ego_row, ctx->pack_actor_row, ctx->pack_n_ego};
+        const int lanes = x.n_ego + x.n_actors;
+        mpcx::PredArgs pa{*ip, lanes, n_obs_pool, obs6, ctx->pred, x.pack_state, x.pack_applied, const_cast<double *>(obs6),
+                          x.ego_row, x.actor_row, x.n_ego};
         hipLaunchKernelGGL(mpcx::predict_kernel<true>, dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
     } else if (n_obs_pool > 0) {
-        mpcx::PredArgs pa{*ip, n_obs_pool, n_obs_pool, obs6, ctx->pred, ctx->pack_state, ctx->pack_applied, ctx->pack_state ? const_cast<double *>(obs6) : nullptr,
+        mpcx::PredArgs pa{*ip, n_obs_pool, n_obs_pool, obs6, ctx->pred, x.pack_state, x.pack_applied, x.pack_state ? const_cast<double *>(obs6) : nullptr,
                           nullptr, nullptr, 0};
         hipLaunchKernelGGL(mpcx::predict_kernel<false>, dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
     }
@@ -850,21 +857,15 @@ extern "C" int32_t mpcx_interaction_batch(mpcx_ctx *ctx, const mpcx_interaction_
     const int fcap = max_rem / 4 - mpcx::QCAP * 2 / 32;
     const size_t lds = (size_t)max_rem * sizeof(double) + ((size_t)fcap * sizeof(unsigned short) + 7) / 8 * 8;
     mpcx::InterArgs ia{*ip, P, state, path_xyyaw, path_cs, path_off, path_len, prev_cut_len, ctx->pred,
-                       obs_off, obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, max_rem, fcap, ctx->inter_prev_save,
-                       ctx->bin_hint, ctx->bin_hint ? ctx->bins : nullptr, ctx->bin_hint ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr,
-                       ctx->inter_near};
+                       obs_off, obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, max_rem, fcap, x.prev_save,
+                       x.bin_hint, x.bin_hint ? ctx->bins : nullptr, x.bin_hint ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr,
+                       x.near};
     hipLaunchKernelGGL(mpcx::interaction_kernel, dim3(P), dim3(64), lds, ctx->stream, ia);
     return mpcx_check_launch(ctx, "interaction kernels");
 }
 
 int32_t mpcx_ensure_pred(mpcx_ctx *ctx, size_t need) {
-    if (need <= ctx->pred_cap) return MPCX_OK;
-    if (ctx->pred) (void)hipFree(ctx->pred);
-    ctx->pred = nullptr; ctx->pred_cap = 0;
-    if (hipMalloc((void **)&ctx->pred, need * sizeof(double)) != hipSuccess)
-        return mpcx_fail(ctx, MPCX_E_LAUNCH, "cannot allocate %zu bytes of prediction scratch", need * sizeof(double));
-    ctx->pred_cap = need;
-    return MPCX_OK;
+    return mpcx_grow(ctx, (void **)&ctx->pred, &ctx->pred_cap, need * sizeof(double), "the prediction scratch");
 }
 
 extern "C" int32_t mpcx_moving_collision_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P,
@@ -881,7 +882,6 @@ extern "C" int32_t mpcx_moving_collision_batch(mpcx_ctx *ctx, const mpcx_interac
         return mpcx_fail(ctx, MPCX_E_INVALID, "moving_collision_batch: null pointer or negative size");
     if (ip->pred_steps < 1 || ip->pred_steps > MPCX_PRED_STEPS_MAX || ip->frame_window < 0)
         return mpcx_fail(ctx, MPCX_E_INVALID, "moving_collision_batch: pred_steps outside 1..%d or negative frame_window", MPCX_PRED_STEPS_MAX);
-    if (P == 0) return MPCX_OK;
     const size_t nposes = (size_t)n_obs_pool * ip->pred_steps;
     int32_t rc = mpcx_ensure_pred(ctx, (nposes ? nposes : 1) * 4);
     if (rc != MPCX_OK) return rc;

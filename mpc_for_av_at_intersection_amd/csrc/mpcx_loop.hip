@@ -39,6 +39,9 @@ static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego
     return MPCX_OK;
 }
 
+// the second part of ctx->prev_cut: 3 ints per agent that the conflict search leaves for the window selection (mpcx_interaction_extras::near)
+static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cut + P; }
+
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c) {
     const int P = c->P;
     ctx->bins_clean = false;        // until the plant kernel of this step is enqueued
@@ -47,7 +50,14 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     // the prediction and the conflict search (a chain of T dependent sincos / tan per agent, 35-45 us) and is joined by the window selection
     rc = mpcx_rollout_fork(ctx, P, c->state, c->u_sol, c->xbar);
     if (rc != MPCX_OK) return rc;
-    ctx->rollout_forked = true;
+    // the conflict search leaves the cut lengths of the previous step in ctx->prev_cut (the queue of the QP kernel puts the agents whose
+    // cut moved at the front) and files every agent under its work-queue key (previous iteration count + "the cut moved"): hard problems first.  The window
+    // selection then writes the queue order and the plant kernel resets bins and ticket, so the counting sort costs no launch of its own.
+    const bool binned = P < (1 << 24);
+    mpcx_interaction_extras ix;
+    ix.prev_save = ctx->prev_cut;
+    ix.near = near_hints(ctx, P);
+    ix.bin_hint = binned ? c->iters : nullptr;
     if (c->exchange == MPCX_SHARD_AGENTS) {
         // agent-sharded layout: this rank's rows travel to every rank, every rank assembles the whole pool (one RCCL all-gather)
         mpcx::PackArgs pa{P, c->state, c->applied, c->obs_local};
@@ -56,60 +66,40 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         if (rc != MPCX_OK) return rc;
         pool_rows = P * ctx->comm_world;
     } else {
-        // local pool: row q is agent q, and the prediction kernel (inside mpcx_interaction_batch) packs it on its way -- no launch of its own
-        ctx->pack_state = c->state; ctx->pack_applied = c->applied;
+        // local pool: row q is agent q, and the prediction kernel (inside the conflict search's stage) packs it on its way -- no launch of its own
+        ix.pack_state = c->state; ix.pack_applied = c->applied;
         if (c->n_actors > 0) {
             // scripted traffic (mpc_intersection.py:118-122): the actors' get() rows go into their pool rows and their step() is taken at once --
             // it shows in the NEXT step's rows, as o.step() at the end of the reference's loop body does (:155-156).  Agent q sits in row ego_row[q].
             rc = mpcx_traffic_enqueue(ctx, c->n_actors, c->actors, c->actor_state, c->tape, c->tape_rows, c->actor_row, c->pool_rows, c->obs6);
-            if (rc != MPCX_OK) { ctx->pack_state = nullptr; ctx->pack_applied = nullptr; return rc; }
-            ctx->pack_ego_row = c->ego_row; ctx->pack_actor_row = c->actor_row;
-            ctx->pack_n_ego = P; ctx->pack_n_actors = c->n_actors;
+            if (rc != MPCX_OK) return rc;
+            ix.ego_row = c->ego_row; ix.actor_row = c->actor_row;
+            ix.n_ego = P; ix.n_actors = c->n_actors;
             pool_rows = c->pool_rows;
         }
     }
-    // the conflict search leaves the cut lengths of the previous step in ctx->prev_cut (the queue of the QP kernel puts the agents whose
-    // cut moved at the front) and files every agent under its work-queue key (previous iteration count + "the cut moved"): hard problems first.  The window
-    // selection then writes the queue order and the plant kernel resets bins and ticket, so the counting sort costs no launch of its own.
-    const bool binned = P < (1 << 24);
-    ctx->inter_prev_save = ctx->prev_cut;
-    ctx->inter_near = ctx->prev_cut + P;             // (its start index, largest of its three nearest indices) per agent, for the window selection
-    ctx->bin_hint = binned ? c->iters : nullptr;
-    rc = mpcx_interaction_batch(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
-                                c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows, c->obs6,
-                                c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len);
-    ctx->inter_prev_save = nullptr;
-    ctx->inter_near = nullptr;
-    ctx->bin_hint = nullptr;
-    ctx->pack_state = nullptr; ctx->pack_applied = nullptr;
-    ctx->pack_ego_row = nullptr; ctx->pack_actor_row = nullptr;
-    ctx->pack_n_ego = ctx->pack_n_actors = 0;
+    rc = mpcx_interaction_enqueue(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
+                                  c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows, c->obs6,
+                                  c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len, ix);
     if (rc != MPCX_OK) return rc;
     // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
     // previous pass's speeds (row 2 of its x) and the rollout uses its inputs.  (Where a pass fails the reference crashes in the next
     // one -- zip over None; here the next pass starts from the untouched warm start, as after a failed step.)
     const int Wd = ctx->mpc.T + 1;
     for (int pass = 0; pass < ctx->lin_passes; pass++) {
-        ctx->bin_scatter = binned && pass == 0;
-        ctx->window_near = ctx->prev_cut + P; ctx->window_tidx = c->traj_idx;
-        rc = mpcx_mpc_prepare_batch_ov(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, c->cut_len, c->dl,
-                                       c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar);
-        ctx->window_near = ctx->window_tidx = nullptr;
+        const bool first = pass == 0;
+        // the first pass writes the queue order and joins the rollout forked above; a later one forks its own
+        const mpcx_window_extras wx{binned && first, near_hints(ctx, P), c->traj_idx, first};
+        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, c->cut_len, c->dl,
+                                 c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar, wx);
         if (rc != MPCX_OK) return rc;
         // (further linearisation passes build their order in line, from the iteration counts of the pass before)
-        const int32_t *hint_before = ctx->order_hint, *now_before = ctx->order_now, *prev_before = ctx->order_prev;
-        ctx->order_hint = c->iters; ctx->order_now = c->cut_len; ctx->order_prev = ctx->prev_cut;
-        ctx->order_ready = binned && pass == 0;
-        rc = mpcx_qp_solve_batch(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol,
-                                 c->status, c->iters, c->kkt);
-        ctx->order_hint = hint_before; ctx->order_now = now_before; ctx->order_prev = prev_before;
-        ctx->order_ready = false;
+        const mpcx_qp_order ord{binned && first, c->iters, c->cut_len, ctx->prev_cut};
+        rc = mpcx_qp_enqueue(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol, c->status, c->iters, c->kkt, ord);
         if (rc != MPCX_OK) return rc;
     }
-    ctx->stats_iters = c->iters;
-    ctx->bin_reset = binned;
-    rc = mpcx_plant_step_batch(ctx, P, c->state, c->u_sol, c->status, c->applied);
-    ctx->stats_iters = nullptr;
+    const mpcx_plant_extras px{c->iters, binned};
+    rc = mpcx_plant_enqueue(ctx, P, c->state, c->u_sol, c->status, c->applied, px);
     if (rc == MPCX_OK) ctx->bins_clean = binned;
     return rc;
 }
@@ -170,13 +160,9 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
     {       // queue bins: counters + (key, slot) per agent.  The plant kernel leaves counters and ticket zeroed step by step; they are
             // filled here only when the host cannot know that (first run, a step that failed half way, a solve outside the loop since)
         const size_t need = (size_t)MPCX_ORDER_COPIES * MPCX_ORDER_BINS + (size_t)c->P;
-        if (need > ctx->bins_cap) {
-            if (ctx->bins) (void)hipFree(ctx->bins);
-            ctx->bins = nullptr; ctx->bins_cap = 0; ctx->bins_clean = false;
-            if (hipMalloc((void **)&ctx->bins, need * sizeof(int32_t)) != hipSuccess)
-                return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: cannot allocate the queue bins of %d agents", c->P);
-            ctx->bins_cap = need;
-        }
+        if (need * sizeof(int32_t) > ctx->bins_cap) ctx->bins_clean = false;
+        rc = mpcx_grow(ctx, (void **)&ctx->bins, &ctx->bins_cap, need * sizeof(int32_t), "the queue bins");
+        if (rc != MPCX_OK) return rc;
         if (!ctx->bins_clean) {
             if (hipMemsetAsync(ctx->bins, 0, (size_t)MPCX_ORDER_COPIES * MPCX_ORDER_BINS * sizeof(int32_t), ctx->stream) != hipSuccess ||
                 hipMemsetAsync(ctx->ticket, 0, MPCX_TICKET_WORDS * sizeof(int32_t), ctx->stream) != hipSuccess)
@@ -184,18 +170,12 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
             ctx->bins_clean = true;
         }
     }
-    if ((size_t)c->P > ctx->prev_cut_cap) {
-        if (ctx->prev_cut) (void)hipFree(ctx->prev_cut);
-        ctx->prev_cut = nullptr; ctx->prev_cut_cap = 0;
-        if (hipMalloc((void **)&ctx->prev_cut, 4 * (size_t)c->P * sizeof(int32_t)) != hipSuccess)      // P cut lengths + 3 P nearest-index hints
-            return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: cannot allocate %d cut lengths", c->P);
-        ctx->prev_cut_cap = (size_t)c->P;
-    }
+    rc = mpcx_grow(ctx, (void **)&ctx->prev_cut, &ctx->prev_cut_cap, 4 * (size_t)c->P * sizeof(int32_t), "the previous cut lengths");   // P cut lengths | near_hints
+    if (rc != MPCX_OK) return rc;
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
             rc = enqueue_step(ctx, ip, c);
-        ctx->rollout_forked = false;
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -230,7 +210,6 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
         rc = enqueue_step(ctx, ip, c);
-        ctx->rollout_forked = false;
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));

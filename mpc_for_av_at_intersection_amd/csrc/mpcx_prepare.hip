@@ -217,22 +217,24 @@ extern "C" int32_t mpcx_mpc_prepare_batch_ov(mpcx_ctx *ctx, int32_t B, const dou
                                              const double *path_xyyaw, const double *path_v, const int32_t *path_off,
                                              const int32_t *path_len, double dl, int32_t *target_ind, const double *ov, int64_t ov_stride,
                                              double *xref, uint8_t *reaches_end, double *xbar) {
+    return mpcx_window_enqueue(ctx, B, state, u_warm, path_xyyaw, path_v, path_off, path_len, dl, target_ind, ov, ov_stride, xref, reaches_end, xbar, {});
+}
+
+int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, const double *path_xyyaw, const double *path_v,
+                            const int32_t *path_off, const int32_t *path_len, double dl, int32_t *target_ind, const double *ov, int64_t ov_stride,
+                            double *xref, uint8_t *reaches_end, double *xbar, const mpcx_window_extras &x) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (B == 0) return MPCX_OK;       // empty batch: nothing to do (zero-size tensors have null data pointers)
     if (B < 0 || !state || !path_xyyaw || !path_off || !path_len || !target_ind || !xref || !reaches_end || !xbar || !(dl > 0))
         return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch: null pointer, negative batch or dl <= 0");
-    if (B == 0) return MPCX_OK;
     if (ov && ov_stride < (int64_t)ctx->mpc.T + 1)
         return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch_ov: ov_stride %lld is smaller than T + 1", (long long)ov_stride);
-    const bool scatter = ctx->bin_scatter;
-    ctx->bin_scatter = false;
     mpcx::RefArgs ra{ctx->mpc, B, state, path_xyyaw, path_v, path_off, path_len, dl, target_ind, xref, reaches_end, ov, (long)ov_stride,
-                     scatter ? ctx->bins : nullptr, scatter ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr, scatter ? ctx->order : nullptr,
-                     ctx->window_near, ctx->window_near ? ctx->window_tidx : nullptr};
+                     x.scatter ? ctx->bins : nullptr, x.scatter ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr, x.scatter ? ctx->order : nullptr,
+                     x.near, x.near ? x.tidx : nullptr};
     // the rollout may already be in flight: mpcx_closed_loop_run forks it at the start of the step, beside the conflict search
-    const bool forked = ctx->rollout_forked;
-    ctx->rollout_forked = false;
+    const bool forked = x.rollout_forked;
     if (!forked) {
         int32_t rc = mpcx_rollout_fork(ctx, B, state, u_warm, xbar);
         if (rc != MPCX_OK) return rc;
@@ -249,7 +251,7 @@ extern "C" int32_t mpcx_mpc_prepare_batch_ov(mpcx_ctx *ctx, int32_t B, const dou
 }
 
 // the warm-start rollout (mpc.py:112-126 `_predict_motion`) on the context's side stream, ordered behind everything enqueued on the
-// context's stream so far; the next mpcx_mpc_prepare_batch[_ov] joins it instead of launching its own
+// context's stream so far; mpcx_window_enqueue joins it (mpcx_window_extras::rollout_forked: instead of forking one of its own)
 int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, double *xbar) {
     mpcx::RollArgs ro{ctx->mpc, B, state, u_warm, xbar};
     if (hipEventRecord(ctx->ev_fork, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0) != hipSuccess)
@@ -268,18 +270,19 @@ int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const d
 
 extern "C" int32_t mpcx_plant_step_batch(mpcx_ctx *ctx, int32_t B, double *state, double *u,
                                          const int32_t *status, double *applied) {
+    return mpcx_plant_enqueue(ctx, B, state, u, status, applied, {});
+}
+
+int32_t mpcx_plant_enqueue(mpcx_ctx *ctx, int32_t B, double *state, double *u, const int32_t *status, double *applied, const mpcx_plant_extras &x) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (B == 0) return MPCX_OK;       // empty batch: nothing to do (zero-size tensors have null data pointers)
     if (B < 0 || !state || !u || !applied) return mpcx_fail(ctx, MPCX_E_INVALID, "plant_step_batch: null pointer");
-    if (B == 0) return MPCX_OK;
     if (ctx->tune && ctx->tune_rows != B)
         return mpcx_fail(ctx, MPCX_E_INVALID, "plant_step_batch: %d tuning rows are set but the batch has %d agents", ctx->tune_rows, B);
-    // inside mpcx_closed_loop_run the step also feeds the run statistics (ctx->stats_iters names the step's iteration counts)
-    const bool st = ctx->stats && ctx->stats_iters && status;
-    const bool rz = ctx->bin_reset && ctx->bins && ctx->ticket;
-    ctx->bin_reset = false;
-    mpcx::PlantArgs pa{ctx->mpc, B, state, u, status, applied, ctx->tune, ctx->stats_iters, ctx->stats, st ? 1 : 0,
+    const bool st = ctx->stats && x.stats_iters && status;
+    const bool rz = x.reset_bins && ctx->bins && ctx->ticket;
+    mpcx::PlantArgs pa{ctx->mpc, B, state, u, status, applied, ctx->tune, x.stats_iters, ctx->stats, st ? 1 : 0,
                        rz ? ctx->bins : nullptr, rz ? ctx->ticket : nullptr};
     hipLaunchKernelGGL(mpcx::plant_kernel, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, pa);
     return mpcx_check_launch(ctx, "plant_kernel");

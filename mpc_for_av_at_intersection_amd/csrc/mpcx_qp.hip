@@ -702,13 +702,7 @@ static inline int32_t *order_fail_list(mpcx_ctx *ctx, size_t B) { return ctx->or
 
 int32_t mpcx_ensure_order(mpcx_ctx *ctx, size_t B) {
     const size_t need = 2 * B + order_blocks(B) * mpcx::ORDER_BINS + 2;       // order | block histograms | list of given-up problems | its counter and ticket
-    if (need <= ctx->order_cap) return MPCX_OK;
-    if (ctx->order) (void)hipFree(ctx->order);
-    ctx->order = nullptr; ctx->order_cap = 0;
-    if (hipMalloc((void **)&ctx->order, need * sizeof(int32_t)) != hipSuccess)
-        return mpcx_fail(ctx, MPCX_E_LAUNCH, "cannot allocate the work-queue order (%zu entries)", B);
-    ctx->order_cap = need;
-    return MPCX_OK;
+    return mpcx_grow(ctx, (void **)&ctx->order, &ctx->order_cap, need * sizeof(int32_t), "the work-queue order");
 }
 
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx) {
@@ -717,16 +711,16 @@ int32_t mpcx_ensure_ticket(mpcx_ctx *ctx) {
     return MPCX_OK;
 }
 
-// both solvers draw their problems from a queue, longest expected job first: order (ctx->order[0..B)) from ctx->order_hint / order_now / order_prev
-int32_t mpcx_qp_build_order(mpcx_ctx *ctx, int32_t B, hipStream_t st) {
+// both solvers draw their problems from a queue, longest expected job first: order (ctx->order[0..B)) from hint / now / prev
+int32_t mpcx_qp_build_order(mpcx_ctx *ctx, int32_t B, const int32_t *hint, const int32_t *now, const int32_t *prev, hipStream_t st) {
     int32_t rc = mpcx_ensure_order(ctx, (size_t)B);
     if (rc != MPCX_OK) return rc;
     rc = mpcx_ensure_ticket(ctx);
     if (rc != MPCX_OK) return rc;
     int32_t *block_hist = ctx->order + B;
     const int nb = (int)order_blocks((size_t)B);
-    hipLaunchKernelGGL(mpcx::qp_order_hist_kernel, dim3(nb), dim3(mpcx::ORDER_BLOCK), 0, st, B, ctx->order_hint, ctx->order_now, ctx->order_prev, block_hist);
-    hipLaunchKernelGGL(mpcx::qp_order_scatter_kernel, dim3(nb), dim3(mpcx::ORDER_BLOCK), 0, st, B, ctx->order_hint, ctx->order_now, ctx->order_prev,
+    hipLaunchKernelGGL(mpcx::qp_order_hist_kernel, dim3(nb), dim3(mpcx::ORDER_BLOCK), 0, st, B, hint, now, prev, block_hist);
+    hipLaunchKernelGGL(mpcx::qp_order_scatter_kernel, dim3(nb), dim3(mpcx::ORDER_BLOCK), 0, st, B, hint, now, prev,
                        block_hist, ctx->order, ctx->ticket);
     return MPCX_OK;
 }
@@ -735,12 +729,20 @@ extern "C" int32_t mpcx_qp_solve_batch(mpcx_ctx *ctx, int32_t B, const double *x
                                        const double *xbar, const uint8_t *reaches_end, const double *u_warm,
                                        double *x_out, double *u_out, int32_t *status, int32_t *iters, double *kkt) {
     if (!ctx) return MPCX_E_INVALID;
+    // the order comes from the caller's own setting (mpcx_qp_set_order_hint)
+    return mpcx_qp_enqueue(ctx, B, x0, xref, xbar, reaches_end, u_warm, x_out, u_out, status, iters, kkt,
+                           {false, ctx->order_hint, ctx->order_now, ctx->order_prev});
+}
+
+int32_t mpcx_qp_enqueue(mpcx_ctx *ctx, int32_t B, const double *x0, const double *xref, const double *xbar, const uint8_t *reaches_end,
+                        const double *u_warm, double *x_out, double *u_out, int32_t *status, int32_t *iters, double *kkt, const mpcx_qp_order &ord) {
+    if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (B == 0) return MPCX_OK;       // empty batch: nothing to do (zero-size tensors have null data pointers)
     if (B < 0 || !x0 || !xref || !xbar || !reaches_end || !x_out || !u_out || !status || !iters || !kkt)
         return mpcx_fail(ctx, MPCX_E_INVALID, "qp_solve_batch: null pointer or negative batch");
     { int32_t rc = mpcx_ensure_ticket(ctx); if (rc != MPCX_OK) return rc; }
-    if (!ctx->order_ready) ctx->bins_clean = false;      // this solve draws tickets outside the closed loop's bookkeeping
+    if (!ord.ready) ctx->bins_clean = false;      // this solve draws tickets outside the closed loop's bookkeeping
     // persistent wavefronts: one per SIMD slot the kernel can occupy (1 wave/SIMD, 4 SIMDs/CU), never more than B
     const int grid = B < ctx->n_cu * 4 ? B : ctx->n_cu * 4;
     if (ctx->tune && ctx->tune_rows != B)
@@ -753,11 +755,10 @@ extern "C" int32_t mpcx_qp_solve_batch(mpcx_ctx *ctx, int32_t B, const double *x
         return mpcx_fail(ctx, MPCX_E_INVALID, "qp_solve_batch: the condensed solver has no five-state (lib/mpc_jerk.py) variant; use solver 0 or 2");
     const bool use_stage = solver == 2 || ctx->mpc.model == MPCX_MODEL_JERK5 || (solver == 0 && (T > 20 || B >= MPCX_STAGE_MIN_BATCH));
     const int32_t *order = nullptr;
-    if (ctx->order_ready) {                       // mpcx_closed_loop_run built it beside the window selection (and the scatter zeroed the ticket)
-        ctx->order_ready = false;
+    if (ord.ready) {                              // mpcx_closed_loop_run built it beside the window selection (and the plant kernel zeroed the ticket)
         order = ctx->order;
-    } else if (ctx->order_hint || ctx->order_now) {      // both solvers draw their problems from a queue: longest expected job first
-        int32_t rc = mpcx_qp_build_order(ctx, B, ctx->stream);
+    } else if (ord.hint || ord.now) {             // both solvers draw their problems from a queue: longest expected job first
+        int32_t rc = mpcx_qp_build_order(ctx, B, ord.hint, ord.now, ord.prev, ctx->stream);
         if (rc != MPCX_OK) return rc;
         order = ctx->order;
     } else if (hipMemsetAsync(ctx->ticket, 0, MPCX_TICKET_WORDS * sizeof(int32_t), ctx->stream) != hipSuccess)
