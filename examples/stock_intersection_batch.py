@@ -3,6 +3,8 @@
 the device in ONE call: the scripted cars are stepped by a HIP kernel (mpcx_traffic_step_batch inside mpcx_closed_loop_run), no host work
 between steps.  Instance 0 is the stock set itself (ego route (4, 1); cars: direction 1 / offset 2 s / straight on and direction -1 /
 offset 4 s / turning, 25 km/h); the others draw route, directions, turning, speeds and start delays (batch.scripted_traffic_batch).
+A run log with capacity 0 (attach_log: the per-ego outcomes only, 24 bytes per ego) says what the reference's loop says about a run: when
+mpc.is_goal held (the reference's loop ends there), whether anybody touched anybody after having been clear, and the worst clearance.
 examples/stock_intersection.py is the same scenario, one instance, through the reference's call surface.
 
     python examples/stock_intersection_batch.py [--instances 1024] [--steps 120] [--horizon 20] [--graph]
@@ -32,6 +34,7 @@ def main():
 
     ctx = Context(0, stream=torch.cuda.Stream(device=0)) if args.graph else Context(0)
     sim = scripted_traffic_batch(ctx, B=args.instances, T=args.horizon, seed=args.seed, A=1, K=2)
+    log = sim.attach_log(0)                 # outcomes only: goal arrival, contact, worst clearance -- written on the device, step by step
     sim.run(1, graph=args.graph)            # first call: allocations (and the capture)
     ctx.synchronize()
     t0 = time.perf_counter()
@@ -41,14 +44,21 @@ def main():
     sim.check()
     snap = sim.snapshot()
     path_len = sim.path_len.cpu().numpy()
-    # an ego has passed once it is beyond the junction: in the last fifth of its path (the batch has no goal test: egos stand at the path end)
-    passed = snap['traj_idx'] >= 0.8 * path_len
+    out = log.outcomes()
+    arrived = out['goal_step'] >= 0         # mpc.is_goal held: the reference's loop would have ended after goal_step iterations
+    under_way = ~arrived                    # an arrived ego stands at its goal: "standing" and "mean speed" are about the others
+    v = snap['state'][under_way, 2]
+    touched = out['contact_step'] >= 0      # clearance < 0 after the ego had been clear of everybody (a car may spawn ON an ego)
+    seen = np.isfinite(out['min_clearance'])
     stats = ctx.closed_loop_stats()
-    print('%d instances x %d steps on the device: %.0f instance-steps/s (%.3f ms per step); %d of %d egos passed the junction, '
-          '%d are standing, mean speed %.2f m/s; %d QP failures; stock instance: ego at path point %d of %d, cars at x = %s'
-          % (args.instances, args.steps, args.instances * (args.steps - 1) / wall, 1e3 * wall / max(args.steps - 1, 1), int(passed.sum()),
-             len(passed), int((np.abs(snap['state'][:, 2]) < 0.1).sum()), float(snap['state'][:, 2].mean()), stats['failures'],
-             int(snap['traj_idx'][0]), int(path_len[0]), np.round(snap['traffic_state'][:2, 0], 2).tolist()))
+    print('%d instances x %d steps on the device: %.0f instance-steps/s (%.3f ms per step); %d of %d egos arrived (median after %s steps), '
+          'of the others %d are standing, mean speed %.2f m/s; %d egos touched a vehicle, worst clearance %.2f m; %d QP failures; '
+          'stock instance: arrived after %d steps, ego at path point %d of %d, cars at x = %s'
+          % (args.instances, args.steps, args.instances * (args.steps - 1) / wall, 1e3 * wall / max(args.steps - 1, 1), int(arrived.sum()),
+             len(arrived), int(np.median(out['goal_step'][arrived])) if arrived.any() else '-', int((np.abs(v) < 0.1).sum()),
+             float(v.mean()) if len(v) else 0.0, int(touched.sum()), float(out['min_clearance'][seen].min()) if seen.any() else float('inf'),
+             stats['failures'], int(out['goal_step'][0]), int(snap['traj_idx'][0]), int(path_len[0]),
+             np.round(snap['traffic_state'][:2, 0], 2).tolist()))
 
 
 if __name__ == '__main__':

@@ -14,6 +14,8 @@
  *   - launches go to the HIP stream given at mpcx_create (NULL = default stream); calls are asynchronous
  *     with respect to the host exactly like a kernel launch, the caller synchronises the stream.
  *   - one mpcx_ctx per host thread / stream; a ctx is not re-entrant.
+ *   - what the reference's loop records ABOUT a run (History rows, the goal test that ends the loop) and the true clearance between the
+ *     vehicles is the run log: mpcx_run_log, mpcx_closed_loop_run_logged, mpcx_record_step_batch.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -355,6 +357,49 @@ int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, c
  * print per run: solver failures; plus iteration counts): out4 = (agent-steps, interior-point iterations, failed solves, max iterations).
  * Synchronises the context's stream. */
 int32_t mpcx_closed_loop_stats(mpcx_ctx *ctx, int64_t *out4 /*host*/, int32_t reset);
+
+/* ---- the run log: what the reference's own loop produces ABOUT a run -- HistorySimulation's rows (lib/simulation.py:58-88 with
+ * get_current_xref_deviation, lib/mpc.py:301-308), the end of the loop (mpc.is_goal, lib/mpc.py:310-326; mpc_intersection.py:97-98) --
+ * plus the true distance between the vehicles, written per step and agent by ONE more kernel at the end of a step (record_kernel, after
+ * the plant step), with no host work between steps, under plain enqueue and graph replay alike.  The rule is csrc/mpcx_record_core.h.
+ * Row s of agent q (s = steps[q] when the step is recorded; dropped when s >= capacity, the outcome words advance all the same):
+ *   rows_f64[s][q][0..7] = x, y, v, yaw (after the plant step), accel, steer (applied), xref_deviation (NaN after a failed solve),
+ *                          clearance (min disc-to-disc distance - 2 radius to every other row of the agent's pool window at the START of
+ *                          the step, the agent's own pose taken from its own pool row obs_skip[q]; +inf if there is nobody else)
+ *   rows_i32[s][q][0..7] = traj_idx, target_ind, cut_len, hit_idx, status, iters, 0, 0
+ * Per-agent outcome words (caller-initialised: steps 0, goal_step -1, contact_step -1, flags 0, min_clearance +inf):
+ *   steps          rows offered so far (the write cursor: device memory, so a replayed graph keeps advancing)
+ *   goal_step      steps taken when is_goal first held (= the reference's number of loop iterations), else -1; goal = last point of the
+ *                  agent's full path, len(cx) = cut_len, target_ind and state as they stand after the step
+ *   flags          bit 0: the agent has been clear of everybody (a step with clearance >= 0)
+ *   min_clearance  minimum of clearance from the first clear step on;  contact_step: first step with clearance < 0 after it, else -1
+ * 96 bytes per agent and step + 24 bytes per agent; capacity 0 = outcomes only (rows_* may then be NULL).  The library checks the
+ * descriptor's pointers and alignment, it cannot check sizes: row buffers smaller than capacity x P x 8 elements, or outcome buffers
+ * smaller than P, are the caller's fault (a write beyond them). */
+typedef struct {
+    int32_t capacity;    /* rows per agent */
+    int32_t reserved;
+    double goal_dis, stop_speed;   /* GOAL_DIS, STOP_SPEED of lib/mpc.py (1.5 m, 0.1389 m/s) */
+    double *rows_f64 /*capacity,P,8*/;
+    int32_t *rows_i32 /*capacity,P,8*/;
+    int32_t *steps /*P*/, *goal_step /*P*/, *contact_step /*P*/, *flags /*P*/;
+    double *min_clearance /*P*/;
+} mpcx_run_log;
+/* one step's record as a stage of its own (what mpcx_closed_loop_run_logged enqueues after the plant step): the buffers are the
+ * closed loop's, after mpcx_plant_step_batch; obs6 the pool as the step's mpcx_interaction_batch saw it.  obs_skip is required. */
+int32_t mpcx_record_step_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P,
+                               const double *state /*P,4*/, const double *applied /*P,2*/, const double *x_sol /*P,4,T+1*/,
+                               const double *path_xyyaw /*npts,3*/, const int32_t *path_off /*P*/, const int32_t *path_len /*P (full length)*/,
+                               const int32_t *target_ind /*P*/, const int32_t *cut_len /*P*/, const int32_t *traj_idx /*P*/,
+                               const int32_t *hit_idx /*P*/, const int32_t *status /*P*/, const int32_t *iters /*P*/,
+                               int32_t n_obs_pool, const double *obs6 /*NOBS,6*/, const int32_t *obs_off /*P*/,
+                               const int32_t *obs_cnt /*P*/, const int32_t *obs_skip /*P*/, const mpcx_run_log *log);
+/* mpcx_closed_loop_run with a run log: every step ends with the record stage.  The log travels beside the descriptor, not inside it:
+ * mpcx_closed_loop keeps its size, so callers built against the struct as it was stay valid; the cached graph's key covers both.
+ * log = NULL (or capacity 0 with every pointer NULL) is mpcx_closed_loop_run itself: the same launches with the same arguments.
+ * Works with scripted traffic, with MPCX_SHARD_AGENTS (the pool is the all-gathered one) and with use_graph. */
+int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                    const mpcx_run_log *log, int32_t n_steps, int32_t use_graph);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

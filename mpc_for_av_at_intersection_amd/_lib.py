@@ -46,6 +46,19 @@ class ClosedLoopC(C.Structure):
                  ('actor_row', C.c_void_p), ('ego_row', C.c_void_p), ('tape_rows', C.c_int64)])
 
 
+class RunLogC(C.Structure):
+    """mirror of mpcx_run_log (include/mpcx.h); every pointer is a device address"""
+    _fields_ = ([('capacity', C.c_int32), ('reserved', C.c_int32), ('goal_dis', C.c_double), ('stop_speed', C.c_double)] +
+                [(n, C.c_void_p) for n in ('rows_f64', 'rows_i32', 'steps', 'goal_step', 'contact_step', 'flags', 'min_clearance')])
+
+
+# the columns of a run-log row (rows_f64[s][q][0..7], rows_i32[s][q][0..5]; two reserved integer columns follow)
+RUN_LOG_F64 = ('x', 'y', 'v', 'yaw', 'accel', 'steer', 'xref_deviation', 'clearance')
+RUN_LOG_I32 = ('traj_idx', 'target_ind', 'cut_len', 'hit_idx', 'status', 'iters')
+RUN_LOG_ROW_BYTES = 96          # per agent and step
+RUN_LOG_AGENT_BYTES = 24        # per agent: steps, goal_step, contact_step, flags, min_clearance
+
+
 class TrafficActorC(C.Structure):
     """mirror of mpcx_traffic_actor (include/mpcx.h): the constants of one scripted vehicle"""
     _fields_ = ([(n, C.c_int32) for n in ('kind', 'direction', 'turning', 'tape_rows', 'tape_off', 'tape_stride')] +
@@ -91,7 +104,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_transform_batch', 'mpcx_cutoff_index_batch', 'mpcx_predict_obstacles_batch', 'mpcx_selftest_wave_ops', 'mpcx_selftest_mfma',
            'mpcx_closed_loop_run', 'mpcx_profile_qp', 'mpcx_profile_qp_read', 'mpcx_set_instance_tuning', 'mpcx_set_qp_solver', 'mpcx_qp_set_order_hint', 'mpcx_expand_multi_batch',
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
-           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch']
+           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
+           'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged']
 
 
 def load():
@@ -150,5 +164,9 @@ def load():
     lib.mpcx_allgather_states.restype = i32; lib.mpcx_allgather_states.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.mpcx_closed_loop_stats.restype = i32; lib.mpcx_closed_loop_stats.argtypes = [vp, C.POINTER(C.c_int64), i32]
     lib.mpcx_traffic_step_batch.restype = i32; lib.mpcx_traffic_step_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int64, vp, i32, vp]
+    lib.mpcx_record_step_batch.restype = i32
+    lib.mpcx_record_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 12 + [i32] + [vp] * 4 + [C.POINTER(RunLogC)]
+    lib.mpcx_closed_loop_run_logged.restype = i32
+    lib.mpcx_closed_loop_run_logged.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC), i32, i32]
     _lib = lib
     return lib

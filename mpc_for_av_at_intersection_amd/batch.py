@@ -10,6 +10,8 @@ SCRIPTED cars (lib/moving_obstacles.py; `traffic=`): they are stepped on the dev
 the instance's rows of the obstacle pool with its agents. All state lives on the device.
 `run(n)` hands the whole loop to mpcx_closed_loop_run (n steps enqueued back to back, optionally as a replayed
 hipGraph); `step_staged()` drives the same kernels stage by stage through the per-stage entry points.
+`attach_log(capacity)` adds the RUN LOG: one more kernel at the end of every step writes the reference's History row, the goal test of
+its loop and the true clearance to the other vehicles, per agent, on the device (RunLog).
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -20,6 +22,107 @@ import torch
 from . import _lib
 from .runtime import (path_first_within, path_plan, path_tables, traffic_pool_layout, Context, InteractionParams, MpcParams, MpcxError,
                       Traffic)
+
+
+RUN_LOG_DTYPE = np.dtype([(n, '<f8') for n in _lib.RUN_LOG_F64] + [(n, '<i4') for n in _lib.RUN_LOG_I32])
+RUN_LOG_MAX_BYTES = 1 << 30     # attach_log refuses a larger log unless told otherwise
+
+
+class RunLog:
+    """The run log of an IntersectionBatch (attach_log): owns the device tensors mpcx_run_log names and reads them back.
+
+    Per step and agent (rows): the state after the plant step, the applied controls, the reference's xref_deviation (mpc.py:301-308; NaN
+    after a failed solve), the clearance to every other vehicle of the agent's pool window at the START of the step (min disc distance
+    - 2 radius; +inf if there is nobody) and the step's integer decisions.  Per agent (outcomes): `steps` recorded, `goal_step` = steps
+    taken when mpc.is_goal (mpc.py:310-326) first held, i.e. the reference's number of loop iterations (-1: not yet), and, counted from the
+    agent's first step with clearance >= 0 on, `min_clearance` and `contact_step` (first step with clearance < 0 after that, -1 = none) --
+    the stock scenario spawns a scripted car ON the ego's start pose, which a plain minimum would report as a contact at step 0.
+    Nothing is frozen at the goal: the log says where the reference's loop would have ended, history() cuts there.
+    Memory: 96 bytes per agent and step (capacity x P rows) + 24 bytes per agent; capacity 0 keeps the outcomes only."""
+
+    def __init__(self, batch: 'IntersectionBatch', capacity: int, goal_dis: float, stop_speed: float):
+        dev, P = batch.ctx.device, batch.P
+        self.batch, self.capacity, self.goal_dis, self.stop_speed = batch, int(capacity), float(goal_dis), float(stop_speed)
+        self.P, self.dt = P, float(batch.params.dt)
+        self.rows_f64 = torch.zeros((self.capacity, P, 8), dtype=torch.float64, device=dev) if self.capacity else None
+        self.rows_i32 = torch.zeros((self.capacity, P, 8), dtype=torch.int32, device=dev) if self.capacity else None
+        self.steps, self.goal_step, self.contact_step, self.flags = (torch.zeros(P, dtype=torch.int32, device=dev) for _ in range(4))
+        self.min_clearance = torch.zeros(P, dtype=torch.float64, device=dev)
+        self.c = _lib.RunLogC()
+        self.c.capacity, self.c.goal_dis, self.c.stop_speed = self.capacity, self.goal_dis, self.stop_speed
+        for n in ('rows_f64', 'rows_i32', 'steps', 'goal_step', 'contact_step', 'flags', 'min_clearance'):
+            t = getattr(self, n)
+            setattr(self.c, n, None if t is None else t.data_ptr())
+        self.reset()
+
+    @property
+    def nbytes(self) -> int:
+        return self.capacity * self.P * _lib.RUN_LOG_ROW_BYTES + self.P * _lib.RUN_LOG_AGENT_BYTES
+
+    def reset(self):
+        """forget everything recorded: the next step is step 0 of the log, the batch's state now is the log's initial state.  The goal
+        test BEFORE that step (the top of the reference's first iteration; only a path of fewer than 5 points can pass it) is made here,
+        on the host, and gives goal_step = 0."""
+        b = self.batch
+        b.ctx.synchronize()
+        self.steps.zero_(); self.flags.zero_()
+        self.contact_step.fill_(-1)
+        self.min_clearance.fill_(float('inf'))
+        self.initial = b.state.cpu().numpy().copy()
+        path = b.path.cpu().numpy()
+        off, ln = b.path_off.cpu().numpy().astype(np.int64), b.path_len.cpu().numpy().astype(np.int64)
+        cut = b.inter['cut_len'].cpu().numpy().astype(np.int64)
+        cut = np.where(cut > 0, cut, ln)            # len(self.cx): the full path until a step has cut it
+        goal = path[off + ln - 1]
+        st = self.initial
+        there = ((np.hypot(st[:, 0] - goal[:, 0], st[:, 1] - goal[:, 1]) <= self.goal_dis) & (np.abs(b.target_ind.cpu().numpy() - cut) < 5) &
+                 (np.abs(st[:, 2]) <= self.stop_speed))
+        self.goal_step.copy_(b.ctx.i32(np.where(there, 0, -1)))
+        b.ctx.synchronize()
+
+    def outcomes(self) -> dict:
+        """host arrays goal_step, contact_step, min_clearance, steps (synchronises)"""
+        self.batch.ctx.synchronize()
+        return {n: getattr(self, n).cpu().numpy().copy() for n in ('goal_step', 'contact_step', 'min_clearance', 'steps')}
+
+    def rows(self, q: Optional[int] = None) -> np.ndarray:
+        """the recorded rows as a structured host array (RUN_LOG_DTYPE), cut at min(steps, capacity): shape (n,) for agent q, (n, P)
+        for all agents (every agent of a batch is offered the same number of rows).  steps > capacity: the log overflowed, the first
+        `capacity` rows are there."""
+        self.batch.ctx.synchronize()
+        steps = self.steps.cpu().numpy()
+        n = min(int(steps.max() if q is None else steps[q]), self.capacity)
+        shape = (n, self.P) if q is None else (n,)
+        out = np.zeros(shape, RUN_LOG_DTYPE)
+        if n:
+            f = (self.rows_f64[:n] if q is None else self.rows_f64[:n, q]).cpu().numpy()
+            w = (self.rows_i32[:n] if q is None else self.rows_i32[:n, q]).cpu().numpy()
+            for k, name in enumerate(_lib.RUN_LOG_F64):
+                out[name] = f[..., k]
+            for k, name in enumerate(_lib.RUN_LOG_I32):
+                out[name] = w[..., k]
+        return out
+
+    def history(self, q: int):
+        """the reference's History of agent q (lib/simulation.py): the initial state first (a = delta = xref_deviation = 0, as
+        HistorySimulation stores it), then one entry per step through History.store, cut where the reference's loop ends (goal_step
+        entries after the initial one).  `t` is the class's own: store() appends current time + dt for the initial entry too, so
+        t[k] = (k + 1) dt, exactly as in the reference's HistorySimulation (not k dt)"""
+        from .lib.simulation import History, State
+        rows = self.rows(q)
+        goal = int(self.goal_step[q:q + 1].cpu()[0])       # (rows() has synchronised)
+        if goal >= 0:
+            if goal > len(rows):
+                raise MpcxError('run log: agent %d arrived after %d steps and only %d rows were kept (capacity %d)' % (q, goal, len(rows), self.capacity))
+            rows = rows[:goal]
+        h = History(sample_time=self.dt)
+        x, y, v, yaw = (float(c) for c in self.initial[q])
+        h.store(State(x=x, y=y, yaw=yaw, v=v), a=0., delta=0., xref_deviation=0.)
+        for r in rows:
+            dev = float(r['xref_deviation'])
+            h.store(State(x=float(r['x']), y=float(r['y']), yaw=float(r['yaw']), v=float(r['v'])), a=float(r['accel']), delta=float(r['steer']),
+                    xref_deviation=None if np.isnan(dev) else dev)
+        return h
 
 
 class IntersectionBatch:
@@ -154,6 +257,32 @@ class IntersectionBatch:
                 raise ValueError('tuning must have shape (B, 16) or (B*A, 16)')
             self.tuning = ctx.f64(tuning)
         self._desc = None
+        self.log: Optional[RunLog] = None
+
+    def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
+                   max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
+        """Record every further step on the device (RunLog): `capacity` rows per agent, 96 bytes each -- 4096 x 8 agents x 100 steps are
+        315 MB --, + 24 bytes per agent; capacity = 0 keeps the per-agent outcomes only.  A log larger than max_bytes is refused
+        (max_bytes = None: no limit).  goal_dis / stop_speed default to GOAL_DIS / STOP_SPEED of lib/mpc.py (1.5 m, 0.1389 m/s).
+        Costs one more launch per step; detach_log() restores the launches of a batch without a log."""
+        from .lib import mpc as _mpc
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError('run log: negative capacity')
+        need = capacity * self.P * _lib.RUN_LOG_ROW_BYTES + self.P * _lib.RUN_LOG_AGENT_BYTES
+        if max_bytes is not None and need > max_bytes:
+            raise ValueError('run log: %d rows x %d agents x %d bytes = %.1f MB exceed the limit of %.1f MB; pass a smaller capacity '
+                             '(0 = outcomes only) or a larger max_bytes (None = no limit)'
+                             % (capacity, self.P, _lib.RUN_LOG_ROW_BYTES, need / 1e6, max_bytes / 1e6))
+        self.log = RunLog(self, capacity, _mpc.GOAL_DIS if goal_dis is None else goal_dis, _mpc.STOP_SPEED if stop_speed is None else stop_speed)
+        self._desc = None
+        return self.log
+
+    def detach_log(self) -> Optional[RunLog]:
+        """stop recording (the RunLog keeps what it holds); the batch enqueues exactly the launches of one that never had a log"""
+        log, self.log = self.log, None
+        self._desc = None
+        return log
 
     def _descriptor(self) -> '_lib.ClosedLoopC':
         d = _lib.ClosedLoopC()
@@ -193,7 +322,7 @@ class IntersectionBatch:
         if self._desc is None:
             self._desc = self._descriptor()
         self._claim_context()
-        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph)
+        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c)
         self.steps_done += n_steps
 
     def step(self):
@@ -242,6 +371,10 @@ class IntersectionBatch:
                       x_prev=self.sol['x'] if it else None)
             c.qp_solve(self.state, self.pre['xref'], self.pre['xbar'], self.pre['reaches_end'], self.sol['u'], out=self.sol)
         c.plant_step(self.state, self.sol['u'], self.sol['status'], self.applied)
+        if self.log is not None:
+            c.record_step(self.ip, self.state, self.applied, self.sol['x'], self.path, self.path_off, self.path_len, self.target_ind,
+                          self.inter['cut_len'], self.traj_idx, self.inter['hit_idx'], self.sol['status'], self.sol['iters'], self.obs6,
+                          self.obs_off, self.obs_cnt, self.obs_skip, self.log.c)
         self.steps_done += 1
 
     def snapshot(self):

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[768] = {};     // descriptor + parameters the cached graph was captured for
+    unsigned char loop_key[896] = {};     // descriptor + run log + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -104,7 +104,15 @@ int32_t mpcx_traffic_validate(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffi
                               const int32_t *pool_row, int32_t n_obs_pool);                                      // mpcx_traffic.hip
 int32_t mpcx_traffic_enqueue(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffic_actor *actors, double *actor_state, const double *tape,
                              int64_t tape_rows, const int32_t *pool_row, int32_t n_obs_pool, double *obs6);       // mpcx_traffic.hip
-int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                      // work-queue word (mpcx_qp.hip)
+// the run log's record stage (mpcx_record.hip): "no log" test, check of the descriptor, the launch alone
+bool mpcx_record_absent(const mpcx_run_log *log);
+int32_t mpcx_record_validate(mpcx_ctx *ctx, const mpcx_run_log *log, const int32_t *obs_skip);
+int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const double *applied,
+                            const double *x_sol, const double *path_xyyaw, const int32_t *path_off, const int32_t *path_len,
+                            const int32_t *target_ind, const int32_t *cut_len, const int32_t *traj_idx, const int32_t *hit_idx,
+                            const int32_t *status, const int32_t *iters, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
+                            const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log);
+int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).
 #define MPCX_JUMP_BONUS 11

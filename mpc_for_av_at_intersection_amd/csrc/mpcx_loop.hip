@@ -1,6 +1,6 @@
 // mpcx_loop.hip -- the reference's scenario loop body (main/scenarios/mpc_intersection.py:95-159) for P agents as a
 // device-resident pipeline: n_steps x [scripted traffic rows -> pool pack -> predict -> conflict search + path cut -> reference window ->
-// rollout -> QP -> plant], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
+// rollout -> QP -> plant (-> run-log record, iff a log is attached)], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
 // host synchronisation or host arithmetic in between.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
@@ -42,7 +42,8 @@ static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego
 // the second part of ctx->prev_cut: 3 ints per agent that the conflict search leaves for the window selection (mpcx_interaction_extras::near)
 static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cut + P; }
 
-static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c) {
+// log: the run log's descriptor or nullptr = none (then exactly the launches of a step without one)
+static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log) {
     const int P = c->P;
     ctx->bins_clean = false;        // until the plant kernel of this step is enqueued
     int32_t rc, pool_rows = P;
@@ -101,14 +102,22 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     const mpcx_plant_extras px{c->iters, binned};
     rc = mpcx_plant_enqueue(ctx, P, c->state, c->u_sol, c->status, c->applied, px);
     if (rc == MPCX_OK) ctx->bins_clean = binned;
-    return rc;
+    if (rc != MPCX_OK || !log) return rc;
+    // the run log: one row per agent from the buffers as the step leaves them; the pool still holds the rows this step's conflict search saw
+    return mpcx_record_enqueue(ctx, ip, P, c->state, c->applied, c->x_sol, c->path_xyyaw, c->path_off, c->path_len, c->target_ind, c->cut_len,
+                               c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, log);
 }
 
-extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
-                                        int32_t n_steps, int32_t use_graph) {
+static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
+                               int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
+    if (mpcx_record_absent(log)) log = nullptr;
+    if (log) {          // refused before anything is launched, whatever n_steps is
+        const int32_t lrc = mpcx_record_validate(ctx, log, c->obs_skip);
+        if (lrc != MPCX_OK) return lrc;
+    }
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
         !c->obs_off || !c->obs_cnt || !c->traj_idx || !c->target_ind || !c->hit_idx || !c->cut_len || !c->hit_xy ||
@@ -175,7 +184,7 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c);
+            rc = enqueue_step(ctx, ip, c, log);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -185,11 +194,13 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_interaction_params) + sizeof(mpcx_mpc_params) + 9 * sizeof(void *) <= sizeof key,
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_interaction_params) + sizeof(mpcx_mpc_params) + 9 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
     size_t o = 0;
     memcpy(key + o, c, sizeof *c); o += sizeof *c;
+    if (log) memcpy(key + o, log, sizeof *log);     // (zeros = no log: a graph captured without the record stage)
+    o += sizeof *log;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
     memcpy(key + o, &ctx->pred, sizeof ctx->pred); o += sizeof ctx->pred;
@@ -209,7 +220,7 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c);
+        rc = enqueue_step(ctx, ip, c, log);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -222,4 +233,14 @@ extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_pa
         if (hipGraphLaunch(ctx->loop_exec, ctx->stream) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipGraphLaunch failed");
     return MPCX_OK;
+}
+
+extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                        int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                               const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, n_steps, use_graph);
 }

@@ -599,10 +599,34 @@ class Context:
                                                    _ptr(pool_row), int(obs6.shape[0]), _ptr(obs6)))
 
     @_ordered
-    def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False):
-        """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between."""
+    def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
+                        log: Optional['_lib.RunLogC'] = None):
+        """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
+        log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged)."""
         cip = ip.to_c()
-        self._chk(self.lib.mpcx_closed_loop_run(self._ctx, C.byref(cip), C.byref(desc), int(n_steps), 1 if graph else 0))
+        if log is None:
+            self._chk(self.lib.mpcx_closed_loop_run(self._ctx, C.byref(cip), C.byref(desc), int(n_steps), 1 if graph else 0))
+        else:
+            self._chk(self.lib.mpcx_closed_loop_run_logged(self._ctx, C.byref(cip), C.byref(desc), C.byref(log), int(n_steps), 1 if graph else 0))
+
+    @_ordered
+    def record_step(self, ip: InteractionParams, state, applied, x_sol, path, path_off, path_len, target_ind, cut_len, traj_idx, hit_idx,
+                    status, iters, obs6, obs_off, obs_cnt, obs_skip, log: '_lib.RunLogC'):
+        """mpcx_record_step_batch: the run log's record of ONE step, from the closed loop's buffers as the plant step leaves them
+        (obs6: the pool as the step's conflict search saw it).  log: a _lib.RunLogC naming caller-owned device buffers."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state'); self._want(applied, torch.float64, (Pn, 2), 'applied')
+        self._want(x_sol, torch.float64, (Pn, 4, self.params.T + 1), 'x_sol'); self._want(obs6, torch.float64, (obs6.shape[0], 6), 'obs6')
+        for nm, t in (('path_off', path_off), ('path_len', path_len), ('target_ind', target_ind), ('cut_len', cut_len), ('traj_idx', traj_idx),
+                      ('hit_idx', hit_idx), ('status', status), ('iters', iters), ('obs_off', obs_off), ('obs_cnt', obs_cnt)):
+            self._want(t, torch.int32, (Pn,), nm)
+        if obs_skip is not None:
+            self._want(obs_skip, torch.int32, (Pn,), 'obs_skip')
+        cip = ip.to_c()
+        self._chk(self.lib.mpcx_record_step_batch(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(applied), _ptr(x_sol), _ptr(path), _ptr(path_off),
+                                                  _ptr(path_len), _ptr(target_ind), _ptr(cut_len), _ptr(traj_idx), _ptr(hit_idx), _ptr(status),
+                                                  _ptr(iters), int(obs6.shape[0]), _ptr(obs6), _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip),
+                                                  C.byref(log)))
 
     @_ordered
     def closed_loop_stats(self, reset: bool = True):
