@@ -86,7 +86,8 @@ int32_t mpcx_qp_solve_batch(mpcx_ctx *ctx, int32_t B,
  * [path_off[b], path_off[b]+path_len[b]) of path_xyyaw (rows x,y,yaw; yaw already smooth_yaw'ed);
  * path_len[b] is the CURRENT (possibly cut) length, as after MPC.set_trajectory_fromarray.
  * target_ind is in-out (mpc.py:226).  target_ind[b] = -1 on the reference's Exception("something wrong").
- * path_v (NULL for lib/mpc.py) is the speed profile `cv` of lib/mpc_with_speed.py:85-108: xref[2,:] = cv[idx]. */
+ * path_v (NULL for lib/mpc.py) is the speed profile `cv` of lib/mpc_with_speed.py:85-108: xref[2,:] = cv[idx] (one value per path point,
+ * shared by every agent on the path; a per-agent stop index goes through mpcx_mpc_prepare_batch_stop). */
 int32_t mpcx_mpc_prepare_batch(mpcx_ctx *ctx, int32_t B, const double *state /*B,4: x,y,v,yaw*/,
                                const double *u_warm /*B,2,T or NULL*/,
                                const double *path_xyyaw /*npts,3*/, const double *path_v /*npts or NULL*/,
@@ -101,6 +102,22 @@ int32_t mpcx_mpc_prepare_batch_ov(mpcx_ctx *ctx, int32_t B, const double *state,
                                   const double *path_xyyaw, const double *path_v, const int32_t *path_off, const int32_t *path_len,
                                   double dl, int32_t *target_ind, const double *ov /*or NULL*/, int64_t ov_stride,
                                   double *xref, uint8_t *reaches_end, double *xbar);
+/* the same with the STOP INDEX of lib/mpc_with_speed.py:276-282, `set_trajectory_fromarray(trajectory_full, cutoff_idx)` as
+ * scenarios/mpc_intersection_new_ref.py:139 calls it: the path stays whole -- path_len[b] is the FULL length, the window is selected over
+ * it and reaches_end is against its last point -- and the speed reference is cv = v_ref, 0 from stop_idx[b] on:
+ *     xref[2, k] = idx_k >= stop_idx[b] ? 0 : (path_v ? path_v[idx_k] : v_ref).
+ * The reference's quirk is kept: stop_idx[b] == MPCX_NO_STOP (999) means "no stop" (`if cutoff_idx != 999`, :281) even where it came
+ * from a real conflict on a path of more than 999 points.  A stop index at or beyond the path length stops nothing either (that is what
+ * mpcx_interaction_batch's cut_len is for an agent without a conflict: its output is a valid stop_idx as it stands).
+ * len_seen (B or NULL, out) <- path_len[b]: the length of this step's tmp_trajectory, which the NEXT step's mpcx_interaction_batch takes as
+ * prev_cut_len (mpc_intersection_new_ref.py:98,131,136: tmp_trajectory = trajectory_full, so its "do not advance" test only bites on the
+ * last path point).  stop_idx = NULL: mpcx_mpc_prepare_batch_ov exactly (v_ref and len_seen are not read); else v_ref must be finite. */
+#define MPCX_NO_STOP 999
+int32_t mpcx_mpc_prepare_batch_stop(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm,
+                                    const double *path_xyyaw, const double *path_v, const int32_t *path_off, const int32_t *path_len,
+                                    double dl, int32_t *target_ind, const double *ov /*or NULL*/, int64_t ov_stride,
+                                    const int32_t *stop_idx /*B or NULL*/, double v_ref, int32_t *len_seen /*B or NULL*/,
+                                    double *xref, uint8_t *reaches_end, double *xbar);
 /* lib/mpc.py:226 `for _ in range(MAX_ITER)` inside mpcx_closed_loop_run: passes >= 1 (default 1 = the stock mpc_config.json) */
 int32_t mpcx_set_linearisation_passes(mpcx_ctx *ctx, int32_t passes);
 
@@ -394,12 +411,49 @@ int32_t mpcx_record_step_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
                                const int32_t *hit_idx /*P*/, const int32_t *status /*P*/, const int32_t *iters /*P*/,
                                int32_t n_obs_pool, const double *obs6 /*NOBS,6*/, const int32_t *obs_off /*P*/,
                                const int32_t *obs_cnt /*P*/, const int32_t *obs_skip /*P*/, const mpcx_run_log *log);
+/* the same with the goal test's len(self.cx) given per agent (goal_len, P; NULL = cut_len, mpcx_record_step_batch itself): the
+ * speed-reference loop keeps the whole path (goal_len = path_len) and logs its stop index in the cut_len column. */
+int32_t mpcx_record_step_batch_goal(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P,
+                                    const double *state, const double *applied, const double *x_sol,
+                                    const double *path_xyyaw, const int32_t *path_off, const int32_t *path_len,
+                                    const int32_t *target_ind, const int32_t *cut_len, const int32_t *traj_idx,
+                                    const int32_t *hit_idx, const int32_t *status, const int32_t *iters,
+                                    int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
+                                    const int32_t *obs_cnt, const int32_t *obs_skip, const int32_t *goal_len /*P or NULL*/,
+                                    const mpcx_run_log *log);
 /* mpcx_closed_loop_run with a run log: every step ends with the record stage.  The log travels beside the descriptor, not inside it:
  * mpcx_closed_loop keeps its size, so callers built against the struct as it was stay valid; the cached graph's key covers both.
  * log = NULL (or capacity 0 with every pointer NULL) is mpcx_closed_loop_run itself: the same launches with the same arguments.
  * Works with scripted traffic, with MPCX_SHARD_AGENTS (the pool is the all-gathered one) and with use_graph. */
 int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
                                     const mpcx_run_log *log, int32_t n_steps, int32_t use_graph);
+/* ---- how the ego yields to a conflict.  The reference has two ways, and so has the loop:
+ *   MPCX_STOP_CUT    scenarios/mpc_intersection.py: the path is cut in front of the conflict and the MPC runs into the path end.  What
+ *                    mpcx_closed_loop_run / mpcx_closed_loop_run_logged do (they forward here with opts = NULL).
+ *   MPCX_STOP_SPEED  scenarios/mpc_intersection_new_ref.py:90-159 with lib/mpc_with_speed.py: the path stays whole and the speed
+ *                    reference is zeroed from the conflict on.  The conflict search runs as before; what it writes to cl->cut_len is now
+ *                    the agent's STOP INDEX (the path length where there is no conflict: no stop; the work-queue key's "the cut moved" compares
+ *                    it with the stop index of the previous step),
+ *                    the window stage is mpcx_mpc_prepare_batch_stop with (cl->path_len, cl->cut_len as stop_idx, v_ref, prev_len as
+ *                    len_seen), the record stage is mpcx_record_step_batch_goal with goal_len = cl->path_len and logs the stop index in
+ *                    the cut_len column.  The conflict search's prev_cut_len is prev_len: caller-owned DEVICE memory, P int32,
+ *                    ZERO-INITIALISED before the batch's first step ("no tmp_trajectory yet") and set to path_len by every step --
+ *                    device memory, because a flag kept on the host would be frozen into a replayed graph.  cl->path_v, if given, is the
+ *                    speed profile in front of the stop index instead of v_ref.  Pair it with the constants of lib/mpc_with_speed.py
+ *                    (Q_v_yaw = (20, 0.5), w_perp 10, MAX_DECEL -5) in mpcx_set_mpc_params.
+ * Scripted traffic, linearisation passes, per-instance tuning, use_graph, the run log and MPCX_SHARD_AGENTS work in both modes.  The
+ * options travel beside the descriptor (mpcx_closed_loop keeps its size); the cached graph's key covers them.  An unknown stop_mode, a
+ * v_ref that is not finite or prev_len = NULL in MPCX_STOP_SPEED is MPCX_E_INVALID before anything is launched. */
+enum { MPCX_STOP_CUT = 0, MPCX_STOP_SPEED = 1 };
+typedef struct {
+    int32_t stop_mode;   /* MPCX_STOP_* */
+    int32_t reserved;
+    double v_ref;        /* MPCX_STOP_SPEED: the speed reference in front of the stop index (MAX_SPEED of lib/mpc_with_speed.py, 25 / 3.6) */
+    int32_t *prev_len;   /* MPCX_STOP_SPEED: P, zero-initialised, see above */
+} mpcx_closed_loop_opts;
+int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                  const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL = MPCX_STOP_CUT*/,
+                                  int32_t n_steps, int32_t use_graph);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

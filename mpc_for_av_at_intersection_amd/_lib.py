@@ -52,6 +52,16 @@ class RunLogC(C.Structure):
                 [(n, C.c_void_p) for n in ('rows_f64', 'rows_i32', 'steps', 'goal_step', 'contact_step', 'flags', 'min_clearance')])
 
 
+class ClosedLoopOptsC(C.Structure):
+    """mirror of mpcx_closed_loop_opts (include/mpcx.h); prev_len is a device address"""
+    _fields_ = [('stop_mode', C.c_int32), ('reserved', C.c_int32), ('v_ref', C.c_double), ('prev_len', C.c_void_p)]
+
+
+STOP_CUT, STOP_SPEED = 0, 1     # mpcx_closed_loop_opts.stop_mode
+STOP_MODES = {'cut': STOP_CUT, 'speed': STOP_SPEED}
+NO_STOP = 999                   # MPCX_NO_STOP: the stop index lib/mpc_with_speed.py:281 reads as "no stop"
+
+
 # the columns of a run-log row (rows_f64[s][q][0..7], rows_i32[s][q][0..5]; two reserved integer columns follow)
 RUN_LOG_F64 = ('x', 'y', 'v', 'yaw', 'accel', 'steer', 'xref_deviation', 'clearance')
 RUN_LOG_I32 = ('traj_idx', 'target_ind', 'cut_len', 'hit_idx', 'status', 'iters')
@@ -105,7 +115,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_closed_loop_run', 'mpcx_profile_qp', 'mpcx_profile_qp_read', 'mpcx_set_instance_tuning', 'mpcx_set_qp_solver', 'mpcx_qp_set_order_hint', 'mpcx_expand_multi_batch',
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
            'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
-           'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged']
+           'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
+           'mpcx_closed_loop_run_opts']
 
 
 def load():
@@ -168,5 +179,12 @@ def load():
     lib.mpcx_record_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 12 + [i32] + [vp] * 4 + [C.POINTER(RunLogC)]
     lib.mpcx_closed_loop_run_logged.restype = i32
     lib.mpcx_closed_loop_run_logged.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC), i32, i32]
+    lib.mpcx_mpc_prepare_batch_stop.restype = i32
+    lib.mpcx_mpc_prepare_batch_stop.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp, C.c_int64, vp, C.c_double, vp, vp, vp, vp]
+    lib.mpcx_record_step_batch_goal.restype = i32
+    lib.mpcx_record_step_batch_goal.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 12 + [i32] + [vp] * 5 + [C.POINTER(RunLogC)]
+    lib.mpcx_closed_loop_run_opts.restype = i32
+    lib.mpcx_closed_loop_run_opts.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                              C.POINTER(ClosedLoopOptsC), i32, i32]
     _lib = lib
     return lib

@@ -10,6 +10,8 @@ SCRIPTED cars (lib/moving_obstacles.py; `traffic=`): they are stepped on the dev
 the instance's rows of the obstacle pool with its agents. All state lives on the device.
 `run(n)` hands the whole loop to mpcx_closed_loop_run (n steps enqueued back to back, optionally as a replayed
 hipGraph); `step_staged()` drives the same kernels stage by stage through the per-stage entry points.
+`stop_mode='speed'` is the reference's NEWER scenario script (main/scenarios/mpc_intersection_new_ref.py with lib/mpc_with_speed.py): the
+path stays whole and the speed reference is zeroed from the conflict on, instead of the path being cut in front of it.
 `attach_log(capacity)` adds the RUN LOG: one more kernel at the end of every step writes the reference's History row, the goal test of
 its loop and the true clearance to the other vehicles, per agent, on the device (RunLog).
 """
@@ -73,6 +75,8 @@ class RunLog:
         off, ln = b.path_off.cpu().numpy().astype(np.int64), b.path_len.cpu().numpy().astype(np.int64)
         cut = b.inter['cut_len'].cpu().numpy().astype(np.int64)
         cut = np.where(cut > 0, cut, ln)            # len(self.cx): the full path until a step has cut it
+        if b.stop_mode == 'speed':
+            cut = ln                                # ... and always in speed mode (cut_len holds the stop index there)
         goal = path[off + ln - 1]
         st = self.initial
         there = ((np.hypot(st[:, 0] - goal[:, 0], st[:, 1] - goal[:, 1]) <= self.goal_dis) & (np.abs(b.target_ind.cpu().numpy() - cut) < 5) &
@@ -129,7 +133,8 @@ class IntersectionBatch:
     def __init__(self, ctx: Context, params: MpcParams, ip: InteractionParams, routes: Sequence[np.ndarray], dl: float,
                  route_of_agent: np.ndarray, start_index: np.ndarray, v0: Optional[np.ndarray] = None,
                  tuning: Optional[np.ndarray] = None, agent_shard: Optional[tuple] = None, exchange=None,
-                 pose_offset: Optional[np.ndarray] = None, traffic: Optional[Traffic] = None):
+                 pose_offset: Optional[np.ndarray] = None, traffic: Optional[Traffic] = None, stop_mode: str = 'cut',
+                 v_ref: Optional[float] = None, route_speed: Optional[Sequence[np.ndarray]] = None):
         """routes: list of (n_r, 3) paths whose yaw column is already unwrapped (MPC.__init__, mpc.py:257);
         route_of_agent, start_index: integer arrays of shape (B, A); tuning: optional (B, 16) or (B*A, 16) array of
         MpcParams.tuning_row()s -- one cost/limit set per instance (or agent), the batched form of the reference's
@@ -143,7 +148,25 @@ class IntersectionBatch:
         pose_offset: optional (B, A, 2) array (lateral offset [m] to the left of the path, heading error [rad]) added to the start
         poses, which otherwise sit exactly on the path (config2_batch).
         traffic: optional runtime.Traffic -- scripted cars per instance (scenarios/mpc_intersection.py:42-45), stepped on the device; the
-        pool then holds [A agents | K actors] per instance (runtime.traffic_pool_layout).  None: exactly the ego-only batch."""
+        pool then holds [A agents | K actors] per instance (runtime.traffic_pool_layout).  None: exactly the ego-only batch.
+        stop_mode: how an ego yields to a conflict.  'cut' (scenarios/mpc_intersection.py): its path is cut in front of the conflict.
+        'speed' (scenarios/mpc_intersection_new_ref.py:90-159 + lib/mpc_with_speed.py:276-282): the path stays whole, the conflict search's
+        cut index is the agent's STOP INDEX and the speed reference xref[2] is v_ref in front of it and 0 from it on (build `params` with
+        lib.mpc_with_speed.params(), whose speed weight 20 tracks it).  inter['cut_len'] and the run log's cut_len column then hold the
+        stop index, the path length where there is none (stop_index() gives it in the reference's own terms); the goal test is against
+        the whole path.  v_ref: default lib.mpc_with_speed.MAX_SPEED.
+        route_speed: optional speed profile, one array per route with one value per path point: xref[2] in front of the stop index (in
+        'cut' mode: everywhere) instead of v_ref (of 0 in 'cut' mode) -- the `cv` of lib/mpc_with_speed.MPC."""
+        if stop_mode not in _lib.STOP_MODES:
+            raise MpcxError('unknown stop_mode %r: \'cut\' or \'speed\' (MPCX_E_INVALID)' % (stop_mode,))
+        if v_ref is None:
+            from .lib.mpc_with_speed import MAX_SPEED as v_ref
+        if not np.isfinite(v_ref):
+            raise MpcxError('v_ref = %r is not finite (MPCX_E_INVALID)' % (v_ref,))
+        if route_speed is not None and (len(route_speed) != len(routes) or any(np.shape(v) != (len(r),) for v, r in zip(route_speed, routes))):
+            raise ValueError('route_speed: one array per route with one value per path point expected, got lengths %s for routes of %s points'
+                             % ([int(np.size(v)) for v in route_speed], [len(r) for r in routes]))
+        self.stop_mode, self.v_ref = stop_mode, float(v_ref)
         # (a copy: the arc-length table below belongs to THIS batch's paths)
         ip = dataclasses.replace(ip, max_path_len=max(int(ip.max_path_len), max(len(r) for r in routes)))     # sizes the interaction kernel's LDS
         self.ctx, self.params, self.ip, self.dl = ctx, params, ip, float(dl)
@@ -245,7 +268,13 @@ class IntersectionBatch:
                         kkt=torch.zeros((P, 4), dtype=f, device=dev))
         self.steps_done = 0
         self.lin_passes = 1          # lib/mpc.py MAX_ITER: (window, rollout, QP) passes per step; the stock mpc_config.json has 1
-        self.path_v = None
+        self.path_v = None if route_speed is None else ctx.f64(np.concatenate([np.asarray(v, dtype=np.float64) for v in route_speed]))
+        # speed mode: the length of the previous step's tmp_trajectory, which the conflict search reads: 0 = none yet, then the path length
+        # (mpc_intersection_new_ref.py:98,131,136).  On the device and set by the step itself: a replayed graph must see it change
+        self.prev_len = torch.zeros(P, dtype=torch.int32, device=dev) if stop_mode == 'speed' else None
+        self._opts = None
+        if stop_mode == 'speed':
+            self._opts = _lib.ClosedLoopOptsC(_lib.STOP_SPEED, 0, self.v_ref, self.prev_len.data_ptr())
         self.tuning = None
         if tuning is not None:
             tuning = np.asarray(tuning, dtype=np.float64)
@@ -322,7 +351,7 @@ class IntersectionBatch:
         if self._desc is None:
             self._desc = self._descriptor()
         self._claim_context()
-        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c)
+        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts)
         self.steps_done += n_steps
 
     def step(self):
@@ -362,19 +391,26 @@ class IntersectionBatch:
                 self.obs6.copy_(self.exchange(loc).reshape(-1, 6))
             else:
                 c.allgather_states(_lib.SHARD_AGENTS, loc, self.obs6)
+        speed = self.stop_mode == 'speed'
         c.interaction(self.ip, self.state, self.path, self.path_cs, self.path_off, self.path_len,
-                      self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self.obs_skip,
+                      self.prev_len if speed else self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self.obs_skip,
                       self.traj_idx, out=self.inter)
         # the previous solution (zeros where the last solve failed or on the first step) is the warm start
         for it in range(self.lin_passes):       # lib/mpc.py:226-237: from the second pass on the previous pass's speeds space the window
-            c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.inter['cut_len'], self.dl, self.target_ind, out=self.pre,
-                      x_prev=self.sol['x'] if it else None)
+            if speed:       # the whole path + the stop index (mpcx_mpc_prepare_batch_stop).  len_seen is a side effect the NEXT step
+                            # relies on: the window kernel leaves the path length in prev_len, which the next interaction() reads
+                c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.path_len, self.dl, self.target_ind, out=self.pre,
+                          path_v=self.path_v, x_prev=self.sol['x'] if it else None, stop_idx=self.inter['cut_len'], v_ref=self.v_ref,
+                          len_seen=self.prev_len)
+            else:
+                c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.inter['cut_len'], self.dl, self.target_ind, out=self.pre,
+                          path_v=self.path_v, x_prev=self.sol['x'] if it else None)
             c.qp_solve(self.state, self.pre['xref'], self.pre['xbar'], self.pre['reaches_end'], self.sol['u'], out=self.sol)
         c.plant_step(self.state, self.sol['u'], self.sol['status'], self.applied)
         if self.log is not None:
             c.record_step(self.ip, self.state, self.applied, self.sol['x'], self.path, self.path_off, self.path_len, self.target_ind,
                           self.inter['cut_len'], self.traj_idx, self.inter['hit_idx'], self.sol['status'], self.sol['iters'], self.obs6,
-                          self.obs_off, self.obs_cnt, self.obs_skip, self.log.c)
+                          self.obs_off, self.obs_cnt, self.obs_skip, self.log.c, goal_len=self.path_len if speed else None)
         self.steps_done += 1
 
     def snapshot(self):
@@ -382,7 +418,7 @@ class IntersectionBatch:
         self.ctx.synchronize()
         keys = ('state', 'applied', 'traj_idx', 'target_ind')
         out = {k: getattr(self, k).cpu().numpy().copy() for k in keys}
-        out['prev_cut'] = self.inter['cut_len'].cpu().numpy().copy()
+        out['prev_cut'] = (self.prev_len if self.stop_mode == 'speed' else self.inter['cut_len']).cpu().numpy().copy()
         out.update({k: v.cpu().numpy().copy() for k, v in self.sol.items()})
         out.update({k: v.cpu().numpy().copy() for k, v in self.inter.items()})
         out.update({k: v.cpu().numpy().copy() for k, v in self.pre.items()})
@@ -390,6 +426,15 @@ class IntersectionBatch:
             out['traffic_state'] = self.traffic_state.cpu().numpy().copy()
             out['obs6'] = self.obs6.cpu().numpy().copy()
         return out
+
+    def stop_index(self) -> np.ndarray:
+        """speed mode: the agents' stop indices of the last step in the reference's own terms (the `cutoff_idx` of
+        mpc_intersection_new_ref.py:122-139): the conflict search's cut index where it found a conflict, _lib.NO_STOP (999) where it
+        did not (synchronises).  The device keeps the path length for "no conflict" -- a stop index nothing reaches."""
+        if self.stop_mode != 'speed':
+            raise MpcxError('stop_index(): the batch runs with stop_mode=%r' % self.stop_mode)
+        self.ctx.synchronize()
+        return np.where(self.inter['hit_idx'].cpu().numpy() >= 0, self.inter['cut_len'].cpu().numpy(), _lib.NO_STOP).astype(np.int32)
 
 
 def stock_routes(ctx: Context, pairs=((1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (3, 2), (4, 1), (4, 2))):
@@ -417,13 +462,13 @@ def stock_routes(ctx: Context, pairs=((1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (3
 
 def synthetic_batch(ctx: Context, B: int, A: int = 8, T: int = 20, seed: int = 0, routes=None, dl=None, cd=None,
                     max_start_frac: float = 0.35, instance_slice: Optional[tuple] = None, agent_shard: Optional[tuple] = None,
-                    exchange=None, mpc: Optional[MpcParams] = None):
+                    exchange=None, mpc: Optional[MpcParams] = None, stop_mode: str = 'cut', v_ref: Optional[float] = None, route_speed=None):
     """B instances x A agents on the stock intersection, one agent per (arm, manoeuvre)
     route, start positions staggered along the approach (seeded), v0 = 0 as in the reference's scripts.
     The workload is a function of (B, A, seed) only; a rank takes its part of it with instance_slice = (lo, hi)
     (instance-sharded) or agent_shard = (rank, world) (agent-sharded, see IntersectionBatch).
     `mpc` replaces the stock controller constants (its T wins over the argument; the wheelbase is always the car's), e.g.
-    MpcParams.jerk() for the controller of lib/mpc_jerk.py."""
+    MpcParams.jerk() for the controller of lib/mpc_jerk.py.  stop_mode, v_ref, route_speed: see IntersectionBatch."""
     if routes is None:
         routes, dl, cd = stock_routes(ctx)
     rng = np.random.default_rng(seed)
@@ -440,7 +485,8 @@ def synthetic_batch(ctx: Context, B: int, A: int = 8, T: int = 20, seed: int = 0
         params = dataclasses.replace(mpc, L=cd.distance_back_to_front_wheel)
     ip = InteractionParams(cutoff_margin=4 * int(np.ceil(cd.radius / dl)), L=cd.distance_back_to_front_wheel, radius=cd.radius,
                            circle_centers=np.asarray(cd.circle_centers).ravel())
-    return IntersectionBatch(ctx, params, ip, routes, dl, route_of_agent, start, agent_shard=agent_shard, exchange=exchange)
+    return IntersectionBatch(ctx, params, ip, routes, dl, route_of_agent, start, agent_shard=agent_shard, exchange=exchange,
+                             stop_mode=stop_mode, v_ref=v_ref, route_speed=route_speed)
 
 
 def scripted_traffic_specs(B: int, K: int, seed: int, L: float, dt: float = 0.2):
@@ -472,28 +518,36 @@ def scripted_traffic_specs(B: int, K: int, seed: int, L: float, dt: float = 0.2)
     return Traffic(actors, state, np.full(B, K, dtype=np.int64))
 
 
-def scripted_traffic_batch(ctx: Context, B: int, T: int = 20, seed: int = 0, A: int = 1, K: int = 2, routes=None, dl=None, cd=None,
-                           max_start_frac: float = 0.35, instance_slice: Optional[tuple] = None, mpc: Optional[MpcParams] = None,
-                           stock_route: int = 6):
-    """The reference's stock scenario (scenarios/mpc_intersection.py: one ego + two scripted cars that never yield) as a seeded family of
-    B instances: the ego's route uniform over the stock routes, A - 1 further egos on the other arms (every ego yields to every other, as
-    in synthetic_batch: start positions staggered along the approach, v0 = 0), K scripted T-intersection cars per instance
-    (scripted_traffic_specs).  Instance 0 is ALWAYS the stock set: route `stock_route` of `routes` ((4, 1) of stock_routes), started at
-    the first path point, with the stock pair of cars.  A function of (B, seed) only (for given A, K), so a rank takes its part with
-    instance_slice = (lo, hi)."""
-    if routes is None:
-        routes, dl, cd = stock_routes(ctx)
-    R = len(routes)
+def scripted_traffic_layout(B: int, A: int, route_lens, seed: int, max_start_frac: float = 0.35, stock_route: int = 6):
+    """the egos of scripted_traffic_batch (host arrays only, no GPU needed): (route_of_agent, start_index), both (B, A), drawn with
+    numpy.random.default_rng([seed, 0]) for routes of route_lens points; instance 0 is the stock set"""
+    R = len(route_lens)
     rng = np.random.default_rng([seed, 0])
     first = rng.integers(0, R, size=B)
     if B:
         first[0] = min(stock_route, R - 1)
     a = np.arange(A)
     route_of_agent = (first[:, None] + 2 * a[None, :] + (2 * a[None, :]) // R) % R        # the next arm first, then the other manoeuvre
-    lens = np.array([len(r) for r in routes])[route_of_agent]
+    lens = np.asarray(route_lens)[route_of_agent]
     start = (rng.random((B, A)) * max_start_frac * lens).astype(np.int64)
     if B:
         start[0, 0] = 0
+    return route_of_agent, start
+
+
+def scripted_traffic_batch(ctx: Context, B: int, T: int = 20, seed: int = 0, A: int = 1, K: int = 2, routes=None, dl=None, cd=None,
+                           max_start_frac: float = 0.35, instance_slice: Optional[tuple] = None, mpc: Optional[MpcParams] = None,
+                           stock_route: int = 6, stop_mode: str = 'cut', v_ref: Optional[float] = None, route_speed=None):
+    """The reference's stock scenario (scenarios/mpc_intersection.py: one ego + two scripted cars that never yield) as a seeded family of
+    B instances: the ego's route uniform over the stock routes, A - 1 further egos on the other arms (every ego yields to every other, as
+    in synthetic_batch: start positions staggered along the approach, v0 = 0), K scripted T-intersection cars per instance
+    (scripted_traffic_specs).  Instance 0 is ALWAYS the stock set: route `stock_route` of `routes` ((4, 1) of stock_routes), started at
+    the first path point, with the stock pair of cars.  A function of (B, seed) only (for given A, K), so a rank takes its part with
+    instance_slice = (lo, hi).  stop_mode, v_ref, route_speed: see IntersectionBatch -- with stop_mode='speed' and
+    mpc=lib.mpc_with_speed.params(cd, 0.2) the family of the reference's newer script, scenarios/mpc_intersection_new_ref.py."""
+    if routes is None:
+        routes, dl, cd = stock_routes(ctx)
+    route_of_agent, start = scripted_traffic_layout(B, A, [len(r) for r in routes], seed, max_start_frac, stock_route)
     params = MpcParams(T=T, L=cd.distance_back_to_front_wheel) if mpc is None else dataclasses.replace(mpc, L=cd.distance_back_to_front_wheel)
     traffic = scripted_traffic_specs(B, K, seed, cd.distance_back_to_front_wheel, dt=params.dt)
     if instance_slice is not None:
@@ -501,7 +555,8 @@ def scripted_traffic_batch(ctx: Context, B: int, T: int = 20, seed: int = 0, A: 
         route_of_agent, start, traffic = route_of_agent[lo:hi], start[lo:hi], traffic.slice(lo, hi)
     ip = InteractionParams(cutoff_margin=4 * int(np.ceil(cd.radius / dl)), L=cd.distance_back_to_front_wheel, radius=cd.radius,
                            circle_centers=np.asarray(cd.circle_centers).ravel())
-    return IntersectionBatch(ctx, params, ip, routes, dl, route_of_agent, start, traffic=traffic)
+    return IntersectionBatch(ctx, params, ip, routes, dl, route_of_agent, start, traffic=traffic, stop_mode=stop_mode, v_ref=v_ref,
+                             route_speed=route_speed)
 
 
 _PLAN_CACHE = {}

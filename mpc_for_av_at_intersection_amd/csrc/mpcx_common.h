@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[896] = {};     // descriptor + run log + parameters the cached graph was captured for
+    unsigned char loop_key[960] = {};     // descriptor + run log + options + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -64,6 +64,9 @@ struct mpcx_interaction_extras {
     const int32_t *ego_row = nullptr, *actor_row = nullptr;
     int32_t n_ego = 0, n_actors = 0;
     int32_t *prev_save = nullptr;       // where the cut lengths as read are left (the queue order's `moved` test)
+    // speed-reference mode: prev_cut_len is the previous PATH length there and cut_len holds the stop index, so the `moved` test and
+    // prev_save read the previous stop index from here (the cut_len buffer itself, before it is rewritten); nullptr: prev_cut_len
+    const int32_t *key_prev = nullptr;
     // the conflict search and the window selection both run calc_nearest_index_in_direction for the same agent, state and path, mostly
     // from the same start index.  The conflict search leaves (its start index, the largest, the smallest of its three nearest indices
     // or -1) here, 3 ints per agent, and the window selection takes the conflict search's answer where that is provably its own.
@@ -74,6 +77,11 @@ struct mpcx_window_extras {
     bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
     const int32_t *near = nullptr, *tidx = nullptr;   // mpcx_interaction_extras::near and the conflict search's updated traj_idx
     bool rollout_forked = false;        // the rollout of this step is in flight on the side stream already (mpcx_rollout_fork)
+    // mpcx_mpc_prepare_batch_stop: the stop index per agent (nullptr: none, the two below are not read), the speed reference in front of
+    // it and where the window kernel leaves the path length it saw
+    const int32_t *stop_idx = nullptr;
+    double v_ref = 0.0;
+    int32_t *len_seen = nullptr;
 };
 struct mpcx_qp_order {                  // where the work-queue order of a solve comes from
     bool ready = false;                 // it is in ctx->order already and the ticket is zero (mpcx_window_extras::scatter)
@@ -111,7 +119,8 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
                             const double *x_sol, const double *path_xyyaw, const int32_t *path_off, const int32_t *path_len,
                             const int32_t *target_ind, const int32_t *cut_len, const int32_t *traj_idx, const int32_t *hit_idx,
                             const int32_t *status, const int32_t *iters, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
-                            const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log);
+                            const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log,
+                            const int32_t *goal_len = nullptr);      // goal_len: mpcx_record_step_batch_goal
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

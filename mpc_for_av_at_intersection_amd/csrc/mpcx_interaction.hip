@@ -88,6 +88,7 @@ struct InterArgs {
     int32_t *prev_save;   // optional: the previous cut length as read (cut_len may alias prev_cut and is overwritten)
     const int32_t *bin_hint;   // optional (closed loop): file the agent under its work-queue key: bin_cnt[p % COPIES][key]++ -> slot, keyslot[p] = key << 24 | slot
     int32_t *bin_cnt, *keyslot;
+    const int32_t *key_prev;   // optional (closed loop, speed-reference mode): what the work-queue key's "moved" test and prev_save take as the previous value of cut_len instead of prev_cut (there prev_cut is the previous PATH length and cut_len the stop index); may alias cut_len
     int32_t *near;        // optional (closed loop): near[3p] = the start index of this agent's nearest-index scan, near[3p+1] / [3p+2] = the largest / smallest of its three nearest indices (absolute), -1 = none
 };
 
@@ -321,12 +322,13 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     int tidx = a.traj_idx[p];
     bool advance = true;
     const int pcut = a.prev_cut ? a.prev_cut[p] : 0;
-    if (a.prev_save && lane == 0) a.prev_save[p] = pcut;
+    const int kprev = a.key_prev ? a.key_prev[p] : pcut;
+    if (a.prev_save && lane == 0) a.prev_save[p] = kprev;
     if (a.near && lane == 0) { a.near[3 * p] = tidx; a.near[3 * p + 1] = -1; a.near[3 * p + 2] = -1; }       // until the scan below has an answer
     // lane 0, next to every store of cut_len: the agent's place in the QP work queue of this step
     auto file_key = [&](int cl) {
         if (a.bin_cnt) {
-            const int k = order_key_of(a.bin_hint ? a.bin_hint[p] : 0, cl != pcut);
+            const int k = order_key_of(a.bin_hint ? a.bin_hint[p] : 0, cl != kprev);
             a.keyslot[p] = (k << 24) | atomicAdd(&a.bin_cnt[(p % MPCX_ORDER_COPIES) * MPCX_ORDER_BINS + k], 1);
         }
     };
@@ -859,7 +861,7 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     mpcx::InterArgs ia{*ip, P, state, path_xyyaw, path_cs, path_off, path_len, prev_cut_len, ctx->pred,
                        obs_off, obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, max_rem, fcap, x.prev_save,
                        x.bin_hint, x.bin_hint ? ctx->bins : nullptr, x.bin_hint ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr,
-                       x.near};
+                       x.key_prev, x.near};
     hipLaunchKernelGGL(mpcx::interaction_kernel, dim3(P), dim3(64), lds, ctx->stream, ia);
     return mpcx_check_launch(ctx, "interaction kernels");
 }

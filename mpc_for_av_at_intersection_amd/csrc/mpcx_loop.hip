@@ -1,10 +1,13 @@
 // mpcx_loop.hip -- the reference's scenario loop body (main/scenarios/mpc_intersection.py:95-159) for P agents as a
-// device-resident pipeline: n_steps x [scripted traffic rows -> pool pack -> predict -> conflict search + path cut -> reference window ->
+// device-resident pipeline (and, with MPCX_STOP_SPEED, that of main/scenarios/mpc_intersection_new_ref.py:90-159: the same stages, the
+// path kept whole and the speed reference zeroed from the conflict on):
+// n_steps x [scripted traffic rows -> pool pack -> predict -> conflict search + path cut -> reference window ->
 // rollout -> QP -> plant (-> run-log record, iff a log is attached)], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
 // host synchronisation or host arithmetic in between.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
 #include "mpcx_common.h"
+#include <cmath>
 #include <cstring>
 
 namespace mpcx {
@@ -43,8 +46,14 @@ static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego
 static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cut + P; }
 
 // log: the run log's descriptor or nullptr = none (then exactly the launches of a step without one)
-static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log) {
+// o: the options (never nullptr here).  MPCX_STOP_SPEED changes three arguments of a step and no launch: the conflict search reads the length
+// of the previous tmp_trajectory from o->prev_len (0 before the batch's first step, the path length afterwards -- the window kernel sets it,
+// device memory, so a replayed graph sees it change), its cut index in c->cut_len is the window stage's stop index over the whole path, and
+// the record stage tests the goal against the whole path.
+static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
+                            const mpcx_closed_loop_opts *o) {
     const int P = c->P;
+    const bool speed = o->stop_mode == MPCX_STOP_SPEED;
     ctx->bins_clean = false;        // until the plant kernel of this step is enqueued
     int32_t rc, pool_rows = P;
     // the warm-start rollout of this step needs only the states and the previous solution: it runs on the side stream BESIDE the pool pack,
@@ -59,6 +68,7 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     ix.prev_save = ctx->prev_cut;
     ix.near = near_hints(ctx, P);
     ix.bin_hint = binned ? c->iters : nullptr;
+    if (speed) ix.key_prev = c->cut_len;        // "the cut moved" = the stop index moved
     if (c->exchange == MPCX_SHARD_AGENTS) {
         // agent-sharded layout: this rank's rows travel to every rank, every rank assembles the whole pool (one RCCL all-gather)
         mpcx::PackArgs pa{P, c->state, c->applied, c->obs_local};
@@ -80,7 +90,7 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         }
     }
     rc = mpcx_interaction_enqueue(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
-                                  c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows, c->obs6,
+                                  speed ? o->prev_len : c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows, c->obs6,
                                   c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len, ix);
     if (rc != MPCX_OK) return rc;
     // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
@@ -90,8 +100,9 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     for (int pass = 0; pass < ctx->lin_passes; pass++) {
         const bool first = pass == 0;
         // the first pass writes the queue order and joins the rollout forked above; a later one forks its own
-        const mpcx_window_extras wx{binned && first, near_hints(ctx, P), c->traj_idx, first};
-        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, c->cut_len, c->dl,
+        mpcx_window_extras wx{binned && first, near_hints(ctx, P), c->traj_idx, first};
+        if (speed) { wx.stop_idx = c->cut_len; wx.v_ref = o->v_ref; wx.len_seen = o->prev_len; }
+        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
                                  c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar, wx);
         if (rc != MPCX_OK) return rc;
         // (further linearisation passes build their order in line, from the iteration counts of the pass before)
@@ -105,14 +116,24 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (rc != MPCX_OK || !log) return rc;
     // the run log: one row per agent from the buffers as the step leaves them; the pool still holds the rows this step's conflict search saw
     return mpcx_record_enqueue(ctx, ip, P, c->state, c->applied, c->x_sol, c->path_xyyaw, c->path_off, c->path_len, c->target_ind, c->cut_len,
-                               c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, log);
+                               c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, log,
+                               speed ? c->path_len : nullptr);
 }
 
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                               int32_t n_steps, int32_t use_graph) {
+                               const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
+    // the options as the graph's key holds them: nullptr and a cut-mode struct, whatever its other fields say, are the same run
+    mpcx_closed_loop_opts opt = {};
+    if (opts && opts->stop_mode != MPCX_STOP_CUT) {     // refused before anything is launched, whatever n_steps is
+        if (opts->stop_mode != MPCX_STOP_SPEED)
+            return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: unknown stop mode %d (MPCX_STOP_CUT or MPCX_STOP_SPEED)", opts->stop_mode);
+        if (!std::isfinite(opts->v_ref)) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: MPCX_STOP_SPEED with a speed reference v_ref that is not finite");
+        if (!opts->prev_len) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: MPCX_STOP_SPEED needs prev_len (P zero-initialised int32)");
+        opt.stop_mode = MPCX_STOP_SPEED; opt.v_ref = opts->v_ref; opt.prev_len = opts->prev_len;
+    }
     if (mpcx_record_absent(log)) log = nullptr;
     if (log) {          // refused before anything is launched, whatever n_steps is
         const int32_t lrc = mpcx_record_validate(ctx, log, c->obs_skip);
@@ -184,7 +205,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log);
+            rc = enqueue_step(ctx, ip, c, log, &opt);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -194,13 +215,15 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_interaction_params) + sizeof(mpcx_mpc_params) + 9 * sizeof(void *) <= sizeof key,
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_interaction_params) + sizeof(mpcx_mpc_params) +
+                  9 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
     size_t o = 0;
     memcpy(key + o, c, sizeof *c); o += sizeof *c;
     if (log) memcpy(key + o, log, sizeof *log);     // (zeros = no log: a graph captured without the record stage)
     o += sizeof *log;
+    memcpy(key + o, &opt, sizeof opt); o += sizeof opt;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
     memcpy(key + o, &ctx->pred, sizeof ctx->pred); o += sizeof ctx->pred;
@@ -220,7 +243,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log);
+        rc = enqueue_step(ctx, ip, c, log, &opt);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -237,10 +260,15 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                             const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, n_steps, use_graph);
 }

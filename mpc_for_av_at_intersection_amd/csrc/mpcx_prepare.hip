@@ -8,6 +8,7 @@
 // Arithmetic follows the reference's operation order; products are kept un-fused (-ffp-contract is
 // irrelevant here because every product/sum below goes through __dmul_rn/__dadd_rn where order matters).
 #include "mpcx_common.h"
+#include <cmath>
 
 namespace mpcx {
 
@@ -27,6 +28,12 @@ struct RefArgs {
     // closed loop: the conflict search ran the same nearest-index scan for this agent (same state, same path) from near[3b]; near[3b+1] /
     // [3b+2] = the largest / smallest of its three nearest indices or -1, near_tidx[b] = its answer.  nullptr: always scan
     const int32_t *near, *near_tidx;
+    // the stop index of lib/mpc_with_speed.py:276-282 (set_trajectory_fromarray(trajectory_full, cutoff_idx)): the window runs over the
+    // agent's WHOLE path and cv = v_ref, 0 from stop_idx[b] on -- unless stop_idx[b] == 999, the reference's "no stop" (:281), whatever
+    // the length of the path.  nullptr: no stop index (then the host passes v_ref = 0, today's xref[2] without a profile)
+    const int32_t *stop_idx;
+    double v_ref;
+    int32_t *len_seen;      // with a stop index: <- n, the length of this step's tmp_trajectory (the next conflict search's prev_cut_len), or nullptr
 };
 
 __device__ __forceinline__ void ref_window_block(const RefArgs &a, int b) {
@@ -65,6 +72,12 @@ __device__ __forceinline__ void ref_window_block(const RefArgs &a, int b) {
     if (hm >= 0 && start >= hs && hl >= start && hm < n) s = a.near_tidx[b];
     else s = (start < 0 || n <= 0) ? -1 : nearest_index_in_direction(path, n, start, x, y, lane);
     if (lane == 0) a.target_ind[b] = s;
+    int stop = 0x7fffffff;
+    if (a.stop_idx) {
+        const int c = a.stop_idx[b];
+        stop = c == MPCX_NO_STOP ? stop : c;
+        if (a.len_seen && lane == 0) a.len_seen[b] = n;
+    }
     double *xr = a.xref + (size_t)b * 4 * W;
     uint8_t *re = a.re + (size_t)b * W;
     if (s < 0) {  // reference raised: leave a defined (zero) window, caller sees target_ind = -1
@@ -83,7 +96,7 @@ __device__ __forceinline__ void ref_window_block(const RefArgs &a, int b) {
         if (idx > n - 1) idx = n - 1;
         xr[0 * W + lane] = path[3 * idx];
         xr[1 * W + lane] = path[3 * idx + 1];
-        xr[2 * W + lane] = pv ? pv[idx] : 0.0;
+        xr[2 * W + lane] = idx >= stop ? 0.0 : (pv ? pv[idx] : a.v_ref);
         xr[3 * W + lane] = path[3 * idx + 2];
         re[lane] = (idx == n - 1);
     }
@@ -220,6 +233,16 @@ extern "C" int32_t mpcx_mpc_prepare_batch_ov(mpcx_ctx *ctx, int32_t B, const dou
     return mpcx_window_enqueue(ctx, B, state, u_warm, path_xyyaw, path_v, path_off, path_len, dl, target_ind, ov, ov_stride, xref, reaches_end, xbar, {});
 }
 
+extern "C" int32_t mpcx_mpc_prepare_batch_stop(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm,
+                                               const double *path_xyyaw, const double *path_v, const int32_t *path_off,
+                                               const int32_t *path_len, double dl, int32_t *target_ind, const double *ov, int64_t ov_stride,
+                                               const int32_t *stop_idx, double v_ref, int32_t *len_seen,
+                                               double *xref, uint8_t *reaches_end, double *xbar) {
+    mpcx_window_extras wx;
+    wx.stop_idx = stop_idx; wx.v_ref = v_ref; wx.len_seen = len_seen;
+    return mpcx_window_enqueue(ctx, B, state, u_warm, path_xyyaw, path_v, path_off, path_len, dl, target_ind, ov, ov_stride, xref, reaches_end, xbar, wx);
+}
+
 int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, const double *path_xyyaw, const double *path_v,
                             const int32_t *path_off, const int32_t *path_len, double dl, int32_t *target_ind, const double *ov, int64_t ov_stride,
                             double *xref, uint8_t *reaches_end, double *xbar, const mpcx_window_extras &x) {
@@ -230,9 +253,11 @@ int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const
         return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch: null pointer, negative batch or dl <= 0");
     if (ov && ov_stride < (int64_t)ctx->mpc.T + 1)
         return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch_ov: ov_stride %lld is smaller than T + 1", (long long)ov_stride);
+    if (x.stop_idx && !std::isfinite(x.v_ref))
+        return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch_stop: v_ref is not finite");
     mpcx::RefArgs ra{ctx->mpc, B, state, path_xyyaw, path_v, path_off, path_len, dl, target_ind, xref, reaches_end, ov, (long)ov_stride,
                      x.scatter ? ctx->bins : nullptr, x.scatter ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr, x.scatter ? ctx->order : nullptr,
-                     x.near, x.near ? x.tidx : nullptr};
+                     x.near, x.near ? x.tidx : nullptr, x.stop_idx, x.stop_idx ? x.v_ref : 0.0, x.stop_idx ? x.len_seen : nullptr};
     // the rollout may already be in flight: mpcx_closed_loop_run forks it at the start of the step, beside the conflict search
     const bool forked = x.rollout_forked;
     if (!forked) {

@@ -54,7 +54,7 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
                             const double *x_sol, const double *path_xyyaw, const int32_t *path_off, const int32_t *path_len,
                             const int32_t *target_ind, const int32_t *cut_len, const int32_t *traj_idx, const int32_t *hit_idx,
                             const int32_t *status, const int32_t *iters, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
-                            const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log) {
+                            const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log, const int32_t *goal_len) {
     mpcx::RecordArgs a;
     a.P = P; a.n_pool = n_obs_pool;
     a.x_stride = 4 * (int64_t)(ctx->mpc.T + 1);
@@ -65,6 +65,7 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
     a.hit_idx = hit_idx; a.status = status; a.iters = iters;
     a.obs_off = obs_off; a.obs_cnt = obs_cnt; a.obs_skip = obs_skip;
     a.log = *log;
+    a.goal_len = goal_len;
     hipLaunchKernelGGL(mpcx::record_kernel, dim3((P + 63) / 64), dim3(64), 0, ctx->stream, a);
     return mpcx_check_launch(ctx, "record_kernel");
 }
@@ -75,6 +76,16 @@ extern "C" int32_t mpcx_record_step_batch(mpcx_ctx *ctx, const mpcx_interaction_
                                           const int32_t *traj_idx, const int32_t *hit_idx, const int32_t *status, const int32_t *iters,
                                           int32_t n_obs_pool, const double *obs6, const int32_t *obs_off, const int32_t *obs_cnt,
                                           const int32_t *obs_skip, const mpcx_run_log *log) {
+    return mpcx_record_step_batch_goal(ctx, ip, P, state, applied, x_sol, path_xyyaw, path_off, path_len, target_ind, cut_len, traj_idx, hit_idx,
+                                       status, iters, n_obs_pool, obs6, obs_off, obs_cnt, obs_skip, nullptr, log);
+}
+
+extern "C" int32_t mpcx_record_step_batch_goal(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state,
+                                          const double *applied, const double *x_sol, const double *path_xyyaw, const int32_t *path_off,
+                                          const int32_t *path_len, const int32_t *target_ind, const int32_t *cut_len,
+                                          const int32_t *traj_idx, const int32_t *hit_idx, const int32_t *status, const int32_t *iters,
+                                          int32_t n_obs_pool, const double *obs6, const int32_t *obs_off, const int32_t *obs_cnt,
+                                          const int32_t *obs_skip, const int32_t *goal_len, const mpcx_run_log *log) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || P < 0 || n_obs_pool < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "record_step_batch: null parameters or negative size");
@@ -85,5 +96,5 @@ extern "C" int32_t mpcx_record_step_batch(mpcx_ctx *ctx, const mpcx_interaction_
         !status || !iters || !obs6 || !obs_off || !obs_cnt)
         return mpcx_fail(ctx, MPCX_E_INVALID, "record_step_batch: null buffer");
     return mpcx_record_enqueue(ctx, ip, P, state, applied, x_sol, path_xyyaw, path_off, path_len, target_ind, cut_len, traj_idx, hit_idx,
-                               status, iters, n_obs_pool, obs6, obs_off, obs_cnt, obs_skip, log);
+                               status, iters, n_obs_pool, obs6, obs_off, obs_cnt, obs_skip, log, goal_len);
 }

@@ -20,7 +20,9 @@
 //   steps          rows offered so far = the agent's write cursor.  Device memory, one word per agent: the launch carries no step index
 //                  (a replayed hipGraph keeps advancing), and no lane reads a word another lane writes.
 //   goal_step      steps taken when mpc.is_goal (main/lib/mpc.py:310-326) first held, else -1: goal = the LAST point of the agent's full
-//                  path, len(self.cx) = this step's cut_len, self.target_ind = this step's target_ind, state after the plant step.  After
+//                  path, len(self.cx) = this step's cut_len (goal_len[q] where goal_len is given: the speed-reference loop of
+//                  main/scenarios/mpc_intersection_new_ref.py keeps the whole path, len(self.cx) = path_len, and the cut_len column holds
+//                  its stop index), self.target_ind = this step's target_ind, state after the plant step.  After
 //                  step s that is the reference's test at the top of iteration s + 1, so goal_step is the reference's number of loop
 //                  iterations.  Set once.
 //   flags, contact_step, min_clearance   AFTER SEPARATION: flags bit 0 = "has been clear" (a step with clearance >= 0 was seen);
@@ -53,6 +55,7 @@ struct RecordArgs {
     const int32_t *path_off, *path_len, *target_ind, *cut_len, *traj_idx, *hit_idx, *status, *iters;
     const int32_t *obs_off, *obs_cnt, *obs_skip;
     mpcx_run_log log;
+    const int32_t *goal_len = nullptr;      // len(self.cx) of the goal test per agent; nullptr: cut_len
 };
 
 MPCX_REC_FN void rec_sincos(double a, double *s, double *c) {
@@ -139,7 +142,7 @@ MPCX_REC_FN int32_t record_agent(const RecordArgs &a, int q, double *f, int32_t 
     const int32_t s = a.log.steps[q];
     if (a.log.goal_step[q] < 0 && len > 0) {
         const double *g = a.path_xyyaw + 3 * ((size_t)off + len - 1);
-        if (rec_is_goal(st[0], st[1], st[2], g[0], g[1], target, cut, a.log.goal_dis, a.log.stop_speed)) a.log.goal_step[q] = s + 1;
+        if (rec_is_goal(st[0], st[1], st[2], g[0], g[1], target, a.goal_len ? a.goal_len[q] : cut, a.log.goal_dis, a.log.stop_speed)) a.log.goal_step[q] = s + 1;
     }
     int32_t flags = a.log.flags[q], contact = a.log.contact_step[q];
     double minc = a.log.min_clearance[q];

@@ -32,7 +32,9 @@ MAX_SPEED = 25 / 3.6
 W_PERP, W_PARA = 10., 1.0          # literals inside _linear_mpc_control (:161,165)
 
 
-def _params(car_dimensions, dt) -> MpcParams:
+def params(car_dimensions, dt) -> MpcParams:
+    """this module's constants as they stand (T, weights, limits) as an MpcParams: what MPC.step hands the device, and what a batch of the
+    speed-reference scenario is built with (batch.IntersectionBatch(..., stop_mode='speed'))"""
     g = globals()
     Tn = int(g['T'])
     return MpcParams(T=Tn, dt=float(dt), L=float(car_dimensions.distance_back_to_front_wheel), w_perp=W_PERP, w_para=W_PARA,
@@ -40,6 +42,9 @@ def _params(car_dimensions, dt) -> MpcParams:
                      Qf_base=tuple(np.diag(np.asarray(g['Qf'], float)) / Tn), max_speed=float(Simulation.MAX_SPEED),
                      min_speed=float(Simulation.MIN_SPEED), max_accel=float(g['MAX_ACCEL']), max_decel=float(g['MAX_DECEL']),
                      max_steer=float(Simulation.MAX_STEER), max_dsteer=float(g['MAX_DSTEER']))
+
+
+_params = params      # the name it had before it became public; tests/test_gpu_callsurface.py still calls it
 
 
 class MPC:
@@ -63,7 +68,7 @@ class MPC:
 
     def step(self, state: State) -> Tuple[float, float]:
         ctx = self._ctx
-        p = _params(self.car_dimensions, self.dt)
+        p = params(self.car_dimensions, self.dt)
         if ctx.params != p:
             ctx.set_mpc_params(p)
         x0 = ctx.f64([[state.x, state.y, state.v, state.yaw]])

@@ -397,10 +397,14 @@ class Context:
         return out
 
     @_ordered
-    def prepare(self, state, u_warm, path, path_off, path_len, dl, target_ind, out=None, path_v=None, x_prev=None):
+    def prepare(self, state, u_warm, path, path_off, path_len, dl, target_ind, out=None, path_v=None, x_prev=None, stop_idx=None,
+                v_ref=0.0, len_seen=None):
         """mpcx_mpc_prepare_batch. target_ind is updated in place. Returns dict(xref, reaches_end, xbar).
         x_prev (B, 4, T+1): the previous linearisation pass's states -- its speeds space the reference window (lib/mpc.py:226-237,
-        MAX_ITER > 1; mpcx_mpc_prepare_batch_ov)."""
+        MAX_ITER > 1; mpcx_mpc_prepare_batch_ov).
+        stop_idx (B, int32): the stop index of lib/mpc_with_speed.py:276-282 over the WHOLE path (path_len = full lengths): xref[2] is
+        v_ref (or path_v) in front of it and 0 from it on, _lib.NO_STOP = no stop; len_seen (B, int32, out) receives path_len
+        (mpcx_mpc_prepare_batch_stop)."""
         T = self.params.T
         B = state.shape[0]
         f = torch.float64
@@ -417,6 +421,15 @@ class Context:
         if x_prev is not None:
             self._want(x_prev, f, (B, 4, T + 1), 'x_prev')
             ov, stride = x_prev.data_ptr() + 2 * (T + 1) * 8, 4 * (T + 1)
+        if stop_idx is not None:
+            self._want(stop_idx, torch.int32, (B,), 'stop_idx')
+            if len_seen is not None:
+                self._want(len_seen, torch.int32, (B,), 'len_seen')
+            self._chk(self.lib.mpcx_mpc_prepare_batch_stop(self._ctx, B, _ptr(state), _ptr(u_warm), _ptr(path), _ptr(path_v), _ptr(path_off),
+                                                           _ptr(path_len), C.c_double(float(dl)), _ptr(target_ind), ov, stride,
+                                                           _ptr(stop_idx), C.c_double(float(v_ref)), _ptr(len_seen),
+                                                           _ptr(out['xref']), _ptr(out['reaches_end']), _ptr(out['xbar'])))
+            return out
         self._chk(self.lib.mpcx_mpc_prepare_batch_ov(self._ctx, B, _ptr(state), _ptr(u_warm), _ptr(path), _ptr(path_v), _ptr(path_off),
                                                      _ptr(path_len), C.c_double(float(dl)), _ptr(target_ind), ov, stride,
                                                      _ptr(out['xref']), _ptr(out['reaches_end']), _ptr(out['xbar'])))
@@ -600,20 +613,25 @@ class Context:
 
     @_ordered
     def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
-                        log: Optional['_lib.RunLogC'] = None):
+                        log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
-        log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged)."""
+        log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
+        opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut."""
         cip = ip.to_c()
-        if log is None:
+        if opts is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_opts(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
+                                                         C.byref(opts), int(n_steps), 1 if graph else 0))
+        elif log is None:
             self._chk(self.lib.mpcx_closed_loop_run(self._ctx, C.byref(cip), C.byref(desc), int(n_steps), 1 if graph else 0))
         else:
             self._chk(self.lib.mpcx_closed_loop_run_logged(self._ctx, C.byref(cip), C.byref(desc), C.byref(log), int(n_steps), 1 if graph else 0))
 
     @_ordered
     def record_step(self, ip: InteractionParams, state, applied, x_sol, path, path_off, path_len, target_ind, cut_len, traj_idx, hit_idx,
-                    status, iters, obs6, obs_off, obs_cnt, obs_skip, log: '_lib.RunLogC'):
+                    status, iters, obs6, obs_off, obs_cnt, obs_skip, log: '_lib.RunLogC', goal_len=None):
         """mpcx_record_step_batch: the run log's record of ONE step, from the closed loop's buffers as the plant step leaves them
-        (obs6: the pool as the step's conflict search saw it).  log: a _lib.RunLogC naming caller-owned device buffers."""
+        (obs6: the pool as the step's conflict search saw it).  log: a _lib.RunLogC naming caller-owned device buffers.
+        goal_len (P, int32): len(self.cx) of the goal test instead of cut_len (mpcx_record_step_batch_goal)."""
         Pn = int(state.shape[0])
         self._want(state, torch.float64, (Pn, 4), 'state'); self._want(applied, torch.float64, (Pn, 2), 'applied')
         self._want(x_sol, torch.float64, (Pn, 4, self.params.T + 1), 'x_sol'); self._want(obs6, torch.float64, (obs6.shape[0], 6), 'obs6')
@@ -623,6 +641,13 @@ class Context:
         if obs_skip is not None:
             self._want(obs_skip, torch.int32, (Pn,), 'obs_skip')
         cip = ip.to_c()
+        if goal_len is not None:
+            self._want(goal_len, torch.int32, (Pn,), 'goal_len')
+            self._chk(self.lib.mpcx_record_step_batch_goal(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(applied), _ptr(x_sol), _ptr(path),
+                                                           _ptr(path_off), _ptr(path_len), _ptr(target_ind), _ptr(cut_len), _ptr(traj_idx),
+                                                           _ptr(hit_idx), _ptr(status), _ptr(iters), int(obs6.shape[0]), _ptr(obs6), _ptr(obs_off),
+                                                           _ptr(obs_cnt), _ptr(obs_skip), _ptr(goal_len), C.byref(log)))
+            return
         self._chk(self.lib.mpcx_record_step_batch(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(applied), _ptr(x_sol), _ptr(path), _ptr(path_off),
                                                   _ptr(path_len), _ptr(target_ind), _ptr(cut_len), _ptr(traj_idx), _ptr(hit_idx), _ptr(status),
                                                   _ptr(iters), int(obs6.shape[0]), _ptr(obs6), _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip),
