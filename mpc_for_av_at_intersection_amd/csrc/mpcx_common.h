@@ -169,59 +169,18 @@ struct QpArgs {
 void launch_qp_stage(const QpArgs &a, hipStream_t st, int n_cu);   // mpcx_qp_quad.hip
 int qp_stage_grid(int B, int n_cu);                                 // wavefronts launch_qp_stage starts for B problems (mpcx_qp_quad.hip)
 
-
 __device__ __forceinline__ double rdlane(double v, int l) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_readlane(lo, l);
     hi = __builtin_amdgcn_readlane(hi, l);
     return __hiloint2double(hi, lo);
 }
-// 1/d and 1/sqrt(d): hardware seed + two Newton steps (full double accuracy, not correctly rounded)
+// 1/d: hardware seed + two Newton steps (full double accuracy, not correctly rounded)
 __device__ __forceinline__ double frcp(double d) {
     double r = __builtin_amdgcn_rcp(d);
     r = fma(fma(-d, r, 1.0), r, r);
     r = fma(fma(-d, r, 1.0), r, r);
     return r;
-}
-__device__ __forceinline__ double frsq(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    double h = 0.5 * d;
-    y = fma(y, fma(-h * y, y, 0.5), y);
-    y = fma(y, fma(-h * y, y, 0.5), y);
-    return y;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmax(v, __shfl_xor(v, d, WAVE));
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmin(v, __shfl_xor(v, d, WAVE));
-    return v;
-}
-// inclusive prefix sum over lanes (lane i gets sum of lanes 0..i)
-__device__ __forceinline__ double scan_up(double v, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        double t = __shfl_up(v, d, WAVE);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-// inclusive suffix sum over lanes (lane i gets sum of lanes i..63)
-__device__ __forceinline__ double scan_down(double v, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        double t = __shfl_down(v, d, WAVE);
-        if (lane + d < WAVE) v += t;
-    }
-    return v;
 }
 
 // ---------------------------------------------------------------- DPP cross-lane helpers (no LDS round trip)
@@ -288,22 +247,68 @@ __device__ __forceinline__ void wave_argmin(double &d, int &i) {
     }
 }
 
-__device__ __forceinline__ double pt_dist(const double *path, int idx, double x, double y) {
-    double dx = __dadd_rn(path[3 * idx], -x), dy = __dadd_rn(path[3 * idx + 1], -y);
-    return __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+template <typename T>      // int, long long
+__device__ __forceinline__ T wave_min_i(T v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) { T o = __shfl_xor(v, s, WAVE); v = o < v ? o : v; }
+    return v;
 }
 
-// trajectories.py:100-126 on path[start .. n) ; returns absolute index or -1 ("something wrong").
-// The three smallest (distance, index) pairs in ascending order, ties by lower index (= numpy's argpartition + argsort on these
-// data): ONE pass over the points keeps each lane's three smallest (the next 64 points are in flight meanwhile; the square root is
-// taken only where the squared distance could enter the lane's three: sqrt is monotone), then the wave-wide minimum is popped
-// three times.  Round 1 made three passes with a square root per point each.
+// trajectories.py:11-37: centre (ex, ey) of the disc at (cx, cy) in the frame of a pose at (px, py) whose heading has cos / sin (c, s)
+__device__ __forceinline__ void disc_centre(double px, double py, double c, double s, double cx, double cy, double &ex, double &ey) {
+    ex = __dadd_rn(__dadd_rn(__dmul_rn(c, cx), -__dmul_rn(s, cy)), px);
+    ey = __dadd_rn(__dadd_rn(__dmul_rn(s, cx), __dmul_rn(c, cy)), py);
+}
+
+// One lane's three smallest (distance, index) pairs of the points offered to it, ascending, ties by lower index (= numpy's argpartition +
+// argsort on these data), with their squared distances.  The conflict search (interaction_kernel) and the window selection
+// (nearest_index_in_direction) both take their three nearest path points from here: the window kernel uses the conflict search's answer as
+// its own (mpcx_interaction_extras::near), so the two must agree bit for bit.
+struct Top3 {
+    double d0 = INFINITY, d1 = INFINITY, d2 = INFINITY, s2 = INFINITY, s1 = INFINITY, s0 = INFINITY;
+    int i0 = 0x7fffffff, i1 = 0x7fffffff, i2 = 0x7fffffff;
+    // point i at (px, py), ego at (x, y).  The square root is taken only where the squared distance could enter the lane's three (sqrt is
+    // monotone, so a larger square cannot give a smaller distance).
+    __device__ __forceinline__ void offer(double px, double py, double x, double y, int i) {
+        const double dx = __dadd_rn(px, -x), dy = __dadd_rn(py, -y);
+        const double q = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+        if (q < s2 || i2 == 0x7fffffff) {
+            const double d = __dsqrt_rn(q);
+            if (d < d2 || (d == d2 && i < i2)) {
+                if (d < d1 || (d == d1 && i < i1)) {
+                    d2 = d1; i2 = i1; s2 = s1;
+                    if (d < d0 || (d == d0 && i < i0)) { d1 = d0; i1 = i0; s1 = s0; d0 = d; i0 = i; s0 = q; }
+                    else { d1 = d; i1 = i; s1 = q; }
+                } else { d2 = d; i2 = i; s2 = q; }
+            }
+        }
+    }
+    // the indices of the wave's three smallest pairs, ascending: pop the wave-wide minimum three times (consumes the lanes' entries)
+    __device__ __forceinline__ void pop3(int (&bi)[3]) {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            double d = d0; int ix = i0;
+            wave_argmin(d, ix);
+            bi[r] = ix;
+            if (i0 == ix) { d0 = d1; i0 = i1; d1 = d2; i1 = i2; d2 = INFINITY; i2 = 0x7fffffff; }
+        }
+    }
+};
+// trajectories.py:117-126 on the three nearest indices (ascending distance): the nearest if its neighbours straddle it, else the forward one
+// of two adjacent nearest, else -1 ("something wrong")
+__device__ __forceinline__ int three_nearest(const int (&bi)[3], int base) {
+    if (abs(bi[1] - bi[2]) == 2) return bi[0] + base;
+    if (abs(bi[0] - bi[1]) == 1) return max(bi[0], bi[1]) + base;
+    return -1;
+}
+
+// trajectories.py:100-126 on path[start .. n) ; returns absolute index or -1 ("something wrong").  ONE pass over the points keeps each lane's
+// three smallest (Top3; the next 64 points are in flight meanwhile).  Round 1 made three passes with a square root per point each.
 __device__ inline int nearest_index_in_direction(const double *path, int n, int start, double x, double y, int lane) {
     const int len = n - start;
     if (len <= 1) return start;
     if (len == 2) return start + 1;
-    double b0d = INFINITY, b1d = INFINITY, b2d = INFINITY, b2s = INFINITY, b1s = INFINITY, b0s = INFINITY;
-    int b0i = 0x7fffffff, b1i = 0x7fffffff, b2i = 0x7fffffff;
+    Top3 top;
     // the points arrive in batches of DEPTH x 64 with the next batch's loads all in flight (one batch deep the scan waited for an
     // L2 round trip per 64 points: there is almost no arithmetic to hide it behind)
     constexpr int DEPTH = 4;
@@ -326,35 +331,20 @@ __device__ inline int nearest_index_in_direction(const double *path, int n, int 
 #pragma unroll
         for (int k = 0; k < DEPTH; k++) {
             const int i = i0 + k * WAVE + lane;
-            if (i < len) {
-                const double dx = __dadd_rn(bx[k], -x), dy = __dadd_rn(by[k], -y);
-                const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
-                if (d2 < b2s || b2i == 0x7fffffff) {
-                    const double d = __dsqrt_rn(d2);
-                    if (d < b2d || (d == b2d && i < b2i)) {
-                        if (d < b1d || (d == b1d && i < b1i)) {
-                            b2d = b1d; b2i = b1i; b2s = b1s;
-                            if (d < b0d || (d == b0d && i < b0i)) { b1d = b0d; b1i = b0i; b1s = b0s; b0d = d; b0i = i; b0s = d2; }
-                            else { b1d = d; b1i = i; b1s = d2; }
-                        } else { b2d = d; b2i = i; b2s = d2; }
-                    }
-                }
-            }
+            if (i < len) top.offer(bx[k], by[k], x, y, i);
         }
 #pragma unroll
         for (int k = 0; k < DEPTH; k++) { bx[k] = nbx[k]; by[k] = nby[k]; }
     }
     int bi[3];
 #pragma unroll
-    for (int r = 0; r < 3; r++) {     // pop the wave-wide minimum three times
-        double d = b0d; int ix = b0i;
+    for (int r = 0; r < 3; r++) {     // Top3::pop3 written out: through the member ref_window_kernel measured 33.59 us against 33.41 (other register allocation)
+        double d = top.d0; int ix = top.i0;
         wave_argmin(d, ix);
         bi[r] = ix;
-        if (b0i == ix) { b0d = b1d; b0i = b1i; b1d = b2d; b1i = b2i; b2d = INFINITY; b2i = 0x7fffffff; }
+        if (top.i0 == ix) { top.d0 = top.d1; top.i0 = top.i1; top.d1 = top.d2; top.i1 = top.i2; top.d2 = INFINITY; top.i2 = 0x7fffffff; }
     }
-    if (abs(bi[1] - bi[2]) == 2) return bi[0] + start;
-    if (abs(bi[0] - bi[1]) == 1) return max(bi[0], bi[1]) + start;
-    return -1;
+    return three_nearest(bi, start);
 }
 
 }  // namespace mpcx

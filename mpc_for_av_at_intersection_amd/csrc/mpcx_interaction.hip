@@ -13,9 +13,21 @@
 // reach, and the FIRST ROW IN THE REFERENCE'S ORDER is recovered as the minimum of an integer key over all hits
 // (bit-exact index outputs).
 #include "mpcx_common.h"
-#include <type_traits>
 
 namespace mpcx {
+
+// developer build (make dev): every ego takes the sequential-cumsum path of interaction_kernel, no plan table (tests run both builds)
+#ifdef MPCX_INTER_FORCE_EXACT
+constexpr bool FORCE_EXACT = true;
+#else
+constexpr bool FORCE_EXACT = false;
+#endif
+
+// trajectories.py:11-37: the two disc centres (x, y, x, y) of a pose at (px, py) whose heading has cos / sin (c, s)
+__device__ __forceinline__ void pose_discs(const mpcx_interaction_params &ip, double px, double py, double c, double s, double *out) {
+#pragma unroll
+    for (int d = 0; d < 2; d++) disc_centre(px, py, c, s, ip.circle_centers[2 * d], ip.circle_centers[2 * d + 1], out[2 * d], out[2 * d + 1]);
+}
 
 struct PredArgs {
     mpcx_interaction_params ip;
@@ -65,12 +77,7 @@ __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
         v = __dadd_rn(v, __dmul_rn(acc, dt));
         yaw = __dadd_rn(yaw, __dmul_rn(__dmul_rn(__ddiv_rn(v, a.ip.L), tn), dt));
         sincos(yaw, &s, &c);
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-            const double cx = a.ip.circle_centers[2 * d], cy = a.ip.circle_centers[2 * d + 1];
-            out[4 * k + 2 * d] = __dadd_rn(__dadd_rn(__dmul_rn(c, cx), -__dmul_rn(s, cy)), x);
-            out[4 * k + 2 * d + 1] = __dadd_rn(__dadd_rn(__dmul_rn(s, cx), __dmul_rn(c, cy)), y);
-        }
+        pose_discs(a.ip, x, y, c, s, out + 4 * k);
     }
 }
 
@@ -98,27 +105,20 @@ __device__ __forceinline__ double dist2d(double ax, double ay, double bx, double
 }
 // dist2d(a,b) <= md, decided from the squared distance except within 1e-12 (relative) of the threshold, where the
 // reference's own expression sqrt(dx*dx + dy*dy) <= md is evaluated: identical decisions, no sqrt on the bulk of the pairs
-__device__ __forceinline__ bool within(double ax, double ay, double bx, double by, double md, double md2lo, double md2hi) {
-    const double dx = __dadd_rn(ax, -bx), dy = __dadd_rn(ay, -by);
-    const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
-    if (d2 > md2hi) return false;
-    if (d2 < md2lo) return true;
-    return __dsqrt_rn(d2) <= md;
-}
-__device__ __forceinline__ long long wave_min_ll(long long v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { long long o = __shfl_xor(v, s, WAVE); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { int o = __shfl_xor(v, s, WAVE); v = o < v ? o : v; }
-    return v;
-}
+struct Within {
+    double md, md2lo, md2hi;
+    __device__ __forceinline__ explicit Within(double md_) : md(md_), md2lo(md_ * md_ * (1.0 - 1e-12)), md2hi(md_ * md_ * (1.0 + 1e-12)) {}
+    __device__ __forceinline__ bool operator()(double ax, double ay, double bx, double by) const {
+        const double dx = __dadd_rn(ax, -bx), dy = __dadd_rn(ay, -by);
+        const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+        if (d2 > md2hi) return false;
+        if (d2 < md2lo) return true;
+        return __dsqrt_rn(d2) <= md;
+    }
+};
 
-// collision_avoidance.py:72-104 on prepared disc tables.  s_ego: ego disc centres of the `na` predicted poses;
-// pred: obstacle disc centres [pool][steps][2][2]; (rem, rcs, n): the detailed path and cos/sin of its yaw.
-// Returns the index of the earliest conflicting pose on the detailed path (and its x,y) or -1 (None).
+// ------------------------------------------------------------------------------------------------------------
+// collision_avoidance.py:72-104 on prepared disc tables (first_conflict below): run_boxes, first_row, earliest_pose.
 //
 // Work distribution.  The reference's row order is frame-major, so the answer lies in the FIRST run of ego frames that has any hit:
 // runs are visited in order and the search stops after the first run with a hit.  Per run, every lane tests the obstacle disc
@@ -126,7 +126,7 @@ __device__ __forceinline__ int wave_min_i(int v) {
 // works its own set bits off, all lanes on the same ego frame, leaving at the first frame with a hit anywhere in the wavefront
 // (round 1: one position per lane through all runs with nested divergent loops; rounds 2-3: survivors compacted into an LDS queue).
 constexpr int NSEG = 8;
-constexpr int QCAP = 8 * WAVE;      // (sizes the slack behind s_ego that used to hold the rounds 2-3 candidate queue; s_box lives there now)
+constexpr int SPARE_ROWS = 32;      // rows of four doubles the launch keeps free behind s_ego [fcap][4]: the first NSEG of them are s_box
 __device__ __forceinline__ double grp8_min(double v) {
     v = fmin(v, dpp_mov<0xB1>(v, v)); v = fmin(v, dpp_mov<0x4E>(v, v)); v = fmin(v, dpp_mov<0x141>(v, v));
     return v;
@@ -146,40 +146,32 @@ __device__ __forceinline__ void divmod_small(int j, int d, float inv_d, int &quo
     quo = q; rem = r;
 }
 
-__device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)[4], int na, const double *pred,
-                              int ooff, int nobs, int oskip, const double *rem, const double *rcs, int n,
-                              double (*s_box)[4], int lane, double &hx, double &hy,
-                              bool boxes_ready = false,          // s_box already holds the runs' boxes (mpcx_interaction_params.plan_box)
-                              const double *pdisc = nullptr      // disc centres of the poses of `rem` (mpcx_interaction_params.path_disc + 4 * row of rem[0]) or nullptr
-                              ) {
-    const double md = 2.0 * ip.radius;
-    const double md2lo = md * md * (1.0 - 1e-12), md2hi = md * md * (1.0 + 1e-12);
+// Boxes of NSEG runs of ego frames (F frames padded, SL per run), inflated by slack > md so that no pair within md is ever skipped.
+// Lane (run = lane / 8, j = lane % 8) folds frames run*SL + j, + 8, ...; an 8-lane butterfly finishes the run.
+__device__ __forceinline__ void run_boxes(const double (*s_ego)[4], int na, int F, int SL, double slack, double (*s_box)[4], int lane) {
+    const int sg = lane >> 3, j = lane & 7;
+    const int fend = (sg + 1) * SL < F ? (sg + 1) * SL : F;
+    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    for (int f = sg * SL + j; f < fend; f += 8) {
+        const int fe = f < na ? f : na - 1;
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            const double ex = s_ego[fe][2 * d], ey = s_ego[fe][2 * d + 1];
+            x0 = fmin(x0, ex); x1 = fmax(x1, ex); y0 = fmin(y0, ey); y1 = fmax(y1, ey);
+        }
+    }
+    x0 = grp8_min(x0); x1 = grp8_max(x1); y0 = grp8_min(y0); y1 = grp8_max(y1);
+    if (j == 0) { s_box[sg][0] = x0 - slack; s_box[sg][1] = x1 + slack; s_box[sg][2] = y0 - slack; s_box[sg][3] = y1 + slack; }
+}
+
+// collision_avoidance.py:72-87: the first row of the pair table within md, as the minimum of a key in the reference's row order.
+// Returns whether there is one; (hox, hoy): the obstacle disc position of that row.
+__device__ __forceinline__ bool first_row(const mpcx_interaction_params &ip, const Within &within, const double (*s_ego)[4], int na, int F, int SL,
+                                          const double (*s_box)[4], const double *pred, int ooff, int nobs, int oskip, int lane,
+                                          double &hox, double &hoy) {
     const int steps = ip.pred_steps, w = ip.frame_window;
     const float inv_steps = 1.0f / (float)steps;
-    const double slack = md * (1.0 + 1e-9) + 1e-9;      // conservative: never culls a pair within md
-
-    // ---- boxes of NSEG runs of ego frames, inflated by slack > md so that no pair within md is ever skipped.
-    // Lane (run = lane / 8, j = lane % 8) folds frames run*SL + j, + 8, ...; an 8-lane butterfly finishes the run.
-    const int F = na > steps ? na : steps;
-    const int SL = (F + NSEG - 1) / NSEG;                 // frames per run
-    if (!boxes_ready) {
-        const int sg = lane >> 3, j = lane & 7;
-        const int fend = (sg + 1) * SL < F ? (sg + 1) * SL : F;
-        double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-        for (int f = sg * SL + j; f < fend; f += 8) {
-            const int fe = f < na ? f : na - 1;
-#pragma unroll
-            for (int d = 0; d < 2; d++) {
-                const double ex = s_ego[fe][2 * d], ey = s_ego[fe][2 * d + 1];
-                x0 = fmin(x0, ex); x1 = fmax(x1, ex); y0 = fmin(y0, ey); y1 = fmax(y1, ey);
-            }
-        }
-        x0 = grp8_min(x0); x1 = grp8_max(x1); y0 = grp8_min(y0); y1 = grp8_max(y1);
-        if (j == 0) { s_box[sg][0] = x0 - slack; s_box[sg][1] = x1 + slack; s_box[sg][2] = y0 - slack; s_box[sg][3] = y1 + slack; }
-    }
-    __syncthreads();
     const long long NOKEY = 0x7fffffffffffffffLL;
-    long long best = NOKEY;
     long long lbest = NOKEY;                               // this lane's own smallest key and the obstacle disc position it belongs to
     double lpx = 0.0, lpy = 0.0;
     int sg_limit = NSEG;                                   // runs >= sg_limit cannot hold the first row any more
@@ -238,7 +230,7 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
                     if (on && abs(g - ff) <= w) {            // else: no offset d in [-w, w] maps padded frame ff onto obstacle frame g
 #pragma unroll
                         for (int ca = 0; ca < 2; ca++) {
-                            if (within(s_ego[fe][2 * ca], s_ego[fe][2 * ca + 1], px, py, md, md2lo, md2hi)) {
+                            if (within(s_ego[fe][2 * ca], s_ego[fe][2 * ca + 1], px, py)) {
                                 // key = reference row order (frame, agent disc, obstacle, offset, obstacle disc); offsets ascend =>
                                 // obstacle frames descend; the first offset reaching g is the one that counts
                                 const long long key = ((((long long)f * 2 + ca) * MPCX_MAX_OBS + o) * MPCX_PRED_STEPS_MAX + (steps - 1 - g)) * 2 + co;
@@ -256,16 +248,20 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
             }
         }
     }
-    best = wave_min_ll(lbest);
-    if (best == NOKEY) return -1;
+    const long long best = wave_min_i(lbest);
+    if (best == NOKEY) return false;
     // the obstacle disc of the first row: the lane that found the key still holds its position (a key belongs to one candidate, a
     // candidate to one lane) -- no decode, no load
     const int owner = (int)__ffsll((long long)__ballot(lbest == best)) - 1;
-    const double ox = rdlane(lpx, owner), oy = rdlane(lpy, owner);
+    hox = rdlane(lpx, owner); hoy = rdlane(lpy, owner);
+    return true;
+}
 
-    // ---- collision_avoidance.py:88-104: earliest pose of the detailed path (front-disc block, then rear-disc block)
-    // The answer is the smallest index of the front-disc block if that block has a hit at all, else the smallest of the
-    // rear-disc block: each block is walked in index order, 64 poses at a time, and left at the first batch with a hit.
+// collision_avoidance.py:88-104: earliest pose of the detailed path (front-disc block, then rear-disc block) within md of (ox, oy).
+// The answer is the smallest index of the front-disc block if that block has a hit at all, else the smallest of the
+// rear-disc block: each block is walked in index order, 64 poses at a time, and left at the first batch with a hit.
+__device__ __forceinline__ int earliest_pose(const mpcx_interaction_params &ip, const Within &within, double ox, double oy, const double *rem,
+                                             const double *rcs, const double *pdisc, int n, int lane) {
     int first = 0x7fffffff;
     constexpr int PD = 4;      // batches of 64 poses in flight: the scan leaves at its first hit, and one batch per memory round trip made it a chain of 2-5
     for (int d = 0; d < 2 && first == 0x7fffffff; d++) {
@@ -283,62 +279,65 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
             for (int k = 0; k < PD; k++) {
                 const int i = i0 + k * WAVE + lane;
                 // (with the host's table the disc centre is read, not rebuilt: px, py hold it)
-                const double ex = pdisc ? px[k] : __dadd_rn(__dadd_rn(__dmul_rn(pc[k], cx), -__dmul_rn(ps[k], cy)), px[k]);
-                const double ey = pdisc ? py[k] : __dadd_rn(__dadd_rn(__dmul_rn(ps[k], cx), __dmul_rn(pc[k], cy)), py[k]);
-                const bool hit = i < n && within(ox, oy, ex, ey, md, md2lo, md2hi);
+                double ex, ey;
+                disc_centre(px[k], py[k], pc[k], ps[k], cx, cy, ex, ey);
+                ex = pdisc ? px[k] : ex; ey = pdisc ? py[k] : ey;
+                const bool hit = i < n && within(ox, oy, ex, ey);
                 const unsigned long long m = __ballot(hit);
                 if (m && first == 0x7fffffff) first = d * n + i0 + k * WAVE + (int)__ffsll((long long)m) - 1;      // wave-uniform
             }
         }
     }
-    first = (first == 0x7fffffff) ? 0 : first % n;      // argmax of an all-False mask is 0
+    return (first == 0x7fffffff) ? 0 : first % n;      // argmax of an all-False mask is 0
+}
+
+// s_ego: ego disc centres of the `na` predicted poses; pred: obstacle disc centres [pool][steps][2][2]; (rem, rcs, n): the detailed path and
+// cos/sin of its yaw.  Returns the index of the earliest conflicting pose on the detailed path (and its x,y) or -1 (None).
+__device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)[4], int na, const double *pred,
+                              int ooff, int nobs, int oskip, const double *rem, const double *rcs, int n,
+                              double (*s_box)[4], int lane, double &hx, double &hy,
+                              bool boxes_ready = false,          // s_box already holds the runs' boxes (mpcx_interaction_params.plan_box)
+                              const double *pdisc = nullptr      // disc centres of the poses of `rem` (mpcx_interaction_params.path_disc + 4 * row of rem[0]) or nullptr
+                              ) {
+    const Within within(2.0 * ip.radius);
+    const double slack = within.md * (1.0 + 1e-9) + 1e-9;      // conservative: never culls a pair within md
+    const int F = na > ip.pred_steps ? na : ip.pred_steps;
+    const int SL = (F + NSEG - 1) / NSEG;                 // frames per run
+    if (!boxes_ready) run_boxes(s_ego, na, F, SL, slack, s_box, lane);
+    __syncthreads();
+    double ox, oy;
+    if (!first_row(ip, within, s_ego, na, F, SL, s_box, pred, ooff, nobs, oskip, lane, ox, oy)) return -1;
+    const int first = earliest_pose(ip, within, ox, oy, rem, rcs, pdisc, n, lane);
     hx = rem[3 * first]; hy = rem[3 * first + 1];
     return first;
 }
 
-constexpr int MAXF_STATIC = MPCX_EGO_FRAMES_MAX;      // moving_collision_kernel (explicit trajectories)
+// lane 0: the agent's outputs and, next to the store of cut_len, its place in the QP work queue of this step (closed loop: an agent that
+// is not filed is never solved)
+__device__ __forceinline__ void finish(const InterArgs &a, int p, int lane, int kprev, int hit, double hx, double hy, int cl) {
+    if (lane != 0) return;
+    a.hit_idx[p] = hit; a.cut_len[p] = cl;
+    if (a.bin_cnt) {
+        const int k = order_key_of(a.bin_hint ? a.bin_hint[p] : 0, cl != kprev);
+        a.keyslot[p] = (k << 24) | atomicAdd(&a.bin_cnt[(p % MPCX_ORDER_COPIES) * MPCX_ORDER_BINS + k], 1);
+    }
+    a.hit_xy[2 * p] = hx; a.hit_xy[2 * p + 1] = hy;
+}
+// no conflict (-1), beyond the launch's capacity (-2), the reference's 'something wrong' (-3): the path stays whole
+__device__ __forceinline__ void leave(const InterArgs &a, int p, int lane, int kprev, int len, int code) { finish(a, p, lane, kprev, code, 0, 0, len); }
 
-__global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
-    // dynamic LDS, sized by the host from the longest path of the call (mpcx_interaction_params.max_path_len):
-    //   s_cum [max_rem] doubles   step / cumulative lengths of the remaining path; once the resampling has consumed them the
-    //                             same bytes hold s_ego [fcap][4] (ego disc centres per kept pose) and s_box (the runs' boxes)
-    //   s_keep [fcap] shorts      indices of the kept poses
-    // (round 4: no static LDS, 16-bit indices, no candidate queue: 6464 B at the benchmark's capacity.  Six wavefronts per SIMD -- launch bound 6: 80 VGPRs, 64 B/lane of
-    // scratch -- measured 0.138 ms against 0.122 at five: the kernel is bound by instruction issue, more wavefronts only share it)
-    extern __shared__ double s_dyn[];
-    const int MAXREM = a.max_rem, MAXF = a.fcap;
-    double *s_cum = s_dyn;
-    unsigned short *s_keep = reinterpret_cast<unsigned short *>(s_dyn + MAXREM);             // (indices < max_rem <= 4096)
-    double (*s_ego)[4] = reinterpret_cast<double (*)[4]>(s_cum);
-    double (*s_box)[4] = reinterpret_cast<double (*)[4]>(s_cum + (size_t)MAXF * 4);           // bounding boxes of the ego discs per run of frames (256 B behind s_ego)
-
-    const int p = blockIdx.x, lane = threadIdx.x;
-    const mpcx_interaction_params &ip = a.ip;
-    const double *path = a.path + 3 * (size_t)a.path_off[p];
-    const double *pcs = a.path_cs + 2 * (size_t)a.path_off[p];
-    const int len = a.path_len[p];
-    const double x = a.state[4 * p], y = a.state[4 * p + 1], v = a.state[4 * p + 2];
-    // ---- mpc_intersection.py:103-105: advance traj_agent_idx unless the previous tmp_trajectory collapsed onto it
-    int tidx = a.traj_idx[p];
-    bool advance = true;
-    const int pcut = a.prev_cut ? a.prev_cut[p] : 0;
-    const int kprev = a.key_prev ? a.key_prev[p] : pcut;
-    if (a.prev_save && lane == 0) a.prev_save[p] = kprev;
-    if (a.near && lane == 0) { a.near[3 * p] = tidx; a.near[3 * p + 1] = -1; a.near[3 * p + 2] = -1; }       // until the scan below has an answer
-    // lane 0, next to every store of cut_len: the agent's place in the QP work queue of this step
-    auto file_key = [&](int cl) {
-        if (a.bin_cnt) {
-            const int k = order_key_of(a.bin_hint ? a.bin_hint[p] : 0, cl != kprev);
-            a.keyslot[p] = (k << 24) | atomicAdd(&a.bin_cnt[(p % MPCX_ORDER_COPIES) * MPCX_ORDER_BINS + k], 1);
-        }
-    };
-    const int t_old = tidx;
-    const int n_old = len - t_old;
+// mpc_intersection.py:103-105: advance traj_agent_idx unless the previous tmp_trajectory collapsed onto it.  Returns the new index, or the
+// exit code: -2 beyond the launch's capacity, -3 where the reference raises (trajectories.py:126).  Without the arc-length table it also
+// leaves the step lengths of path[t_old ..] in s_cum.
+constexpr int DEPTH = 4;
+__device__ __forceinline__ int locate(const InterArgs &a, int p, int lane, const double *path, int len, int t_old, double x, double y,
+                                      int pcut, int nobs, bool tab, double *s_cum) {
+    const int MAXREM = a.max_rem, n_old = len - t_old;
+    if (a.near && lane == 0) { a.near[3 * p] = t_old; a.near[3 * p + 1] = -1; a.near[3 * p + 2] = -1; }       // until the scan below has an answer
     // The first batches of the distance pass are requested BEFORE it is known whether the ego advances at all (their addresses need only the
     // path and the old index): they travel together with the six values of the test below instead of one memory round trip later.  The
     // test itself loads all six values and compares them without short-circuit branches -- (a != b) || (c != d) || ... is a chain of up
     // to three dependent round trips for exactly the egos that stand still.
-    constexpr int DEPTH = 4;
     double bx[DEPTH], by[DEPTH];
 #pragma unroll
     for (int k = 0; k < DEPTH; k++) {
@@ -347,28 +346,18 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
         const double vx = q[0], vy = q[1];
         bx[k] = i < n_old ? vx : 0.0; by[k] = i < n_old ? vy : 0.0;
     }
-    {
-        const int last = pcut > 0 ? pcut - 1 : tidx;
-        const double ax = path[3 * tidx], ay = path[3 * tidx + 1], ath = path[3 * tidx + 2];
-        const double lx = path[3 * last], ly = path[3 * last + 1], lth = path[3 * last + 2];
-        advance = (pcut <= 0) | (ax != lx) | (ay != ly) | (ath != lth);
-    }
-    const int nobs = a.obs_cnt[p] - ((a.obs_skip && a.obs_skip[p] >= 0) ? 1 : 0);
-    if (n_old > MAXREM || nobs > MPCX_MAX_OBS) {
-        if (lane == 0) { a.hit_idx[p] = -2; a.cut_len[p] = len; file_key(len); a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; }
-        return;
-    }
-    // ONE pass over the remaining path: distances to the ego (per-lane three smallest, ties by lower index) for
+    const int last = pcut > 0 ? pcut - 1 : t_old;
+    const double ax = path[3 * t_old], ay = path[3 * t_old + 1], ath = path[3 * t_old + 2];
+    const double lx = path[3 * last], ly = path[3 * last + 1], lth = path[3 * last + 2];
+    const bool advance = (pcut <= 0) | (ax != lx) | (ay != ly) | (ath != lth);
+    if (n_old > MAXREM || nobs > MPCX_MAX_OBS) return -2;
+    // ONE pass over the remaining path: distances to the ego (per-lane three smallest, ties by lower index: Top3) for
     // trajectories.py:100-126, and the step lengths |p_i - p_{i-1}| for resample_curve (trajectories.py:72-75).
-    // Each point is loaded once (the predecessor comes from the neighbour lane), the next 64 points are in flight while
-    // the current ones are worked on, and the ego distance takes its square root only where the squared distance could
-    // enter the lane's three smallest (sqrt is monotone, so a larger square cannot give a smaller distance).
+    // Each point is loaded once (the predecessor comes from the neighbour lane) and the next 64 points are in flight while
+    // the current ones are worked on.
     // With the caller's arc-length table (mpcx_interaction_params.path_cum) the step lengths are not needed here at all -- no
     // square root, no neighbour shuffles, nothing stored -- and an agent that does not advance skips the pass.
-    const double *cumtab = ip.path_cum ? ip.path_cum + (size_t)a.path_off[p] : nullptr;
-    const bool tab = cumtab != nullptr;
-    double b0d = INFINITY, b1d = INFINITY, b2d = INFINITY, b0s = INFINITY, b1s = INFINITY, b2s = INFINITY;
-    int b0i = 0x7fffffff, b1i = 0x7fffffff, b2i = 0x7fffffff;
+    Top3 top;
     if (!tab || advance) {
         // the points arrive in batches of DEPTH x 64: the loads of the next batch are all in flight while this one is worked on (one
         // batch deep the pass waited for an L2 round trip per 64 points: it is bound by its loads, not by its arithmetic)
@@ -392,363 +381,396 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
                     lastx = rdlane(px, WAVE - 1); lasty = rdlane(py, WAVE - 1);
                     if (i < n_old) s_cum[i] = (i == 0) ? 0.0 : dist2d(px, py, qx, qy);
                 }
-                if (i < n_old) {
-                    if (advance) {
-                        const double dx = __dadd_rn(px, -x), dy = __dadd_rn(py, -y);
-                        const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
-                        if (d2 < b2s || b2i == 0x7fffffff) {
-                            const double d = __dsqrt_rn(d2);
-                            if (d < b2d || (d == b2d && i < b2i)) {
-                                if (d < b1d || (d == b1d && i < b1i)) {
-                                    b2d = b1d; b2i = b1i; b2s = b1s;
-                                    if (d < b0d || (d == b0d && i < b0i)) { b1d = b0d; b1i = b0i; b1s = b0s; b0d = d; b0i = i; b0s = d2; }
-                                    else { b1d = d; b1i = i; b1s = d2; }
-                                } else { b2d = d; b2i = i; b2s = d2; }
-                            }
-                        }
-                    }
-                }
+                if (i < n_old && advance) top.offer(px, py, x, y, i);
             }
 #pragma unroll
             for (int k = 0; k < DEPTH; k++) { bx[k] = nbx[k]; by[k] = nby[k]; }
         }
     }
-    if (advance) {
-        if (n_old <= 1) tidx = t_old;
-        else if (n_old == 2) tidx = t_old + 1;
-        else {
-            int bi[3];
+    int tidx = t_old;
+    if (advance && n_old == 2) tidx = t_old + 1;
+    else if (advance && n_old > 2) {
+        int bi[3];
+        top.pop3(bi);
+        tidx = three_nearest(bi, t_old);
+        if (a.near && lane == 0 && tidx >= 0) { a.near[3 * p + 1] = t_old + max(bi[0], max(bi[1], bi[2])); a.near[3 * p + 2] = t_old + min(bi[0], min(bi[1], bi[2])); }
+    }
+    return tidx < 0 ? -3 : tidx;
+}
+
+struct Ego {                       // what the resampling parts share about one ego (wave-uniform but for the lane)
+    const mpcx_interaction_params &ip;
+    int lane, MAXF;
+    double *s_cum;                 // LDS: step / cumulative lengths, s_cum[shift + i] belongs to point i of the trajectory
+    unsigned short *s_keep;        // LDS: indices of the kept poses
+    const double *cumtab;          // the caller's arc-length table from the path's first point on, or nullptr
+    const double *rem;             // trajectory = trajectory_full[traj_agent_idx:], n points
+    int tidx, shift, n;
+    double v;
+    bool accel_phase;              // the predicted speed v + a (i + 1) starts below max_speed
+    double dl_const, inv_const;    // dl once it has saturated: dt * max_speed, and its reciprocal
+    double cum0;                   // the table's value at the trajectory's first point
+    double marg;                   // how far the fast running sum can be from np.cumsum's
+};
+
+// ---- mpc_intersection.py:110-116 + trajectories.py:72-86: ego prediction = resample_curve(trajectory, dl_k).
+// np.cumsum adds strictly left to right.  Replaying that on one lane cost a third of this kernel, so the cumulative
+// lengths first come from a PARALLEL scan (all terms >= 0: it differs from the sequential sum by <= 2.4e-11 for 1024
+// terms summing to <= 200 m) and the bucket floor(c_i / dl_i) of every point is accepted only when c_i / dl_i is farther
+// from an integer than that error can move it (margin 1e-10 / dl_i).  If a single point of this ego is too close to call,
+// the ego is redone with the sequential sum -- same outputs as before in every case, about 1e-6 of the egos take that path.
+__device__ __forceinline__ void prefix_fast(const Ego &e) {
+    double carry = 0.0;
+    for (int i0 = 0; i0 < e.n; i0 += WAVE) {
+        const int i = i0 + e.lane;
+        double t = (i >= 1 && i < e.n) ? e.s_cum[e.shift + i] : 0.0;     // the first point of the new trajectory has no predecessor
+        t += dpp_mov<0x111>(0.0, t);
+        t += dpp_mov<0x112>(0.0, t);
+        t += dpp_mov<0x114>(0.0, t);
+        t += dpp_mov<0x118>(0.0, t);
+        t += dpp_mov<0x142, 0xA>(0.0, t);       // row_bcast:15 -> rows 1, 3
+        t += dpp_mov<0x143, 0xC>(0.0, t);       // row_bcast:31 -> rows 2, 3
+        t += carry;
+        carry = rdlane(t, WAVE - 1);
+        if (i < e.n) e.s_cum[e.shift + i] = t;
+    }
+}
+// running sums from the table, four batches of loads in flight (one by one the pass waited a memory round trip per 64 points)
+__device__ __forceinline__ void sums_from_table(const Ego &e) {
+    for (int i0 = 0; i0 < e.n; i0 += 4 * WAVE) {
+        double t[4];
 #pragma unroll
-            for (int r = 0; r < 3; r++) {     // pop the wave-wide minimum three times
-                double d = b0d; int ix = b0i;
-                wave_argmin(d, ix);
-                bi[r] = ix;
-                if (b0i == ix) { b0d = b1d; b0i = b1i; b1d = b2d; b1i = b2i; b2d = INFINITY; b2i = 0x7fffffff; }
-            }
-            if (abs(bi[1] - bi[2]) == 2) tidx = bi[0] + t_old;
-            else if (abs(bi[0] - bi[1]) == 1) tidx = max(bi[0], bi[1]) + t_old;
-            else tidx = -1;
-            if (a.near && lane == 0 && tidx >= 0) { a.near[3 * p + 1] = t_old + max(bi[0], max(bi[1], bi[2])); a.near[3 * p + 2] = t_old + min(bi[0], min(bi[1], bi[2])); }
-        }
+        for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + e.lane; t[k] = e.cumtab[e.tidx + (i < e.n ? i : 0)]; }
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + e.lane; if (i < e.n) e.s_cum[e.shift + i] = t[k] - e.cum0; }
     }
-    if (tidx < 0) {
-        if (lane == 0) { a.hit_idx[p] = -3; a.cut_len[p] = len; file_key(len); a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; }
-        return;
-    }
-    if (lane == 0) a.traj_idx[p] = tidx;
-    const double *rem = path + 3 * (size_t)tidx;      // trajectory = trajectory_full[traj_agent_idx:]
-    const double *rcs = pcs + 2 * (size_t)tidx;
-    const int n = len - tidx;
-    const int shift = tidx - t_old;                   // s_cum[shift + i] = step length into point i of the new trajectory
-    if (nobs <= 0) {    // collision_avoidance.py:69-70
-        if (lane == 0) { a.hit_idx[p] = -1; a.cut_len[p] = len; file_key(len); a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; }
-        return;
+}
+__device__ __forceinline__ void prefix_exact(const Ego &e) {
+    const int n = e.n, shift = e.shift;
+    double *s_cum = e.s_cum;
+    for (int i = e.lane; i < n; i += WAVE) {        // the step lengths again (prefix_fast overwrote them)
+        const double *q = e.rem + 3 * (size_t)i;
+        s_cum[shift + i] = (i == 0) ? 0.0 : dist2d(q[0], q[1], q[-3], q[-2]);
     }
     __syncthreads();
-    // ---- mpc_intersection.py:110-116 + trajectories.py:72-86: ego prediction = resample_curve(trajectory, dl_k).
-    // np.cumsum adds strictly left to right.  Replaying that on one lane cost a third of this kernel, so the cumulative
-    // lengths first come from a PARALLEL scan (all terms >= 0: it differs from the sequential sum by <= 2.4e-11 for 1024
-    // terms summing to <= 200 m) and the bucket floor(c_i / dl_i) of every point is accepted only when c_i / dl_i is farther
-    // from an integer than that error can move it (margin 1e-10 / dl_i).  If a single point of this ego is too close to call,
-    // the ego is redone with the sequential sum -- same outputs as before in every case, about 1e-6 of the egos take that path.
-    const bool accel_phase = v < ip.max_speed;
-    const double dl_const = __dmul_rn(ip.dt, ip.max_speed);
-    auto prefix_fast = [&]() {
-        double carry = 0.0;
-        for (int i0 = 0; i0 < n; i0 += WAVE) {
-            const int i = i0 + lane;
-            double t = (i >= 1 && i < n) ? s_cum[shift + i] : 0.0;     // the first point of the new trajectory has no predecessor
-            t += dpp_mov<0x111>(0.0, t);
-            t += dpp_mov<0x112>(0.0, t);
-            t += dpp_mov<0x114>(0.0, t);
-            t += dpp_mov<0x118>(0.0, t);
-            t += dpp_mov<0x142, 0xA>(0.0, t);       // row_bcast:15 -> rows 1, 3
-            t += dpp_mov<0x143, 0xC>(0.0, t);       // row_bcast:31 -> rows 2, 3
-            t += carry;
-            carry = rdlane(t, WAVE - 1);
-            if (i < n) s_cum[shift + i] = t;
+    if (e.lane == 0) {                      // np.cumsum: strictly sequential adds (one lane; loads batched 16 at a time)
+        double c = 0.0;
+        int i = 1;
+        for (; i + 16 <= n; i += 16) {
+            double t[16];
+#pragma unroll
+            for (int q = 0; q < 16; q++) t[q] = s_cum[shift + i + q];
+#pragma unroll
+            for (int q = 0; q < 16; q++) { c = __dadd_rn(c, t[q]); t[q] = c; }
+#pragma unroll
+            for (int q = 0; q < 16; q++) s_cum[shift + i + q] = t[q];
         }
-    };
-    auto prefix_exact = [&]() {
-        for (int i = lane; i < n; i += WAVE) {        // the step lengths again (prefix_fast overwrote them)
-            const double *q = rem + 3 * (size_t)i;
-            s_cum[shift + i] = (i == 0) ? 0.0 : dist2d(q[0], q[1], q[-3], q[-2]);
-        }
-        __syncthreads();
-        if (lane == 0) {                      // np.cumsum: strictly sequential adds (one lane; loads batched 16 at a time)
-            double c = 0.0;
-            int i = 1;
-            for (; i + 16 <= n; i += 16) {
-                double t[16];
-#pragma unroll
-                for (int q = 0; q < 16; q++) t[q] = s_cum[shift + i + q];
-#pragma unroll
-                for (int q = 0; q < 16; q++) { c = __dadd_rn(c, t[q]); t[q] = c; }
-#pragma unroll
-                for (int q = 0; q < 16; q++) s_cum[shift + i + q] = t[q];
+        for (; i < n; i++) { c = __dadd_rn(c, s_cum[shift + i]); s_cum[shift + i] = c; }
+    }
+    __syncthreads();
+}
+// the fast sums' bucket floor(r), r = c * inv, is not safe to take for np.cumsum's floor(c / dl)
+__device__ __forceinline__ bool risky(const Ego &e, double c, double r, double dl, double inv) {
+    return c != 0.0 && (!(dl > 0.0) || !(r < 4e15) || !(fabs(r - rint(r)) > e.marg * inv + 2e-15 * fabs(r)));      // c == 0 is exact in every summation order
+}
+// does the predicted speed of point i stay below max_speed (dl_i is not the constant yet)?  Monotone in i for max_accel >= 0.
+__device__ __forceinline__ bool below_max_speed(const Ego &e, int i) {
+    return e.accel_phase && (!(e.ip.max_accel >= 0.0) || __dadd_rn(__dmul_rn(e.ip.max_accel, (double)(i + 1)), e.v) < e.ip.max_speed);
+}
+
+// Point by point over the sums in s_cum: bucket of every point, keep the points where the bucket advances (+ first and last); returns the
+// number kept.  Two instantiations: the fast pass carries no division and no 64-bit integers.
+// check = true: the fast pass -- running sums from the table (or the parallel scan), quotient by reciprocal (<= 2 ulp from the
+// division), bucket accepted only outside the margin; check = false: np.cumsum's own sums (prefix_exact) and the division
+template <bool check>
+__device__ __forceinline__ int resample_by_scan(const Ego &e, bool &unsure) {
+    const mpcx_interaction_params &ip = e.ip;
+    const int lane = e.lane, n = e.n;
+    int base = 0;
+    long long q_carry = 0;                // bucket of the last element of the previous 64-block
+    double qd_carry = 0.0;                // (fast pass: the buckets as doubles -- floor() of a quotient below 2^52 is an exact integer)
+    unsure = false;
+    for (int i0 = 0; i0 < n; i0 += WAVE) {
+        const int i = i0 + lane;
+        long long q = 0;
+        double qd = 0.0;
+        if (i < n) {
+            double dl = e.dl_const, inv = e.inv_const;
+            // the predicted speed v + a (i + 1) is monotone in i: once the FIRST point of a 64-point block has reached max_speed every
+            // later one has, and dl is the constant (a car needs four points for that: only the first block takes this branch)
+            if (below_max_speed(e, i0)) {
+                const double r = __dadd_rn(__dmul_rn(ip.max_accel, (double)(i + 1)), e.v);   // cumsum of equal terms (exact for 2.0) + v
+                dl = __dmul_rn(ip.dt, fmin(r, ip.max_speed));
+                if (check) inv = frcp(dl);
             }
-            for (; i < n; i++) { c = __dadd_rn(c, s_cum[shift + i]); s_cum[shift + i] = c; }
-        }
-        __syncthreads();
-    };
-    // bucket of every point, keep the points where the bucket advances (+ first and last); returns the number kept
-    const double cum0 = tab ? cumtab[tidx] : 0.0;
-    const double inv_const = frcp(dl_const);
-    const double marg = tab ? ip.path_cum_err + 1e-13 : 1.01e-10;     // how far the fast running sum can be from np.cumsum's
-    auto resample = [&](auto check_tag, bool &unsure) -> int {
-        constexpr bool check = decltype(check_tag)::value;      // two instantiations: the fast pass carries no division and no 64-bit integers
-        // check = true: the fast pass -- running sums from the table (or the parallel scan), quotient by reciprocal (<= 2 ulp from the
-        // division), bucket accepted only outside the margin; check = false: np.cumsum's own sums (prefix_exact) and the division
-        int base = 0;
-        long long q_carry = 0;                // bucket of the last element of the previous 64-block
-        double qd_carry = 0.0;                // (fast pass: the buckets as doubles -- floor() of a quotient below 2^52 is an exact integer)
-        unsure = false;
-        for (int i0 = 0; i0 < n; i0 += WAVE) {
-            const int i = i0 + lane;
-            long long q = 0;
-            double qd = 0.0;
-            if (i < n) {
-                double dl = dl_const, inv = inv_const;
-                // the predicted speed v + a (i + 1) is monotone in i: once the FIRST point of a 64-point block has reached max_speed every
-                // later one has, and dl is the constant (a car needs four points for that: only the first block takes this branch)
-                if (accel_phase && (!(ip.max_accel >= 0.0) || __dadd_rn(__dmul_rn(ip.max_accel, (double)(i0 + 1)), v) < ip.max_speed)) {
-                    const double r = __dadd_rn(__dmul_rn(ip.max_accel, (double)(i + 1)), v);   // cumsum of equal terms (exact for 2.0) + v
-                    dl = __dmul_rn(ip.dt, fmin(r, ip.max_speed));
-                    if (check) inv = frcp(dl);
-                }
-                const double c = s_cum[shift + i];
-                if constexpr (check) {
-                    const double r = c * inv;
-                    qd = floor(r);
-                    if (c != 0.0) {               // c == 0 is exact in every summation order
-                        const double room = fabs(r - rint(r));
-                        if (!(dl > 0.0) || !(r < 4e15) || !(room > marg * inv + 2e-15 * fabs(r))) unsure = true;
-                    }
-                } else
-                    q = (long long)floor(__ddiv_rn(c, dl));
-            }
-            bool adv;
+            const double c = e.s_cum[e.shift + i];
             if constexpr (check) {
-                const double qprev = lane_prev(qd, qd_carry);       // wave_shr:1, lane 0 takes the previous block's last bucket
-                qd_carry = rdlane(qd, WAVE - 1);
-                adv = qd - qprev >= 1.0;
-            } else {
-                long long qprev = __shfl_up(q, 1, WAVE);
-                if (lane == 0) qprev = q_carry;
-                q_carry = __shfl(q, WAVE - 1, WAVE);
-                adv = q - qprev >= 1;
-            }
-            const bool keep = (i < n) && ((i == 0) || (i == n - 1) || adv);
-            const unsigned long long m = __ballot(keep);
-            const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-            if (keep && pos < MAXF) s_keep[pos] = i;
-            base += __popcll(m);
+                const double r = c * inv;
+                qd = floor(r);
+                if (risky(e, c, r, dl, inv)) unsure = true;
+            } else
+                q = (long long)floor(__ddiv_rn(c, dl));
         }
-        return base;
-    };
-    // Round 4: the kept poses by SEARCH instead of a scan.  Beyond the first 64 points dl is a constant (the predicted speed has saturated), so
-    // the buckets floor(c_i / dl) never decrease along the path and the kept points -- those whose bucket exceeds their predecessor's -- are
-    // the FIRST point of every bucket value that occurs: one binary search in the arc-length table per bucket boundary (~36 of them, one per
-    // lane) instead of a pass over all ~700 points (which was a third of this kernel's instructions), and the table no longer goes through
-    // LDS.  The margin test that guards the fast sums is only needed where it can fail: at the two points around every boundary and at
-    // the last point (a quotient close to an integer m elsewhere would put a boundary point at least as close to m).  First 64 points: as
-    // before, point by point (dl varies there while the ego accelerates).  Same kept set as the scan, bit for bit (tests + the
-    // MPCX_INTER_FORCE_EXACT build, which still takes the sequential path).
-    const bool search_ok = tab && n > WAVE &&
-                           (!accel_phase || (ip.max_accel >= 0.0 && !(__dadd_rn(__dmul_rn(ip.max_accel, (double)(WAVE + 1)), v) < ip.max_speed)));
-    auto resample_search = [&](bool &unsure) -> int {
-        const double *ct = cumtab + tidx;
-        auto risky = [&](double c, double r, double dl_, double inv_) -> bool {
-            return c != 0.0 && (!(dl_ > 0.0) || !(r < 4e15) || !(fabs(r - rint(r)) > marg * inv_ + 2e-15 * fabs(r)));
-        };
-        unsure = false;
-        // ---- points 0..63 (n > 64: none of them is the last point)
-        double dl = dl_const, inv = inv_const;
-        if (accel_phase && (!(ip.max_accel >= 0.0) || __dadd_rn(__dmul_rn(ip.max_accel, 1.0), v) < ip.max_speed)) {
-            const double r = __dadd_rn(__dmul_rn(ip.max_accel, (double)(lane + 1)), v);
-            dl = __dmul_rn(ip.dt, fmin(r, ip.max_speed));
-            inv = frcp(dl);
-        }
-        const double c0 = ct[lane] - cum0;
-        const double r0 = c0 * inv;
-        const double qd = floor(r0);
-        if (risky(c0, r0, dl, inv)) unsure = true;
-        const double qprev = lane_prev(qd, 0.0);
-        const bool keep0 = (lane == 0) || (qd - qprev >= 1.0);
-        const unsigned long long m0 = __ballot(keep0);
-        {
-            const int pos = __popcll(m0 & ((1ull << lane) - 1ull));
-            if (keep0 && pos < MAXF) s_keep[pos] = lane;
-        }
-        int base = __popcll(m0);
-        const double Q63 = rdlane(qd, WAVE - 1);
-        // ---- point 64 (the first with the constant dl) and the last point
-        const double c64 = ct[WAVE] - cum0, cl = ct[n - 1] - cum0;
-        const double r64 = c64 * inv_const, rl = cl * inv_const;
-        const double Q64 = floor(r64), Ql = floor(rl);
-        if (risky(c64, r64, dl_const, inv_const) || risky(cl, rl, dl_const, inv_const)) unsure = true;
-        if (__ballot(unsure)) return base;                    // (wave-uniform) the caller redoes the ego with the sequential sums
-        if ((Q64 - Q63 >= 1.0) || n - 1 == WAVE) {
-            if (lane == 0 && base < MAXF) s_keep[base] = WAVE;
-            base++;
-        }
-        // ---- one target bucket value per lane: idx(b) = first i in [65, n) with floor(c_i / dl) >= b, b = Q64 + 1 .. Ql
-        const int ntar = (int)(Ql - Q64);                     // 0 <= ntar: the buckets do not decrease; < 4e15 checked above
-        int last_idx = WAVE;                                  // the largest index handled so far
-        if (ntar > 0) {
-            int span = n - 1 - (WAVE + 1), iters = 0;         // search range [65, n - 1]: r_{n-1} >= Ql >= b, so the answer exists
-            while (span > 0) { iters++; span >>= 1; }
-            // planner paths are sampled at (nearly) equal arc-length steps, so the boundary is where a straight line through c_64 and
-            // c_{n-1} puts it: ONE probe of the two points around the guess -- they are the two points the margin test needs anyway --
-            // instead of a chain of ~10 dependent loads; the binary search remains for a path on which the guess misses
-            const double hstep = (cl - c64) / (double)(n - 1 - WAVE);
-            const double inv_h = hstep > 0.0 ? 1.0 / hstep : 0.0;
-            for (int t0 = 0; t0 < ntar; t0 += WAVE) {
-                const int t = t0 + lane;
-                const bool valid = t < ntar;
-                const double b = valid ? Q64 + 1.0 + (double)t : Ql;
-                double gd = ceil((b * dl_const - c64) * inv_h) + (double)WAVE;
-                gd = fmin(fmax(gd, (double)(WAVE + 1)), (double)(n - 1));
-                int idx = (int)gd;
-                double cj = ct[idx] - cum0, ci = ct[idx - 1] - cum0;
-                const bool miss = valid && !((ci * inv_const < b) && (cj * inv_const >= b));
-                if (__ballot(miss)) {                         // wave-uniform
-                    int lo = miss ? WAVE + 1 : idx, hi = miss ? n - 1 : idx;
-                    for (int it = 0; it < iters; it++) {      // uniform trip count; a lane that has converged repeats its last probe
-                        const int mid = lo < hi ? (lo + hi) >> 1 : lo;
-                        const double cm = ct[mid] - cum0;
-                        const bool ge = cm * inv_const >= b;
-                        if (lo < hi) { if (ge) hi = mid; else lo = mid + 1; }
-                    }
-                    idx = lo;
-                    cj = ct[idx] - cum0; ci = ct[idx - 1] - cum0;
-                }
-                if (valid && (risky(cj, cj * inv_const, dl_const, inv_const) || risky(ci, ci * inv_const, dl_const, inv_const))) unsure = true;
-                int prev = __shfl_up(idx, 1, WAVE);
-                if (lane == 0) prev = last_idx;
-                const bool isnew = valid && idx != prev;
-                const unsigned long long mk = __ballot(isnew);
-                const int pos = base + __popcll(mk & ((1ull << lane) - 1ull));
-                if (isnew && pos < MAXF) s_keep[pos] = idx;
-                base += __popcll(mk);
-                const int nv = ntar - t0 < WAVE ? ntar - t0 : WAVE;
-                last_idx = __shfl(idx, nv - 1, WAVE);
-            }
-        }
-        if (n - 1 > WAVE && last_idx != n - 1) {              // keep_last_point
-            if (lane == 0 && base < MAXF) s_keep[base] = n - 1;
-            base++;
-        }
-        return base;
-    };
-    bool unsure = false;
-    int na = 0;
-    // Round 4: the ego prediction from the host's table (mpcx_interaction_params.plan_*).  Once the predicted speed has saturated dl is the
-    // constant DT * MAX_SPEED; if the points before that (four from standstill with the stock constants) all stay in bucket 0 with their
-    // own, smaller dl -- then they do with the constant one too -- the bucket sequence of trajectory_full[tidx:] is the one the host
-    // resampled with the constant dl, i.e. the kept poses depend on tidx alone: their number, their disc centres and the run boxes are ONE
-    // read of row tidx (one memory round trip) instead of the resampling pass, the disc arithmetic and the box reductions.
-    bool plan_ok = false;
-    const size_t prow = (size_t)a.path_off[p] + tidx;
-#ifndef MPCX_INTER_FORCE_EXACT
-    if (ip.plan_cnt && tab && ip.plan_dl == dl_const && ip.plan_steps == ip.pred_steps && ip.plan_radius == ip.radius && ip.plan_cap <= MAXF && ip.plan_cap <= WAVE) {
-        const int cnt = ip.plan_cnt[prow];
-        // the row's disc centres and boxes are requested together with its count (the table has plan_cap poses per row whatever the count is):
-        // one memory round trip, not two
-        const double *pd = ip.plan_disc + prow * (size_t)ip.plan_cap * 4;
-        const int f0 = lane < 2 * ip.plan_cap ? lane : 0, f1 = lane + WAVE < 2 * ip.plan_cap ? lane + WAVE : 0;
-        const double e0x = pd[2 * f0], e0y = pd[2 * f0 + 1], e1x = pd[2 * f1], e1y = pd[2 * f1 + 1];
-        const double bxv = ip.plan_box[prow * (4 * NSEG) + (lane < 4 * NSEG ? lane : 0)];
-        // lane i: has the predicted speed of point i reached MAX_SPEED?  (monotone in i for max_accel >= 0)
-        const bool sat = !accel_phase || !(__dadd_rn(__dmul_rn(ip.max_accel, (double)(lane + 1)), v) < ip.max_speed);
-        const unsigned long long sm = __ballot(sat);
-        const int isat = sm ? (int)__ffsll((long long)sm) - 1 : WAVE;
-        bool bad = false;
-        if (lane < isat && lane < n) {       // points with their own dl: bucket 0 needs c_i < dl_i, with the table's error bound on the safe side
-            const double r = __dadd_rn(__dmul_rn(ip.max_accel, (double)(lane + 1)), v);
-            const double dli = __dmul_rn(ip.dt, r);
-            const double ci = cumtab[tidx + lane] - cum0;
-            bad = !(ci + marg < dli * (1.0 - 1e-12)) || !(dli > 0.0);
-        }
-        plan_ok = cnt > 0 && cnt <= ip.plan_cap && ip.max_accel >= 0.0 && isat < WAVE && !__ballot(bad);
-        if (plan_ok) {
-            na = cnt;
-            // lane f handles disc f & 1 of pose f >> 1 (and f + 64 likewise; plan_cap <= 64 poses)
-            if (lane < 2 * na) { s_ego[lane >> 1][2 * (lane & 1)] = e0x; s_ego[lane >> 1][2 * (lane & 1) + 1] = e0y; }
-            if (lane + WAVE < 2 * na) { s_ego[(lane + WAVE) >> 1][2 * (lane & 1)] = e1x; s_ego[(lane + WAVE) >> 1][2 * (lane & 1) + 1] = e1y; }
-            if (lane < 4 * NSEG) (&s_box[0][0])[lane] = bxv;
-        }
-    }
-#endif
-    if (!plan_ok) {      // else: poses, discs and boxes came from the table
-        if (search_ok) {
-            na = resample_search(unsure);
+        bool adv;
+        if constexpr (check) {
+            const double qprev = lane_prev(qd, qd_carry);       // wave_shr:1, lane 0 takes the previous block's last bucket
+            qd_carry = rdlane(qd, WAVE - 1);
+            adv = qd - qprev >= 1.0;
         } else {
-            if (tab) {      // running sums from the table, four batches of loads in flight (one by one the pass waited a memory round trip per 64 points)
-                for (int i0 = 0; i0 < n; i0 += 4 * WAVE) {
-                    double t[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + lane; t[k] = cumtab[tidx + (i < n ? i : 0)]; }
-#pragma unroll
-                    for (int k = 0; k < 4; k++) { const int i = i0 + k * WAVE + lane; if (i < n) s_cum[shift + i] = t[k] - cum0; }
+            long long qprev = __shfl_up(q, 1, WAVE);
+            if (lane == 0) qprev = q_carry;
+            q_carry = __shfl(q, WAVE - 1, WAVE);
+            adv = q - qprev >= 1;
+        }
+        const bool keep = (i < n) && ((i == 0) || (i == n - 1) || adv);
+        const unsigned long long m = __ballot(keep);
+        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && pos < e.MAXF) e.s_keep[pos] = i;
+        base += __popcll(m);
+    }
+    return base;
+}
+
+// Round 4: the kept poses by SEARCH instead of a scan.  Beyond the first 64 points dl is a constant (the predicted speed has saturated), so
+// the buckets floor(c_i / dl) never decrease along the path and the kept points -- those whose bucket exceeds their predecessor's -- are
+// the FIRST point of every bucket value that occurs: one binary search in the arc-length table per bucket boundary (~36 of them, one per
+// lane) instead of a pass over all ~700 points (which was a third of this kernel's instructions), and the table no longer goes through
+// LDS.  The margin test that guards the fast sums is only needed where it can fail: at the two points around every boundary and at
+// the last point (a quotient close to an integer m elsewhere would put a boundary point at least as close to m).  First 64 points: as
+// before, point by point (dl varies there while the ego accelerates).  Same kept set as the scan, bit for bit (tests + the
+// MPCX_INTER_FORCE_EXACT build, which still takes the sequential path).  Needs the table, n > 64 and the constant dl from point 64 on.
+__device__ __forceinline__ int resample_by_search(const Ego &e, bool &unsure) {
+    const int lane = e.lane, n = e.n, MAXF = e.MAXF;
+    const double dl_const = e.dl_const, inv_const = e.inv_const, cum0 = e.cum0;
+    unsigned short *s_keep = e.s_keep;
+    const double *ct = e.cumtab + e.tidx;
+    unsure = false;
+    // ---- points 0..63 (n > 64: none of them is the last point)
+    double dl = dl_const, inv = inv_const;
+    if (below_max_speed(e, 0)) {
+        const double r = __dadd_rn(__dmul_rn(e.ip.max_accel, (double)(lane + 1)), e.v);
+        dl = __dmul_rn(e.ip.dt, fmin(r, e.ip.max_speed));
+        inv = frcp(dl);
+    }
+    const double c0 = ct[lane] - cum0;
+    const double r0 = c0 * inv;
+    const double qd = floor(r0);
+    if (risky(e, c0, r0, dl, inv)) unsure = true;
+    const double qprev = lane_prev(qd, 0.0);
+    const bool keep0 = (lane == 0) || (qd - qprev >= 1.0);
+    const unsigned long long m0 = __ballot(keep0);
+    {
+        const int pos = __popcll(m0 & ((1ull << lane) - 1ull));
+        if (keep0 && pos < MAXF) s_keep[pos] = lane;
+    }
+    int base = __popcll(m0);
+    const double Q63 = rdlane(qd, WAVE - 1);
+    // ---- point 64 (the first with the constant dl) and the last point
+    const double c64 = ct[WAVE] - cum0, cl = ct[n - 1] - cum0;
+    const double r64 = c64 * inv_const, rl = cl * inv_const;
+    const double Q64 = floor(r64), Ql = floor(rl);
+    if (risky(e, c64, r64, dl_const, inv_const) || risky(e, cl, rl, dl_const, inv_const)) unsure = true;
+    if (__ballot(unsure)) return base;                    // (wave-uniform) the caller redoes the ego with the sequential sums
+    if ((Q64 - Q63 >= 1.0) || n - 1 == WAVE) {
+        if (lane == 0 && base < MAXF) s_keep[base] = WAVE;
+        base++;
+    }
+    // ---- one target bucket value per lane: idx(b) = first i in [65, n) with floor(c_i / dl) >= b, b = Q64 + 1 .. Ql
+    const int ntar = (int)(Ql - Q64);                     // 0 <= ntar: the buckets do not decrease; < 4e15 checked above
+    int last_idx = WAVE;                                  // the largest index handled so far
+    if (ntar > 0) {
+        int span = n - 1 - (WAVE + 1), iters = 0;         // search range [65, n - 1]: r_{n-1} >= Ql >= b, so the answer exists
+        while (span > 0) { iters++; span >>= 1; }
+        // planner paths are sampled at (nearly) equal arc-length steps, so the boundary is where a straight line through c_64 and
+        // c_{n-1} puts it: ONE probe of the two points around the guess -- they are the two points the margin test needs anyway --
+        // instead of a chain of ~10 dependent loads; the binary search remains for a path on which the guess misses
+        const double hstep = (cl - c64) / (double)(n - 1 - WAVE);
+        const double inv_h = hstep > 0.0 ? 1.0 / hstep : 0.0;
+        for (int t0 = 0; t0 < ntar; t0 += WAVE) {
+            const int t = t0 + lane;
+            const bool valid = t < ntar;
+            const double b = valid ? Q64 + 1.0 + (double)t : Ql;
+            double gd = ceil((b * dl_const - c64) * inv_h) + (double)WAVE;
+            gd = fmin(fmax(gd, (double)(WAVE + 1)), (double)(n - 1));
+            int idx = (int)gd;
+            double cj = ct[idx] - cum0, ci = ct[idx - 1] - cum0;
+            const bool miss = valid && !((ci * inv_const < b) && (cj * inv_const >= b));
+            if (__ballot(miss)) {                         // wave-uniform
+                int lo = miss ? WAVE + 1 : idx, hi = miss ? n - 1 : idx;
+                for (int it = 0; it < iters; it++) {      // uniform trip count; a lane that has converged repeats its last probe
+                    const int mid = lo < hi ? (lo + hi) >> 1 : lo;
+                    const double cm = ct[mid] - cum0;
+                    const bool ge = cm * inv_const >= b;
+                    if (lo < hi) { if (ge) hi = mid; else lo = mid + 1; }
                 }
-            } else prefix_fast();
-            __syncthreads();
-            na = resample(std::true_type{}, unsure);
+                idx = lo;
+                cj = ct[idx] - cum0; ci = ct[idx - 1] - cum0;
+            }
+            if (valid && (risky(e, cj, cj * inv_const, dl_const, inv_const) || risky(e, ci, ci * inv_const, dl_const, inv_const))) unsure = true;
+            int prev = __shfl_up(idx, 1, WAVE);
+            if (lane == 0) prev = last_idx;
+            const bool isnew = valid && idx != prev;
+            const unsigned long long mk = __ballot(isnew);
+            const int pos = base + __popcll(mk & ((1ull << lane) - 1ull));
+            if (isnew && pos < MAXF) s_keep[pos] = idx;
+            base += __popcll(mk);
+            const int nv = ntar - t0 < WAVE ? ntar - t0 : WAVE;
+            last_idx = __shfl(idx, nv - 1, WAVE);
         }
     }
-#ifdef MPCX_INTER_FORCE_EXACT
-    unsure = true;                            // dev build: every ego takes the sequential path (tests run both builds)
-#endif
+    if (n - 1 > WAVE && last_idx != n - 1) {              // keep_last_point
+        if (lane == 0 && base < MAXF) s_keep[base] = n - 1;
+        base++;
+    }
+    return base;
+}
+
+// Round 4: the ego prediction from the host's table (mpcx_interaction_params.plan_*).  Once the predicted speed has saturated dl is the
+// constant DT * MAX_SPEED; if the points before that (four from standstill with the stock constants) all stay in bucket 0 with their
+// own, smaller dl -- then they do with the constant one too -- the bucket sequence of trajectory_full[tidx:] is the one the host
+// resampled with the constant dl, i.e. the kept poses depend on tidx alone: their number, their disc centres and the run boxes are ONE
+// read of row tidx (one memory round trip) instead of the resampling pass, the disc arithmetic and the box reductions.
+// Returns whether the table applies to this ego; then na poses are in s_ego and the runs' boxes in s_box.
+__device__ __forceinline__ bool ego_from_plan(const Ego &e, size_t prow, double (*s_ego)[4], double (*s_box)[4], int &na) {
+    const mpcx_interaction_params &ip = e.ip;
+    const int lane = e.lane;
+    if (!(ip.plan_cnt && e.cumtab && ip.plan_dl == e.dl_const && ip.plan_steps == ip.pred_steps && ip.plan_radius == ip.radius && ip.plan_cap <= e.MAXF && ip.plan_cap <= WAVE))
+        return false;
+    const int cnt = ip.plan_cnt[prow];
+    // the row's disc centres and boxes are requested together with its count (the table has plan_cap poses per row whatever the count is):
+    // one memory round trip, not two
+    const double *pd = ip.plan_disc + prow * (size_t)ip.plan_cap * 4;
+    const int f0 = lane < 2 * ip.plan_cap ? lane : 0, f1 = lane + WAVE < 2 * ip.plan_cap ? lane + WAVE : 0;
+    const double e0x = pd[2 * f0], e0y = pd[2 * f0 + 1], e1x = pd[2 * f1], e1y = pd[2 * f1 + 1];
+    const double bxv = ip.plan_box[prow * (4 * NSEG) + (lane < 4 * NSEG ? lane : 0)];
+    // lane i: has the predicted speed of point i reached MAX_SPEED?  (monotone in i for max_accel >= 0)
+    const bool sat = !e.accel_phase || !(__dadd_rn(__dmul_rn(ip.max_accel, (double)(lane + 1)), e.v) < ip.max_speed);
+    const unsigned long long sm = __ballot(sat);
+    const int isat = sm ? (int)__ffsll((long long)sm) - 1 : WAVE;
+    bool bad = false;
+    if (lane < isat && lane < e.n) {       // points with their own dl: bucket 0 needs c_i < dl_i, with the table's error bound on the safe side
+        const double r = __dadd_rn(__dmul_rn(ip.max_accel, (double)(lane + 1)), e.v);
+        const double dli = __dmul_rn(ip.dt, r);
+        const double ci = e.cumtab[e.tidx + lane] - e.cum0;
+        bad = !(ci + e.marg < dli * (1.0 - 1e-12)) || !(dli > 0.0);
+    }
+    if (!(cnt > 0 && cnt <= ip.plan_cap && ip.max_accel >= 0.0 && isat < WAVE && !__ballot(bad))) return false;
+    na = cnt;
+    // lane f handles disc f & 1 of pose f >> 1 (and f + 64 likewise; plan_cap <= 64 poses)
+    if (lane < 2 * na) { s_ego[lane >> 1][2 * (lane & 1)] = e0x; s_ego[lane >> 1][2 * (lane & 1) + 1] = e0y; }
+    if (lane + WAVE < 2 * na) { s_ego[(lane + WAVE) >> 1][2 * (lane & 1)] = e1x; s_ego[(lane + WAVE) >> 1][2 * (lane & 1) + 1] = e1y; }
+    if (lane < 4 * NSEG) (&s_box[0][0])[lane] = bxv;
+    return true;
+}
+
+// The ego frames come from exactly one of: the plan table (from_plan: discs and boxes are in LDS already), the boundary search, the
+// point-by-point scan over the fast sums -- each of the last two redone with np.cumsum's own sums where a bucket was too close to call.
+// Returns the number of frames; but for from_plan their path indices are in s_keep.
+__device__ __forceinline__ int ego_frames(const Ego &e, size_t prow, double (*s_ego)[4], double (*s_box)[4], bool &from_plan) {
+    int na = 0;
+    bool unsure = false;
+    from_plan = !FORCE_EXACT && ego_from_plan(e, prow, s_ego, s_box, na);
+    if (from_plan) return na;
+    if (e.cumtab && e.n > WAVE && !below_max_speed(e, WAVE)) na = resample_by_search(e, unsure);
+    else {
+        if (e.cumtab) sums_from_table(e);
+        else prefix_fast(e);
+        __syncthreads();
+        na = resample_by_scan<true>(e, unsure);
+    }
+    if (FORCE_EXACT) unsure = true;
     if (__ballot(unsure)) {
         __syncthreads();
-        prefix_exact();
-        na = resample(std::false_type{}, unsure);
+        prefix_exact(e);
+        na = resample_by_scan<false>(e, unsure);
     }
-    if (na > MAXF) {
-        if (lane == 0) { a.hit_idx[p] = -2; a.cut_len[p] = len; file_key(len); a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; }
-        return;
+    return na;
+}
+
+// ego disc centres per kept pose
+__device__ __forceinline__ void ego_discs(const Ego &e, const double *rcs, int na, double (*s_ego)[4]) {
+    for (int f = e.lane; f < na; f += WAVE) {
+        const int i = e.s_keep[f];
+        const double px = e.rem[3 * i], py = e.rem[3 * i + 1], c = rcs[2 * i], s = rcs[2 * i + 1];
+        pose_discs(e.ip, px, py, c, s, s_ego[f]);
     }
-    __syncthreads();
-    // ego disc centres per kept pose
-    if (!plan_ok)
-    for (int f = lane; f < na; f += WAVE) {
-        const int i = s_keep[f];
-        const double px = rem[3 * i], py = rem[3 * i + 1], c = rcs[2 * i], s = rcs[2 * i + 1];
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-            const double cx = ip.circle_centers[2 * d], cy = ip.circle_centers[2 * d + 1];
-            s_ego[f][2 * d] = __dadd_rn(__dadd_rn(__dmul_rn(c, cx), -__dmul_rn(s, cy)), px);
-            s_ego[f][2 * d + 1] = __dadd_rn(__dadd_rn(__dmul_rn(s, cx), __dmul_rn(c, cy)), py);
-        }
-    }
-    __syncthreads();
-    const int ooff = a.obs_off[p], oskip = a.obs_skip ? a.obs_skip[p] : -1;
-    // conflict search (+ scan of the detailed path on a hit)
-    double hx, hy;
-    const double *pdisc = ip.plan_cnt ? ip.path_disc + 4 * prow : nullptr;     // disc centres of trajectory_full[tidx:] from the host's table
-    const int first = first_conflict(ip, s_ego, na, a.pred, ooff, nobs, oskip, rem, rcs, n, s_box, lane, hx, hy, plan_ok, pdisc);
-    if (first < 0) {
-        if (lane == 0) { a.hit_idx[p] = -1; a.cut_len[p] = len; file_key(len); a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; }
-        return;
-    }
-    // ---- collision_avoidance.py:107-119 on trajectory_full, then mpc_intersection.py:130-134
+}
+
+// collision_avoidance.py:107-119 on trajectory_full, then mpc_intersection.py:130-134: the cut length for a conflict at path point
+// `at` = (hx, hy)
+__device__ __forceinline__ int cut_index(const mpcx_interaction_params &ip, const double *path, size_t path_row, int len, int tidx, int at,
+                                         double hx, double hy, int lane) {
     int cut = 0x7fffffff;
     if (ip.path_first_within) {
-        // (hx, hy) IS path point tidx + first: the first point within 1 mm of it is a property of the path, tabulated by the host with
+        // (hx, hy) IS path point `at`: the first point within 1 mm of it is a property of the path, tabulated by the host with
         // the reference's own expression (mpcx_interaction_params.path_first_within) -- no scan of the path up to the conflict
-        cut = ip.path_first_within[(size_t)a.path_off[p] + tidx + first];
+        cut = ip.path_first_within[path_row + at];
     } else {
-        const double cr = 0.001, cr2lo = cr * cr * (1.0 - 1e-12), cr2hi = cr * cr * (1.0 + 1e-12);
-        // (hx, hy) IS path point tidx + first, so the first index within 1 mm cannot lie beyond it: scan [0, tidx + first]
-        const int jend = tidx + first + 1 < len ? tidx + first + 1 : len;
+        const Within within(0.001);
+        // (hx, hy) IS path point `at`, so the first index within 1 mm cannot lie beyond it: scan [0, at]
+        const int jend = at + 1 < len ? at + 1 : len;
         for (int j = lane; j < jend; j += WAVE)         // same decision as sqrt(dx*dx + dy*dy) <= 0.001, no sqrt on the bulk
-            if (within(path[3 * j], path[3 * j + 1], hx, hy, cr, cr2lo, cr2hi)) cut = j < cut ? j : cut;
+            if (within(path[3 * j], path[3 * j + 1], hx, hy)) cut = j < cut ? j : cut;
         cut = wave_min_i(cut);
     }
     int cl = len;
     if (cut != 0x7fffffff) { cl = cut - ip.cutoff_margin; cl = cl > tidx + 1 ? cl : tidx + 1; }
-    if (lane == 0) { a.hit_idx[p] = first; a.hit_xy[2 * p] = hx; a.hit_xy[2 * p + 1] = hy; a.cut_len[p] = cl; file_key(cl); }
+    return cl;
+}
+
+__global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
+    // dynamic LDS, sized by the host from the longest path of the call (mpcx_interaction_params.max_path_len):
+    //   s_cum [max_rem] doubles   step / cumulative lengths of the remaining path; once the resampling has consumed them the
+    //                             same bytes hold s_ego [fcap][4] (ego disc centres per kept pose) and s_box (the runs' boxes)
+    //   s_keep [fcap] shorts      indices of the kept poses
+    // (round 4: no static LDS, 16-bit indices, no candidate queue: 6464 B at the benchmark's capacity.  Six wavefronts per SIMD -- launch bound 6: 80 VGPRs, 64 B/lane of
+    // scratch -- measured 0.138 ms against 0.122 at five: the kernel is bound by instruction issue, more wavefronts only share it)
+    extern __shared__ double s_dyn[];
+    const int MAXREM = a.max_rem, MAXF = a.fcap;
+    double *s_cum = s_dyn;
+    unsigned short *s_keep = reinterpret_cast<unsigned short *>(s_dyn + MAXREM);             // (indices < max_rem <= 4096)
+    double (*s_ego)[4] = reinterpret_cast<double (*)[4]>(s_cum);
+    double (*s_box)[4] = reinterpret_cast<double (*)[4]>(s_cum + (size_t)MAXF * 4);           // bounding boxes of the ego discs per run of frames (256 B behind s_ego)
+
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const mpcx_interaction_params &ip = a.ip;
+    const size_t poff = (size_t)a.path_off[p];
+    const double *path = a.path + 3 * poff;
+    const int len = a.path_len[p];
+    const double x = a.state[4 * p], y = a.state[4 * p + 1], v = a.state[4 * p + 2];
+    const int t_old = a.traj_idx[p];
+    const int pcut = a.prev_cut ? a.prev_cut[p] : 0;
+    const int kprev = a.key_prev ? a.key_prev[p] : pcut;
+    if (a.prev_save && lane == 0) a.prev_save[p] = kprev;
+    const int nobs = a.obs_cnt[p] - ((a.obs_skip && a.obs_skip[p] >= 0) ? 1 : 0);
+    const double *cumtab = ip.path_cum ? ip.path_cum + poff : nullptr;
+
+    const int tidx = locate(a, p, lane, path, len, t_old, x, y, pcut, nobs, cumtab != nullptr, s_cum);
+    if (tidx < 0) { leave(a, p, lane, kprev, len, tidx); return; }
+    if (lane == 0) a.traj_idx[p] = tidx;
+    if (nobs <= 0) { leave(a, p, lane, kprev, len, -1); return; }    // collision_avoidance.py:69-70
+    __syncthreads();
+
+    const double dl_const = __dmul_rn(ip.dt, ip.max_speed);
+    const Ego e{ip, lane, MAXF, s_cum, s_keep, cumtab,
+                path + 3 * (size_t)tidx,              // trajectory = trajectory_full[traj_agent_idx:]
+                tidx, tidx - t_old, len - tidx, v, v < ip.max_speed, dl_const, frcp(dl_const),
+                cumtab ? cumtab[tidx] : 0.0, cumtab ? ip.path_cum_err + 1e-13 : 1.01e-10};
+    const double *rcs = a.path_cs + 2 * (poff + tidx);
+    const size_t prow = poff + tidx;
+    bool from_plan;
+    const int na = ego_frames(e, prow, s_ego, s_box, from_plan);
+    if (na > MAXF) { leave(a, p, lane, kprev, len, -2); return; }
+    __syncthreads();
+    if (!from_plan) ego_discs(e, rcs, na, s_ego);      // else: poses, discs and boxes came from the table
+    __syncthreads();
+    // conflict search (+ scan of the detailed path on a hit)
+    const int ooff = a.obs_off[p], oskip = a.obs_skip ? a.obs_skip[p] : -1;
+    double hx, hy;
+    const double *pdisc = ip.plan_cnt ? ip.path_disc + 4 * prow : nullptr;     // disc centres of trajectory_full[tidx:] from the host's table
+    const int first = first_conflict(ip, s_ego, na, a.pred, ooff, nobs, oskip, e.rem, rcs, e.n, s_box, lane, hx, hy, from_plan, pdisc);
+    if (first < 0) { leave(a, p, lane, kprev, len, -1); return; }
+    finish(a, p, lane, kprev, first, hx, hy, cut_index(ip, path, poff, len, tidx, tidx + first, hx, hy, lane));
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -764,12 +786,7 @@ __global__ __launch_bounds__(256) void pose_disc_kernel(PoseDiscArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     const double px = a.pose[3 * i], py = a.pose[3 * i + 1], c = a.cs[2 * i], s = a.cs[2 * i + 1];
-#pragma unroll
-    for (int d = 0; d < 2; d++) {
-        const double cx = a.ip.circle_centers[2 * d], cy = a.ip.circle_centers[2 * d + 1];
-        a.out[4 * i + 2 * d] = __dadd_rn(__dadd_rn(__dmul_rn(c, cx), -__dmul_rn(s, cy)), px);
-        a.out[4 * i + 2 * d + 1] = __dadd_rn(__dadd_rn(__dmul_rn(s, cx), __dmul_rn(c, cy)), py);
-    }
+    pose_discs(a.ip, px, py, c, s, a.out + 4 * i);
 }
 
 struct MovArgs {
@@ -786,23 +803,17 @@ struct MovArgs {
 };
 
 __global__ __launch_bounds__(64) void moving_collision_kernel(MovArgs a) {
-    constexpr int MAXF = MAXF_STATIC;
-    __shared__ double s_ego[MAXF][4];
+    __shared__ double s_ego[MPCX_EGO_FRAMES_MAX][4];
     __shared__ double s_box[NSEG][4];
     const int p = blockIdx.x, lane = threadIdx.x;
     const mpcx_interaction_params &ip = a.ip;
     const int na = a.ego_len[p], n = a.path_len[p], nobs = a.obs_cnt[p];
     if (nobs <= 0) { if (lane == 0) { a.hit_idx[p] = -1; a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; } return; }
-    if (na > MAXF || na < 1 || n < 1 || nobs > MPCX_MAX_OBS) { if (lane == 0) { a.hit_idx[p] = -2; a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; } return; }
+    if (na > MPCX_EGO_FRAMES_MAX || na < 1 || n < 1 || nobs > MPCX_MAX_OBS) { if (lane == 0) { a.hit_idx[p] = -2; a.hit_xy[2 * p] = 0; a.hit_xy[2 * p + 1] = 0; } return; }
     const double *ego = a.ego + 3 * (size_t)a.ego_off[p], *ecs = a.ego_cs + 2 * (size_t)a.ego_off[p];
     for (int f = lane; f < na; f += WAVE) {
         const double px = ego[3 * f], py = ego[3 * f + 1], c = ecs[2 * f], s = ecs[2 * f + 1];
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-            const double cx = ip.circle_centers[2 * d], cy = ip.circle_centers[2 * d + 1];
-            s_ego[f][2 * d] = __dadd_rn(__dadd_rn(__dmul_rn(c, cx), -__dmul_rn(s, cy)), px);
-            s_ego[f][2 * d + 1] = __dadd_rn(__dadd_rn(__dmul_rn(s, cx), __dmul_rn(c, cy)), py);
-        }
+        pose_discs(ip, px, py, c, s, s_ego[f]);
     }
     __syncthreads();
     double hx, hy;
@@ -856,7 +867,7 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     max_rem = (max_rem + 63) / 64 * 64;
     if (max_rem > MPCX_MAX_PATH_LEN)
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: max_path_len %d exceeds %d", ip->max_path_len, MPCX_MAX_PATH_LEN);
-    const int fcap = max_rem / 4 - mpcx::QCAP * 2 / 32;
+    const int fcap = max_rem / 4 - mpcx::SPARE_ROWS;
     const size_t lds = (size_t)max_rem * sizeof(double) + ((size_t)fcap * sizeof(unsigned short) + 7) / 8 * 8;
     mpcx::InterArgs ia{*ip, P, state, path_xyyaw, path_cs, path_off, path_len, prev_cut_len, ctx->pred,
                        obs_off, obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, max_rem, fcap, x.prev_save,

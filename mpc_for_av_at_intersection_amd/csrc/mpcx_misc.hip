@@ -58,8 +58,7 @@ __global__ __launch_bounds__(64) void cutoff_kernel(CutArgs a) {
         const double dx = __dadd_rn(pts[3 * j], -x), dy = __dadd_rn(pts[3 * j + 1], -y);
         if (__dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy))) <= a.radius) best = j < best ? j : best;
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) { int o = __shfl_xor(best, s, WAVE); best = o < best ? o : best; }
+    best = wave_min_i(best);
     if (lane == 0) a.out[p] = (best == 0x7fffffff) ? -1 : best;
 }
 
