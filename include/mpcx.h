@@ -455,6 +455,38 @@ int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *
                                   const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL = MPCX_STOP_CUT*/,
                                   int32_t n_steps, int32_t use_graph);
 
+/* ---- retirement at the goal: the end of the reference's loop, `if mpc.is_goal(state): break` (scenarios/mpc_intersection.py:92-93,
+ * mpc_intersection_new_ref.py:92-93), per agent and on the device.  done[q] != 0: agent q has arrived and is retired.  The last launch
+ * of every step (retire_kernel, after the record stage; the rule is csrc/mpcx_retire_core.h) counts the step in steps_driven[q] and makes
+ * the run log's goal test -- mpc.is_goal (lib/mpc.py:310-326) on the state after the plant step, len(cx) = this step's cut_len
+ * (MPCX_STOP_SPEED: path_len), the same function the record stage calls -- for every agent still driving; on arrival it sets done[q] = 1
+ * and zeroes applied[q].  From the next step on the agent
+ *   - keeps its state row (the state the reference's loop ended with) and its applied row (0, 0): to the others it is a parked car;
+ *   - is not filed in the QP work queue and not solved: u_sol, x_sol, status, iters, kkt, xref, xbar, reaches_end, target_ind, traj_idx,
+ *     hit_idx, hit_xy and cut_len (MPCX_STOP_SPEED: prev_len too) stay bit for bit as its last driven step left them;
+ *   - still has its pool row packed every step (from the frozen state and the zero controls): the other agents' view of the pool and of
+ *     obs_off / obs_cnt / obs_skip does not change;
+ *   - gets no further row in the run log (its cursor `steps` stops at goal_step; min_clearance and contact_step stay) and counts
+ *     neither as an agent-step nor with iterations in mpcx_closed_loop_stats.
+ * Scripted actors and agents still driving are unaffected.  With a run log attached and both started together, goal_step[q] ==
+ * steps_driven[q] for every retired agent.  Both arrays are caller-owned DEVICE memory, zero-initialised (the goal test BEFORE the
+ * first step, which only a path of fewer than 5 points can pass, is the caller's: set done[q] = 1 there); everything that changes is
+ * device memory, so a replayed graph retires agents like a plain run.  The struct travels beside the descriptor (mpcx_closed_loop and
+ * mpcx_closed_loop_opts keep their sizes); the cached graph's key covers it by value.
+ * retire = NULL or an all-zero struct: no retirement, mpcx_closed_loop_run_opts itself -- the same launches with the same arguments.
+ * MPCX_E_INVALID before anything is launched, whatever n_steps is: only one of the two pointers set; goal_dis or stop_speed not finite
+ * or negative; P >= 2^24 (no queue order is built there); more than one linearisation pass (mpcx_set_linearisation_passes: the later
+ * passes build their queue with the counting sort of mpcx_qp_solve_batch, which knows nothing of retired agents -- a follow-up).
+ * Works with scripted traffic, the run log, both stop modes, use_graph and MPCX_SHARD_AGENTS (every rank retires its own agents). */
+typedef struct {
+    int32_t *done;         /* P, caller-owned, zero = driving; set to 1 by the step in which the agent arrives */
+    int32_t *steps_driven; /* P, caller-owned: steps taken while driving = the reference's number of loop iterations once done */
+    double goal_dis, stop_speed;   /* GOAL_DIS, STOP_SPEED of lib/mpc.py (with a run log: the log's) */
+} mpcx_retire;
+int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                    const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                    const mpcx_retire *retire /*or NULL*/, int32_t n_steps, int32_t use_graph);
+
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes
  * to every rank by whatever means it has (torch.distributed broadcast in this package), every rank calls mpcx_comm_init.

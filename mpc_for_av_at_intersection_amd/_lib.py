@@ -57,6 +57,11 @@ class ClosedLoopOptsC(C.Structure):
     _fields_ = [('stop_mode', C.c_int32), ('reserved', C.c_int32), ('v_ref', C.c_double), ('prev_len', C.c_void_p)]
 
 
+class RetireC(C.Structure):
+    """mirror of mpcx_retire (include/mpcx.h): retirement at the goal; done and steps_driven are device addresses"""
+    _fields_ = [('done', C.c_void_p), ('steps_driven', C.c_void_p), ('goal_dis', C.c_double), ('stop_speed', C.c_double)]
+
+
 STOP_CUT, STOP_SPEED = 0, 1     # mpcx_closed_loop_opts.stop_mode
 STOP_MODES = {'cut': STOP_CUT, 'speed': STOP_SPEED}
 NO_STOP = 999                   # MPCX_NO_STOP: the stop index lib/mpc_with_speed.py:281 reads as "no stop"
@@ -116,7 +121,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
            'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
            'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
-           'mpcx_closed_loop_run_opts']
+           'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire']
 
 
 def load():
@@ -186,5 +191,8 @@ def load():
     lib.mpcx_closed_loop_run_opts.restype = i32
     lib.mpcx_closed_loop_run_opts.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
                                               C.POINTER(ClosedLoopOptsC), i32, i32]
+    lib.mpcx_closed_loop_run_retire.restype = i32
+    lib.mpcx_closed_loop_run_retire.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), i32, i32]
     _lib = lib
     return lib

@@ -14,6 +14,8 @@ hipGraph); `step_staged()` drives the same kernels stage by stage through the pe
 path stays whole and the speed reference is zeroed from the conflict on, instead of the path being cut in front of it.
 `attach_log(capacity)` adds the RUN LOG: one more kernel at the end of every step writes the reference's History row, the goal test of
 its loop and the true clearance to the other vehicles, per agent, on the device (RunLog).
+`retire_at_goal()` ends an agent's episode where the reference's loop ends (`if mpc.is_goal(state): break`): from the step after its
+arrival on it is a parked car that is not solved, not logged and not counted; `run_until_done()` runs until every agent has arrived.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -40,6 +42,9 @@ class RunLog:
     agent's first step with clearance >= 0 on, `min_clearance` and `contact_step` (first step with clearance < 0 after that, -1 = none) --
     the stock scenario spawns a scripted car ON the ego's start pose, which a plain minimum would report as a contact at step 0.
     Nothing is frozen at the goal: the log says where the reference's loop would have ended, history() cuts there.
+    With IntersectionBatch.retire_at_goal() an agent gets no row after the step of its arrival: its `steps` stops at goal_step, its
+    min_clearance and contact_step stay.  rows() for all agents then has as many rows as the longest episode, and the rows of an agent
+    beyond its own `steps` are zero (rows(q) is cut at that agent's own `steps`).
     Memory: 96 bytes per agent and step (capacity x P rows) + 24 bytes per agent; capacity 0 keeps the outcomes only."""
 
     def __init__(self, batch: 'IntersectionBatch', capacity: int, goal_dis: float, stop_speed: float):
@@ -91,7 +96,8 @@ class RunLog:
 
     def rows(self, q: Optional[int] = None) -> np.ndarray:
         """the recorded rows as a structured host array (RUN_LOG_DTYPE), cut at min(steps, capacity): shape (n,) for agent q, (n, P)
-        for all agents (every agent of a batch is offered the same number of rows).  steps > capacity: the log overflowed, the first
+        for all agents (every agent of a batch is offered the same number of rows -- unless agents are retired at their goal: then n
+        is the largest `steps` and an agent's rows beyond its own `steps` are zero).  steps > capacity: the log overflowed, the first
         `capacity` rows are there."""
         self.batch.ctx.synchronize()
         steps = self.steps.cpu().numpy()
@@ -105,6 +111,8 @@ class RunLog:
                 out[name] = f[..., k]
             for k, name in enumerate(_lib.RUN_LOG_I32):
                 out[name] = w[..., k]
+            if q is None:       # agents retired at their goal: nothing beyond an agent's own cursor (a reused buffer may hold older rows)
+                out[np.arange(n)[:, None] >= np.minimum(steps, self.capacity)[None, :]] = 0
         return out
 
     def history(self, q: int):
@@ -287,6 +295,9 @@ class IntersectionBatch:
             self.tuning = ctx.f64(tuning)
         self._desc = None
         self.log: Optional[RunLog] = None
+        self.done: Optional[torch.Tensor] = None             # retire_at_goal(): int32 (P,), != 0 = arrived and retired
+        self.steps_driven: Optional[torch.Tensor] = None     # ... int32 (P,), steps taken while driving
+        self._retire = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -303,7 +314,11 @@ class IntersectionBatch:
             raise ValueError('run log: %d rows x %d agents x %d bytes = %.1f MB exceed the limit of %.1f MB; pass a smaller capacity '
                              '(0 = outcomes only) or a larger max_bytes (None = no limit)'
                              % (capacity, self.P, _lib.RUN_LOG_ROW_BYTES, need / 1e6, max_bytes / 1e6))
-        self.log = RunLog(self, capacity, _mpc.GOAL_DIS if goal_dis is None else goal_dis, _mpc.STOP_SPEED if stop_speed is None else stop_speed)
+        goal_dis, stop_speed = _mpc.GOAL_DIS if goal_dis is None else goal_dis, _mpc.STOP_SPEED if stop_speed is None else stop_speed
+        if self._retire is not None and (float(goal_dis), float(stop_speed)) != (self._retire.goal_dis, self._retire.stop_speed):
+            raise MpcxError('run log: goal_dis / stop_speed (%r, %r) differ from those agents are retired with (%r, %r): goal_step and '
+                            'steps_driven would disagree' % (goal_dis, stop_speed, self._retire.goal_dis, self._retire.stop_speed))
+        self.log = RunLog(self, capacity, goal_dis, stop_speed)
         self._desc = None
         return self.log
 
@@ -312,6 +327,73 @@ class IntersectionBatch:
         log, self.log = self.log, None
         self._desc = None
         return log
+
+    def _goal_now(self, goal_dis: float, stop_speed: float) -> np.ndarray:
+        """mpc.is_goal (lib/mpc.py:310-326) on the host for every agent as the batch stands: the test at the top of the reference's next
+        loop iteration (RunLog.reset() makes the same one for goal_step = 0).  Before the first step only a path of fewer than 5 points
+        passes it.  Synchronises."""
+        self.ctx.synchronize()
+        path = self.path.cpu().numpy()
+        off, ln = self.path_off.cpu().numpy().astype(np.int64), self.path_len.cpu().numpy().astype(np.int64)
+        cut = self.inter['cut_len'].cpu().numpy().astype(np.int64)
+        cut = ln if self.stop_mode == 'speed' else np.where(cut > 0, cut, ln)       # len(self.cx)
+        goal, st = path[off + ln - 1], self.state.cpu().numpy()
+        return ((np.hypot(st[:, 0] - goal[:, 0], st[:, 1] - goal[:, 1]) <= goal_dis) & (np.abs(self.target_ind.cpu().numpy() - cut) < 5) &
+                (np.abs(st[:, 2]) <= stop_speed))
+
+    def retire_at_goal(self, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None):
+        """End every agent's episode where the reference's loop ends (`if mpc.is_goal(state): break`, scenarios/mpc_intersection.py:92-93):
+        the step in which an agent arrives sets done[q] = 1, and from the next step on the agent keeps its state, has applied = (0, 0) -- to
+        the others it is a parked car --, is not solved (its sol / pre / inter rows, target_ind and traj_idx stay as its last driven step
+        left them), gets no further row in the run log and is not counted in closed_loop_stats().  Its pool row is still packed every step:
+        arrived cars stay in the scene.  Costs one more launch per step (mpcx_closed_loop_run_retire); keep_driving() switches it off.
+        goal_dis / stop_speed default to GOAL_DIS / STOP_SPEED of lib/mpc.py, as attach_log's do; with a log attached they must be the log's,
+        so that goal_step == steps_driven for every retired agent (both count from the call that created them: attach the log and switch
+        retirement on at the same step).  Allocates `done` and `steps_driven` (device, int32, P), makes the goal test before the first step
+        on the host, and drops the cached descriptor.  Needs run(): step_staged(), a callable exchange and lin_passes > 1 are refused."""
+        from .lib import mpc as _mpc
+        goal_dis = float(_mpc.GOAL_DIS if goal_dis is None else goal_dis)
+        stop_speed = float(_mpc.STOP_SPEED if stop_speed is None else stop_speed)
+        if not (np.isfinite(goal_dis) and np.isfinite(stop_speed) and goal_dis >= 0 and stop_speed >= 0):
+            raise MpcxError('retire_at_goal: goal_dis = %r, stop_speed = %r must be finite and >= 0 (MPCX_E_INVALID)' % (goal_dis, stop_speed))
+        if self.log is not None and (goal_dis, stop_speed) != (self.log.goal_dis, self.log.stop_speed):
+            raise MpcxError('retire_at_goal: goal_dis / stop_speed (%r, %r) differ from the attached run log\'s (%r, %r): goal_step and '
+                            'steps_driven would disagree' % (goal_dis, stop_speed, self.log.goal_dis, self.log.stop_speed))
+        there = self._goal_now(goal_dis, stop_speed)
+        self.done = self.ctx.i32(there.astype(np.int32))
+        self.steps_driven = torch.zeros(self.P, dtype=torch.int32, device=self.ctx.device)
+        if there.any():
+            self.applied[torch.as_tensor(there, device=self.ctx.device)] = 0.0
+        self._retire = _lib.RetireC(self.done.data_ptr(), self.steps_driven.data_ptr(), goal_dis, stop_speed)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def keep_driving(self):
+        """switch retirement off: the batch enqueues exactly the launches of one that never had it.  Agents already retired stay where
+        they are and are driven again from there; `done` and `steps_driven` keep what they hold until the next retire_at_goal()"""
+        self._retire = None
+        self._desc = None
+
+    def active_count(self) -> int:
+        """agents still driving (one small reduction and one synchronisation)"""
+        if self._retire is None:
+            return self.P
+        return int((self.done == 0).sum().item())
+
+    def run_until_done(self, max_steps: int, chunk: int = 16, graph: bool = False) -> int:
+        """run(chunk) until every agent has arrived (active_count() == 0) or max_steps have been taken; returns the steps taken.  The
+        count is read back once per chunk, so a chunk may take up to chunk - 1 steps after the last arrival: each costs a near-empty
+        launch sequence and changes nothing but the scripted cars."""
+        if self._retire is None:
+            raise MpcxError('run_until_done: retirement is off (retire_at_goal() first): nothing ever ends the run')
+        if chunk < 1:
+            raise ValueError('run_until_done: chunk must be >= 1')
+        taken = 0
+        while taken < max_steps and self.active_count() > 0:
+            n = min(int(chunk), int(max_steps) - taken)
+            self.run(n, graph)
+            taken += n
+        return taken
 
     def _descriptor(self) -> '_lib.ClosedLoopC':
         d = _lib.ClosedLoopC()
@@ -344,14 +426,21 @@ class IntersectionBatch:
 
     def run(self, n_steps: int, graph: bool = False):
         """n_steps of the closed loop with no host work in between (mpcx_closed_loop_run)."""
+        if self._retire is not None and self.lin_passes > 1:
+            raise MpcxError('retirement at the goal with lin_passes = %d: the later linearisation passes build their work queue without '
+                            'the retired mask (MPCX_E_INVALID); keep_driving() or lin_passes = 1' % self.lin_passes)
         if callable(self.exchange):          # rehearsal exchange (torch.distributed): the host moves the rows between stages
+            if self._retire is not None:
+                raise MpcxError('retirement at the goal with a callable exchange: it steps through step_staged(), whose per-stage entry '
+                                'points have no retired mask; use exchange=\'rccl\' or keep_driving()')
             for _ in range(n_steps):
                 self.step_staged()
             return
         if self._desc is None:
             self._desc = self._descriptor()
         self._claim_context()
-        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts)
+        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
+                                 retire=self._retire)
         self.steps_done += n_steps
 
     def step(self):
@@ -369,6 +458,8 @@ class IntersectionBatch:
 
     def step_staged(self):
         """the same step through the per-stage entry points (one host call per stage)"""
+        if self._retire is not None:
+            raise MpcxError('step_staged() with retirement at the goal: the per-stage entry points have no retired mask; run() or keep_driving()')
         c = self.ctx
         self._claim_context()
         # what MovingObstacle*.get() would return for every agent: (x, y, v, yaw, a, steer)
@@ -425,6 +516,8 @@ class IntersectionBatch:
         if self.traffic is not None:         # the actors' states (x, y, theta, counter / cursor) and the pool as the last step saw it
             out['traffic_state'] = self.traffic_state.cpu().numpy().copy()
             out['obs6'] = self.obs6.cpu().numpy().copy()
+        if self._retire is not None:
+            out['done'], out['steps_driven'] = self.done.cpu().numpy().copy(), self.steps_driven.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:

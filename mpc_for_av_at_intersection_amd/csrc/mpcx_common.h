@@ -11,13 +11,13 @@ struct mpcx_ctx {
     hipStream_t stream = nullptr;
     mpcx_mpc_params mpc = {};
     bool have_mpc = false;
-    int32_t *ticket = nullptr;  // device words: [0] work-queue head of the persistent QP kernel, [4] the list of problems the condensed solver gives up on, [5] the head of the launch that works that list off; 8 allocated
+    int32_t *ticket = nullptr;  // device words: [0] work-queue head of the persistent QP kernel, [4] the list of problems the condensed solver gives up on, [5] the head of the launch that works that list off, [6] the length of the step's queue under retirement; 8 allocated
     int n_cu = 0;               // compute units of the device
     // device scratch that grows on demand (mpcx_grow); every capacity is in bytes
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[960] = {};     // descriptor + run log + options + parameters the cached graph was captured for
+    unsigned char loop_key[960] = {};     // descriptor + run log + options + retirement + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -72,6 +72,7 @@ struct mpcx_interaction_extras {
     // or -1) here, 3 ints per agent, and the window selection takes the conflict search's answer where that is provably its own.
     int32_t *near = nullptr;
     const int32_t *bin_hint = nullptr;  // iteration counts of the previous step: every agent is filed in ctx->bins under its queue key
+    const int32_t *done = nullptr;      // retirement (mpcx_retire::done): an agent with done[p] != 0 is not searched, not filed and none of its outputs is written
 };
 struct mpcx_window_extras {
     bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
@@ -82,14 +83,20 @@ struct mpcx_window_extras {
     const int32_t *stop_idx = nullptr;
     double v_ref = 0.0;
     int32_t *len_seen = nullptr;
+    // retirement (mpcx_retire::done; needs scatter): a retired agent gets no place in the order and no output; queue_len <- the length of
+    // this step's queue (the agents that were filed), which the solve then draws its tickets up to
+    const int32_t *done = nullptr;
+    int32_t *queue_len = nullptr;
 };
 struct mpcx_qp_order {                  // where the work-queue order of a solve comes from
     bool ready = false;                 // it is in ctx->order already and the ticket is zero (mpcx_window_extras::scatter)
     const int32_t *hint = nullptr, *now = nullptr, *prev = nullptr;   // else built from these as mpcx_qp_set_order_hint describes; all nullptr: no order
+    const int32_t *queue_len = nullptr; // with ready: the order holds *queue_len entries, not B (device word; retirement)
 };
 struct mpcx_plant_extras {
     const int32_t *stats_iters = nullptr;   // the step's iteration counts: the step feeds the run statistics (ctx->stats)
     bool reset_bins = false;                // zero the queue bins and the ticket for the next step
+    const int32_t *done = nullptr;          // retirement: a retired agent's state, applied and u are left alone and it feeds no statistics
 };
 int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const double *path_xyyaw,
                                const double *path_cs, const int32_t *path_off, const int32_t *path_len, const int32_t *prev_cut_len,
@@ -107,7 +114,8 @@ int32_t mpcx_check_launch(mpcx_ctx *ctx, const char *what);
 // grow-on-demand device scratch: *p holds at least need_bytes afterwards (contents are not kept); `what` names it in the error text (mpcx_api.hip)
 int32_t mpcx_grow(mpcx_ctx *ctx, void **p, size_t *cap_bytes, size_t need_bytes, const char *what);
 int32_t mpcx_ensure_pred(mpcx_ctx *ctx, size_t need_doubles);   // prediction scratch (mpcx_interaction.hip)
-int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, double *xbar);   // mpcx_prepare.hip
+// done (retirement): the xbar rows of retired agents are neither computed nor written
+int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, double *xbar, const int32_t *done = nullptr);   // mpcx_prepare.hip
 int32_t mpcx_traffic_validate(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffic_actor *actors, const double *tape, int64_t tape_rows,
                               const int32_t *pool_row, int32_t n_obs_pool);                                      // mpcx_traffic.hip
 int32_t mpcx_traffic_enqueue(mpcx_ctx *ctx, int32_t n_actors, const mpcx_traffic_actor *actors, double *actor_state, const double *tape,
@@ -120,13 +128,20 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
                             const int32_t *target_ind, const int32_t *cut_len, const int32_t *traj_idx, const int32_t *hit_idx,
                             const int32_t *status, const int32_t *iters, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
                             const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log,
-                            const int32_t *goal_len = nullptr);      // goal_len: mpcx_record_step_batch_goal
+                            const int32_t *goal_len = nullptr,       // goal_len: mpcx_record_step_batch_goal
+                            const int32_t *done = nullptr);          // retirement: a retired agent is skipped entirely
+// retirement at the goal (mpcx_retire.hip): "no retirement" test, check of the struct, the launch alone
+bool mpcx_retire_absent(const mpcx_retire *r);
+int32_t mpcx_retire_validate(mpcx_ctx *ctx, const mpcx_retire *r, int32_t P);
+int32_t mpcx_retire_enqueue(mpcx_ctx *ctx, int32_t P, const double *state, double *applied, const double *path_xyyaw, const int32_t *path_off,
+                            const int32_t *path_len, const int32_t *target_ind, const int32_t *goal_len, const mpcx_retire *r);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).
 #define MPCX_JUMP_BONUS 11
 #define MPCX_ORDER_BINS 64
 #define MPCX_TICKET_WORDS 8      /* ctx->ticket: the queue head and the other per-launch counters, zeroed together */
+#define MPCX_TICKET_QUEUE_LEN 6  /* ... of which this word holds the length of the step's queue under retirement (written by the window stage) */
 #define MPCX_ORDER_COPIES 16
 namespace mpcx {
 __device__ __forceinline__ int order_key_of(int hint, bool moved) {
@@ -159,7 +174,8 @@ struct QpArgs {
     int has_order;
     // second chance for problems the condensed solver gives up on (MAXITER / NUMERIC): with defer_fail it leaves their outputs
     // untouched and appends their indices to fail_list; the stage solver then runs over that list, whose length it reads from
-    // *queue_len (has_queue_len) instead of B
+    // *queue_len (has_queue_len) instead of B.  The closed loop with retirement at the goal passes the first launch a queue_len of its own:
+    // the number of agents filed in this step's queue (both solvers draw tickets up to it)
     int defer_fail;
     int32_t *fail_list, *fail_count;
     const int32_t *queue_len;

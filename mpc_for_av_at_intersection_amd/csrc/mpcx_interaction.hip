@@ -97,6 +97,7 @@ struct InterArgs {
     int32_t *bin_cnt, *keyslot;
     const int32_t *key_prev;   // optional (closed loop, speed-reference mode): what the work-queue key's "moved" test and prev_save take as the previous value of cut_len instead of prev_cut (there prev_cut is the previous PATH length and cut_len the stop index); may alias cut_len
     int32_t *near;        // optional (closed loop): near[3p] = the start index of this agent's nearest-index scan, near[3p+1] / [3p+2] = the largest / smallest of its three nearest indices (absolute), -1 = none
+    const int32_t *done;  // retirement (read by the RETIRE instantiation only): done[p] != 0 = agent p has arrived -- no search, no output, not filed in a bin
 };
 
 __device__ __forceinline__ double dist2d(double ax, double ay, double bx, double by) {
@@ -718,7 +719,13 @@ __device__ __forceinline__ int cut_index(const mpcx_interaction_params &ip, cons
     return cl;
 }
 
+// RETIRE: the closed loop with retirement at the goal (mpcx_retire).  A template parameter, not a null test, as predict_kernel<MAPPED>:
+// the launch without retirement runs the code it ran before there was any.
+template <bool RETIRE>
 __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
+    // a retired agent: nothing is read, written or filed -- its outputs stay as its last driven step left them, and an agent that is
+    // not filed is never solved (predict_kernel has packed its pool row all the same: to the others it is a parked car)
+    if constexpr (RETIRE) { if (a.done[blockIdx.x] != 0) return; }
     // dynamic LDS, sized by the host from the longest path of the call (mpcx_interaction_params.max_path_len):
     //   s_cum [max_rem] doubles   step / cumulative lengths of the remaining path; once the resampling has consumed them the
     //                             same bytes hold s_ego [fcap][4] (ego disc centres per kept pose) and s_box (the runs' boxes)
@@ -872,8 +879,9 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     mpcx::InterArgs ia{*ip, P, state, path_xyyaw, path_cs, path_off, path_len, prev_cut_len, ctx->pred,
                        obs_off, obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, max_rem, fcap, x.prev_save,
                        x.bin_hint, x.bin_hint ? ctx->bins : nullptr, x.bin_hint ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr,
-                       x.key_prev, x.near};
-    hipLaunchKernelGGL(mpcx::interaction_kernel, dim3(P), dim3(64), lds, ctx->stream, ia);
+                       x.key_prev, x.near, x.done};
+    if (x.done) hipLaunchKernelGGL(mpcx::interaction_kernel<true>, dim3(P), dim3(64), lds, ctx->stream, ia);
+    else hipLaunchKernelGGL(mpcx::interaction_kernel<false>, dim3(P), dim3(64), lds, ctx->stream, ia);
     return mpcx_check_launch(ctx, "interaction kernels");
 }
 

@@ -3,7 +3,8 @@
 // path kept whole and the speed reference zeroed from the conflict on):
 // n_steps x [scripted traffic rows -> pool pack -> predict -> conflict search + path cut -> reference window ->
 // rollout -> QP -> plant (-> run-log record, iff a log is attached)], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
-// host synchronisation or host arithmetic in between.  Every stage is the kernel behind the per-stage C entry
+// host synchronisation or host arithmetic in between.  With retirement at the goal (mpcx_retire) the step ends with retire_kernel, and an agent
+// that has arrived is skipped by every stage but the pool pack.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
 #include "mpcx_common.h"
@@ -50,15 +51,23 @@ static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cu
 // of the previous tmp_trajectory from o->prev_len (0 before the batch's first step, the path length afterwards -- the window kernel sets it,
 // device memory, so a replayed graph sees it change), its cut index in c->cut_len is the window stage's stop index over the whole path, and
 // the record stage tests the goal against the whole path.
+// r: retirement at the goal or nullptr = none (then exactly the launches of a step without it, with the same arguments).  With it every
+// stage gets r->done: the conflict search returns at once for a retired agent and does not file it, the window stage gives it no place in
+// the order and leaves the length of the queue in a spare word of ctx->ticket (the plant kernel zeroes it with the others), both solvers
+// draw tickets up to that length, the rollout, the plant and the record stage skip the agent, and retire_kernel ends the step.  The pool
+// row of a retired agent is still packed (by predict_kernel, or by pack_pool_kernel in the agent-sharded layout) from its frozen state and
+// zero controls, and the scripted cars step as ever.
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                            const mpcx_closed_loop_opts *o) {
+                            const mpcx_closed_loop_opts *o, const mpcx_retire *r) {
     const int P = c->P;
+    const int32_t *done = r ? r->done : nullptr;
+    int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
     const bool speed = o->stop_mode == MPCX_STOP_SPEED;
     ctx->bins_clean = false;        // until the plant kernel of this step is enqueued
     int32_t rc, pool_rows = P;
     // the warm-start rollout of this step needs only the states and the previous solution: it runs on the side stream BESIDE the pool pack,
     // the prediction and the conflict search (a chain of T dependent sincos / tan per agent, 35-45 us) and is joined by the window selection
-    rc = mpcx_rollout_fork(ctx, P, c->state, c->u_sol, c->xbar);
+    rc = mpcx_rollout_fork(ctx, P, c->state, c->u_sol, c->xbar, done);
     if (rc != MPCX_OK) return rc;
     // the conflict search leaves the cut lengths of the previous step in ctx->prev_cut (the queue of the QP kernel puts the agents whose
     // cut moved at the front) and files every agent under its work-queue key (previous iteration count + "the cut moved"): hard problems first.  The window
@@ -68,6 +77,7 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     ix.prev_save = ctx->prev_cut;
     ix.near = near_hints(ctx, P);
     ix.bin_hint = binned ? c->iters : nullptr;
+    ix.done = done;
     if (speed) ix.key_prev = c->cut_len;        // "the cut moved" = the stop index moved
     if (c->exchange == MPCX_SHARD_AGENTS) {
         // agent-sharded layout: this rank's rows travel to every rank, every rank assembles the whole pool (one RCCL all-gather)
@@ -102,26 +112,35 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         // the first pass writes the queue order and joins the rollout forked above; a later one forks its own
         mpcx_window_extras wx{binned && first, near_hints(ctx, P), c->traj_idx, first};
         if (speed) { wx.stop_idx = c->cut_len; wx.v_ref = o->v_ref; wx.len_seen = o->prev_len; }
+        wx.done = done; wx.queue_len = queue_len;       // (retirement is refused with more than one pass or without bins)
         rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
                                  c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar, wx);
         if (rc != MPCX_OK) return rc;
         // (further linearisation passes build their order in line, from the iteration counts of the pass before)
-        const mpcx_qp_order ord{binned && first, c->iters, c->cut_len, ctx->prev_cut};
+        const mpcx_qp_order ord{binned && first, c->iters, c->cut_len, ctx->prev_cut, queue_len};
         rc = mpcx_qp_enqueue(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol, c->status, c->iters, c->kkt, ord);
         if (rc != MPCX_OK) return rc;
     }
-    const mpcx_plant_extras px{c->iters, binned};
+    const mpcx_plant_extras px{c->iters, binned, done};
     rc = mpcx_plant_enqueue(ctx, P, c->state, c->u_sol, c->status, c->applied, px);
     if (rc == MPCX_OK) ctx->bins_clean = binned;
-    if (rc != MPCX_OK || !log) return rc;
+    if (rc != MPCX_OK) return rc;
     // the run log: one row per agent from the buffers as the step leaves them; the pool still holds the rows this step's conflict search saw
-    return mpcx_record_enqueue(ctx, ip, P, c->state, c->applied, c->x_sol, c->path_xyyaw, c->path_off, c->path_len, c->target_ind, c->cut_len,
-                               c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, log,
-                               speed ? c->path_len : nullptr);
+    if (log) {
+        rc = mpcx_record_enqueue(ctx, ip, P, c->state, c->applied, c->x_sol, c->path_xyyaw, c->path_off, c->path_len, c->target_ind, c->cut_len,
+                                 c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, log,
+                                 speed ? c->path_len : nullptr, done);
+        if (rc != MPCX_OK) return rc;
+    }
+    // retirement: the goal test of the record stage (len(cx) = cut_len, the whole path in speed mode), after it, so that the arrival
+    // step's row logs the controls really applied
+    if (r) rc = mpcx_retire_enqueue(ctx, P, c->state, c->applied, c->path_xyyaw, c->path_off, c->path_len, c->target_ind,
+                                    speed ? c->path_len : c->cut_len, r);
+    return rc;
 }
 
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                               const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
+                               const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
@@ -138,6 +157,11 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (log) {          // refused before anything is launched, whatever n_steps is
         const int32_t lrc = mpcx_record_validate(ctx, log, c->obs_skip);
         if (lrc != MPCX_OK) return lrc;
+    }
+    if (mpcx_retire_absent(retire)) retire = nullptr;
+    if (retire) {       // refused before anything is launched, whatever n_steps is
+        const int32_t rrc = mpcx_retire_validate(ctx, retire, c->P);
+        if (rrc != MPCX_OK) return rrc;
     }
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
@@ -205,7 +229,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt);
+            rc = enqueue_step(ctx, ip, c, log, &opt, retire);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -215,8 +239,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_interaction_params) + sizeof(mpcx_mpc_params) +
-                  9 * sizeof(void *) <= sizeof key,
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_interaction_params) +
+                  sizeof(mpcx_mpc_params) + 9 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
     size_t o = 0;
@@ -224,6 +248,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (log) memcpy(key + o, log, sizeof *log);     // (zeros = no log: a graph captured without the record stage)
     o += sizeof *log;
     memcpy(key + o, &opt, sizeof opt); o += sizeof opt;
+    if (retire) memcpy(key + o, retire, sizeof *retire);     // (zeros = no retirement: a graph captured without it)
+    o += sizeof *retire;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
     memcpy(key + o, &ctx->pred, sizeof ctx->pred); o += sizeof ctx->pred;
@@ -243,7 +269,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt);
+        rc = enqueue_step(ctx, ip, c, log, &opt, retire);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -260,15 +286,21 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                               int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, retire, n_steps, use_graph);
 }

@@ -34,8 +34,15 @@ struct RefArgs {
     const int32_t *stop_idx;
     double v_ref;
     int32_t *len_seen;      // with a stop index: <- n, the length of this step's tmp_trajectory (the next conflict search's prev_cut_len), or nullptr
+    // retirement (read by the RETIRE instantiation only, which needs `order`): done[b] != 0 = agent b has arrived; queue_len <- the number
+    // of agents filed in this step's queue
+    const int32_t *done;
+    int32_t *queue_len;
 };
 
+// RETIRE: the closed loop with retirement at the goal (mpcx_retire) -- a template parameter, not a null test: the launch without
+// retirement runs the code it ran before there was any
+template <bool RETIRE>
 __device__ __forceinline__ void ref_window_block(const RefArgs &a, int b) {
     const int lane = threadIdx.x & 63;
     const int T = a.p.T, W = T + 1;
@@ -54,6 +61,12 @@ __device__ __forceinline__ void ref_window_block(const RefArgs &a, int b) {
         int sfx = c;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_down(sfx, d); sfx += lane + d < 64 ? o : 0; }
+        if constexpr (RETIRE) {
+            // lane 0's suffix sum is the sum of all bins over all copies = the agents the conflict search filed = the length of this step's
+            // queue.  The first wavefront of the launch leaves it for the solve, whether its own agent is retired or not
+            if (b == 0 && lane == 0) *a.queue_len = sfx;
+            if (a.done[b] != 0) return;       // retired: no place in the order, no output, len_seen untouched
+        }
         const int ks = a.keyslot[b];
         const int first = __shfl(sfx - c + lower, ks >> 24);
         if (lane == 0) a.order[first + (ks & 0xFFFFFF)] = b;
@@ -121,6 +134,7 @@ struct RollArgs {
     int B;
     const double *state, *u_warm;
     double *xbar;
+    const int32_t *done;    // retirement (read by the RETIRE instantiation only): the row of an agent with done[b] != 0 is neither computed nor written
 };
 
 // Rollout of 64 instances by one wavefront (lane = instance: the reference's operation order, one dependent chain of T x (sincos, tan,
@@ -129,6 +143,9 @@ struct RollArgs {
 // each its own write transaction: 165 MB of write traffic for 45 MB of output.
 // (round 4: the staging buffer is dynamic LDS sized for the horizon in use -- 43.5 KB at T = 20 instead of 68 KB for T = 32: this kernel runs
 // beside the conflict search on the side stream, and its two workgroups per CU left that kernel's 6.5-KB workgroups 24 KB of a CU's LDS)
+// RETIRE: a retired agent's xbar row stays as its last driven step left it (its state and inputs are frozen, so the row would come out
+// the same from the step after its arrival on -- but not the same as that last driven step's, which started one state earlier)
+template <bool RETIRE>
 __global__ __launch_bounds__(64) void rollout_kernel(RollArgs a) {
     extern __shared__ double s_roll[];                   // [64][4 W + 1]; +1: rows of 4 W doubles would sit 8 lanes to a bank group
     const int T = a.p.T, W = T + 1;
@@ -136,7 +153,9 @@ __global__ __launch_bounds__(64) void rollout_kernel(RollArgs a) {
     auto s_x = [&](int lane) -> double * { return s_roll + (size_t)lane * RS; };
     const int b0 = (int)blockIdx.x * 64;
     const int n = a.B - b0 < 64 ? a.B - b0 : 64;
-    if (threadIdx.x < (unsigned)n) {
+    bool gone = false;
+    if constexpr (RETIRE) gone = threadIdx.x < (unsigned)n && a.done[b0 + (int)threadIdx.x] != 0;
+    if (threadIdx.x < (unsigned)n && !gone) {
         const int b = b0 + (int)threadIdx.x;
         double x = a.state[4 * b], y = a.state[4 * b + 1], v = a.state[4 * b + 2], th = a.state[4 * b + 3];
         double *xb = s_x(threadIdx.x);
@@ -150,7 +169,12 @@ __global__ __launch_bounds__(64) void rollout_kernel(RollArgs a) {
     }
     __syncthreads();
     double *out = a.xbar + (size_t)b0 * 4 * W;
-    for (int i = threadIdx.x; i < n * 4 * W; i += blockDim.x) out[i] = s_x(i / (4 * W))[i % (4 * W)];
+    if constexpr (RETIRE) {
+        const unsigned long long gm = __ballot(gone);       // one wavefront per block: bit l = lane l's agent is retired
+        for (int i = threadIdx.x; i < n * 4 * W; i += blockDim.x)
+            if (!((gm >> (i / (4 * W))) & 1ull)) out[i] = s_x(i / (4 * W))[i % (4 * W)];
+    } else
+        for (int i = threadIdx.x; i < n * 4 * W; i += blockDim.x) out[i] = s_x(i / (4 * W))[i % (4 * W)];
 }
 
 // The two halves of mpc.py:211-239's preparation are independent -- the rollout is a chain of T dependent sincos / tan evaluations per
@@ -159,9 +183,10 @@ __global__ __launch_bounds__(64) void rollout_kernel(RollArgs a) {
 // round 3 both were workgroups of one launch; the rollout's 68-KB staging buffer would have been allocated for every workgroup of it.)
 // Window workgroups of four wavefronts = four instances: fewer, larger workgroups to dispatch (57 -> 54 us).
 constexpr int PREP_WAVES = 4;
+template <bool RETIRE>
 __global__ __launch_bounds__(64 * PREP_WAVES) void ref_window_kernel(RefArgs ra) {
     const int b = (int)blockIdx.x * PREP_WAVES + (threadIdx.x >> 6);
-    if (b < ra.B) ref_window_block(ra, b);
+    if (b < ra.B) ref_window_block<RETIRE>(ra, b);
 }
 
 struct PlantArgs {
@@ -176,6 +201,7 @@ struct PlantArgs {
     unsigned long long *stats;    // ... and the run statistics they are added to: agent-steps, iterations, failed solves, max iterations
     int has_stats;
     int32_t *zero_bins, *zero_ticket;   // closed loop: the queue bins and the ticket are zeroed for the next step (nullptr otherwise)
+    const int32_t *done;                // retirement or nullptr: the lane of an agent with done[b] != 0 leaves state, applied and u alone and feeds no statistics
 };
 
 // MPC.step's tail (mpc.py:294-297) + Simulation.step
@@ -185,8 +211,9 @@ __global__ __launch_bounds__(256) void plant_kernel(PlantArgs a) {
         if (threadIdx.x < MPCX_TICKET_WORDS) a.zero_ticket[threadIdx.x] = 0;
     }
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool gone = a.done && b < a.B && a.done[b] != 0;
     if (a.has_stats) {          // run statistics (mpcx_closed_loop_stats)
-        const bool in = b < a.B;
+        const bool in = b < a.B && !gone;
         const int it = in ? a.iters[b] : 0;
         const int bad = (in && a.status[b] != MPCX_QP_OPTIMAL) ? 1 : 0;
         int s_it = it, s_bad = bad, s_n = in ? 1 : 0, s_mx = it;
@@ -203,7 +230,7 @@ __global__ __launch_bounds__(256) void plant_kernel(PlantArgs a) {
             if ((unsigned long long)s_mx > w[3]) w[3] = (unsigned long long)s_mx;
         }
     }
-    if (b >= a.B) return;
+    if (b >= a.B || gone) return;
     const int T = a.p.T;
     double di = a.applied[2 * b], ai;
     const bool ok = !a.status || a.status[b] == MPCX_QP_OPTIMAL;
@@ -257,11 +284,15 @@ int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const
         return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch_stop: v_ref is not finite");
     mpcx::RefArgs ra{ctx->mpc, B, state, path_xyyaw, path_v, path_off, path_len, dl, target_ind, xref, reaches_end, ov, (long)ov_stride,
                      x.scatter ? ctx->bins : nullptr, x.scatter ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr, x.scatter ? ctx->order : nullptr,
-                     x.near, x.near ? x.tidx : nullptr, x.stop_idx, x.stop_idx ? x.v_ref : 0.0, x.stop_idx ? x.len_seen : nullptr};
+                     x.near, x.near ? x.tidx : nullptr, x.stop_idx, x.stop_idx ? x.v_ref : 0.0, x.stop_idx ? x.len_seen : nullptr,
+                     x.done, x.queue_len};
+    const bool retire = x.done != nullptr;
+    if (retire && (!x.scatter || !x.queue_len))
+        return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch: retirement needs the queue order built beside the window selection");
     // the rollout may already be in flight: mpcx_closed_loop_run forks it at the start of the step, beside the conflict search
     const bool forked = x.rollout_forked;
     if (!forked) {
-        int32_t rc = mpcx_rollout_fork(ctx, B, state, u_warm, xbar);
+        int32_t rc = mpcx_rollout_fork(ctx, B, state, u_warm, xbar, x.done);
         if (rc != MPCX_OK) return rc;
     }
     // a rollout forked long ago (mpcx_closed_loop_run: at the start of the step) is joined IN FRONT of the window selection: the queue
@@ -269,7 +300,9 @@ int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const
     // a rollout forked just now runs beside the window selection and is joined behind it
     if (forked && hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "mpc_prepare_batch: cannot join the side stream");
-    hipLaunchKernelGGL(mpcx::ref_window_kernel, dim3((B + mpcx::PREP_WAVES - 1) / mpcx::PREP_WAVES), dim3(64 * mpcx::PREP_WAVES), 0, ctx->stream, ra);
+    const dim3 wgrid((B + mpcx::PREP_WAVES - 1) / mpcx::PREP_WAVES), wblock(64 * mpcx::PREP_WAVES);
+    if (retire) hipLaunchKernelGGL(mpcx::ref_window_kernel<true>, wgrid, wblock, 0, ctx->stream, ra);
+    else hipLaunchKernelGGL(mpcx::ref_window_kernel<false>, wgrid, wblock, 0, ctx->stream, ra);
     if (!forked && hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "mpc_prepare_batch: cannot join the side stream");
     return mpcx_check_launch(ctx, "prepare kernels");
@@ -277,11 +310,13 @@ int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const
 
 // the warm-start rollout (mpc.py:112-126 `_predict_motion`) on the context's side stream, ordered behind everything enqueued on the
 // context's stream so far; mpcx_window_enqueue joins it (mpcx_window_extras::rollout_forked: instead of forking one of its own)
-int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, double *xbar) {
-    mpcx::RollArgs ro{ctx->mpc, B, state, u_warm, xbar};
+int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, double *xbar, const int32_t *done) {
+    mpcx::RollArgs ro{ctx->mpc, B, state, u_warm, xbar, done};
     if (hipEventRecord(ctx->ev_fork, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "mpc_prepare_batch: cannot fork the side stream");
-    hipLaunchKernelGGL(mpcx::rollout_kernel, dim3((B + 63) / 64), dim3(64), 64 * (4 * (size_t)(ctx->mpc.T + 1) + 1) * sizeof(double), ctx->side, ro);
+    const size_t roll_lds = 64 * (4 * (size_t)(ctx->mpc.T + 1) + 1) * sizeof(double);
+    if (done) hipLaunchKernelGGL(mpcx::rollout_kernel<true>, dim3((B + 63) / 64), dim3(64), roll_lds, ctx->side, ro);
+    else hipLaunchKernelGGL(mpcx::rollout_kernel<false>, dim3((B + 63) / 64), dim3(64), roll_lds, ctx->side, ro);
     // a refused launch is the rollout's failure, not that of whichever call checks the error state next (the staging buffer is above
     // 64 KB for T >= 31: gfx950 grants up to 160 KB of LDS per workgroup without hipFuncAttributeMaxDynamicSharedMemorySize)
     const int32_t rc = mpcx_check_launch(ctx, "rollout_kernel");
@@ -308,7 +343,7 @@ int32_t mpcx_plant_enqueue(mpcx_ctx *ctx, int32_t B, double *state, double *u, c
     const bool st = ctx->stats && x.stats_iters && status;
     const bool rz = x.reset_bins && ctx->bins && ctx->ticket;
     mpcx::PlantArgs pa{ctx->mpc, B, state, u, status, applied, ctx->tune, x.stats_iters, ctx->stats, st ? 1 : 0,
-                       rz ? ctx->bins : nullptr, rz ? ctx->ticket : nullptr};
+                       rz ? ctx->bins : nullptr, rz ? ctx->ticket : nullptr, x.done};
     hipLaunchKernelGGL(mpcx::plant_kernel, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, pa);
     return mpcx_check_launch(ctx, "plant_kernel");
 }

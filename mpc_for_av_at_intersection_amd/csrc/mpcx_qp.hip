@@ -101,7 +101,8 @@ __global__ __launch_bounds__(64, 1) void qp_kernel(QpArgs a) {
     int b = 0;
     if (lane == 0) b = atomicAdd(a.ticket, 1);
     b = __builtin_amdgcn_readfirstlane(b);
-    if (b >= a.B) break;
+    // (retirement at the goal: the queue holds *queue_len agents, the ones that were filed -- wave-uniform, as in the stage solver)
+    if (b >= (a.has_queue_len ? *a.queue_len : a.B)) break;
     if (a.has_order) b = a.order[b];      // hardest first (mpcx_qp_set_order_hint): a wavefront that draws a long problem draws nothing
                                           // else while the short ones are shared out among the others
     lds_sync();                       // the previous problem's LDS reads are done before this one overwrites the tables
@@ -765,6 +766,7 @@ int32_t mpcx_qp_enqueue(mpcx_ctx *ctx, int32_t B, const double *x0, const double
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "qp_solve_batch: hipMemsetAsync failed");
     mpcx::QpArgs a{ctx->mpc, B, ctx->ticket, u_warm != nullptr, x0, xref, xbar, u_warm, reaches_end, x_out, u_out, kkt, status, iters,
                    ctx->tune, ctx->tune != nullptr, order, order != nullptr, 0, nullptr, nullptr, nullptr, 0};
+    if (ord.ready && ord.queue_len) { a.queue_len = ord.queue_len; a.has_queue_len = 1; }     // retirement: tickets up to the device-side count
     if (!use_stage) {
         // The condensed solver's 64-row LDL' loses a few more digits than the Riccati recursion on the worst-conditioned problems
         // (lam/s ~ 1e10 in M = H + G'DG): about one problem in 2e6 of the benchmark workload breaks down there short of the

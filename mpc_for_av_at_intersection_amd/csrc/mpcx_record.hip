@@ -12,6 +12,7 @@ namespace mpcx {
 __global__ __launch_bounds__(64) void record_kernel(RecordArgs a) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= a.P) return;
+    if (a.done && a.done[q] != 0) return;   // retired at the goal: no row, cursor and outcome words stay
     double f[REC_F64];
     int32_t w[REC_I32];
     const int32_t s = record_agent(a, q, f, w);
@@ -54,7 +55,8 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
                             const double *x_sol, const double *path_xyyaw, const int32_t *path_off, const int32_t *path_len,
                             const int32_t *target_ind, const int32_t *cut_len, const int32_t *traj_idx, const int32_t *hit_idx,
                             const int32_t *status, const int32_t *iters, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
-                            const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log, const int32_t *goal_len) {
+                            const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log, const int32_t *goal_len,
+                            const int32_t *done) {
     mpcx::RecordArgs a;
     a.P = P; a.n_pool = n_obs_pool;
     a.x_stride = 4 * (int64_t)(ctx->mpc.T + 1);
@@ -66,6 +68,7 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
     a.obs_off = obs_off; a.obs_cnt = obs_cnt; a.obs_skip = obs_skip;
     a.log = *log;
     a.goal_len = goal_len;
+    a.done = done;
     hipLaunchKernelGGL(mpcx::record_kernel, dim3((P + 63) / 64), dim3(64), 0, ctx->stream, a);
     return mpcx_check_launch(ctx, "record_kernel");
 }

@@ -31,6 +31,8 @@
 //                  first contact would be step 0 there.  The rows keep the raw value.)
 // The window is walked over at most MPCX_MAX_OBS + 1 rows (what the conflict search handles; it flags a larger one with hit_idx -2), every
 // pool index is checked against the pool before it is read.
+// Under retirement at the goal (mpcx_retire) the rule is not run for a retired agent: its cursor stops at goal_step, its outcome words
+// stay, and the goal test below is the one mpcx_retire_core.h calls for the retirement itself.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -56,6 +58,7 @@ struct RecordArgs {
     const int32_t *obs_off, *obs_cnt, *obs_skip;
     mpcx_run_log log;
     const int32_t *goal_len = nullptr;      // len(self.cx) of the goal test per agent; nullptr: cut_len
+    const int32_t *done = nullptr;          // retirement (mpcx_retire::done) or nullptr: record_kernel skips an agent with done[q] != 0 entirely
 };
 
 MPCX_REC_FN void rec_sincos(double a, double *s, double *c) {

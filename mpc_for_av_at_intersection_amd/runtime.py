@@ -613,12 +613,18 @@ class Context:
 
     @_ordered
     def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
-                        log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None):
+                        log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None,
+                        retire: Optional['_lib.RetireC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
-        opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut."""
+        opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
+        retire: a _lib.RetireC -- agents are retired at their goal (mpcx_closed_loop_run_retire); None = they are driven on."""
         cip = ip.to_c()
-        if opts is not None:
+        if retire is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_retire(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
+                                                           None if opts is None else C.byref(opts), C.byref(retire), int(n_steps),
+                                                           1 if graph else 0))
+        elif opts is not None:
             self._chk(self.lib.mpcx_closed_loop_run_opts(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
                                                          C.byref(opts), int(n_steps), 1 if graph else 0))
         elif log is None:
