@@ -16,6 +16,9 @@
  *   - one mpcx_ctx per host thread / stream; a ctx is not re-entrant.
  *   - what the reference's loop records ABOUT a run (History rows, the goal test that ends the loop) and the true clearance between the
  *     vehicles is the run log: mpcx_run_log, mpcx_closed_loop_run_logged, mpcx_record_step_batch.
+ *   - the end of an agent's episode (the loop's `if mpc.is_goal(state): break`) is retirement at the goal: mpcx_retire,
+ *     mpcx_closed_loop_run_retire; taking the arrived car out of everybody else's scene as well is departure: mpcx_scene,
+ *     mpcx_closed_loop_run_scene.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -486,6 +489,36 @@ typedef struct {
 int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
                                     const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
                                     const mpcx_retire *retire /*or NULL*/, int32_t n_steps, int32_t use_graph);
+
+/* ---- departure: taking vehicles out of the scene.  absent[r] != 0: pool row r is not in the scene -- no other agent's conflict search
+ * considers it (interaction_kernel builds the list of the PRESENT rows of its window, so a window with departed cars is a shorter
+ * obstacle list, not the same list behind a test), the run log's clearance and contact of the other agents ignore it, and its prediction
+ * is not computed (nothing reads it).  The defining property: for every driving agent a step with the mask equals a step whose obstacle
+ * list is the agent's pool window minus its own row and the absent rows, relative order kept.
+ * With a scene, retire_kernel sets absent[obs_skip[q]] -- agent q's own pool row, the same index with and without scripted traffic
+ * (obs_skip[q] == ego_row[q] there) -- in the step in which q arrives.  It is the step's last launch, so the others see the car gone from
+ * the NEXT step on.  The retired agent's own frozen buffers, done / steps_driven, the queue length and the statistics are exactly those of
+ * retirement alone, and its pool row is still packed every step: it is simply not looked at.
+ * The caller may preset words, e.g. a scripted actor's row, to hide that vehicle from everybody.  An agent whose own row is absent but
+ * which still drives (done[q] == 0) is a GHOST: it sees the others, they do not see it, and its own clearance is still measured from
+ * its own (packed) row.
+ * absent is caller-owned DEVICE memory, n_rows int32 words, zero-initialised; everything that changes is device memory, so a replayed
+ * graph departs agents like a plain run.  The struct travels beside the descriptor (no other struct changes size); the cached graph's key
+ * covers it by value.  scene = NULL or an all-zero struct: mpcx_closed_loop_run_retire itself -- the same launches with the same arguments.
+ * MPCX_E_INVALID ("scene: ...") before anything is launched, whatever n_steps is: n_rows is not the pool's row count (pool_rows with
+ * scripted traffic, else P); a scene without retirement; a scene with MPCX_SHARD_AGENTS (a remote rank's mask would have to travel with
+ * the all-gather -- a follow-up); obs_skip NULL, or an agent whose own row obs_skip[q] lies outside the pool (read back once per call, as
+ * the row maps of scripted traffic are).  A window of more than 64 rows is beyond the kernel's capacity with a scene (hit_idx -2) however
+ * many of its rows are absent.  Works with scripted traffic, the run log, both stop modes and use_graph. */
+typedef struct {
+    int32_t *absent;     /* n_rows, caller-owned, zero = in the scene */
+    int32_t n_rows;      /* rows of the pool: pool_rows with scripted traffic, else P */
+    int32_t reserved;
+} mpcx_scene;
+int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                   const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                   const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                   int32_t n_steps, int32_t use_graph);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

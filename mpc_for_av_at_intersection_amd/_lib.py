@@ -62,6 +62,11 @@ class RetireC(C.Structure):
     _fields_ = [('done', C.c_void_p), ('steps_driven', C.c_void_p), ('goal_dis', C.c_double), ('stop_speed', C.c_double)]
 
 
+class SceneC(C.Structure):
+    """mirror of mpcx_scene (include/mpcx.h): departure; absent is a device address (n_rows int32, one per pool row)"""
+    _fields_ = [('absent', C.c_void_p), ('n_rows', C.c_int32), ('reserved', C.c_int32)]
+
+
 STOP_CUT, STOP_SPEED = 0, 1     # mpcx_closed_loop_opts.stop_mode
 STOP_MODES = {'cut': STOP_CUT, 'speed': STOP_SPEED}
 NO_STOP = 999                   # MPCX_NO_STOP: the stop index lib/mpc_with_speed.py:281 reads as "no stop"
@@ -121,7 +126,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
            'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
            'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
-           'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire']
+           'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene']
 
 
 def load():
@@ -194,5 +199,8 @@ def load():
     lib.mpcx_closed_loop_run_retire.restype = i32
     lib.mpcx_closed_loop_run_retire.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
                                                 C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), i32, i32]
+    lib.mpcx_closed_loop_run_scene.restype = i32
+    lib.mpcx_closed_loop_run_scene.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                               C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), i32, i32]
     _lib = lib
     return lib

@@ -16,6 +16,8 @@ path stays whole and the speed reference is zeroed from the conflict on, instead
 its loop and the true clearance to the other vehicles, per agent, on the device (RunLog).
 `retire_at_goal()` ends an agent's episode where the reference's loop ends (`if mpc.is_goal(state): break`): from the step after its
 arrival on it is a parked car that is not solved, not logged and not counted; `run_until_done()` runs until every agent has arrived.
+`retire_at_goal(leave_scene=True)` is DEPARTURE: the arrived car is also taken out of the scene -- from the next step on nobody's conflict
+search and nobody's clearance sees it (two stock routes share every exit arm: a car parked on the goal would block the second for good).
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -298,6 +300,8 @@ class IntersectionBatch:
         self.done: Optional[torch.Tensor] = None             # retire_at_goal(): int32 (P,), != 0 = arrived and retired
         self.steps_driven: Optional[torch.Tensor] = None     # ... int32 (P,), steps taken while driving
         self._retire = None
+        self.absent: Optional[torch.Tensor] = None           # retire_at_goal(leave_scene=True): int32 (pool rows,), != 0 = not in the scene
+        self._scene = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -341,7 +345,7 @@ class IntersectionBatch:
         return ((np.hypot(st[:, 0] - goal[:, 0], st[:, 1] - goal[:, 1]) <= goal_dis) & (np.abs(self.target_ind.cpu().numpy() - cut) < 5) &
                 (np.abs(st[:, 2]) <= stop_speed))
 
-    def retire_at_goal(self, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None):
+    def retire_at_goal(self, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None, leave_scene: bool = False):
         """End every agent's episode where the reference's loop ends (`if mpc.is_goal(state): break`, scenarios/mpc_intersection.py:92-93):
         the step in which an agent arrives sets done[q] = 1, and from the next step on the agent keeps its state, has applied = (0, 0) -- to
         the others it is a parked car --, is not solved (its sol / pre / inter rows, target_ind and traj_idx stay as its last driven step
@@ -350,7 +354,17 @@ class IntersectionBatch:
         goal_dis / stop_speed default to GOAL_DIS / STOP_SPEED of lib/mpc.py, as attach_log's do; with a log attached they must be the log's,
         so that goal_step == steps_driven for every retired agent (both count from the call that created them: attach the log and switch
         retirement on at the same step).  Allocates `done` and `steps_driven` (device, int32, P), makes the goal test before the first step
-        on the host, and drops the cached descriptor.  Needs run(): step_staged(), a callable exchange and lin_passes > 1 are refused."""
+        on the host, and drops the cached descriptor.  Needs run(): step_staged(), a callable exchange and lin_passes > 1 are refused.
+        leave_scene=True is DEPARTURE (mpcx_closed_loop_run_scene): the arrival also sets the agent's word of `absent` (device, int32, one
+        per pool row, allocated here; the rows of agents that pass the goal test now are set at once), and from the next step on that row is
+        in nobody's obstacle list and nobody's clearance, and is not predicted.  The agent's own buffers, done, steps_driven, the log and
+        the statistics are those of retirement alone.  Rows may also be preset by the caller (`sim.absent[row] = 1` before run()), e.g. a
+        scripted actor's row (`sim.actor_row`), to hide that vehicle from everybody.  An agent whose own row (`sim.obs_skip[q]`) is absent
+        but which still drives is a ghost: it sees the others, they do not see it.  Refused with exchange='rccl' (a remote rank's mask
+        would have to travel with the all-gather)."""
+        if leave_scene and (self.exchange == 'rccl' or self.obs_local is not None):
+            raise MpcxError('retire_at_goal(leave_scene=True) in the agent-sharded layout: a remote rank\'s absent mask would have to travel '
+                            'with the all-gather (MPCX_E_INVALID); leave_scene=False, or shard by instances')
         from .lib import mpc as _mpc
         goal_dis = float(_mpc.GOAL_DIS if goal_dis is None else goal_dis)
         stop_speed = float(_mpc.STOP_SPEED if stop_speed is None else stop_speed)
@@ -365,13 +379,23 @@ class IntersectionBatch:
         if there.any():
             self.applied[torch.as_tensor(there, device=self.ctx.device)] = 0.0
         self._retire = _lib.RetireC(self.done.data_ptr(), self.steps_driven.data_ptr(), goal_dis, stop_speed)
+        self.absent, self._scene = None, None
+        if leave_scene:
+            rows = int(self.obs6.shape[0])
+            self.absent = torch.zeros(rows, dtype=torch.int32, device=self.ctx.device)
+            if there.any():
+                self.absent[self.obs_skip.long()[torch.as_tensor(there, device=self.ctx.device)]] = 1
+            self._scene = _lib.SceneC(self.absent.data_ptr(), rows, 0)
         self._desc = None
         self.ctx.synchronize()
 
     def keep_driving(self):
         """switch retirement off: the batch enqueues exactly the launches of one that never had it.  Agents already retired stay where
-        they are and are driven again from there; `done` and `steps_driven` keep what they hold until the next retire_at_goal()"""
+        they are and are driven again from there; `done` and `steps_driven` keep what they hold until the next retire_at_goal().  The
+        scene goes with it: every car, departed or hidden, is visible again from the next step on (`absent` keeps what it holds and is
+        no longer read)"""
         self._retire = None
+        self._scene = None
         self._desc = None
 
     def active_count(self) -> int:
@@ -440,7 +464,7 @@ class IntersectionBatch:
             self._desc = self._descriptor()
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
-                                 retire=self._retire)
+                                 retire=self._retire, scene=self._scene)
         self.steps_done += n_steps
 
     def step(self):
@@ -518,6 +542,8 @@ class IntersectionBatch:
             out['obs6'] = self.obs6.cpu().numpy().copy()
         if self._retire is not None:
             out['done'], out['steps_driven'] = self.done.cpu().numpy().copy(), self.steps_driven.cpu().numpy().copy()
+        if self._scene is not None:
+            out['absent'] = self.absent.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:

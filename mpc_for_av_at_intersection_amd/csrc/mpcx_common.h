@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[960] = {};     // descriptor + run log + options + retirement + parameters the cached graph was captured for
+    unsigned char loop_key[976] = {};     // descriptor + run log + options + retirement + scene + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -73,6 +73,8 @@ struct mpcx_interaction_extras {
     int32_t *near = nullptr;
     const int32_t *bin_hint = nullptr;  // iteration counts of the previous step: every agent is filed in ctx->bins under its queue key
     const int32_t *done = nullptr;      // retirement (mpcx_retire::done): an agent with done[p] != 0 is not searched, not filed and none of its outputs is written
+    // departure (mpcx_scene::absent, n_obs_pool words; needs done): pool rows with absent[r] != 0 are neither predicted nor in anybody's obstacle list
+    const int32_t *absent = nullptr;
 };
 struct mpcx_window_extras {
     bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
@@ -129,12 +131,17 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
                             const int32_t *status, const int32_t *iters, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
                             const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log,
                             const int32_t *goal_len = nullptr,       // goal_len: mpcx_record_step_batch_goal
-                            const int32_t *done = nullptr);          // retirement: a retired agent is skipped entirely
+                            const int32_t *done = nullptr,           // retirement: a retired agent is skipped entirely
+                            const int32_t *absent = nullptr);        // departure (mpcx_scene::absent): the clearance skips absent pool rows
 // retirement at the goal (mpcx_retire.hip): "no retirement" test, check of the struct, the launch alone
 bool mpcx_retire_absent(const mpcx_retire *r);
 int32_t mpcx_retire_validate(mpcx_ctx *ctx, const mpcx_retire *r, int32_t P);
 int32_t mpcx_retire_enqueue(mpcx_ctx *ctx, int32_t P, const double *state, double *applied, const double *path_xyyaw, const int32_t *path_off,
-                            const int32_t *path_len, const int32_t *target_ind, const int32_t *goal_len, const mpcx_retire *r);
+                            const int32_t *path_len, const int32_t *target_ind, const int32_t *goal_len, const mpcx_retire *r,
+                            const mpcx_scene *scene = nullptr, const int32_t *own_row = nullptr);     // departure: absent[own_row[q]] <- 1 on arrival
+// departure (mpcx_retire.hip): "no scene" test, check of the struct against the run
+bool mpcx_scene_absent(const mpcx_scene *s);
+int32_t mpcx_scene_validate(mpcx_ctx *ctx, const mpcx_scene *s, const mpcx_retire *retire, int32_t exchange, size_t pool_rows, const int32_t *obs_skip);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -42,10 +42,13 @@ struct PredArgs {
     // n_ego + i predicts the row actor_row[i] that traffic_kernel has just written; n = n_ego + n_actors lanes
     const int32_t *ego_row, *actor_row;
     int n_ego;
+    // departure (SCENE instantiations only; mpcx_scene::absent, n_pool words): a row with absent[o] != 0 is packed as ever and not predicted --
+    // no conflict search reads the prediction of an absent row
+    const int32_t *absent;
 };
 
 // moving_obstacles_prediction.py:21-28: v is updated BEFORE yaw; disc centres as trajectories.py:11-37
-template <bool MAPPED>
+template <bool MAPPED, bool SCENE = false>
 __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
     int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= a.n) return;
@@ -66,6 +69,7 @@ __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
         const double *s6 = a.obs6 + 6 * (size_t)o;
         x = s6[0]; y = s6[1]; v = s6[2]; yaw = s6[3]; acc = s6[4]; steer = s6[5];
     }
+    if constexpr (SCENE) { if (a.absent[o] != 0) return; }       // (0 <= o < n_pool = the mask's length, checked by the host)
     const double tn = tan(steer);
     const double dt = a.ip.dt;
     double s, c;
@@ -98,6 +102,8 @@ struct InterArgs {
     const int32_t *key_prev;   // optional (closed loop, speed-reference mode): what the work-queue key's "moved" test and prev_save take as the previous value of cut_len instead of prev_cut (there prev_cut is the previous PATH length and cut_len the stop index); may alias cut_len
     int32_t *near;        // optional (closed loop): near[3p] = the start index of this agent's nearest-index scan, near[3p+1] / [3p+2] = the largest / smallest of its three nearest indices (absolute), -1 = none
     const int32_t *done;  // retirement (read by the RETIRE instantiation only): done[p] != 0 = agent p has arrived -- no search, no output, not filed in a bin
+    const int32_t *absent;    // departure (read by the SCENE instantiation only): absent[r] != 0 = pool row r is not in the scene; n_rows words
+    int n_rows;
 };
 
 __device__ __forceinline__ double dist2d(double ax, double ay, double bx, double by) {
@@ -165,11 +171,34 @@ __device__ __forceinline__ void run_boxes(const double (*s_ego)[4], int na, int 
     if (j == 0) { s_box[sg][0] = x0 - slack; s_box[sg][1] = x1 + slack; s_box[sg][2] = y0 - slack; s_box[sg][3] = y1 + slack; }
 }
 
+// departure (mpcx_scene): the obstacle list of an agent as the window offsets (< 64, six bits each) of the PRESENT rows of its window in rank
+// order, at most MPCX_MAX_OBS of them, packed into two wave-uniform words (ten + six entries): scalar registers, no LDS, and the
+// candidate -> pool row lookup in first_row's load loop is a shift and a mask with no memory wait in front of the loads it feeds.
+struct RowList {
+    unsigned long long lo, hi;
+    static constexpr int PER = 10, BITS = 6;
+    static_assert(MPCX_MAX_OBS <= PER + 64 / BITS, "two words do not hold the list");
+    // m: bit k set = row (window offset) k is present; wave-uniform, at most MPCX_MAX_OBS bits set
+    static __device__ __forceinline__ RowList of(unsigned long long m) {
+        RowList l = {0, 0};
+        for (int r = 0; m; r++, m &= m - 1) {
+            const unsigned long long k = (unsigned long long)(__ffsll((long long)m) - 1);
+            if (r < PER) l.lo |= k << (BITS * r); else l.hi |= k << (BITS * (r - PER));
+        }
+        return l;
+    }
+    __device__ __forceinline__ int operator[](int o) const {
+        const bool first = o < PER;
+        return (int)(((first ? lo : hi) >> (BITS * (first ? o : o - PER))) & 63ull);
+    }
+};
 // collision_avoidance.py:72-87: the first row of the pair table within md, as the minimum of a key in the reference's row order.
 // Returns whether there is one; (hox, hoy): the obstacle disc position of that row.
+// SCENE: candidate rank o is the o-th PRESENT row of the window, rows[o] its offset in the window (present_rows below); nobs counts those.
+template <bool SCENE = false>
 __device__ __forceinline__ bool first_row(const mpcx_interaction_params &ip, const Within &within, const double (*s_ego)[4], int na, int F, int SL,
                                           const double (*s_box)[4], const double *pred, int ooff, int nobs, int oskip, int lane,
-                                          double &hox, double &hoy) {
+                                          double &hox, double &hoy, const RowList rows = {0, 0}) {
     const int steps = ip.pred_steps, w = ip.frame_window;
     const float inv_steps = 1.0f / (float)steps;
     const long long NOKEY = 0x7fffffffffffffffLL;
@@ -188,8 +217,12 @@ __device__ __forceinline__ bool first_row(const mpcx_interaction_params &ip, con
             const int co = cc & 1;
             int g, o;                                                              // o: local obstacle rank
             divmod_small(cc >> 1, steps, inv_steps, o, g);
-            int pool = ooff + o;
-            if (oskip >= 0 && pool >= oskip) pool += 1;                                    // skip self
+            int pool;
+            if constexpr (SCENE) pool = ooff + rows[o];                                    // the list leaves out self and the absent rows
+            else {
+                pool = ooff + o;
+                if (oskip >= 0 && pool >= oskip) pool += 1;                                // skip self
+            }
             const double *qq = pred + ((size_t)pool * steps + g) * 4 + 2 * co;
             ox[u] = qq[0]; oy[u] = qq[1];
         }
@@ -294,11 +327,13 @@ __device__ __forceinline__ int earliest_pose(const mpcx_interaction_params &ip, 
 
 // s_ego: ego disc centres of the `na` predicted poses; pred: obstacle disc centres [pool][steps][2][2]; (rem, rcs, n): the detailed path and
 // cos/sin of its yaw.  Returns the index of the earliest conflicting pose on the detailed path (and its x,y) or -1 (None).
+template <bool SCENE = false>
 __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)[4], int na, const double *pred,
                               int ooff, int nobs, int oskip, const double *rem, const double *rcs, int n,
                               double (*s_box)[4], int lane, double &hx, double &hy,
                               bool boxes_ready = false,          // s_box already holds the runs' boxes (mpcx_interaction_params.plan_box)
-                              const double *pdisc = nullptr      // disc centres of the poses of `rem` (mpcx_interaction_params.path_disc + 4 * row of rem[0]) or nullptr
+                              const double *pdisc = nullptr,     // disc centres of the poses of `rem` (mpcx_interaction_params.path_disc + 4 * row of rem[0]) or nullptr
+                              const RowList rows = {0, 0}        // SCENE: the window offsets of the nobs present rows
                               ) {
     const Within within(2.0 * ip.radius);
     const double slack = within.md * (1.0 + 1e-9) + 1e-9;      // conservative: never culls a pair within md
@@ -307,7 +342,7 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
     if (!boxes_ready) run_boxes(s_ego, na, F, SL, slack, s_box, lane);
     __syncthreads();
     double ox, oy;
-    if (!first_row(ip, within, s_ego, na, F, SL, s_box, pred, ooff, nobs, oskip, lane, ox, oy)) return -1;
+    if (!first_row<SCENE>(ip, within, s_ego, na, F, SL, s_box, pred, ooff, nobs, oskip, lane, ox, oy, rows)) return -1;
     const int first = earliest_pose(ip, within, ox, oy, rem, rcs, pdisc, n, lane);
     hx = rem[3 * first]; hy = rem[3 * first + 1];
     return first;
@@ -719,9 +754,22 @@ __device__ __forceinline__ int cut_index(const mpcx_interaction_params &ip, cons
     return cl;
 }
 
+// departure (mpcx_scene): which rows of the agent's window [off, off + cnt) are in the scene and not its own, as a bit per window offset.
+// One load of a mask word per lane and a ballot (cnt <= 64; a larger window is beyond the launch's capacity); the number of obstacles is its
+// population count.  Rows outside the pool count as absent, so nothing is read from there later.
+__device__ __forceinline__ unsigned long long present_rows(const InterArgs &a, int p, int lane, int cnt, int off, int own) {
+    const int r = off + lane;
+    const bool in = lane < cnt && r >= 0 && r < a.n_rows;
+    const int32_t gone = a.absent[in ? r : 0];          // clamped address, selected afterwards (n_rows >= 1: checked by the host)
+    return __ballot(in && r != own && gone == 0);
+}
+
 // RETIRE: the closed loop with retirement at the goal (mpcx_retire).  A template parameter, not a null test, as predict_kernel<MAPPED>:
 // the launch without retirement runs the code it ran before there was any.
-template <bool RETIRE>
+// SCENE (with RETIRE only): departure (mpcx_scene).  The obstacle list is the list of PRESENT rows of the window, built once per agent, and
+// first_row walks nobs = its length candidates' worth of rows: a window with departed cars is less work.  The other two instantiations
+// are the code they were.
+template <bool RETIRE, bool SCENE = false>
 __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     // a retired agent: nothing is read, written or filed -- its outputs stay as its last driven step left them, and an agent that is
     // not filed is never solved (predict_kernel has packed its pool row all the same: to the others it is a parked car)
@@ -749,7 +797,15 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     const int pcut = a.prev_cut ? a.prev_cut[p] : 0;
     const int kprev = a.key_prev ? a.key_prev[p] : pcut;
     if (a.prev_save && lane == 0) a.prev_save[p] = kprev;
-    const int nobs = a.obs_cnt[p] - ((a.obs_skip && a.obs_skip[p] >= 0) ? 1 : 0);
+    int nobs;
+    RowList rows = {0, 0};
+    if constexpr (SCENE) {
+        const int cnt = a.obs_cnt[p];
+        const unsigned long long present = present_rows(a, p, lane, cnt, a.obs_off[p], a.obs_skip ? a.obs_skip[p] : -1);     // wave-uniform
+        nobs = cnt > WAVE ? MPCX_MAX_OBS + 1 : __popcll(present);       // (beyond one ballot, or too many: locate() leaves with -2)
+        if (nobs <= MPCX_MAX_OBS) rows = RowList::of(present);
+    } else
+        nobs = a.obs_cnt[p] - ((a.obs_skip && a.obs_skip[p] >= 0) ? 1 : 0);
     const double *cumtab = ip.path_cum ? ip.path_cum + poff : nullptr;
 
     const int tidx = locate(a, p, lane, path, len, t_old, x, y, pcut, nobs, cumtab != nullptr, s_cum);
@@ -775,7 +831,7 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     const int ooff = a.obs_off[p], oskip = a.obs_skip ? a.obs_skip[p] : -1;
     double hx, hy;
     const double *pdisc = ip.plan_cnt ? ip.path_disc + 4 * prow : nullptr;     // disc centres of trajectory_full[tidx:] from the host's table
-    const int first = first_conflict(ip, s_ego, na, a.pred, ooff, nobs, oskip, e.rem, rcs, e.n, s_box, lane, hx, hy, from_plan, pdisc);
+    const int first = first_conflict<SCENE>(ip, s_ego, na, a.pred, ooff, nobs, oskip, e.rem, rcs, e.n, s_box, lane, hx, hy, from_plan, pdisc, rows);
     if (first < 0) { leave(a, p, lane, kprev, len, -1); return; }
     finish(a, p, lane, kprev, first, hx, hy, cut_index(ip, path, poff, len, tidx, tidx + first, hx, hy, lane));
 }
@@ -853,17 +909,20 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: null pointer or negative size");
     if (ip->pred_steps < 1 || ip->pred_steps > MPCX_PRED_STEPS_MAX || ip->frame_window < 0 || !(ip->dt > 0) || !(ip->L > 0))
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: pred_steps outside 1..%d or bad dt/L/frame_window", MPCX_PRED_STEPS_MAX);
+    if (x.absent && (!x.done || n_obs_pool < 1)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: a scene without retirement or without a pool");
     { int32_t rc = mpcx_ensure_pred(ctx, (size_t)(n_obs_pool > 0 ? n_obs_pool : 1) * ip->pred_steps * 4); if (rc != MPCX_OK) return rc; }
     if (n_obs_pool > 0 && x.pack_state && x.ego_row) {
         // closed loop with scripted traffic: only the rows that hold an agent or an actor are predicted (the others are outside every window)
         const int lanes = x.n_ego + x.n_actors;
         mpcx::PredArgs pa{*ip, lanes, n_obs_pool, obs6, ctx->pred, x.pack_state, x.pack_applied, const_cast<double *>(obs6),
-                          x.ego_row, x.actor_row, x.n_ego};
-        hipLaunchKernelGGL(mpcx::predict_kernel<true>, dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
+                          x.ego_row, x.actor_row, x.n_ego, x.absent};
+        if (x.absent) hipLaunchKernelGGL((mpcx::predict_kernel<true, true>), dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
+        else hipLaunchKernelGGL(mpcx::predict_kernel<true>, dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
     } else if (n_obs_pool > 0) {
         mpcx::PredArgs pa{*ip, n_obs_pool, n_obs_pool, obs6, ctx->pred, x.pack_state, x.pack_applied, x.pack_state ? const_cast<double *>(obs6) : nullptr,
-                          nullptr, nullptr, 0};
-        hipLaunchKernelGGL(mpcx::predict_kernel<false>, dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
+                          nullptr, nullptr, 0, x.absent};
+        if (x.absent) hipLaunchKernelGGL((mpcx::predict_kernel<false, true>), dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
+        else hipLaunchKernelGGL(mpcx::predict_kernel<false>, dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
     }
     // capacity: max_path_len path points (0 = MPCX_MAX_REMAINING; never below 512), rounded up to whole wavefronts; the LDS that
     // holds their cumulative lengths later holds the ego discs of max_rem / 4 - 32 resampled poses and the runs' boxes.
@@ -879,8 +938,9 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     mpcx::InterArgs ia{*ip, P, state, path_xyyaw, path_cs, path_off, path_len, prev_cut_len, ctx->pred,
                        obs_off, obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, max_rem, fcap, x.prev_save,
                        x.bin_hint, x.bin_hint ? ctx->bins : nullptr, x.bin_hint ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr,
-                       x.key_prev, x.near, x.done};
-    if (x.done) hipLaunchKernelGGL(mpcx::interaction_kernel<true>, dim3(P), dim3(64), lds, ctx->stream, ia);
+                       x.key_prev, x.near, x.done, x.absent, n_obs_pool};
+    if (x.absent) hipLaunchKernelGGL((mpcx::interaction_kernel<true, true>), dim3(P), dim3(64), lds, ctx->stream, ia);
+    else if (x.done) hipLaunchKernelGGL(mpcx::interaction_kernel<true>, dim3(P), dim3(64), lds, ctx->stream, ia);
     else hipLaunchKernelGGL(mpcx::interaction_kernel<false>, dim3(P), dim3(64), lds, ctx->stream, ia);
     return mpcx_check_launch(ctx, "interaction kernels");
 }

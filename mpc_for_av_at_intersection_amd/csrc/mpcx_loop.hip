@@ -4,7 +4,8 @@
 // n_steps x [scripted traffic rows -> pool pack -> predict -> conflict search + path cut -> reference window ->
 // rollout -> QP -> plant (-> run-log record, iff a log is attached)], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
 // host synchronisation or host arithmetic in between.  With retirement at the goal (mpcx_retire) the step ends with retire_kernel, and an agent
-// that has arrived is skipped by every stage but the pool pack.  Every stage is the kernel behind the per-stage C entry
+// that has arrived is skipped by every stage but the pool pack; with a scene (mpcx_scene) its arrival also takes it out of everybody
+// else's obstacle list.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
 #include "mpcx_common.h"
@@ -32,14 +33,14 @@ __global__ __launch_bounds__(256) void pack_pool_kernel(PackArgs a) {
 
 }  // namespace mpcx
 
-// the agents' pool rows (device) lie inside the pool
-static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego_row, int32_t pool_rows) {
+// the agents' pool rows (device) lie inside the pool; who: what the message starts with
+static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego_row, int32_t pool_rows, const char *who = "closed_loop_run") {
     std::vector<int32_t> rows((size_t)P);
     if (hipMemcpy(rows.data(), ego_row, rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: cannot read ego_row back for its check");
+        return mpcx_fail(ctx, MPCX_E_LAUNCH, "%s: cannot read the agents' pool rows back for their check", who);
     for (int32_t q = 0; q < P; q++)
         if (rows[q] < 0 || rows[q] >= pool_rows)
-            return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: agent %d sits in pool row %d of %d", q, rows[q], pool_rows);
+            return mpcx_fail(ctx, MPCX_E_INVALID, "%s: agent %d sits in pool row %d of %d", who, q, rows[q], pool_rows);
     return MPCX_OK;
 }
 
@@ -57,8 +58,12 @@ static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cu
 // draw tickets up to that length, the rollout, the plant and the record stage skip the agent, and retire_kernel ends the step.  The pool
 // row of a retired agent is still packed (by predict_kernel, or by pack_pool_kernel in the agent-sharded layout) from its frozen state and
 // zero controls, and the scripted cars step as ever.
+// sc: the scene (departure) or nullptr = none (then exactly the launches of a step with retirement alone, with the same arguments).  With it
+// the prediction skips absent pool rows, the conflict search runs its SCENE instantiation on the list of present rows, the record stage's
+// clearance leaves absent rows out, and retire_kernel sets absent[obs_skip[q]] for an agent that arrives -- the last launch of the step,
+// so the others see the car gone from the next step on.
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                            const mpcx_closed_loop_opts *o, const mpcx_retire *r) {
+                            const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc) {
     const int P = c->P;
     const int32_t *done = r ? r->done : nullptr;
     int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
@@ -78,6 +83,7 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     ix.near = near_hints(ctx, P);
     ix.bin_hint = binned ? c->iters : nullptr;
     ix.done = done;
+    ix.absent = sc ? sc->absent : nullptr;
     if (speed) ix.key_prev = c->cut_len;        // "the cut moved" = the stop index moved
     if (c->exchange == MPCX_SHARD_AGENTS) {
         // agent-sharded layout: this rank's rows travel to every rank, every rank assembles the whole pool (one RCCL all-gather)
@@ -129,18 +135,19 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (log) {
         rc = mpcx_record_enqueue(ctx, ip, P, c->state, c->applied, c->x_sol, c->path_xyyaw, c->path_off, c->path_len, c->target_ind, c->cut_len,
                                  c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, log,
-                                 speed ? c->path_len : nullptr, done);
+                                 speed ? c->path_len : nullptr, done, sc ? sc->absent : nullptr);
         if (rc != MPCX_OK) return rc;
     }
     // retirement: the goal test of the record stage (len(cx) = cut_len, the whole path in speed mode), after it, so that the arrival
     // step's row logs the controls really applied
     if (r) rc = mpcx_retire_enqueue(ctx, P, c->state, c->applied, c->path_xyyaw, c->path_off, c->path_len, c->target_ind,
-                                    speed ? c->path_len : c->cut_len, r);
+                                    speed ? c->path_len : c->cut_len, r, sc, c->obs_skip);
     return rc;
 }
 
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                               const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, int32_t n_steps, int32_t use_graph) {
+                               const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, int32_t n_steps,
+                               int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
@@ -162,6 +169,14 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (retire) {       // refused before anything is launched, whatever n_steps is
         const int32_t rrc = mpcx_retire_validate(ctx, retire, c->P);
         if (rrc != MPCX_OK) return rrc;
+    }
+    if (mpcx_scene_absent(scene)) scene = nullptr;
+    if (scene) {        // refused before anything is launched, whatever n_steps is
+        const bool traffic = c->n_actors > 0;
+        const size_t rows = traffic ? (size_t)(c->pool_rows > 0 ? c->pool_rows : 0) : (size_t)c->P;
+        int32_t src = mpcx_scene_validate(ctx, scene, retire, c->exchange, rows, c->obs_skip);
+        if (src == MPCX_OK && c->P > 0) src = mpcx_loop_check_rows(ctx, c->P, c->obs_skip, scene->n_rows, "scene");
+        if (src != MPCX_OK) return src;
     }
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
@@ -229,7 +244,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt, retire);
+            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -239,7 +254,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_interaction_params) +
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_interaction_params) +
                   sizeof(mpcx_mpc_params) + 9 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
@@ -250,6 +265,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     memcpy(key + o, &opt, sizeof opt); o += sizeof opt;
     if (retire) memcpy(key + o, retire, sizeof *retire);     // (zeros = no retirement: a graph captured without it)
     o += sizeof *retire;
+    if (scene) memcpy(key + o, scene, sizeof *scene);        // (zeros = no scene: a graph captured without departure)
+    o += sizeof *scene;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
     memcpy(key + o, &ctx->pred, sizeof ctx->pred); o += sizeof ctx->pred;
@@ -269,7 +286,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt, retire);
+        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -286,21 +303,27 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                              const mpcx_scene *scene, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, n_steps, use_graph);
 }

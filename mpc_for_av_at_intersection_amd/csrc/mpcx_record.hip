@@ -56,7 +56,7 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
                             const int32_t *target_ind, const int32_t *cut_len, const int32_t *traj_idx, const int32_t *hit_idx,
                             const int32_t *status, const int32_t *iters, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
                             const int32_t *obs_cnt, const int32_t *obs_skip, const mpcx_run_log *log, const int32_t *goal_len,
-                            const int32_t *done) {
+                            const int32_t *done, const int32_t *absent) {
     mpcx::RecordArgs a;
     a.P = P; a.n_pool = n_obs_pool;
     a.x_stride = 4 * (int64_t)(ctx->mpc.T + 1);
@@ -69,6 +69,7 @@ int32_t mpcx_record_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
     a.log = *log;
     a.goal_len = goal_len;
     a.done = done;
+    a.absent = absent;
     hipLaunchKernelGGL(mpcx::record_kernel, dim3((P + 63) / 64), dim3(64), 0, ctx->stream, a);
     return mpcx_check_launch(ctx, "record_kernel");
 }

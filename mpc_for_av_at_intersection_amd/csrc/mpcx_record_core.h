@@ -14,6 +14,8 @@
 //                                      min |c_ego - c_r| - 2 radius.  Poses from the pool as this step's conflict search saw them (the pool
 //                                      is written at the start of a step and not touched again); the ego's own pose is its own pool row.
 //                                      +inf if the window holds nobody else (or the agent has no row of its own to compare from).
+//                                      With a scene (mpcx_scene) the rows with absent[r] != 0 are left out, as the step's conflict search left
+//                                      them out; the agent's own row is its pose whether it is absent (a ghost) or not.
 //   row (8 int32)    traj_idx, target_ind, cut_len, hit_idx, status, iters as they stand after the step, 0, 0
 //
 // and the per-agent outcome words, which exist whatever the row capacity:
@@ -59,6 +61,7 @@ struct RecordArgs {
     mpcx_run_log log;
     const int32_t *goal_len = nullptr;      // len(self.cx) of the goal test per agent; nullptr: cut_len
     const int32_t *done = nullptr;          // retirement (mpcx_retire::done) or nullptr: record_kernel skips an agent with done[q] != 0 entirely
+    const int32_t *absent = nullptr;        // departure (mpcx_scene::absent, n_pool words) or nullptr: the clearance skips pool rows with absent[r] != 0
 };
 
 MPCX_REC_FN void rec_sincos(double a, double *s, double *c) {
@@ -90,6 +93,7 @@ MPCX_REC_FN double rec_clearance(const RecordArgs &a, int q) {
     for (int k = 0; k < cnt; k++) {
         const int r = off + k;
         if (r == own || r < 0 || r >= a.n_pool) continue;
+        if (a.absent && a.absent[r] != 0) continue;         // departed (or hidden): not in the scene
         const double *o = a.obs6 + 6 * (size_t)r;
         double od[4];
         rec_discs(a.cc, o[0], o[1], o[3], od);

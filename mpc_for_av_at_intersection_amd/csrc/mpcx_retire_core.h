@@ -11,7 +11,10 @@
 // For an agent that is still driving (done[q] == 0) the rule counts the step in steps_driven[q] and, where the test holds, sets
 // done[q] = 1 and zeroes applied[q]: to the other agents a retired car is parked, without acceleration or steering (the last real controls
 // of a decelerating ego would make the prediction roll it backwards over the whole horizon).  A retired agent's words are left alone.
-// Per agent it reads 3 + 3 doubles and four words and writes at most two words and two doubles; no lane reads what another lane writes.
+// With a scene (mpcx_scene: departure) the arrival also sets absent[own_row[q]], the word of the agent's own pool row (the loop passes obs_skip,
+// which names that row with and without scripted traffic): from the next step on the car is gone from everybody's obstacle list.  Agents'
+// rows are distinct rows, so this too is a word no other lane touches; a row outside the pool is never written.
+// Per agent it reads 3 + 3 doubles and four words and writes at most three words and two doubles; no lane reads what another lane writes.
 #pragma once
 #include "mpcx_record_core.h"
 
@@ -23,6 +26,9 @@ struct RetireArgs {
     double *applied;
     const int32_t *path_off, *path_len, *target_ind, *goal_len;
     mpcx_retire r;
+    int32_t *absent = nullptr;              // departure (mpcx_scene::absent, n_rows words) or nullptr: none
+    const int32_t *own_row = nullptr;       // ... the agent's own pool row (obs_skip)
+    int32_t n_rows = 0;
 };
 
 // returns whether the agent arrived in this step
@@ -36,6 +42,10 @@ MPCX_REC_FN bool retire_agent(const RetireArgs &a, int q) {
     if (!rec_is_goal(st[0], st[1], st[2], g[0], g[1], a.target_ind[q], a.goal_len[q], a.r.goal_dis, a.r.stop_speed)) return false;
     a.r.done[q] = 1;
     a.applied[2 * (size_t)q] = 0.0; a.applied[2 * (size_t)q + 1] = 0.0;
+    if (a.absent) {
+        const int32_t row = a.own_row[q];
+        if (row >= 0 && row < a.n_rows) a.absent[row] = 1;
+    }
     return true;
 }
 

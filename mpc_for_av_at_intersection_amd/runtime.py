@@ -614,13 +614,19 @@ class Context:
     @_ordered
     def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
                         log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None,
-                        retire: Optional['_lib.RetireC'] = None):
+                        retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
-        retire: a _lib.RetireC -- agents are retired at their goal (mpcx_closed_loop_run_retire); None = they are driven on."""
+        retire: a _lib.RetireC -- agents are retired at their goal (mpcx_closed_loop_run_retire); None = they are driven on.
+        scene: a _lib.SceneC -- departure: pool rows with absent != 0 are out of the scene and an arrival sets the agent's own word
+        (mpcx_closed_loop_run_scene; refused without retire); None = arrived cars stay in the scene."""
         cip = ip.to_c()
-        if retire is not None:
+        if scene is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_scene(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
+                                                          None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
+                                                          C.byref(scene), int(n_steps), 1 if graph else 0))
+        elif retire is not None:
             self._chk(self.lib.mpcx_closed_loop_run_retire(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
                                                            None if opts is None else C.byref(opts), C.byref(retire), int(n_steps),
                                                            1 if graph else 0))
