@@ -520,6 +520,51 @@ int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params 
                                    const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
                                    int32_t n_steps, int32_t use_graph);
 
+/* ---- admission: letting vehicles INTO the scene on a schedule, the counterpart of departure.  A scheduled agent waits in the state
+ * retirement and departure already define -- done[q] = 1 and absent[obs_skip[q]] = 1, both preset by the caller: it is not solved, not
+ * logged, not counted and not seen, and its buffers stay bit for bit as they were allocated, so that it starts like the first step of a
+ * fresh batch.  wait[q] says when it asks to enter:
+ *   -1   not scheduled, or already entered: the agent is not touched;
+ *   > 0  steps still to wait: decremented once per step, nothing else;
+ *   0    DUE: the agent asks to enter in this step.
+ * A due agent is admitted iff its start pose (its state row: it never moved) has clearance >= gap -- the run log's clearance: two discs
+ * per car, min distance - 2 radius -- to every BLOCKING row of its pool window obs_off .. + obs_cnt minus its own row.  A row blocks if it
+ * is present at the start of the step (absent[r] == 0 as the previous step left it) or if it is the own row of another agent q' < q that
+ * is also due in this step, whether or not q' itself gets in.  The second clause is the tie-break: the outcome does not depend on the order
+ * in which lanes run and two cars due at one pose never enter together; the price is that q may wait one step longer than strictly
+ * necessary.  The poses are those this step's pool will hold: an agent's state row, a scripted actor's get() row of this step (computed from
+ * a copy of its state; the actor is not stepped).  A pool row that belongs to neither is nobody.
+ * On admission done[q] = 0, absent[obs_skip[q]] = 0, wait[q] = -1 and entered_step[q] = *clock, the number of closed-loop steps completed
+ * since admission was switched on -- a device word the stage advances once per step, so a replayed graph counts like a plain run.
+ * The stage is two small launches (csrc/mpcx_admit.hip; the rule is csrc/mpcx_admit_core.h) and the FIRST thing a step does: the admitted
+ * agent is driven, packed, predicted, seen and logged by this very step.  An agent whose own row lies outside the pool is never admitted
+ * and never written.
+ * All three arrays are caller-owned DEVICE memory.  The struct travels beside the descriptor (no other struct changes size); the cached
+ * graph's key covers it by value.  admit = NULL or an all-zero struct: mpcx_closed_loop_run_scene itself -- the same launches with the same
+ * arguments.  MPCX_E_INVALID ("admit: ...") before anything is launched, whatever n_steps is: admission without a scene (which in turn needs
+ * retirement and refuses MPCX_SHARD_AGENTS); one of the three pointers NULL; gap not finite or negative.
+ * Works with scripted traffic, the run log, both stop modes and use_graph. */
+typedef struct {
+    int32_t *wait;          /* P, caller-owned device memory: -1 not scheduled / entered, > 0 steps to wait, 0 due */
+    int32_t *entered_step;  /* P, caller-owned: clock value at admission; caller-initialised (-1 for scheduled agents) */
+    int32_t *clock;         /* 1 word, caller-owned, zero-initialised */
+    int32_t reserved;
+    double gap;             /* metres of clearance the entry needs; 0 = the car overlaps nobody */
+} mpcx_admit;
+int32_t mpcx_closed_loop_run_admit(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                   const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                   const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                   const mpcx_admit *admit /*or NULL*/, int32_t n_steps, int32_t use_graph);
+/* one step's admission as a stage of its own (what mpcx_closed_loop_run_admit enqueues at the head of a step): done is mpcx_retire::done,
+ * absent is mpcx_scene::absent over the n_obs_pool rows of the pool, obs_skip names the agents' own rows; the actors are those of
+ * mpcx_traffic_step_batch (n_actors = 0: none) and are read, not stepped.  Needs no mpcx_set_mpc_params. */
+int32_t mpcx_admit_step_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state /*P,4*/,
+                              const int32_t *obs_off /*P*/, const int32_t *obs_cnt /*P*/, const int32_t *obs_skip /*P*/,
+                              int32_t *done /*P*/, int32_t n_obs_pool, int32_t *absent /*NOBS*/,
+                              int32_t n_actors, const mpcx_traffic_actor *actors /*n_actors*/, const double *actor_state /*n_actors,4*/,
+                              const double *tape /*rows,6 or NULL*/, int64_t tape_rows, const int32_t *actor_row /*n_actors*/,
+                              const mpcx_admit *admit);
+
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes
  * to every rank by whatever means it has (torch.distributed broadcast in this package), every rank calls mpcx_comm_init.

@@ -67,6 +67,11 @@ class SceneC(C.Structure):
     _fields_ = [('absent', C.c_void_p), ('n_rows', C.c_int32), ('reserved', C.c_int32)]
 
 
+class AdmitC(C.Structure):
+    """mirror of mpcx_admit (include/mpcx.h): admission; wait, entered_step (P int32 each) and clock (1 int32) are device addresses"""
+    _fields_ = [('wait', C.c_void_p), ('entered_step', C.c_void_p), ('clock', C.c_void_p), ('reserved', C.c_int32), ('gap', C.c_double)]
+
+
 STOP_CUT, STOP_SPEED = 0, 1     # mpcx_closed_loop_opts.stop_mode
 STOP_MODES = {'cut': STOP_CUT, 'speed': STOP_SPEED}
 NO_STOP = 999                   # MPCX_NO_STOP: the stop index lib/mpc_with_speed.py:281 reads as "no stop"
@@ -126,7 +131,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
            'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
            'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
-           'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene']
+           'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
+           'mpcx_admit_step_batch']
 
 
 def load():
@@ -202,5 +208,11 @@ def load():
     lib.mpcx_closed_loop_run_scene.restype = i32
     lib.mpcx_closed_loop_run_scene.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
                                                C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), i32, i32]
+    lib.mpcx_closed_loop_run_admit.restype = i32
+    lib.mpcx_closed_loop_run_admit.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                               C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC), i32, i32]
+    lib.mpcx_admit_step_batch.restype = i32
+    lib.mpcx_admit_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, C.c_int64, vp,
+                                          C.POINTER(AdmitC)]
     _lib = lib
     return lib

@@ -18,6 +18,9 @@ its loop and the true clearance to the other vehicles, per agent, on the device 
 arrival on it is a parked car that is not solved, not logged and not counted; `run_until_done()` runs until every agent has arrived.
 `retire_at_goal(leave_scene=True)` is DEPARTURE: the arrived car is also taken out of the scene -- from the next step on nobody's conflict
 search and nobody's clearance sees it (two stock routes share every exit arm: a car parked on the goal would block the second for good).
+`enter_on_schedule(wait, gap)` is ADMISSION, the counterpart: scheduled agents wait outside the scene and enter, on the device, in the step
+their count-down ends -- or the first later step in which their start pose is `gap` clear of everybody present (entry_schedule() draws
+seeded arrival times per approach queue).
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -268,12 +271,13 @@ class IntersectionBatch:
             self.tape = ctx.f64(traffic.tape) if traffic.tape is not None and len(traffic.tape) else None
         self.obs_local = torch.zeros((P, 6), dtype=f, device=dev) if agent_shard is not None else None
         # cut_len doubles as "length of the previous tmp_trajectory" (0 = none yet) for the next step
-        self.inter = dict(hit_idx=torch.empty(P, dtype=torch.int32, device=dev), hit_xy=torch.empty((P, 2), dtype=f, device=dev),
+        # (every output is zero until a step has written it: an agent that waits to enter the scene is never stepped, and shows zeros)
+        self.inter = dict(hit_idx=torch.zeros(P, dtype=torch.int32, device=dev), hit_xy=torch.zeros((P, 2), dtype=f, device=dev),
                           cut_len=torch.zeros(P, dtype=torch.int32, device=dev))
-        self.pre = dict(xref=torch.empty((P, 4, T + 1), dtype=f, device=dev),
-                        reaches_end=torch.empty((P, T + 1), dtype=torch.uint8, device=dev),
-                        xbar=torch.empty((P, 4, T + 1), dtype=f, device=dev))
-        self.sol = dict(x=torch.empty((P, 4, T + 1), dtype=f, device=dev), u=torch.zeros((P, 2, T), dtype=f, device=dev),
+        self.pre = dict(xref=torch.zeros((P, 4, T + 1), dtype=f, device=dev),
+                        reaches_end=torch.zeros((P, T + 1), dtype=torch.uint8, device=dev),
+                        xbar=torch.zeros((P, 4, T + 1), dtype=f, device=dev))
+        self.sol = dict(x=torch.zeros((P, 4, T + 1), dtype=f, device=dev), u=torch.zeros((P, 2, T), dtype=f, device=dev),
                         status=torch.zeros(P, dtype=torch.int32, device=dev), iters=torch.zeros(P, dtype=torch.int32, device=dev),
                         kkt=torch.zeros((P, 4), dtype=f, device=dev))
         self.steps_done = 0
@@ -302,6 +306,11 @@ class IntersectionBatch:
         self._retire = None
         self.absent: Optional[torch.Tensor] = None           # retire_at_goal(leave_scene=True): int32 (pool rows,), != 0 = not in the scene
         self._scene = None
+        self.wait: Optional[torch.Tensor] = None             # enter_on_schedule(): int32 (P,), -1 = in / not scheduled, > 0 steps to wait, 0 due
+        self.entered_step: Optional[torch.Tensor] = None     # ... int32 (P,), the clock at the agent's admission, -1 = not yet in
+        self.clock: Optional[torch.Tensor] = None            # ... int32 (1,), steps completed since enter_on_schedule()
+        self.scheduled_step: Optional[np.ndarray] = None     # ... host, (P,): the step the agent was scheduled for (0 = from the start)
+        self._admit = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -380,6 +389,7 @@ class IntersectionBatch:
             self.applied[torch.as_tensor(there, device=self.ctx.device)] = 0.0
         self._retire = _lib.RetireC(self.done.data_ptr(), self.steps_driven.data_ptr(), goal_dis, stop_speed)
         self.absent, self._scene = None, None
+        self._admit = None                  # (admission lives on a scene: enter_on_schedule() after this call)
         if leave_scene:
             rows = int(self.obs6.shape[0])
             self.absent = torch.zeros(rows, dtype=torch.int32, device=self.ctx.device)
@@ -393,10 +403,66 @@ class IntersectionBatch:
         """switch retirement off: the batch enqueues exactly the launches of one that never had it.  Agents already retired stay where
         they are and are driven again from there; `done` and `steps_driven` keep what they hold until the next retire_at_goal().  The
         scene goes with it: every car, departed or hidden, is visible again from the next step on (`absent` keeps what it holds and is
-        no longer read)"""
+        no longer read).  Admission goes with it too: agents still waiting are driven from where they stand, from the next step on"""
         self._retire = None
         self._scene = None
+        self._admit = None
         self._desc = None
+
+    def enter_on_schedule(self, wait, gap: float = 0.0):
+        """ADMISSION (mpcx_closed_loop_run_admit), the counterpart of departure: agent q with wait[q] >= 0 is taken out of the scene now
+        (done[q] = 1 and its own row absent: not solved, not logged, not counted, not seen; its buffers stay as they were allocated) and
+        asks to enter in the step in which its count-down ends -- wait[q] = 0: the very next step.  It is let in, on the device and as
+        the first thing of a step, once its start pose has clearance >= gap [m] (the run log's clearance) to every vehicle present and to
+        every lower-numbered agent that is due in the same step; until then it asks again every step.  From its admission on it is an
+        agent like any other, and the step of its admission is the first step it drives.
+        wait: integer array (B, A) or (P,), -1 = present from the start.  Needs retire_at_goal(leave_scene=True) first.  Allocates `wait`,
+        `entered_step` (-1 until the agent is in; 0 for agents present from the start) and `clock` (steps completed since this call) on
+        the device and drops the cached descriptor.  enter_now() switches admission off; keep_driving() does so together with retirement."""
+        if self._scene is None:
+            raise MpcxError('enter_on_schedule: admission needs a scene (MPCX_E_INVALID): retire_at_goal(leave_scene=True) first -- a waiting '
+                            'agent is a retired one whose own row is absent')
+        gap = float(gap)
+        if not (np.isfinite(gap) and gap >= 0.0):
+            raise MpcxError('enter_on_schedule: gap = %r must be finite and >= 0 (MPCX_E_INVALID)' % (gap,))
+        w = np.asarray(wait)
+        if not np.issubdtype(w.dtype, np.integer) or w.size != self.P or w.shape not in ((self.B, self.A), (self.P,)):
+            raise ValueError('enter_on_schedule: wait must be an integer array of shape (B, A) = %s or (P,)' % ((self.B, self.A),))
+        w = w.reshape(-1).astype(np.int64)
+        if (w < -1).any() or (w > np.iinfo(np.int32).max).any():
+            raise ValueError('enter_on_schedule: wait holds -1 (present from the start) or a number of steps >= 0')
+        self.ctx.synchronize()
+        sched = torch.as_tensor(w >= 0, device=self.ctx.device)
+        self.done[sched] = 1
+        self.absent[self.obs_skip.long()[sched]] = 1
+        self.wait = self.ctx.i32(w)
+        self.entered_step = self.ctx.i32(np.where(w >= 0, -1, 0))
+        self.clock = torch.zeros(1, dtype=torch.int32, device=self.ctx.device)
+        self.scheduled_step = np.maximum(w, 0)
+        self._admit = _lib.AdmitC(self.wait.data_ptr(), self.entered_step.data_ptr(), self.clock.data_ptr(), 0, gap)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def enter_now(self):
+        """switch admission off and nothing else: the batch enqueues exactly the launches of one that never had it.  Agents still waiting
+        stay outside the scene (retired, their rows absent); `wait`, `entered_step` and `clock` keep what they hold"""
+        self._admit = None
+        self._desc = None
+
+    def waiting_count(self) -> int:
+        """agents scheduled and not yet in (one small reduction and one synchronisation); 0 with admission off"""
+        if self._admit is None:
+            return 0
+        return int((self.wait >= 0).sum().item())
+
+    def entry_delay(self) -> np.ndarray:
+        """(P,) steps between the step an agent was scheduled for and the step it entered in -- what the gate held it back for; 0 for
+        agents present from the start, -1 for agents not yet in (synchronises)"""
+        if self.entered_step is None:
+            raise MpcxError('entry_delay(): enter_on_schedule() has not been called')
+        self.ctx.synchronize()
+        e = self.entered_step.cpu().numpy().astype(np.int64)
+        return np.where(e >= 0, e - self.scheduled_step, -1)
 
     def active_count(self) -> int:
         """agents still driving (one small reduction and one synchronisation)"""
@@ -405,7 +471,8 @@ class IntersectionBatch:
         return int((self.done == 0).sum().item())
 
     def run_until_done(self, max_steps: int, chunk: int = 16, graph: bool = False) -> int:
-        """run(chunk) until every agent has arrived (active_count() == 0) or max_steps have been taken; returns the steps taken.  The
+        """run(chunk) until every agent has arrived (active_count() == 0; with admission on: and nobody is waiting to enter,
+        waiting_count() == 0) or max_steps have been taken; returns the steps taken.  The
         count is read back once per chunk, so a chunk may take up to chunk - 1 steps after the last arrival: each costs a near-empty
         launch sequence and changes nothing but the scripted cars."""
         if self._retire is None:
@@ -413,7 +480,7 @@ class IntersectionBatch:
         if chunk < 1:
             raise ValueError('run_until_done: chunk must be >= 1')
         taken = 0
-        while taken < max_steps and self.active_count() > 0:
+        while taken < max_steps and (self.active_count() > 0 or self.waiting_count() > 0):
             n = min(int(chunk), int(max_steps) - taken)
             self.run(n, graph)
             taken += n
@@ -455,8 +522,8 @@ class IntersectionBatch:
                             'the retired mask (MPCX_E_INVALID); keep_driving() or lin_passes = 1' % self.lin_passes)
         if callable(self.exchange):          # rehearsal exchange (torch.distributed): the host moves the rows between stages
             if self._retire is not None:
-                raise MpcxError('retirement at the goal with a callable exchange: it steps through step_staged(), whose per-stage entry '
-                                'points have no retired mask; use exchange=\'rccl\' or keep_driving()')
+                raise MpcxError('retirement at the goal%s with a callable exchange: it steps through step_staged(), whose per-stage entry '
+                                'points have no retired mask; use exchange=\'rccl\' or keep_driving()' % (' (and admission)' if self._admit is not None else ''))
             for _ in range(n_steps):
                 self.step_staged()
             return
@@ -464,7 +531,7 @@ class IntersectionBatch:
             self._desc = self._descriptor()
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
-                                 retire=self._retire, scene=self._scene)
+                                 retire=self._retire, scene=self._scene, admit=self._admit)
         self.steps_done += n_steps
 
     def step(self):
@@ -483,7 +550,8 @@ class IntersectionBatch:
     def step_staged(self):
         """the same step through the per-stage entry points (one host call per stage)"""
         if self._retire is not None:
-            raise MpcxError('step_staged() with retirement at the goal: the per-stage entry points have no retired mask; run() or keep_driving()')
+            raise MpcxError('step_staged() with retirement at the goal%s: the per-stage entry points have no retired mask; run() or keep_driving()'
+                            % (' and admission' if self._admit is not None else ''))
         c = self.ctx
         self._claim_context()
         # what MovingObstacle*.get() would return for every agent: (x, y, v, yaw, a, steer)
@@ -544,6 +612,8 @@ class IntersectionBatch:
             out['done'], out['steps_driven'] = self.done.cpu().numpy().copy(), self.steps_driven.cpu().numpy().copy()
         if self._scene is not None:
             out['absent'] = self.absent.cpu().numpy().copy()
+        if self._admit is not None:
+            out['wait'], out['entered_step'] = self.wait.cpu().numpy().copy(), self.entered_step.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:
@@ -554,6 +624,32 @@ class IntersectionBatch:
             raise MpcxError('stop_index(): the batch runs with stop_mode=%r' % self.stop_mode)
         self.ctx.synchronize()
         return np.where(self.inter['hit_idx'].cpu().numpy() >= 0, self.inter['cut_len'].cpu().numpy(), _lib.NO_STOP).astype(np.int32)
+
+
+def entry_schedule(route_of_agent, routes, start_index, mean_headway_steps: float, seed: int) -> np.ndarray:
+    """Seeded arrival times for IntersectionBatch.enter_on_schedule: a (B, A) integer `wait` array.  Per instance, the agents whose start
+    poses coincide (the same route point x, y: e.g. the two stock routes of one approach arm, both from index 0) form one approach QUEUE, in
+    agent order.  The k-th car of a queue is due at the cumulative sum of k + 1 draws of rng.geometric(1 / mean_headway_steps) - 1 -- memoryless
+    headways with that mean (>= 1; 1 = everybody at once, all zeros) --, rng = numpy.random.default_rng(seed); draws are taken instance-major,
+    queue by queue in the order of the queues' first agents.  Pure numpy and deterministic: no GPU, no state."""
+    route_of_agent, start_index = np.asarray(route_of_agent, dtype=np.int64), np.asarray(start_index, dtype=np.int64)
+    if route_of_agent.ndim != 2 or route_of_agent.shape != start_index.shape:
+        raise ValueError('entry_schedule: route_of_agent and start_index must both have shape (B, A)')
+    if not mean_headway_steps >= 1:
+        raise ValueError('entry_schedule: mean_headway_steps must be >= 1')
+    rng = np.random.default_rng(seed)
+    B, A = route_of_agent.shape
+    wait = np.zeros((B, A), dtype=np.int64)
+    for b in range(B):
+        pose = [tuple(float(v) for v in np.asarray(routes[route_of_agent[b, a]])[start_index[b, a], :2]) for a in range(A)]
+        seen = []
+        for a in range(A):
+            if pose[a] in seen:
+                continue
+            seen.append(pose[a])
+            queue = [k for k in range(A) if pose[k] == pose[a]]
+            wait[b, queue] = np.cumsum(rng.geometric(1.0 / mean_headway_steps, size=len(queue)) - 1)
+    return wait
 
 
 def stock_routes(ctx: Context, pairs=((1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (3, 2), (4, 1), (4, 2))):

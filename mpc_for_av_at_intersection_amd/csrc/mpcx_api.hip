@@ -67,6 +67,7 @@ void mpcx_destroy(mpcx_ctx *ctx) {
     (void)mpcx_comm_destroy(ctx);
     if (ctx->stats) (void)hipFree(ctx->stats);
     if (ctx->xchg) (void)hipFree(ctx->xchg);
+    if (ctx->admit_tab) (void)hipFree(ctx->admit_tab);
     delete ctx;
 }
 

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[976] = {};     // descriptor + run log + options + retirement + scene + parameters the cached graph was captured for
+    unsigned char loop_key[1016] = {};    // descriptor + run log + options + retirement + scene + admission + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -51,6 +51,8 @@ struct mpcx_ctx {
     int comm_world = 1, comm_rank = 0;
     double *xchg = nullptr;     // all-gather landing buffer of the agent-sharded layout
     size_t xchg_cap = 0;
+    double *admit_tab = nullptr;    // table of the admission stage (mpcx_admit.hip): [pool rows][3] poses | [pool rows] int32 tags
+    size_t admit_tab_cap = 0;
     char err[256] = {};
 };
 
@@ -142,6 +144,15 @@ int32_t mpcx_retire_enqueue(mpcx_ctx *ctx, int32_t P, const double *state, doubl
 // departure (mpcx_retire.hip): "no scene" test, check of the struct against the run
 bool mpcx_scene_absent(const mpcx_scene *s);
 int32_t mpcx_scene_validate(mpcx_ctx *ctx, const mpcx_scene *s, const mpcx_retire *retire, int32_t exchange, size_t pool_rows, const int32_t *obs_skip);
+// admission (mpcx_admit.hip): "no admission" test, check of the struct against the run, the table (grown and cleared outside any capture),
+// the two launches alone
+bool mpcx_admit_absent(const mpcx_admit *a);
+int32_t mpcx_admit_validate(mpcx_ctx *ctx, const mpcx_admit *a, const mpcx_retire *retire, const mpcx_scene *scene, int32_t exchange);
+int32_t mpcx_admit_prepare(mpcx_ctx *ctx, size_t n_rows);
+int32_t mpcx_admit_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const int32_t *obs_off,
+                           const int32_t *obs_cnt, const int32_t *obs_skip, int32_t *done, int32_t n_obs_pool, int32_t *absent,
+                           int32_t n_actors, const mpcx_traffic_actor *actors, const double *actor_state, const double *tape,
+                           int64_t tape_rows, const int32_t *actor_row, const mpcx_admit *admit);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -5,7 +5,7 @@
 // rollout -> QP -> plant (-> run-log record, iff a log is attached)], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
 // host synchronisation or host arithmetic in between.  With retirement at the goal (mpcx_retire) the step ends with retire_kernel, and an agent
 // that has arrived is skipped by every stage but the pool pack; with a scene (mpcx_scene) its arrival also takes it out of everybody
-// else's obstacle list.  Every stage is the kernel behind the per-stage C entry
+// else's obstacle list; with admission (mpcx_admit) the step begins with the two launches that let waiting agents in.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
 #include "mpcx_common.h"
@@ -62,14 +62,23 @@ static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cu
 // the prediction skips absent pool rows, the conflict search runs its SCENE instantiation on the list of present rows, the record stage's
 // clearance leaves absent rows out, and retire_kernel sets absent[obs_skip[q]] for an agent that arrives -- the last launch of the step,
 // so the others see the car gone from the next step on.
+// ad: admission or nullptr = none (then exactly the launches of a step with a scene, with the same arguments).  With it the step BEGINS with the
+// two launches of mpcx_admit.hip: a waiting agent (done[q] = 1, its own row absent) that is due and whose start pose is clear has both words
+// cleared before the rollout is forked -- the side stream's rollout already reads done --, so every stage of this step drives and sees it.
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                            const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc) {
+                            const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc, const mpcx_admit *ad) {
     const int P = c->P;
     const int32_t *done = r ? r->done : nullptr;
     int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
     const bool speed = o->stop_mode == MPCX_STOP_SPEED;
     ctx->bins_clean = false;        // until the plant kernel of this step is enqueued
     int32_t rc, pool_rows = P;
+    if (ad) {       // (validated: a scene, retirement, the local pool)
+        const int32_t na = c->n_actors > 0 ? c->n_actors : 0;
+        rc = mpcx_admit_enqueue(ctx, ip, P, c->state, c->obs_off, c->obs_cnt, c->obs_skip, r->done, sc->n_rows, sc->absent, na, c->actors,
+                                c->actor_state, c->tape, c->tape_rows, c->actor_row, ad);
+        if (rc != MPCX_OK) return rc;
+    }
     // the warm-start rollout of this step needs only the states and the previous solution: it runs on the side stream BESIDE the pool pack,
     // the prediction and the conflict search (a chain of T dependent sincos / tan per agent, 35-45 us) and is joined by the window selection
     rc = mpcx_rollout_fork(ctx, P, c->state, c->u_sol, c->xbar, done);
@@ -146,8 +155,8 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
 }
 
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                               const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, int32_t n_steps,
-                               int32_t use_graph) {
+                               const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, const mpcx_admit *admit,
+                               int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
@@ -177,6 +186,11 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         int32_t src = mpcx_scene_validate(ctx, scene, retire, c->exchange, rows, c->obs_skip);
         if (src == MPCX_OK && c->P > 0) src = mpcx_loop_check_rows(ctx, c->P, c->obs_skip, scene->n_rows, "scene");
         if (src != MPCX_OK) return src;
+    }
+    if (mpcx_admit_absent(admit)) admit = nullptr;
+    if (admit) {        // refused before anything is launched, whatever n_steps is
+        const int32_t arc = mpcx_admit_validate(ctx, admit, retire, scene, c->exchange);
+        if (arc != MPCX_OK) return arc;
     }
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
@@ -211,6 +225,10 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     }
     rc = mpcx_ensure_ticket(ctx);
     if (rc != MPCX_OK) return rc;
+    if (admit) {
+        rc = mpcx_admit_prepare(ctx, (size_t)scene->n_rows);
+        if (rc != MPCX_OK) return rc;
+    }
     {
         const size_t slots = ((size_t)c->P + 63) / 64;
         if (slots > ctx->stats_slots) {         // a larger batch: the counters so far are folded into slot 0 of the new table
@@ -244,7 +262,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene);
+            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -254,8 +272,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_interaction_params) +
-                  sizeof(mpcx_mpc_params) + 9 * sizeof(void *) <= sizeof key,
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_interaction_params) +
+                  sizeof(mpcx_mpc_params) + 10 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
     size_t o = 0;
@@ -267,6 +285,9 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     o += sizeof *retire;
     if (scene) memcpy(key + o, scene, sizeof *scene);        // (zeros = no scene: a graph captured without departure)
     o += sizeof *scene;
+    if (admit) memcpy(key + o, admit, sizeof *admit);        // (zeros = no admission: a graph captured without its two launches)
+    o += sizeof *admit;
+    memcpy(key + o, &ctx->admit_tab, sizeof ctx->admit_tab); o += sizeof ctx->admit_tab;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
     memcpy(key + o, &ctx->pred, sizeof ctx->pred); o += sizeof ctx->pred;
@@ -286,7 +307,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene);
+        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -303,27 +324,33 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_admit(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                              const mpcx_scene *scene, const mpcx_admit *admit, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, n_steps, use_graph);
 }

@@ -614,15 +614,23 @@ class Context:
     @_ordered
     def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
                         log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None,
-                        retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None):
+                        retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None,
+                        admit: Optional['_lib.AdmitC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
         retire: a _lib.RetireC -- agents are retired at their goal (mpcx_closed_loop_run_retire); None = they are driven on.
         scene: a _lib.SceneC -- departure: pool rows with absent != 0 are out of the scene and an arrival sets the agent's own word
-        (mpcx_closed_loop_run_scene; refused without retire); None = arrived cars stay in the scene."""
+        (mpcx_closed_loop_run_scene; refused without retire); None = arrived cars stay in the scene.
+        admit: a _lib.AdmitC -- admission: waiting agents enter on their schedule once their start pose is clear (mpcx_closed_loop_run_admit;
+        refused without scene); None = everybody is in from the start."""
         cip = ip.to_c()
-        if scene is not None:
+        if admit is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_admit(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
+                                                          None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
+                                                          None if scene is None else C.byref(scene), C.byref(admit), int(n_steps),
+                                                          1 if graph else 0))
+        elif scene is not None:
             self._chk(self.lib.mpcx_closed_loop_run_scene(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
                                                           None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
                                                           C.byref(scene), int(n_steps), 1 if graph else 0))
@@ -637,6 +645,32 @@ class Context:
             self._chk(self.lib.mpcx_closed_loop_run(self._ctx, C.byref(cip), C.byref(desc), int(n_steps), 1 if graph else 0))
         else:
             self._chk(self.lib.mpcx_closed_loop_run_logged(self._ctx, C.byref(cip), C.byref(desc), C.byref(log), int(n_steps), 1 if graph else 0))
+
+    @_ordered
+    def admit_step(self, ip: InteractionParams, state, obs_off, obs_cnt, obs_skip, done, absent, admit: '_lib.AdmitC', actors=None,
+                   actor_state=None, actor_row=None, tape=None):
+        """mpcx_admit_step_batch: ONE step's admission as the closed loop enqueues it at the head of a step.  done (P) and absent (pool
+        rows) are the retirement and scene words, int32, updated in place; admit: a _lib.AdmitC naming caller-owned device buffers (wait and
+        entered_step: P int32, clock: 1 int32).  actors / actor_state / actor_row / tape: scripted cars as traffic_step takes them; they
+        are read, not stepped."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state'); self._want(done, torch.int32, (Pn,), 'done')
+        self._want(absent, torch.int32, (absent.shape[0],), 'absent')
+        for nm, t in (('obs_off', obs_off), ('obs_cnt', obs_cnt), ('obs_skip', obs_skip)):
+            self._want(t, torch.int32, (Pn,), nm)
+        n = 0
+        if actor_state is not None:
+            n = int(actor_state.shape[0])
+            self._want(actors, torch.uint8, (n * _lib.TRAFFIC_ACTOR_DTYPE.itemsize,), 'actors')
+            self._want(actor_state, torch.float64, (n, 4), 'actor_state'); self._want(actor_row, torch.int32, (n,), 'actor_row')
+            if tape is not None:
+                self._want(tape, torch.float64, (tape.shape[0], 6), 'tape')
+        cip = ip.to_c()
+        self._chk(self.lib.mpcx_admit_step_batch(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip), _ptr(done),
+                                                 int(absent.shape[0]), _ptr(absent), n, _ptr(actors) if n else None,
+                                                 _ptr(actor_state) if n else None, _ptr(tape) if n else None,
+                                                 0 if (tape is None or not n) else int(tape.shape[0]), _ptr(actor_row) if n else None,
+                                                 C.byref(admit)))
 
     @_ordered
     def record_step(self, ip: InteractionParams, state, applied, x_sol, path, path_off, path_len, target_ind, cut_len, traj_idx, hit_idx,
