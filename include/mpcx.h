@@ -18,7 +18,8 @@
  *     vehicles is the run log: mpcx_run_log, mpcx_closed_loop_run_logged, mpcx_record_step_batch.
  *   - the end of an agent's episode (the loop's `if mpc.is_goal(state): break`) is retirement at the goal: mpcx_retire,
  *     mpcx_closed_loop_run_retire; taking the arrived car out of everybody else's scene as well is departure: mpcx_scene,
- *     mpcx_closed_loop_run_scene.
+ *     mpcx_closed_loop_run_scene; letting vehicles in on a schedule is admission: mpcx_admit, mpcx_closed_loop_run_admit; re-using a
+ *     departed agent's slot for the next vehicle is respawn: mpcx_respawn, mpcx_closed_loop_run_respawn.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -564,6 +565,61 @@ int32_t mpcx_admit_step_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip, 
                               int32_t n_actors, const mpcx_traffic_actor *actors /*n_actors*/, const double *actor_state /*n_actors,4*/,
                               const double *tape /*rows,6 or NULL*/, int64_t tape_rows, const int32_t *actor_row /*n_actors*/,
                               const mpcx_admit *admit);
+
+/* ---- respawn: re-using a departed agent's slot for the next vehicle, which makes retirement, departure and admission an OPEN intersection.
+ * A slot (agent index q) serves a stream of `generations` vehicles, all on the slot's route from the slot's start pose.  The LAST launch of
+ * every step (respawn_kernel, after retire_kernel; csrc/mpcx_respawn.hip, the rule is csrc/mpcx_respawn_core.h) looks at every agent that is
+ * not driving.  Agent q HAS ARRIVED iff done[q] != 0, wait[q] == -1, entered_step[q] >= 0, served[q] < generations and its own row
+ * obs_skip[q] lies inside the pool.  With `clock` = admission's word as this step's admission stage left it (already advanced: the index of
+ * the NEXT step) the arrival, in this order,
+ *   1. writes episode record g = served[q] of slot q:
+ *        ep_i32[q][g][0..7] = entered_step, arrived_step = clock - 1, steps_driven, row_end = the run log's cursor steps[q] (-1 without a log),
+ *                             the log's contact_step (in cursor units; -1 if none or no log), the log's flags (0 without a log), due[q][g], 0
+ *        ep_f64[q][g][0..1] = the log's min_clearance (+inf without a log), 0
+ *      so that the episode's log rows are [row_end - steps_driven, row_end) of the slot's rows;
+ *   2. increments served[q];
+ *   3. if served[q] < generations, puts the slot's per-agent state back to "first step of a fresh batch" -- state = start_state, applied = 0,
+ *      traj_idx = target_ind = start_idx, cut_len = 0 (MPCX_STOP_SPEED: prev_len = 0 too), u_sol = 0, iters = 0, steps_driven = 0; with a log
+ *      goal_step = contact_step = -1, flags = 0, min_clearance = +inf, while the cursor `steps` keeps counting: a slot's log rows are its
+ *      vehicles' rows one after the other -- and hands it to the admission gate: entered_step = -1, wait = max(0, due[q][served[q]] - clock).
+ *      The next vehicle asks to enter in step max(next step, its due step) and goes through the gate like any scheduled agent: a reset slot
+ *      is a waiting agent in exactly the state admission defines (done[q] = 1, own row absent, wait[q] >= 0);
+ *   4. otherwise the slot is finished: it stays departed and is never touched again.
+ * x_sol, xref, xbar, reaches_end, status, kkt, hit_idx and hit_xy are pure outputs: they stay as the last vehicle left them until the new
+ * vehicle's first step overwrites them, and nothing reads them for a waiting agent.  steps_driven == arrived_step - entered_step + 1 in every
+ * record, because an agent in the scene drives every step -- except for a slot found arrived when respawn is switched on (an agent that
+ * arrived earlier, or an unscheduled one retired by the caller's goal test before the first step): it counts as arriving in that step.
+ * due[q][0] is recorded only: the FIRST vehicle of a slot enters as the caller's mpcx_admit::wait says.
+ * Everything that changes is device memory, so a replayed graph respawns like a plain run.  The struct travels beside the descriptor (no
+ * other struct changes size); the cached graph's key covers it by value.  respawn = NULL or an all-zero struct: mpcx_closed_loop_run_admit
+ * itself -- the same launches with the same arguments.  MPCX_E_INVALID ("respawn: ...") before anything is launched, whatever n_steps is:
+ * respawn without admission (which in turn needs a scene and retirement, and so refuses MPCX_SHARD_AGENTS and more than one linearisation
+ * pass); generations < 1; one of the six pointers NULL.  The step order becomes admit -> ... -> record -> retire -> respawn.
+ * Works with scripted traffic, the run log, both stop modes and use_graph. */
+typedef struct {
+    int32_t generations;          /* G >= 1: vehicles per slot */
+    int32_t reserved;
+    const double  *start_state;   /* P,4 */
+    const int32_t *start_idx;     /* P */
+    const int32_t *due;           /* P,G: step index at which vehicle g of slot q asks to enter; [q][0] is recorded only */
+    int32_t *served;              /* P, zero-initialised */
+    int32_t *ep_i32;              /* P,G,8 */
+    double  *ep_f64;              /* P,G,2 */
+} mpcx_respawn;
+int32_t mpcx_closed_loop_run_respawn(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                     const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                     const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                     const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                     int32_t n_steps, int32_t use_graph);
+/* one step's respawn as a stage of its own (what mpcx_closed_loop_run_respawn enqueues at the end of a step): the buffers are the closed
+ * loop's; prev_len is mpcx_closed_loop_opts::prev_len (NULL in MPCX_STOP_CUT), obs_skip names the agents' own rows among the n_obs_pool rows
+ * of the pool, log may be NULL.  The stage reads retire->done and admit->clock and writes retire->steps_driven, admit->wait and
+ * admit->entered_step.  u_sol is P x 2 x T doubles, T that of mpcx_set_mpc_params. */
+int32_t mpcx_respawn_step_batch(mpcx_ctx *ctx, int32_t P, double *state /*P,4*/, double *applied /*P,2*/, double *u_sol /*P,2,T*/,
+                                int32_t *traj_idx /*P*/, int32_t *target_ind /*P*/, int32_t *cut_len /*P*/, int32_t *iters /*P*/,
+                                int32_t *prev_len /*P or NULL*/, const int32_t *obs_skip /*P*/, int32_t n_obs_pool,
+                                const mpcx_run_log *log /*or NULL*/, const mpcx_retire *retire, const mpcx_admit *admit,
+                                const mpcx_respawn *respawn);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

@@ -72,6 +72,18 @@ class AdmitC(C.Structure):
     _fields_ = [('wait', C.c_void_p), ('entered_step', C.c_void_p), ('clock', C.c_void_p), ('reserved', C.c_int32), ('gap', C.c_double)]
 
 
+class RespawnC(C.Structure):
+    """mirror of mpcx_respawn (include/mpcx.h): respawn; start_state (P,4 float64), start_idx (P), due (P,G), served (P), ep_i32 (P,G,8) and
+    ep_f64 (P,G,2 float64) are device addresses"""
+    _fields_ = [('generations', C.c_int32), ('reserved', C.c_int32), ('start_state', C.c_void_p), ('start_idx', C.c_void_p), ('due', C.c_void_p),
+                ('served', C.c_void_p), ('ep_i32', C.c_void_p), ('ep_f64', C.c_void_p)]
+
+
+# the words of an episode record (ep_i32[q][g][0..6], one reserved; ep_f64[q][g][0], one reserved)
+EPISODE_I32 = ('entered', 'arrived', 'steps_driven', 'row_end', 'contact_step', 'flags', 'due')
+EPISODE_F64 = ('min_clearance',)
+
+
 STOP_CUT, STOP_SPEED = 0, 1     # mpcx_closed_loop_opts.stop_mode
 STOP_MODES = {'cut': STOP_CUT, 'speed': STOP_SPEED}
 NO_STOP = 999                   # MPCX_NO_STOP: the stop index lib/mpc_with_speed.py:281 reads as "no stop"
@@ -132,7 +144,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
            'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
            'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
-           'mpcx_admit_step_batch']
+           'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch']
 
 
 def load():
@@ -214,5 +226,12 @@ def load():
     lib.mpcx_admit_step_batch.restype = i32
     lib.mpcx_admit_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, C.c_int64, vp,
                                           C.POINTER(AdmitC)]
+    lib.mpcx_closed_loop_run_respawn.restype = i32
+    lib.mpcx_closed_loop_run_respawn.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                 C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                 C.POINTER(RespawnC), i32, i32]
+    lib.mpcx_respawn_step_batch.restype = i32
+    lib.mpcx_respawn_step_batch.argtypes = [vp, i32] + [vp] * 9 + [i32, C.POINTER(RunLogC), C.POINTER(RetireC), C.POINTER(AdmitC),
+                                                                   C.POINTER(RespawnC)]
     _lib = lib
     return lib

@@ -21,6 +21,9 @@ search and nobody's clearance sees it (two stock routes share every exit arm: a 
 `enter_on_schedule(wait, gap)` is ADMISSION, the counterpart: scheduled agents wait outside the scene and enter, on the device, in the step
 their count-down ends -- or the first later step in which their start pose is `gap` clear of everybody present (entry_schedule() draws
 seeded arrival times per approach queue).
+`respawn_on_schedule(due, gap)` is RESPAWN, which makes the three an open intersection: every slot serves a stream of vehicles -- when one
+arrives its episode is recorded (episodes()), the slot is reset to a fresh start and the next vehicle goes through the gate at its due step
+(demand_schedule() draws seeded arrival streams per approach queue).
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -35,6 +38,8 @@ from .runtime import (path_first_within, path_plan, path_tables, traffic_pool_la
 
 RUN_LOG_DTYPE = np.dtype([(n, '<f8') for n in _lib.RUN_LOG_F64] + [(n, '<i4') for n in _lib.RUN_LOG_I32])
 RUN_LOG_MAX_BYTES = 1 << 30     # attach_log refuses a larger log unless told otherwise
+EPISODE_DTYPE = np.dtype([(n, '<i4') for n in ('slot', 'generation', 'due', 'entered', 'arrived', 'steps_driven', 'delay')] + [('contact', '?'),
+                         ('min_clearance', '<f8'), ('row_begin', '<i4'), ('row_end', '<i4')])
 
 
 class RunLog:
@@ -311,6 +316,13 @@ class IntersectionBatch:
         self.clock: Optional[torch.Tensor] = None            # ... int32 (1,), steps completed since enter_on_schedule()
         self.scheduled_step: Optional[np.ndarray] = None     # ... host, (P,): the step the agent was scheduled for (0 = from the start)
         self._admit = None
+        self.served: Optional[torch.Tensor] = None           # respawn_on_schedule(): int32 (P,), episodes finished per slot
+        self.due: Optional[torch.Tensor] = None              # ... int32 (P, G), the step at which vehicle g of slot q asks to enter
+        self.ep_i32: Optional[torch.Tensor] = None           # ... int32 (P, G, 8) and float64 (P, G, 2): the episode table (_lib.EPISODE_*)
+        self.ep_f64: Optional[torch.Tensor] = None
+        self.start_state: Optional[torch.Tensor] = None      # ... float64 (P, 4) and int32 (P,): what a reset puts a slot back to
+        self.start_idx: Optional[torch.Tensor] = None
+        self._respawn = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -390,6 +402,7 @@ class IntersectionBatch:
         self._retire = _lib.RetireC(self.done.data_ptr(), self.steps_driven.data_ptr(), goal_dis, stop_speed)
         self.absent, self._scene = None, None
         self._admit = None                  # (admission lives on a scene: enter_on_schedule() after this call)
+        self._respawn = None                # (... and respawn on admission)
         if leave_scene:
             rows = int(self.obs6.shape[0])
             self.absent = torch.zeros(rows, dtype=torch.int32, device=self.ctx.device)
@@ -403,10 +416,12 @@ class IntersectionBatch:
         """switch retirement off: the batch enqueues exactly the launches of one that never had it.  Agents already retired stay where
         they are and are driven again from there; `done` and `steps_driven` keep what they hold until the next retire_at_goal().  The
         scene goes with it: every car, departed or hidden, is visible again from the next step on (`absent` keeps what it holds and is
-        no longer read).  Admission goes with it too: agents still waiting are driven from where they stand, from the next step on"""
+        no longer read).  Admission goes with it too: agents still waiting are driven from where they stand, from the next step on -- and
+        respawn with admission: no slot is reset any more"""
         self._retire = None
         self._scene = None
         self._admit = None
+        self._respawn = None
         self._desc = None
 
     def enter_on_schedule(self, wait, gap: float = 0.0):
@@ -440,14 +455,84 @@ class IntersectionBatch:
         self.clock = torch.zeros(1, dtype=torch.int32, device=self.ctx.device)
         self.scheduled_step = np.maximum(w, 0)
         self._admit = _lib.AdmitC(self.wait.data_ptr(), self.entered_step.data_ptr(), self.clock.data_ptr(), 0, gap)
+        self._respawn = None                # (a new schedule and a new clock: respawn_on_schedule() sets both up itself)
         self._desc = None
         self.ctx.synchronize()
 
     def enter_now(self):
         """switch admission off and nothing else: the batch enqueues exactly the launches of one that never had it.  Agents still waiting
-        stay outside the scene (retired, their rows absent); `wait`, `entered_step` and `clock` keep what they hold"""
+        stay outside the scene (retired, their rows absent); `wait`, `entered_step` and `clock` keep what they hold.  Respawn lives on admission
+        and is switched off with it"""
         self._admit = None
+        self._respawn = None
         self._desc = None
+
+    def respawn_on_schedule(self, due, gap: float = 0.0):
+        """RESPAWN (mpcx_closed_loop_run_respawn): every slot (agent index q) serves a stream of G vehicles, all on the slot's route from the
+        slot's start pose -- `state` and `traj_idx` of the batch as it stands.  due[q][g] is the step (counted from this call) at which vehicle
+        g of slot q asks to enter.  When a slot's vehicle arrives, the last launch of that step writes the finished episode into the episode
+        table (episodes()), puts the slot's per-agent state back to the first step of a fresh batch and hands it to the admission gate with
+        wait = max(0, due of the next vehicle - next step); after its G-th vehicle the slot stays departed.  All on the device, under plain
+        enqueue and graph replay alike; costs one more launch per step.
+        due: integer array (B, A, G) or (P, G), values >= 0.  Needs retire_at_goal(leave_scene=True) first.  Calls
+        enter_on_schedule(wait=due[..., 0], gap): every FIRST vehicle goes through the gate too -- two slots that share a start pose must never
+        be present together at step 0 (in cut mode both cars would stand inside each other and yield for ever).  Allocates `served` and the
+        episode table, and drops the cached descriptor.  With a run log attached a slot's rows are its vehicles' rows one after the other:
+        size the log for the sum.  stop_respawning() switches respawn off alone; enter_now() and keep_driving() switch it off with what it
+        lives on."""
+        if self._scene is None:
+            raise MpcxError('respawn_on_schedule: respawn needs admission, which needs a scene (MPCX_E_INVALID): retire_at_goal(leave_scene=True) first')
+        d = np.asarray(due)
+        if not np.issubdtype(d.dtype, np.integer) or d.ndim not in (2, 3) or d.shape[:-1] not in ((self.B, self.A), (self.P,)) or d.shape[-1] < 1:
+            raise ValueError('respawn_on_schedule: due must be an integer array of shape (B, A, G) = %s or (P, G), G >= 1' % ((self.B, self.A, 'G'),))
+        d = d.reshape(self.P, -1).astype(np.int64)
+        if (d < 0).any() or (d > np.iinfo(np.int32).max).any():
+            raise ValueError('respawn_on_schedule: due holds step indices >= 0')
+        G = int(d.shape[1])
+        self.enter_on_schedule(d[:, 0], gap)
+        dev = self.ctx.device
+        self.start_state, self.start_idx = self.state.clone(), self.traj_idx.clone()
+        self.due = self.ctx.i32(d)
+        self.served = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        self.ep_i32 = torch.zeros((self.P, G, 8), dtype=torch.int32, device=dev)
+        self.ep_f64 = torch.zeros((self.P, G, 2), dtype=torch.float64, device=dev)
+        self._respawn = _lib.RespawnC(G, 0, self.start_state.data_ptr(), self.start_idx.data_ptr(), self.due.data_ptr(), self.served.data_ptr(),
+                                      self.ep_i32.data_ptr(), self.ep_f64.data_ptr())
+        self._desc = None
+        self.ctx.synchronize()
+
+    def stop_respawning(self):
+        """switch respawn off and nothing else: the batch enqueues exactly the launches of one with admission alone.  Vehicles in flight
+        finish (and stay departed), waiting ones still enter; `served` and the episode table keep what they hold"""
+        self._respawn = None
+        self._desc = None
+
+    def served_count(self) -> int:
+        """episodes finished so far, over all slots (one small reduction and one synchronisation)"""
+        if self.served is None:
+            raise MpcxError('served_count(): respawn_on_schedule() has not been called')
+        return int(self.served.sum().item())
+
+    def episodes(self) -> np.ndarray:
+        """one row per finished episode, slot-major (EPISODE_DTYPE; synchronises): slot, generation, due, entered, arrived (step indices
+        counted from respawn_on_schedule()), steps_driven (= arrived - entered + 1), delay = entered - due -- what the gate and the slot's
+        previous vehicle held it back for --, and, with a run log attached (else False, +inf, -1, -1): contact, min_clearance as RunLog defines
+        them for the episode, and row_begin, row_end: the episode's rows are RunLog.rows(slot)[row_begin:row_end]"""
+        if self.served is None:
+            raise MpcxError('episodes(): respawn_on_schedule() has not been called')
+        self.ctx.synchronize()
+        served, w, f = self.served.cpu().numpy(), self.ep_i32.cpu().numpy(), self.ep_f64.cpu().numpy()
+        q, g = np.nonzero(np.arange(w.shape[1])[None, :] < served[:, None])
+        out = np.zeros(len(q), EPISODE_DTYPE)
+        rec = {n: w[q, g, k] for k, n in enumerate(_lib.EPISODE_I32)}
+        out['slot'], out['generation'] = q, g
+        for n in ('due', 'entered', 'arrived', 'steps_driven', 'row_end'):
+            out[n] = rec[n]
+        out['delay'] = rec['entered'] - rec['due']
+        out['contact'] = rec['contact_step'] >= 0
+        out['min_clearance'] = f[q, g, 0]
+        out['row_begin'] = np.where(rec['row_end'] >= 0, rec['row_end'] - rec['steps_driven'], -1)
+        return out
 
     def waiting_count(self) -> int:
         """agents scheduled and not yet in (one small reduction and one synchronisation); 0 with admission off"""
@@ -531,7 +616,7 @@ class IntersectionBatch:
             self._desc = self._descriptor()
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
-                                 retire=self._retire, scene=self._scene, admit=self._admit)
+                                 retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn)
         self.steps_done += n_steps
 
     def step(self):
@@ -614,6 +699,8 @@ class IntersectionBatch:
             out['absent'] = self.absent.cpu().numpy().copy()
         if self._admit is not None:
             out['wait'], out['entered_step'] = self.wait.cpu().numpy().copy(), self.entered_step.cpu().numpy().copy()
+        if self._respawn is not None:
+            out['served'] = self.served.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:
@@ -650,6 +737,37 @@ def entry_schedule(route_of_agent, routes, start_index, mean_headway_steps: floa
             queue = [k for k in range(A) if pose[k] == pose[a]]
             wait[b, queue] = np.cumsum(rng.geometric(1.0 / mean_headway_steps, size=len(queue)) - 1)
     return wait
+
+
+def demand_schedule(route_of_agent, routes, start_index, mean_headway_steps: float, generations: int, seed: int) -> np.ndarray:
+    """Seeded demand for IntersectionBatch.respawn_on_schedule: a (B, A, G) integer `due` array.  Per instance, the slots whose start poses
+    coincide form one approach QUEUE, in agent order (as in entry_schedule).  A queue of n slots draws ONE memoryless arrival stream of n G
+    vehicles -- the k-th is due at the cumulative sum of k + 1 draws of rng.geometric(1 / mean_headway_steps) - 1 -- and deals it to its slots
+    in turn: vehicle k goes to slot k mod n as that slot's generation k div n, so every slot's due steps are non-decreasing.  rng =
+    numpy.random.default_rng(seed); draws are taken instance-major, queue by queue in the order of the queues' first agents.  Pure numpy and
+    deterministic: no GPU, no state."""
+    route_of_agent, start_index = np.asarray(route_of_agent, dtype=np.int64), np.asarray(start_index, dtype=np.int64)
+    if route_of_agent.ndim != 2 or route_of_agent.shape != start_index.shape:
+        raise ValueError('demand_schedule: route_of_agent and start_index must both have shape (B, A)')
+    if not mean_headway_steps >= 1:
+        raise ValueError('demand_schedule: mean_headway_steps must be >= 1')
+    G = int(generations)
+    if G < 1:
+        raise ValueError('demand_schedule: generations must be >= 1')
+    rng = np.random.default_rng(seed)
+    B, A = route_of_agent.shape
+    due = np.zeros((B, A, G), dtype=np.int64)
+    for b in range(B):
+        pose = [tuple(float(v) for v in np.asarray(routes[route_of_agent[b, a]])[start_index[b, a], :2]) for a in range(A)]
+        seen = []
+        for a in range(A):
+            if pose[a] in seen:
+                continue
+            seen.append(pose[a])
+            queue = [k for k in range(A) if pose[k] == pose[a]]
+            stream = np.cumsum(rng.geometric(1.0 / mean_headway_steps, size=len(queue) * G) - 1)
+            due[b, queue, :] = stream.reshape(G, len(queue)).T
+    return due
 
 
 def stock_routes(ctx: Context, pairs=((1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (3, 2), (4, 1), (4, 2))):

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1016] = {};    // descriptor + run log + options + retirement + scene + admission + parameters the cached graph was captured for
+    unsigned char loop_key[1016] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -153,6 +153,13 @@ int32_t mpcx_admit_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int
                            const int32_t *obs_cnt, const int32_t *obs_skip, int32_t *done, int32_t n_obs_pool, int32_t *absent,
                            int32_t n_actors, const mpcx_traffic_actor *actors, const double *actor_state, const double *tape,
                            int64_t tape_rows, const int32_t *actor_row, const mpcx_admit *admit);
+// respawn (mpcx_respawn.hip): "no respawn" test, check of the struct against the run, the launch alone
+bool mpcx_respawn_absent(const mpcx_respawn *s);
+int32_t mpcx_respawn_validate(mpcx_ctx *ctx, const mpcx_respawn *s, const mpcx_admit *admit);
+int32_t mpcx_respawn_enqueue(mpcx_ctx *ctx, int32_t P, double *state, double *applied, double *u_sol, int32_t *traj_idx, int32_t *target_ind,
+                             int32_t *cut_len, int32_t *iters, int32_t *prev_len /*or nullptr*/, const int32_t *obs_skip, int32_t n_obs_pool,
+                             const mpcx_run_log *log /*or nullptr*/, const mpcx_retire *retire, const mpcx_admit *admit,
+                             const mpcx_respawn *respawn);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

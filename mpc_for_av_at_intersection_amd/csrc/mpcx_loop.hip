@@ -5,7 +5,8 @@
 // rollout -> QP -> plant (-> run-log record, iff a log is attached)], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
 // host synchronisation or host arithmetic in between.  With retirement at the goal (mpcx_retire) the step ends with retire_kernel, and an agent
 // that has arrived is skipped by every stage but the pool pack; with a scene (mpcx_scene) its arrival also takes it out of everybody
-// else's obstacle list; with admission (mpcx_admit) the step begins with the two launches that let waiting agents in.  Every stage is the kernel behind the per-stage C entry
+// else's obstacle list; with admission (mpcx_admit) the step begins with the two launches that let waiting agents in; with respawn
+// (mpcx_respawn) it ends with respawn_kernel, which resets an arrived agent's slot for the next vehicle of its stream.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
 #include "mpcx_common.h"
@@ -65,8 +66,12 @@ static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cu
 // ad: admission or nullptr = none (then exactly the launches of a step with a scene, with the same arguments).  With it the step BEGINS with the
 // two launches of mpcx_admit.hip: a waiting agent (done[q] = 1, its own row absent) that is due and whose start pose is clear has both words
 // cleared before the rollout is forked -- the side stream's rollout already reads done --, so every stage of this step drives and sees it.
+// rs: respawn or nullptr = none (then exactly the launches of a step with admission, with the same arguments).  With it the step ENDS with
+// respawn_kernel, after retire_kernel: an agent that has arrived leaves an episode record and, while its slot has vehicles left, is reset to
+// the first step of a fresh batch and waits for the gate (wait >= 0).  The next step's rollout is forked after this launch in stream order.
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                            const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc, const mpcx_admit *ad) {
+                            const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc, const mpcx_admit *ad,
+                            const mpcx_respawn *rs) {
     const int P = c->P;
     const int32_t *done = r ? r->done : nullptr;
     int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
@@ -151,12 +156,16 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     // step's row logs the controls really applied
     if (r) rc = mpcx_retire_enqueue(ctx, P, c->state, c->applied, c->path_xyyaw, c->path_off, c->path_len, c->target_ind,
                                     speed ? c->path_len : c->cut_len, r, sc, c->obs_skip);
+    if (rc != MPCX_OK) return rc;
+    if (rs)         // (validated: admission, and with it a scene and retirement)
+        rc = mpcx_respawn_enqueue(ctx, P, c->state, c->applied, c->u_sol, c->traj_idx, c->target_ind, c->cut_len, c->iters,
+                                  speed ? o->prev_len : nullptr, c->obs_skip, sc->n_rows, log, r, ad, rs);
     return rc;
 }
 
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                                const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, const mpcx_admit *admit,
-                               int32_t n_steps, int32_t use_graph) {
+                               const mpcx_respawn *respawn, int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
@@ -191,6 +200,11 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (admit) {        // refused before anything is launched, whatever n_steps is
         const int32_t arc = mpcx_admit_validate(ctx, admit, retire, scene, c->exchange);
         if (arc != MPCX_OK) return arc;
+    }
+    if (mpcx_respawn_absent(respawn)) respawn = nullptr;
+    if (respawn) {      // refused before anything is launched, whatever n_steps is
+        const int32_t prc = mpcx_respawn_validate(ctx, respawn, admit);
+        if (prc != MPCX_OK) return prc;
     }
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
@@ -262,7 +276,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit);
+            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -272,7 +286,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_interaction_params) +
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_interaction_params) +
                   sizeof(mpcx_mpc_params) + 10 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
@@ -287,6 +301,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     o += sizeof *scene;
     if (admit) memcpy(key + o, admit, sizeof *admit);        // (zeros = no admission: a graph captured without its two launches)
     o += sizeof *admit;
+    if (respawn) memcpy(key + o, respawn, sizeof *respawn);  // (zeros = no respawn: a graph captured without its launch)
+    o += sizeof *respawn;
     memcpy(key + o, &ctx->admit_tab, sizeof ctx->admit_tab); o += sizeof ctx->admit_tab;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
@@ -307,7 +323,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit);
+        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -324,33 +340,40 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_admit(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, const mpcx_admit *admit, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_respawn(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                                const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
+                                                int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, n_steps, use_graph);
 }

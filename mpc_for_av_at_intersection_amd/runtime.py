@@ -615,7 +615,7 @@ class Context:
     def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
                         log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None,
                         retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None,
-                        admit: Optional['_lib.AdmitC'] = None):
+                        admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
@@ -623,9 +623,16 @@ class Context:
         scene: a _lib.SceneC -- departure: pool rows with absent != 0 are out of the scene and an arrival sets the agent's own word
         (mpcx_closed_loop_run_scene; refused without retire); None = arrived cars stay in the scene.
         admit: a _lib.AdmitC -- admission: waiting agents enter on their schedule once their start pose is clear (mpcx_closed_loop_run_admit;
-        refused without scene); None = everybody is in from the start."""
+        refused without scene); None = everybody is in from the start.
+        respawn: a _lib.RespawnC -- respawn: an arrived agent's slot is reset for the next vehicle of its stream and handed back to the
+        admission gate (mpcx_closed_loop_run_respawn; refused without admit); None = a departed slot stays empty."""
         cip = ip.to_c()
-        if admit is not None:
+        if respawn is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_respawn(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
+                                                            None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
+                                                            None if scene is None else C.byref(scene), None if admit is None else C.byref(admit),
+                                                            C.byref(respawn), int(n_steps), 1 if graph else 0))
+        elif admit is not None:
             self._chk(self.lib.mpcx_closed_loop_run_admit(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
                                                           None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
                                                           None if scene is None else C.byref(scene), C.byref(admit), int(n_steps),
@@ -671,6 +678,25 @@ class Context:
                                                  _ptr(actor_state) if n else None, _ptr(tape) if n else None,
                                                  0 if (tape is None or not n) else int(tape.shape[0]), _ptr(actor_row) if n else None,
                                                  C.byref(admit)))
+
+    @_ordered
+    def respawn_step(self, state, applied, u_sol, traj_idx, target_ind, cut_len, iters, obs_skip, n_obs_pool: int, retire: '_lib.RetireC',
+                     admit: '_lib.AdmitC', respawn: '_lib.RespawnC', prev_len=None, log: Optional['_lib.RunLogC'] = None):
+        """mpcx_respawn_step_batch: ONE step's respawn as the closed loop enqueues it at the end of a step (after the retire stage).  The
+        buffers are the closed loop's, updated in place: state (P, 4), applied (P, 2), u_sol (P, 2, T), int32 traj_idx, target_ind, cut_len,
+        iters (P each), prev_len (P; the speed stop mode only); obs_skip names the agents' own rows among the n_obs_pool rows of the pool.
+        retire / admit / respawn / log: structs naming caller-owned device buffers (done is read, steps_driven, wait, entered_step, served,
+        the episode table and the log's outcome words are written)."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state'); self._want(applied, torch.float64, (Pn, 2), 'applied')
+        self._want(u_sol, torch.float64, (Pn, 2, self.params.T), 'u_sol')
+        for nm, t in (('traj_idx', traj_idx), ('target_ind', target_ind), ('cut_len', cut_len), ('iters', iters), ('obs_skip', obs_skip)):
+            self._want(t, torch.int32, (Pn,), nm)
+        if prev_len is not None:
+            self._want(prev_len, torch.int32, (Pn,), 'prev_len')
+        self._chk(self.lib.mpcx_respawn_step_batch(self._ctx, Pn, _ptr(state), _ptr(applied), _ptr(u_sol), _ptr(traj_idx), _ptr(target_ind),
+                                                   _ptr(cut_len), _ptr(iters), _ptr(prev_len), _ptr(obs_skip), int(n_obs_pool),
+                                                   None if log is None else C.byref(log), C.byref(retire), C.byref(admit), C.byref(respawn)))
 
     @_ordered
     def record_step(self, ip: InteractionParams, state, applied, x_sol, path, path_off, path_len, target_ind, cut_len, traj_idx, hit_idx,
