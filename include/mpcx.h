@@ -19,7 +19,8 @@
  *   - the end of an agent's episode (the loop's `if mpc.is_goal(state): break`) is retirement at the goal: mpcx_retire,
  *     mpcx_closed_loop_run_retire; taking the arrived car out of everybody else's scene as well is departure: mpcx_scene,
  *     mpcx_closed_loop_run_scene; letting vehicles in on a schedule is admission: mpcx_admit, mpcx_closed_loop_run_admit; re-using a
- *     departed agent's slot for the next vehicle is respawn: mpcx_respawn, mpcx_closed_loop_run_respawn.
+ *     departed agent's slot for the next vehicle is respawn: mpcx_respawn, mpcx_closed_loop_run_respawn.  A route per vehicle of such a slot is mpcx_routes,
+ *     mpcx_closed_loop_run_routes; mpcx_episode_summary reduces the episode table per instance and route.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -620,6 +621,66 @@ int32_t mpcx_respawn_step_batch(mpcx_ctx *ctx, int32_t P, double *state /*P,4*/,
                                 int32_t *prev_len /*P or NULL*/, const int32_t *obs_skip /*P*/, int32_t n_obs_pool,
                                 const mpcx_run_log *log /*or NULL*/, const mpcx_retire *retire, const mpcx_admit *admit,
                                 const mpcx_respawn *respawn);
+
+/* ---- routes: every vehicle of a slot takes its own route from its own start pose.  With respawn alone a slot is bound to one route and one
+ * start pose for the whole run; with routes vehicle g of slot q drives route route_of[q][g] (an index into the n_routes-word tables route_off /
+ * route_len, which name runs of the descriptor's path tables -- every path table is indexed by absolute path point, so a route is two words)
+ * from start_state[q][g] and path index start_idx[q][g].  respawn_route_kernel (csrc/mpcx_route.hip; the rule is csrc/mpcx_route_core.h)
+ * is launched IN PLACE OF respawn_kernel: a step has the launches of a respawn step.  For agent q, in this order:
+ *   1. g = served[q], read before anything else;
+ *   2. the respawn rule itself (csrc/mpcx_respawn_core.h, called, not restated);
+ *   3. if the agent arrived: ep_i32[q][g][7] = route_of[q][g] -- the reserved word of the episode record now names the episode's route;
+ *   4. if the slot was reset (served[q] < generations now), with g' = g + 1 and r = route_of[q][g'], what the reset wrote is overwritten:
+ *      state[q] = start_state[q][g'], traj_idx[q] = target_ind[q] = start_idx[q][g'], path_off[q] = route_off[r], path_len[q] = route_len[r];
+ *   5. a DEFECTIVE next vehicle -- r outside [0, n_routes) or start_idx[q][g'] outside [0, route_len[r]) -- is never driven: the slot is left
+ *      with wait = -1, entered_step = -1, done set and its row absent, so it neither drives nor waits and never arrives again; path_off and
+ *      path_len are not touched.
+ * mpcx_respawn::start_state / start_idx are still required and still what the plain reset writes; with routes nothing reads them afterwards.
+ * Vehicle 0 of a slot is the caller's: path_off, path_len, state, traj_idx and target_ind as the batch stands when the run starts.
+ * path_off and path_len MUST be the descriptor's own (the stages read them afresh every step; here they become writable).  Every access is
+ * to words of agent q plus the read-only route tables: the outcome does not depend on the order of the lanes.  Everything that changes is
+ * device memory, so a replayed graph routes like a plain run.  The struct travels beside the descriptor (no other struct changes size); the
+ * cached graph's key covers it by value.  routes = NULL or an all-zero struct: mpcx_closed_loop_run_respawn itself -- the same launches with
+ * the same arguments.  MPCX_E_INVALID ("routes: ...") before anything is launched, whatever n_steps is: routes without respawn; one of the
+ * seven pointers NULL; n_routes < 1; path_off / path_len that are not the descriptor's; a route_len[r] below 1 or above the conflict
+ * search's capacity (mpcx_interaction_params.max_path_len as mpcx_interaction_batch rounds it).  route_off and route_len are read back once
+ * per call, as the row maps of scripted traffic are; the per-vehicle tables are not: the kernel's own test (5.) covers them.  That a route's
+ * run lies inside the path tables is the caller's word, as path_off / path_len are. */
+typedef struct {
+    int32_t n_routes;             /* R >= 1 */
+    int32_t reserved;
+    const int32_t *route_off;     /* R: first path point of route r in the descriptor's path tables */
+    const int32_t *route_len;     /* R: its length in points */
+    const int32_t *route_of;      /* P,G: the route of vehicle g of slot q */
+    const double  *start_state;   /* P,G,4 */
+    const int32_t *start_idx;     /* P,G */
+    int32_t *path_off;            /* P: mpcx_closed_loop::path_off itself */
+    int32_t *path_len;            /* P: mpcx_closed_loop::path_len itself */
+} mpcx_routes;
+int32_t mpcx_closed_loop_run_routes(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                    const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                    const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                    const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                    const mpcx_routes *routes /*or NULL*/, int32_t n_steps, int32_t use_graph);
+/* one step's routed respawn as a stage of its own: mpcx_respawn_step_batch with the routes struct (NULL or all-zero: that call itself).
+ * routes->path_off / path_len are the P words the stage may write; max_path_len bounds route_len as the closed loop's check does (0: no
+ * upper bound is checked). */
+int32_t mpcx_respawn_step_batch_routes(mpcx_ctx *ctx, int32_t P, double *state /*P,4*/, double *applied /*P,2*/, double *u_sol /*P,2,T*/,
+                                       int32_t *traj_idx /*P*/, int32_t *target_ind /*P*/, int32_t *cut_len /*P*/, int32_t *iters /*P*/,
+                                       int32_t *prev_len /*P or NULL*/, const int32_t *obs_skip /*P*/, int32_t n_obs_pool,
+                                       const mpcx_run_log *log /*or NULL*/, const mpcx_retire *retire, const mpcx_admit *admit,
+                                       const mpcx_respawn *respawn, const mpcx_routes *routes /*or NULL*/, int32_t max_path_len);
+/* the per-movement table of a routed run, reduced on the device: per instance b (A consecutive slots of the P = B A) and route r, over the
+ * FINISHED episodes (g < served[q]) whose word 7 is r,
+ *   out_i64[b][r][0..3] = the number of episodes, the number with a contact (contact_step >= 0), the sum of entered - due, the sum of
+ *                         steps_driven
+ *   out_f64[b][r]       = the minimum of min_clearance (+inf if there are none; a NaN is skipped)
+ * Integer sums and a minimum only: the table is exact whatever the mapping of records to lanes.  One wavefront per instance (csrc/
+ * mpcx_route.hip, summary_kernel).  Episodes whose word 7 lies outside [0, R) are in no row.  All pointers are device pointers; enqueued on
+ * the context's stream.  MPCX_E_INVALID: a negative size, A < 1 with P > 0, P not a multiple of A, G < 1, R < 1, a NULL pointer. */
+int32_t mpcx_episode_summary(mpcx_ctx *ctx, int32_t P, int32_t A, int32_t G, int32_t R, const int32_t *served /*P*/,
+                             const int32_t *ep_i32 /*P,G,8*/, const double *ep_f64 /*P,G,2*/, int64_t *out_i64 /*B,R,4*/,
+                             double *out_f64 /*B,R*/);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

@@ -79,9 +79,20 @@ class RespawnC(C.Structure):
                 ('served', C.c_void_p), ('ep_i32', C.c_void_p), ('ep_f64', C.c_void_p)]
 
 
-# the words of an episode record (ep_i32[q][g][0..6], one reserved; ep_f64[q][g][0], one reserved)
+class RoutesC(C.Structure):
+    """mirror of mpcx_routes (include/mpcx.h): a route per vehicle; route_off, route_len (R), route_of (P,G), start_state (P,G,4 float64),
+    start_idx (P,G) and the descriptor's own path_off, path_len (P) are device addresses"""
+    _fields_ = [('n_routes', C.c_int32), ('reserved', C.c_int32), ('route_off', C.c_void_p), ('route_len', C.c_void_p), ('route_of', C.c_void_p),
+                ('start_state', C.c_void_p), ('start_idx', C.c_void_p), ('path_off', C.c_void_p), ('path_len', C.c_void_p)]
+
+
+# the words of an episode record (ep_i32[q][g][0..6]; word 7 is 0, with routes the episode's route: EPISODE_ROUTE_WORD; ep_f64[q][g][0], one
+# reserved)
 EPISODE_I32 = ('entered', 'arrived', 'steps_driven', 'row_end', 'contact_step', 'flags', 'due')
 EPISODE_F64 = ('min_clearance',)
+EPISODE_ROUTE_WORD = 7
+# the columns of mpcx_episode_summary's integer table (out_i64[b][r][0..3]); out_f64[b][r] is the minimum of min_clearance
+SUMMARY_I64 = ('count', 'contacts', 'delay_sum', 'steps_driven_sum')
 
 
 STOP_CUT, STOP_SPEED = 0, 1     # mpcx_closed_loop_opts.stop_mode
@@ -144,7 +155,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
            'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
            'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
-           'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch']
+           'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
+           'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary']
 
 
 def load():
@@ -233,5 +245,14 @@ def load():
     lib.mpcx_respawn_step_batch.restype = i32
     lib.mpcx_respawn_step_batch.argtypes = [vp, i32] + [vp] * 9 + [i32, C.POINTER(RunLogC), C.POINTER(RetireC), C.POINTER(AdmitC),
                                                                    C.POINTER(RespawnC)]
+    lib.mpcx_closed_loop_run_routes.restype = i32
+    lib.mpcx_closed_loop_run_routes.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                C.POINTER(RespawnC), C.POINTER(RoutesC), i32, i32]
+    lib.mpcx_respawn_step_batch_routes.restype = i32
+    lib.mpcx_respawn_step_batch_routes.argtypes = [vp, i32] + [vp] * 9 + [i32, C.POINTER(RunLogC), C.POINTER(RetireC), C.POINTER(AdmitC),
+                                                                          C.POINTER(RespawnC), C.POINTER(RoutesC), i32]
+    lib.mpcx_episode_summary.restype = i32
+    lib.mpcx_episode_summary.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     _lib = lib
     return lib

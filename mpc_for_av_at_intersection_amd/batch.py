@@ -24,6 +24,9 @@ seeded arrival times per approach queue).
 `respawn_on_schedule(due, gap)` is RESPAWN, which makes the three an open intersection: every slot serves a stream of vehicles -- when one
 arrives its episode is recorded (episodes()), the slot is reset to a fresh start and the next vehicle goes through the gate at its due step
 (demand_schedule() draws seeded arrival streams per approach queue).
+`respawn_on_schedule(due, gap, route=...)` gives every vehicle of a slot its OWN ROUTE (and start index): the reset also writes the slot's
+`path_off` / `path_len`, so turning proportions vary per vehicle with no host work between steps (turning_demand() draws seeded routes per
+approach arm; episode_routes() and movement_summary() read the run per movement, the latter reduced on the device).
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -40,6 +43,7 @@ RUN_LOG_DTYPE = np.dtype([(n, '<f8') for n in _lib.RUN_LOG_F64] + [(n, '<i4') fo
 RUN_LOG_MAX_BYTES = 1 << 30     # attach_log refuses a larger log unless told otherwise
 EPISODE_DTYPE = np.dtype([(n, '<i4') for n in ('slot', 'generation', 'due', 'entered', 'arrived', 'steps_driven', 'delay')] + [('contact', '?'),
                          ('min_clearance', '<f8'), ('row_begin', '<i4'), ('row_end', '<i4')])
+MOVEMENT_DTYPE = np.dtype([(n, '<i8') for n in _lib.SUMMARY_I64] + [('min_clearance', '<f8')])
 
 
 class RunLog:
@@ -214,6 +218,7 @@ class IntersectionBatch:
         offs = np.cumsum([0] + [len(r) for r in routes])
         table = np.concatenate(routes, axis=0).astype(np.float64)
         self.path = ctx.f64(table)
+        self._route_offs, self._route_table = offs.astype(np.int64), table      # host copies: respawn_on_schedule(route=...) looks poses up
         self.path_cs = ctx.f64(np.column_stack([np.cos(table[:, 2]), np.sin(table[:, 2])]))
         # paths are constants of the run: their arc lengths are summed once here instead of by every agent in every step (the conflict
         # search takes its resampling buckets from this table wherever that is safe, mpcx_interaction_params.path_cum)
@@ -323,6 +328,12 @@ class IntersectionBatch:
         self.start_state: Optional[torch.Tensor] = None      # ... float64 (P, 4) and int32 (P,): what a reset puts a slot back to
         self.start_idx: Optional[torch.Tensor] = None
         self._respawn = None
+        self.route_of: Optional[torch.Tensor] = None         # respawn_on_schedule(route=...): int32 (P, G), the route of vehicle g of slot q
+        self.route_start_state: Optional[torch.Tensor] = None    # ... float64 (P, G, 4) and int32 (P, G): every vehicle's start pose and index
+        self.route_start_idx: Optional[torch.Tensor] = None
+        self.route_off: Optional[torch.Tensor] = None        # ... int32 (R,) each: the routes' runs in the path tables
+        self.route_len: Optional[torch.Tensor] = None
+        self._routes = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -403,6 +414,7 @@ class IntersectionBatch:
         self.absent, self._scene = None, None
         self._admit = None                  # (admission lives on a scene: enter_on_schedule() after this call)
         self._respawn = None                # (... and respawn on admission)
+        self._routes = None
         if leave_scene:
             rows = int(self.obs6.shape[0])
             self.absent = torch.zeros(rows, dtype=torch.int32, device=self.ctx.device)
@@ -422,6 +434,7 @@ class IntersectionBatch:
         self._scene = None
         self._admit = None
         self._respawn = None
+        self._routes = None
         self._desc = None
 
     def enter_on_schedule(self, wait, gap: float = 0.0):
@@ -456,18 +469,20 @@ class IntersectionBatch:
         self.scheduled_step = np.maximum(w, 0)
         self._admit = _lib.AdmitC(self.wait.data_ptr(), self.entered_step.data_ptr(), self.clock.data_ptr(), 0, gap)
         self._respawn = None                # (a new schedule and a new clock: respawn_on_schedule() sets both up itself)
+        self._routes = None
         self._desc = None
         self.ctx.synchronize()
 
     def enter_now(self):
         """switch admission off and nothing else: the batch enqueues exactly the launches of one that never had it.  Agents still waiting
         stay outside the scene (retired, their rows absent); `wait`, `entered_step` and `clock` keep what they hold.  Respawn lives on admission
-        and is switched off with it"""
+        and is switched off with it, and routing with respawn"""
         self._admit = None
         self._respawn = None
+        self._routes = None
         self._desc = None
 
-    def respawn_on_schedule(self, due, gap: float = 0.0):
+    def respawn_on_schedule(self, due, gap: float = 0.0, route=None, start_index=None):
         """RESPAWN (mpcx_closed_loop_run_respawn): every slot (agent index q) serves a stream of G vehicles, all on the slot's route from the
         slot's start pose -- `state` and `traj_idx` of the batch as it stands.  due[q][g] is the step (counted from this call) at which vehicle
         g of slot q asks to enter.  When a slot's vehicle arrives, the last launch of that step writes the finished episode into the episode
@@ -479,7 +494,16 @@ class IntersectionBatch:
         be present together at step 0 (in cut mode both cars would stand inside each other and yield for ever).  Allocates `served` and the
         episode table, and drops the cached descriptor.  With a run log attached a slot's rows are its vehicles' rows one after the other:
         size the log for the sum.  stop_respawning() switches respawn off alone; enter_now() and keep_driving() switch it off with what it
-        lives on."""
+        lives on.
+        route: ROUTES (mpcx_closed_loop_run_routes) -- an integer array of due's shape, (B, A, G) or (P, G), indexing the batch's `routes`:
+        vehicle g of slot q drives route[q][g], and the reset that hands the slot to the gate also writes the slot's `path_off` / `path_len`
+        (same number of launches as respawn alone; nothing in the hot kernels changes).  start_index: same shape, the path index every vehicle
+        starts from; default the slot's current `traj_idx`, which must lie inside every route the slot takes (else ValueError).  A vehicle's
+        start pose is the route point at its start index and its start speed the slot's current one; `pose_offset` is NOT re-applied: every
+        routed vehicle, the first included, starts exactly on its route.  Everything is validated in numpy before anything is uploaded or
+        changed; vehicle 0's route, pose and index are written into `path_off`, `path_len`, `state`, `traj_idx` and `target_ind` here, before
+        the first vehicle goes through the gate.  The finished episodes then carry their route (episode_routes(), movement_summary()).
+        route=None: exactly the batch described above -- a slot keeps its route and start pose."""
         if self._scene is None:
             raise MpcxError('respawn_on_schedule: respawn needs admission, which needs a scene (MPCX_E_INVALID): retire_at_goal(leave_scene=True) first')
         d = np.asarray(due)
@@ -489,6 +513,18 @@ class IntersectionBatch:
         if (d < 0).any() or (d > np.iinfo(np.int32).max).any():
             raise ValueError('respawn_on_schedule: due holds step indices >= 0')
         G = int(d.shape[1])
+        routed = None
+        if route is None:
+            if start_index is not None:
+                raise ValueError('respawn_on_schedule: start_index is the start index per vehicle of a routed run: pass route too')
+        else:
+            routed = self._routed_tables(route, start_index, np.asarray(due).shape, G)
+            self.ctx.synchronize()
+            r0, s0 = routed['route'][:, 0], routed['start_idx'][:, 0]
+            self.path_off.copy_(self.ctx.i32(self._route_offs[r0]))             # (in place: the descriptor and the routes struct name these words)
+            self.path_len.copy_(self.ctx.i32(np.diff(self._route_offs)[r0]))
+            self.state.copy_(self.ctx.f64(routed['start_state'][:, 0]))
+            self.traj_idx.copy_(self.ctx.i32(s0)); self.target_ind.copy_(self.ctx.i32(s0))
         self.enter_on_schedule(d[:, 0], gap)
         dev = self.ctx.device
         self.start_state, self.start_idx = self.state.clone(), self.traj_idx.clone()
@@ -498,13 +534,53 @@ class IntersectionBatch:
         self.ep_f64 = torch.zeros((self.P, G, 2), dtype=torch.float64, device=dev)
         self._respawn = _lib.RespawnC(G, 0, self.start_state.data_ptr(), self.start_idx.data_ptr(), self.due.data_ptr(), self.served.data_ptr(),
                                       self.ep_i32.data_ptr(), self.ep_f64.data_ptr())
+        self.route_of = self.route_start_state = self.route_start_idx = self.route_off = self.route_len = None
+        if routed is not None:
+            self.route_of, self.route_start_idx = self.ctx.i32(routed['route']), self.ctx.i32(routed['start_idx'])
+            self.route_start_state = self.ctx.f64(routed['start_state'])
+            self.route_off, self.route_len = self.ctx.i32(self._route_offs[:-1]), self.ctx.i32(np.diff(self._route_offs))
+            self._routes = _lib.RoutesC(len(self._route_offs) - 1, 0, self.route_off.data_ptr(), self.route_len.data_ptr(), self.route_of.data_ptr(),
+                                        self.route_start_state.data_ptr(), self.route_start_idx.data_ptr(), self.path_off.data_ptr(),
+                                        self.path_len.data_ptr())
         self._desc = None
         self.ctx.synchronize()
 
+    def _routed_tables(self, route, start_index, due_shape, G: int) -> dict:
+        """respawn_on_schedule(route=...): the per-vehicle tables on the host -- route (P, G), start_idx (P, G), start_state (P, G, 4) --,
+        everything checked in numpy (ValueError); nothing is uploaded or changed"""
+        offs, lens = self._route_offs, np.diff(self._route_offs)
+        R = len(lens)
+        r = np.asarray(route)
+        if not np.issubdtype(r.dtype, np.integer) or r.shape != tuple(due_shape):
+            raise ValueError('respawn_on_schedule: route must be an integer array of due\'s shape %s, got %s' % (tuple(due_shape), r.shape))
+        r = r.reshape(self.P, G).astype(np.int64)
+        if (r < 0).any() or (r >= R).any():
+            raise ValueError('respawn_on_schedule: route indexes the batch\'s %d routes' % R)
+        if start_index is None:
+            s = np.repeat(self.traj_idx.cpu().numpy().astype(np.int64)[:, None], G, axis=1)
+        else:
+            s = np.asarray(start_index)
+            if not np.issubdtype(s.dtype, np.integer) or s.shape != tuple(due_shape):
+                raise ValueError('respawn_on_schedule: start_index must be an integer array of due\'s shape %s, got %s' % (tuple(due_shape), s.shape))
+            s = s.reshape(self.P, G).astype(np.int64)
+        bad = (s < 0) | (s >= lens[r])
+        if bad.any():
+            q, g = (int(v[0]) for v in np.nonzero(bad))
+            raise ValueError('respawn_on_schedule: vehicle %d of slot %d starts at index %d of route %d, which has %d points%s'
+                             % (g, q, s[q, g], r[q, g], lens[r[q, g]], '' if start_index is not None else
+                                ' (the default start index is the slot\'s current traj_idx: it must lie inside every route the slot takes)'))
+        pts = self._route_table[offs[r] + s]
+        st = np.zeros((self.P, G, 4))
+        st[..., 0], st[..., 1], st[..., 3] = pts[..., 0], pts[..., 1], pts[..., 2]
+        st[..., 2] = self.state.cpu().numpy()[:, 2][:, None]
+        return dict(route=r, start_idx=s, start_state=st)
+
     def stop_respawning(self):
         """switch respawn off and nothing else: the batch enqueues exactly the launches of one with admission alone.  Vehicles in flight
-        finish (and stay departed), waiting ones still enter; `served` and the episode table keep what they hold"""
+        finish (and stay departed), waiting ones still enter; `served` and the episode table keep what they hold.  Routing goes with it: a
+        slot keeps the route its last reset gave it"""
         self._respawn = None
+        self._routes = None
         self._desc = None
 
     def served_count(self) -> int:
@@ -532,6 +608,33 @@ class IntersectionBatch:
         out['contact'] = rec['contact_step'] >= 0
         out['min_clearance'] = f[q, g, 0]
         out['row_begin'] = np.where(rec['row_end'] >= 0, rec['row_end'] - rec['steps_driven'], -1)
+        return out
+
+    def episode_routes(self) -> np.ndarray:
+        """the route of every finished episode, aligned with the rows of episodes() (int32; synchronises): word 7 of the episode record,
+        which a routed run writes (without routes it is 0 for every episode)"""
+        if self.served is None:
+            raise MpcxError('episode_routes(): respawn_on_schedule() has not been called')
+        self.ctx.synchronize()
+        served, w = self.served.cpu().numpy(), self.ep_i32.cpu().numpy()
+        q, g = np.nonzero(np.arange(w.shape[1])[None, :] < served[:, None])
+        return w[q, g, _lib.EPISODE_ROUTE_WORD].astype(np.int32)
+
+    def movement_summary(self) -> np.ndarray:
+        """the per-movement table of a routed run, reduced on the device (mpcx_episode_summary; one small launch, (B, R) records back instead
+        of the P G records of the episode table; synchronises): a structured array (B, R) of MOVEMENT_DTYPE -- per instance and route, over
+        the finished episodes on that route: count, contacts (episodes with a contact), delay_sum (sum of entered - due), steps_driven_sum,
+        and min_clearance (the minimum over them; +inf if there are none or without a run log)"""
+        if self.route_of is None:
+            raise MpcxError('movement_summary(): respawn_on_schedule(route=...) has not been called')
+        R = len(self._route_offs) - 1
+        out_i, out_f = self.ctx.episode_summary(self.A, R, self.served, self.ep_i32, self.ep_f64)
+        self.ctx.synchronize()
+        out = np.zeros((self.B, R), MOVEMENT_DTYPE)
+        wi = out_i.cpu().numpy()
+        for k, n in enumerate(_lib.SUMMARY_I64):
+            out[n] = wi[..., k]
+        out['min_clearance'] = out_f.cpu().numpy()
         return out
 
     def waiting_count(self) -> int:
@@ -616,7 +719,7 @@ class IntersectionBatch:
             self._desc = self._descriptor()
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
-                                 retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn)
+                                 retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes)
         self.steps_done += n_steps
 
     def step(self):
@@ -701,6 +804,8 @@ class IntersectionBatch:
             out['wait'], out['entered_step'] = self.wait.cpu().numpy().copy(), self.entered_step.cpu().numpy().copy()
         if self._respawn is not None:
             out['served'] = self.served.cpu().numpy().copy()
+        if self._routes is not None:         # the route every slot is on now: the run of the path tables its path_off names
+            out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         return out
 
     def stop_index(self) -> np.ndarray:
@@ -768,6 +873,47 @@ def demand_schedule(route_of_agent, routes, start_index, mean_headway_steps: flo
             stream = np.cumsum(rng.geometric(1.0 / mean_headway_steps, size=len(queue) * G) - 1)
             due[b, queue, :] = stream.reshape(G, len(queue)).T
     return due
+
+
+def turning_demand(route_of_agent, routes, start_index, share, generations: int, seed: int) -> np.ndarray:
+    """Seeded turning movements for IntersectionBatch.respawn_on_schedule(route=...): a (B, A, G) integer `route` array.  The CANDIDATE routes
+    of slot (b, a) are those whose point at the slot's start index equals the slot's start pose -- the point of its own route
+    route_of_agent[b, a] at start_index[b, a] -- bit for bit in x, y and yaw: the routes of its approach arm, in route order.  Every vehicle
+    of the slot draws one of them with probability share[r] / (sum of share over the candidates).  A slot with a single candidate makes no
+    draw; the others draw their G vehicles at once, rng.choice(n candidates, size=G, p=...), rng = numpy.random.default_rng(seed), instance-
+    major then slot-major.  share: one weight >= 0 per route; the candidates of a drawing slot must not all have weight 0.  Pure numpy and
+    deterministic: no GPU, no state."""
+    route_of_agent, start_index = np.asarray(route_of_agent, dtype=np.int64), np.asarray(start_index, dtype=np.int64)
+    if route_of_agent.ndim != 2 or route_of_agent.shape != start_index.shape:
+        raise ValueError('turning_demand: route_of_agent and start_index must both have shape (B, A)')
+    R = len(routes)
+    share = np.asarray(share, dtype=np.float64)
+    if share.shape != (R,) or not np.isfinite(share).all() or (share < 0).any():
+        raise ValueError('turning_demand: share holds one finite weight >= 0 per route (%d)' % R)
+    G = int(generations)
+    if G < 1:
+        raise ValueError('turning_demand: generations must be >= 1')
+    if R == 0 or (route_of_agent < 0).any() or (route_of_agent >= R).any():
+        raise ValueError('turning_demand: route_of_agent indexes the %d routes' % R)
+    routes = [np.asarray(r, dtype=np.float64) for r in routes]
+    rng = np.random.default_rng(seed)
+    B, A = route_of_agent.shape
+    out = np.zeros((B, A, G), dtype=np.int64)
+    for b in range(B):
+        for a in range(A):
+            own, s = int(route_of_agent[b, a]), int(start_index[b, a])
+            if not 0 <= s < len(routes[own]):
+                raise ValueError('turning_demand: slot (%d, %d) starts at index %d of route %d, which has %d points' % (b, a, s, own, len(routes[own])))
+            pose = routes[own][s, :3].tobytes()
+            cand = [k for k in range(R) if s < len(routes[k]) and routes[k][s, :3].tobytes() == pose]
+            if len(cand) == 1:
+                out[b, a, :] = cand[0]
+                continue
+            w = share[cand]
+            if not w.sum() > 0:
+                raise ValueError('turning_demand: the candidate routes %s of slot (%d, %d) all have share 0' % (cand, b, a))
+            out[b, a, :] = np.asarray(cand)[rng.choice(len(cand), size=G, p=w / w.sum())]
+    return out
 
 
 def stock_routes(ctx: Context, pairs=((1, 1), (1, 2), (2, 1), (2, 2), (3, 1), (3, 2), (4, 1), (4, 2))):

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1016] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + parameters the cached graph was captured for
+    unsigned char loop_key[1080] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + routes + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -160,6 +160,15 @@ int32_t mpcx_respawn_enqueue(mpcx_ctx *ctx, int32_t P, double *state, double *ap
                              int32_t *cut_len, int32_t *iters, int32_t *prev_len /*or nullptr*/, const int32_t *obs_skip, int32_t n_obs_pool,
                              const mpcx_run_log *log /*or nullptr*/, const mpcx_retire *retire, const mpcx_admit *admit,
                              const mpcx_respawn *respawn);
+// routes (mpcx_route.hip): "no routes" test, check of the struct against the run (reads the R-word tables back), the launch alone -- which
+// takes the place of mpcx_respawn_enqueue
+bool mpcx_routes_absent(const mpcx_routes *s);
+int32_t mpcx_routes_validate(mpcx_ctx *ctx, const mpcx_routes *s, const mpcx_respawn *respawn, const int32_t *path_off, const int32_t *path_len,
+                             int32_t max_len /*0: no upper bound*/);
+int32_t mpcx_route_enqueue(mpcx_ctx *ctx, int32_t P, double *state, double *applied, double *u_sol, int32_t *traj_idx, int32_t *target_ind,
+                           int32_t *cut_len, int32_t *iters, int32_t *prev_len /*or nullptr*/, const int32_t *obs_skip, int32_t n_obs_pool,
+                           const mpcx_run_log *log /*or nullptr*/, const mpcx_retire *retire, const mpcx_admit *admit,
+                           const mpcx_respawn *respawn, const mpcx_routes *routes);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

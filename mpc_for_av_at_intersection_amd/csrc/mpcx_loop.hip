@@ -69,9 +69,12 @@ static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cu
 // rs: respawn or nullptr = none (then exactly the launches of a step with admission, with the same arguments).  With it the step ENDS with
 // respawn_kernel, after retire_kernel: an agent that has arrived leaves an episode record and, while its slot has vehicles left, is reset to
 // the first step of a fresh batch and waits for the gate (wait >= 0).  The next step's rollout is forked after this launch in stream order.
+// rt: routes or nullptr = none (then exactly the launches of a step with respawn, with the same arguments).  With them respawn_route_kernel
+// takes respawn_kernel's place -- the same number of launches --: the reset also writes the next vehicle's route into c->path_off / c->path_len
+// and its own start pose and index, which every stage of the next step reads afresh.
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                             const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc, const mpcx_admit *ad,
-                            const mpcx_respawn *rs) {
+                            const mpcx_respawn *rs, const mpcx_routes *rt) {
     const int P = c->P;
     const int32_t *done = r ? r->done : nullptr;
     int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
@@ -157,7 +160,10 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (r) rc = mpcx_retire_enqueue(ctx, P, c->state, c->applied, c->path_xyyaw, c->path_off, c->path_len, c->target_ind,
                                     speed ? c->path_len : c->cut_len, r, sc, c->obs_skip);
     if (rc != MPCX_OK) return rc;
-    if (rs)         // (validated: admission, and with it a scene and retirement)
+    if (rs && rt)   // (validated: respawn, and the descriptor's own path_off / path_len)
+        rc = mpcx_route_enqueue(ctx, P, c->state, c->applied, c->u_sol, c->traj_idx, c->target_ind, c->cut_len, c->iters,
+                                speed ? o->prev_len : nullptr, c->obs_skip, sc->n_rows, log, r, ad, rs, rt);
+    else if (rs)    // (validated: admission, and with it a scene and retirement)
         rc = mpcx_respawn_enqueue(ctx, P, c->state, c->applied, c->u_sol, c->traj_idx, c->target_ind, c->cut_len, c->iters,
                                   speed ? o->prev_len : nullptr, c->obs_skip, sc->n_rows, log, r, ad, rs);
     return rc;
@@ -165,7 +171,7 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
 
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                                const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, const mpcx_admit *admit,
-                               const mpcx_respawn *respawn, int32_t n_steps, int32_t use_graph) {
+                               const mpcx_respawn *respawn, const mpcx_routes *routes, int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
@@ -205,6 +211,15 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (respawn) {      // refused before anything is launched, whatever n_steps is
         const int32_t prc = mpcx_respawn_validate(ctx, respawn, admit);
         if (prc != MPCX_OK) return prc;
+    }
+    if (mpcx_routes_absent(routes)) routes = nullptr;
+    if (routes) {       // refused before anything is launched, whatever n_steps is
+        // the longest route the conflict search handles: max_path_len as mpcx_interaction_enqueue rounds it
+        int32_t cap = ip->max_path_len > 0 ? ip->max_path_len : MPCX_MAX_REMAINING;
+        if (cap < 512) cap = 512;
+        cap = (cap + 63) / 64 * 64;
+        const int32_t trc = mpcx_routes_validate(ctx, routes, respawn, c->path_off, c->path_len, cap);
+        if (trc != MPCX_OK) return trc;
     }
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
@@ -276,7 +291,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn);
+            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -286,7 +301,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_interaction_params) +
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_routes) + sizeof(mpcx_interaction_params) +
                   sizeof(mpcx_mpc_params) + 10 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
@@ -303,6 +318,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     o += sizeof *admit;
     if (respawn) memcpy(key + o, respawn, sizeof *respawn);  // (zeros = no respawn: a graph captured without its launch)
     o += sizeof *respawn;
+    if (routes) memcpy(key + o, routes, sizeof *routes);     // (zeros = no routes: a graph captured with respawn_kernel)
+    o += sizeof *routes;
     memcpy(key + o, &ctx->admit_tab, sizeof ctx->admit_tab); o += sizeof ctx->admit_tab;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
@@ -323,7 +340,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn);
+        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -340,40 +357,47 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_admit(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, const mpcx_admit *admit, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_respawn(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                 const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                 const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                 int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, n_steps, use_graph);
+    return mpcx_closed_loop_run_routes(ctx, ip, c, log, opts, retire, scene, admit, respawn, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_routes(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                               const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
+                                               const mpcx_routes *routes, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, n_steps, use_graph);
 }

@@ -615,7 +615,8 @@ class Context:
     def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
                         log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None,
                         retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None,
-                        admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None):
+                        admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None,
+                        routes: Optional['_lib.RoutesC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
@@ -625,9 +626,17 @@ class Context:
         admit: a _lib.AdmitC -- admission: waiting agents enter on their schedule once their start pose is clear (mpcx_closed_loop_run_admit;
         refused without scene); None = everybody is in from the start.
         respawn: a _lib.RespawnC -- respawn: an arrived agent's slot is reset for the next vehicle of its stream and handed back to the
-        admission gate (mpcx_closed_loop_run_respawn; refused without admit); None = a departed slot stays empty."""
+        admission gate (mpcx_closed_loop_run_respawn; refused without admit); None = a departed slot stays empty.
+        routes: a _lib.RoutesC -- every vehicle of a slot takes its own route from its own start pose (mpcx_closed_loop_run_routes; refused
+        without respawn); None = a slot keeps its route."""
         cip = ip.to_c()
-        if respawn is not None:
+        if routes is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_routes(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
+                                                           None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
+                                                           None if scene is None else C.byref(scene), None if admit is None else C.byref(admit),
+                                                           None if respawn is None else C.byref(respawn), C.byref(routes), int(n_steps),
+                                                           1 if graph else 0))
+        elif respawn is not None:
             self._chk(self.lib.mpcx_closed_loop_run_respawn(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
                                                             None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
                                                             None if scene is None else C.byref(scene), None if admit is None else C.byref(admit),
@@ -681,12 +690,15 @@ class Context:
 
     @_ordered
     def respawn_step(self, state, applied, u_sol, traj_idx, target_ind, cut_len, iters, obs_skip, n_obs_pool: int, retire: '_lib.RetireC',
-                     admit: '_lib.AdmitC', respawn: '_lib.RespawnC', prev_len=None, log: Optional['_lib.RunLogC'] = None):
+                     admit: '_lib.AdmitC', respawn: '_lib.RespawnC', prev_len=None, log: Optional['_lib.RunLogC'] = None,
+                     routes: Optional['_lib.RoutesC'] = None, max_path_len: int = 0):
         """mpcx_respawn_step_batch: ONE step's respawn as the closed loop enqueues it at the end of a step (after the retire stage).  The
         buffers are the closed loop's, updated in place: state (P, 4), applied (P, 2), u_sol (P, 2, T), int32 traj_idx, target_ind, cut_len,
         iters (P each), prev_len (P; the speed stop mode only); obs_skip names the agents' own rows among the n_obs_pool rows of the pool.
         retire / admit / respawn / log: structs naming caller-owned device buffers (done is read, steps_driven, wait, entered_step, served,
-        the episode table and the log's outcome words are written)."""
+        the episode table and the log's outcome words are written).
+        routes: a _lib.RoutesC -- mpcx_respawn_step_batch_routes: the reset also writes the next vehicle's route (routes.path_off / path_len,
+        P int32 each), start pose and index; max_path_len bounds the route lengths (0: no upper bound)."""
         Pn = int(state.shape[0])
         self._want(state, torch.float64, (Pn, 4), 'state'); self._want(applied, torch.float64, (Pn, 2), 'applied')
         self._want(u_sol, torch.float64, (Pn, 2, self.params.T), 'u_sol')
@@ -694,9 +706,31 @@ class Context:
             self._want(t, torch.int32, (Pn,), nm)
         if prev_len is not None:
             self._want(prev_len, torch.int32, (Pn,), 'prev_len')
+        if routes is not None:
+            self._chk(self.lib.mpcx_respawn_step_batch_routes(self._ctx, Pn, _ptr(state), _ptr(applied), _ptr(u_sol), _ptr(traj_idx),
+                                                              _ptr(target_ind), _ptr(cut_len), _ptr(iters), _ptr(prev_len), _ptr(obs_skip),
+                                                              int(n_obs_pool), None if log is None else C.byref(log), C.byref(retire),
+                                                              C.byref(admit), C.byref(respawn), C.byref(routes), int(max_path_len)))
+            return
         self._chk(self.lib.mpcx_respawn_step_batch(self._ctx, Pn, _ptr(state), _ptr(applied), _ptr(u_sol), _ptr(traj_idx), _ptr(target_ind),
                                                    _ptr(cut_len), _ptr(iters), _ptr(prev_len), _ptr(obs_skip), int(n_obs_pool),
                                                    None if log is None else C.byref(log), C.byref(retire), C.byref(admit), C.byref(respawn)))
+
+    @_ordered
+    def episode_summary(self, A: int, R: int, served, ep_i32, ep_f64):
+        """mpcx_episode_summary: the per-instance, per-route table of the finished episodes of a routed run, reduced on the device.
+        served (P,), ep_i32 (P, G, 8) int32, ep_f64 (P, G, 2) float64, P = B A.  Returns device tensors (B, R, 4) int64 -- _lib.SUMMARY_I64:
+        count, contacts, sum of entered - due, sum of steps_driven -- and (B, R) float64, the minimum of min_clearance (+inf: none)."""
+        Pn, G = int(ep_i32.shape[0]), int(ep_i32.shape[1])
+        self._want(served, torch.int32, (Pn,), 'served'); self._want(ep_i32, torch.int32, (Pn, G, 8), 'ep_i32')
+        self._want(ep_f64, torch.float64, (Pn, G, 2), 'ep_f64')
+        if A < 1 or Pn % int(A):
+            raise MpcxError('episode_summary: %d slots do not divide into instances of %d (MPCX_E_INVALID)' % (Pn, A))
+        B = Pn // int(A)
+        out_i = torch.zeros((B, int(R), 4), dtype=torch.int64, device=self.device)
+        out_f = torch.full((B, int(R)), float('inf'), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.mpcx_episode_summary(self._ctx, Pn, int(A), G, int(R), _ptr(served), _ptr(ep_i32), _ptr(ep_f64), _ptr(out_i), _ptr(out_f)))
+        return out_i, out_f
 
     @_ordered
     def record_step(self, ip: InteractionParams, state, applied, x_sol, path, path_off, path_len, target_ind, cut_len, traj_idx, hit_idx,
