@@ -19,7 +19,8 @@
  *   - the end of an agent's episode (the loop's `if mpc.is_goal(state): break`) is retirement at the goal: mpcx_retire,
  *     mpcx_closed_loop_run_retire; taking the arrived car out of everybody else's scene as well is departure: mpcx_scene,
  *     mpcx_closed_loop_run_scene; letting vehicles in on a schedule is admission: mpcx_admit, mpcx_closed_loop_run_admit; re-using a
- *     departed agent's slot for the next vehicle is respawn: mpcx_respawn, mpcx_closed_loop_run_respawn.  A route per vehicle of such a slot is mpcx_routes,
+ *     departed agent's slot for the next vehicle is respawn: mpcx_respawn, mpcx_closed_loop_run_respawn.  Who yields to whom at the crossing is
+ *     right of way: mpcx_precedence, mpcx_closed_loop_run_precedence.  A route per vehicle of such a slot is mpcx_routes,
  *     mpcx_closed_loop_run_routes; mpcx_episode_summary reduces the episode table per instance and route.
  */
 #ifndef MPCX_H
@@ -681,6 +682,57 @@ int32_t mpcx_respawn_step_batch_routes(mpcx_ctx *ctx, int32_t P, double *state /
 int32_t mpcx_episode_summary(mpcx_ctx *ctx, int32_t P, int32_t A, int32_t G, int32_t R, const int32_t *served /*P*/,
                              const int32_t *ep_i32 /*P,G,8*/, const double *ep_f64 /*P,G,2*/, int64_t *out_i64 /*B,R,4*/,
                              double *out_f64 /*B,R*/);
+
+/* ---- right of way: who yields to whom.  The reference's other cars are scripted and never yield, and its ego yields to all of them; in a loop
+ * of many egos that rule makes everybody yield to everybody, and cars that meet at the crossing wait for each other for ever.  Precedence is
+ * an opt-in rule beside mpcx_scene that breaks the mutual wait.  One int32 word per pool row, prec[n_rows], caller-owned DEVICE memory; a
+ * SMALLER word goes first.  For a driving agent q with own row o = obs_skip[q] and a present row r != o of its window:
+ *   prec[r] <= prec[o]   q sees r as it does without precedence, through its prediction (equal words: the reference's mutual yield);
+ *   prec[r] >  prec[o]   r yields to q, and q sees r STANDING: every frame of r's prediction is the two disc centres of r's current pose.
+ * Absent rows stay invisible.  A scripted actor's row keeps the word the caller gave it: zero means everybody (whose word is >= 0) sees it
+ * moving.  The defining property: for every driving agent a step with precedence equals a step of the scene loop in which every yielding
+ * row (x, y, v, yaw, a, steer) of its obstacle list is replaced by (x, y, 0, yaw, 0, 0), relative order kept -- the rollout of such a row
+ * reproduces its pose exactly, so this holds bit for bit.  A yielding car is thus still an obstacle where it stands (a car with precedence
+ * does not drive into one that is already in its way); what it no longer does is claim the road ahead of it.  With all words equal the run
+ * is the scene run bit for bit.  The run log's clearance and contact (true clearance), the admission gate, retirement, respawn and routes
+ * do not change.
+ * stand[n_rows][4] is caller-owned device scratch: predict_kernel's STAND instantiation stores every predicted row's standing record there,
+ * and interaction_kernel's PREC instantiation loads a yielding row's candidates from it instead of from the prediction.
+ * mode:
+ *   MPCX_PRECEDENCE_FIXED   the loop never writes prec: the caller's words hold.
+ *   MPCX_PRECEDENCE_ENTRY   first come, first served; needs admission.  Right after a step's admission stage one more launch
+ *                           (precedence_stamp_kernel, csrc/mpcx_precedence.hip; the rule is csrc/mpcx_precedence_core.h) writes, for every
+ *                           agent with entered_step[q] >= 0, prec[obs_skip[q]] = entered_step[q] * 64 + (obs_skip[q] - obs_off[q]): ties
+ *                           go to the lower window offset (a scene window holds at most 64 rows).  The words of waiting agents and of
+ *                           other rows are not touched; a respawned vehicle gets its word in the step that admits it and so queues behind
+ *                           everybody already in the scene.  entered_step * 64 wraps from step 2^25 on: the caller's limit.
+ * The struct travels beside the descriptor (no other struct changes size); the cached graph's key covers it by value.  precedence = NULL
+ * or an all-zero struct: mpcx_closed_loop_run_routes itself -- the same launches with the same arguments.  MPCX_E_INVALID
+ * ("precedence: ...") before anything is launched, whatever n_steps is: an unknown mode; precedence without a scene (which in turn needs
+ * retirement and refuses MPCX_SHARD_AGENTS and more than one linearisation pass); prec or stand NULL; n_rows that is not the pool's row
+ * count; MPCX_PRECEDENCE_ENTRY without admission.  Works with scripted traffic, the run log, both stop modes and use_graph. */
+enum { MPCX_PRECEDENCE_FIXED = 1, MPCX_PRECEDENCE_ENTRY = 2 };
+typedef struct {
+    int32_t *prec;       /* n_rows, caller-owned: the precedence word of every pool row, a smaller word goes first */
+    double *stand;       /* n_rows x 4, caller-owned scratch: the standing records */
+    int32_t n_rows;      /* rows of the pool: mpcx_scene::n_rows */
+    int32_t mode;        /* MPCX_PRECEDENCE_* */
+} mpcx_precedence;
+int32_t mpcx_closed_loop_run_precedence(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                        const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                        const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                        const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                        const mpcx_routes *routes /*or NULL*/, const mpcx_precedence *precedence /*or NULL*/,
+                                        int32_t n_steps, int32_t use_graph);
+/* one step's admission followed by the entry-order stamp, as a stage of its own (what mpcx_closed_loop_run_precedence enqueues at the head
+ * of a step): mpcx_admit_step_batch with the precedence struct (NULL or all-zero: that call itself; MPCX_PRECEDENCE_FIXED: that call after
+ * the struct's check).  The scene the struct is checked against is `absent` over the n_obs_pool rows. */
+int32_t mpcx_admit_step_batch_precedence(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state /*P,4*/,
+                                         const int32_t *obs_off /*P*/, const int32_t *obs_cnt /*P*/, const int32_t *obs_skip /*P*/,
+                                         int32_t *done /*P*/, int32_t n_obs_pool, int32_t *absent /*NOBS*/,
+                                         int32_t n_actors, const mpcx_traffic_actor *actors /*n_actors*/, const double *actor_state /*n_actors,4*/,
+                                         const double *tape /*rows,6 or NULL*/, int64_t tape_rows, const int32_t *actor_row /*n_actors*/,
+                                         const mpcx_admit *admit, const mpcx_precedence *precedence /*or NULL*/);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

@@ -86,6 +86,17 @@ class RoutesC(C.Structure):
                 ('start_state', C.c_void_p), ('start_idx', C.c_void_p), ('path_off', C.c_void_p), ('path_len', C.c_void_p)]
 
 
+class PrecedenceC(C.Structure):
+    """mirror of mpcx_precedence (include/mpcx.h): right of way; prec (n_rows int32, a smaller word goes first) and stand (n_rows x 4
+    float64, scratch) are device addresses"""
+    _fields_ = [('prec', C.c_void_p), ('stand', C.c_void_p), ('n_rows', C.c_int32), ('mode', C.c_int32)]
+
+
+PRECEDENCE_FIXED, PRECEDENCE_ENTRY = 1, 2       # mpcx_precedence.mode
+PRECEDENCE_WINDOW = 64                          # MPCX_PRECEDENCE_WINDOW: the entry-order word is entered_step * 64 + window offset
+PRECEDENCE_MAX_STEP = (2 ** 31 - 1 - (PRECEDENCE_WINDOW - 1)) // PRECEDENCE_WINDOW      # the largest entered_step whose word fits
+
+
 # the words of an episode record (ep_i32[q][g][0..6]; word 7 is 0, with routes the episode's route: EPISODE_ROUTE_WORD; ep_f64[q][g][0], one
 # reserved)
 EPISODE_I32 = ('entered', 'arrived', 'steps_driven', 'row_end', 'contact_step', 'flags', 'due')
@@ -156,7 +167,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
            'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
            'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
-           'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary']
+           'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence']
 
 
 def load():
@@ -254,5 +265,12 @@ def load():
                                                                           C.POINTER(RespawnC), C.POINTER(RoutesC), i32]
     lib.mpcx_episode_summary.restype = i32
     lib.mpcx_episode_summary.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.mpcx_closed_loop_run_precedence.restype = i32
+    lib.mpcx_closed_loop_run_precedence.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                    C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                    C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), i32, i32]
+    lib.mpcx_admit_step_batch_precedence.restype = i32
+    lib.mpcx_admit_step_batch_precedence.argtypes = [vp, C.POINTER(InteractionParamsC), i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp,
+                                                     C.c_int64, vp, C.POINTER(AdmitC), C.POINTER(PrecedenceC)]
     _lib = lib
     return lib

@@ -27,6 +27,9 @@ arrives its episode is recorded (episodes()), the slot is reset to a fresh start
 `respawn_on_schedule(due, gap, route=...)` gives every vehicle of a slot its OWN ROUTE (and start index): the reset also writes the slot's
 `path_off` / `path_len`, so turning proportions vary per vehicle with no host work between steps (turning_demand() draws seeded routes per
 approach arm; episode_routes() and movement_summary() read the run per movement, the latter reduced on the device).
+`give_way(order)` is RIGHT OF WAY: every pool row has a precedence word, and an agent sees the cars whose word is larger than its own as
+standing cars at their present pose -- which ends the mutual wait of yield-to-everybody at the crossing; order='entry' is first come, first
+served, stamped on the device as vehicles are admitted.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -334,6 +337,9 @@ class IntersectionBatch:
         self.route_off: Optional[torch.Tensor] = None        # ... int32 (R,) each: the routes' runs in the path tables
         self.route_len: Optional[torch.Tensor] = None
         self._routes = None
+        self.prec: Optional[torch.Tensor] = None             # give_way(): int32 (pool rows,), the precedence words, a smaller word goes first
+        self.stand: Optional[torch.Tensor] = None            # ... float64 (pool rows, 4), the standing records (scratch)
+        self._precedence = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -415,6 +421,7 @@ class IntersectionBatch:
         self._admit = None                  # (admission lives on a scene: enter_on_schedule() after this call)
         self._respawn = None                # (... and respawn on admission)
         self._routes = None
+        self._precedence = None             # (right of way lives on a scene too: give_way() after this call)
         if leave_scene:
             rows = int(self.obs6.shape[0])
             self.absent = torch.zeros(rows, dtype=torch.int32, device=self.ctx.device)
@@ -435,6 +442,7 @@ class IntersectionBatch:
         self._admit = None
         self._respawn = None
         self._routes = None
+        self._precedence = None             # (right of way lives on the scene)
         self._desc = None
 
     def enter_on_schedule(self, wait, gap: float = 0.0):
@@ -480,6 +488,8 @@ class IntersectionBatch:
         self._admit = None
         self._respawn = None
         self._routes = None
+        if self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY:
+            self._precedence = None         # (the order of entry is admission's: give_way(order=<array>) keeps a fixed order)
         self._desc = None
 
     def respawn_on_schedule(self, due, gap: float = 0.0, route=None, start_index=None):
@@ -574,6 +584,53 @@ class IntersectionBatch:
         st[..., 0], st[..., 1], st[..., 3] = pts[..., 0], pts[..., 1], pts[..., 2]
         st[..., 2] = self.state.cpu().numpy()[:, 2][:, None]
         return dict(route=r, start_idx=s, start_state=st)
+
+    def give_way(self, order='entry'):
+        """RIGHT OF WAY (mpcx_closed_loop_run_precedence).  Without it every agent yields to every other agent -- the reference's rule for
+        its one ego among scripted cars --, and cars that meet at the crossing wait for each other for ever.  With it there is one precedence
+        word per pool row, `prec` (device, int32; a smaller word goes first), and an agent sees a present car whose word is LARGER than its
+        own as a STANDING car at its present pose: still an obstacle where it is, no longer a claim on the road ahead of it.  Cars with a
+        smaller or equal word are seen through their prediction, as ever (equal words: the mutual yield).  The run log's clearance and
+        contact stay true clearance; the admission gate, retirement, respawn and routes do not change.
+        order='entry': first come, first served (MPCX_PRECEDENCE_ENTRY; needs enter_on_schedule() or respawn_on_schedule() first): one more
+        small launch per step writes entered_step * 64 + window offset into the word of every agent in the scene, so a vehicle that enters
+        -- a respawned one too -- queues behind everybody already there, ties to the lower agent index.
+        order=<integer array (B, A) or (P,)>: a fixed word per agent (MPCX_PRECEDENCE_FIXED); the loop never writes `prec`.
+        The rows of scripted cars hold zero -- every agent with a word >= 0 sees them moving; write `sim.prec[sim.actor_row]` to change that.
+        Needs retire_at_goal(leave_scene=True) first.  Allocates `prec` and `stand` and drops the cached descriptor.  yield_to_everyone()
+        switches it off; keep_driving() and retire_at_goal() drop it with the scene, enter_now() drops order='entry' with admission."""
+        if self._scene is None:
+            raise MpcxError('give_way: right of way needs a scene (MPCX_E_INVALID): retire_at_goal(leave_scene=True) first')
+        rows = int(self.obs6.shape[0])
+        words = np.zeros(rows, dtype=np.int64)
+        if isinstance(order, str):
+            if order != 'entry':
+                raise ValueError('give_way: order is \'entry\' or an integer array with one word per agent, got %r' % (order,))
+            if self._admit is None:
+                raise MpcxError('give_way(order=\'entry\'): the order of entry needs admission (MPCX_E_INVALID): enter_on_schedule() or '
+                                'respawn_on_schedule() first')
+            mode = _lib.PRECEDENCE_ENTRY
+        else:
+            w = np.asarray(order)
+            if not np.issubdtype(w.dtype, np.integer) or w.size != self.P or w.shape not in ((self.B, self.A), (self.P,)):
+                raise ValueError('give_way: order must be \'entry\' or an integer array of shape (B, A) = %s or (P,)' % ((self.B, self.A),))
+            w = w.reshape(-1).astype(np.int64)
+            if (w < np.iinfo(np.int32).min).any() or (w > np.iinfo(np.int32).max).any():
+                raise ValueError('give_way: the precedence words are int32')
+            self.ctx.synchronize()
+            words[self.obs_skip.cpu().numpy().astype(np.int64)] = w
+            mode = _lib.PRECEDENCE_FIXED
+        self.prec = self.ctx.i32(words)
+        self.stand = torch.zeros((rows, 4), dtype=torch.float64, device=self.ctx.device)
+        self._precedence = _lib.PrecedenceC(self.prec.data_ptr(), self.stand.data_ptr(), rows, mode)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def yield_to_everyone(self):
+        """switch right of way off and nothing else: the batch enqueues exactly the launches of one that never had it, and every agent
+        yields to every other again (`prec` keeps what it holds and is no longer read)"""
+        self._precedence = None
+        self._desc = None
 
     def stop_respawning(self):
         """switch respawn off and nothing else: the batch enqueues exactly the launches of one with admission alone.  Vehicles in flight
@@ -715,11 +772,16 @@ class IntersectionBatch:
             for _ in range(n_steps):
                 self.step_staged()
             return
+        if (self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY and
+                self.steps_done + int(n_steps) > _lib.PRECEDENCE_MAX_STEP):
+            raise MpcxError('give_way(order=\'entry\'): step %d is beyond the last step whose entry-order word fits int32 (%d)'
+                            % (self.steps_done + int(n_steps), _lib.PRECEDENCE_MAX_STEP))
         if self._desc is None:
             self._desc = self._descriptor()
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
-                                 retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes)
+                                 retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes,
+                                 precedence=self._precedence)
         self.steps_done += n_steps
 
     def step(self):
@@ -806,6 +868,8 @@ class IntersectionBatch:
             out['served'] = self.served.cpu().numpy().copy()
         if self._routes is not None:         # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
+        if self._precedence is not None:     # the precedence word of every pool row (a smaller word goes first)
+            out['precedence'] = self.prec.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:

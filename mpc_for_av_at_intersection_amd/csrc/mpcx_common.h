@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1080] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + routes + parameters the cached graph was captured for
+    unsigned char loop_key[1104] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + routes + precedence + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -77,6 +77,10 @@ struct mpcx_interaction_extras {
     const int32_t *done = nullptr;      // retirement (mpcx_retire::done): an agent with done[p] != 0 is not searched, not filed and none of its outputs is written
     // departure (mpcx_scene::absent, n_obs_pool words; needs done): pool rows with absent[r] != 0 are neither predicted nor in anybody's obstacle list
     const int32_t *absent = nullptr;
+    // right of way (mpcx_precedence::prec / stand, n_obs_pool words / rows of four doubles; needs absent): the prediction also stores every
+    // predicted row's standing record, and an agent sees the present rows whose word is larger than its own row's through that record
+    const int32_t *prec = nullptr;
+    double *stand = nullptr;
 };
 struct mpcx_window_extras {
     bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
@@ -169,6 +173,11 @@ int32_t mpcx_route_enqueue(mpcx_ctx *ctx, int32_t P, double *state, double *appl
                            int32_t *cut_len, int32_t *iters, int32_t *prev_len /*or nullptr*/, const int32_t *obs_skip, int32_t n_obs_pool,
                            const mpcx_run_log *log /*or nullptr*/, const mpcx_retire *retire, const mpcx_admit *admit,
                            const mpcx_respawn *respawn, const mpcx_routes *routes);
+// right of way (mpcx_precedence.hip): "no precedence" test, check of the struct against the run, the entry-order stamp's launch alone
+bool mpcx_precedence_absent(const mpcx_precedence *s);
+int32_t mpcx_precedence_validate(mpcx_ctx *ctx, const mpcx_precedence *s, const mpcx_scene *scene, const mpcx_admit *admit);
+int32_t mpcx_precedence_enqueue(mpcx_ctx *ctx, int32_t P, const int32_t *obs_off, const int32_t *obs_skip, const mpcx_admit *admit,
+                                const mpcx_precedence *precedence);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -45,10 +45,13 @@ struct PredArgs {
     // departure (SCENE instantiations only; mpcx_scene::absent, n_pool words): a row with absent[o] != 0 is packed as ever and not predicted --
     // no conflict search reads the prediction of an absent row
     const int32_t *absent;
+    // right of way (STAND instantiations only; mpcx_precedence::stand, n_pool rows of four doubles): every predicted row also leaves its
+    // STANDING record, the two disc centres of its current pose -- what every frame of the prediction of (x, y, 0, yaw, 0, 0) would hold
+    double *stand;
 };
 
 // moving_obstacles_prediction.py:21-28: v is updated BEFORE yaw; disc centres as trajectories.py:11-37
-template <bool MAPPED, bool SCENE = false>
+template <bool MAPPED, bool SCENE = false, bool STAND = false>
 __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
     int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= a.n) return;
@@ -74,6 +77,7 @@ __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
     const double dt = a.ip.dt;
     double s, c;
     sincos(yaw, &s, &c);
+    if constexpr (STAND) pose_discs(a.ip, x, y, c, s, a.stand + 4 * (size_t)o);
     double *out = a.pred + (size_t)o * a.ip.pred_steps * 4;
     for (int k = 0; k < a.ip.pred_steps; k++) {
         x = __dadd_rn(x, __dmul_rn(__dmul_rn(v, c), dt));
@@ -104,6 +108,9 @@ struct InterArgs {
     const int32_t *done;  // retirement (read by the RETIRE instantiation only): done[p] != 0 = agent p has arrived -- no search, no output, not filed in a bin
     const int32_t *absent;    // departure (read by the SCENE instantiation only): absent[r] != 0 = pool row r is not in the scene; n_rows words
     int n_rows;
+    // right of way (read by the PREC instantiation only): prec[r] = the precedence word of pool row r, stand[r][4] = its standing record
+    const int32_t *prec;
+    const double *stand;
 };
 
 __device__ __forceinline__ double dist2d(double ax, double ay, double bx, double by) {
@@ -195,10 +202,13 @@ struct RowList {
 // collision_avoidance.py:72-87: the first row of the pair table within md, as the minimum of a key in the reference's row order.
 // Returns whether there is one; (hox, hoy): the obstacle disc position of that row.
 // SCENE: candidate rank o is the o-th PRESENT row of the window, rows[o] its offset in the window (present_rows below); nobs counts those.
-template <bool SCENE = false>
+// PREC (with SCENE): bit o of `yields` set = the row of rank o yields to this agent, which sees it STANDING: every frame of its prediction is
+// its standing record stand[pool][4] -- the candidate's address is selected between the two tables, everything after the load is the same.
+template <bool SCENE = false, bool PREC = false>
 __device__ __forceinline__ bool first_row(const mpcx_interaction_params &ip, const Within &within, const double (*s_ego)[4], int na, int F, int SL,
                                           const double (*s_box)[4], const double *pred, int ooff, int nobs, int oskip, int lane,
-                                          double &hox, double &hoy, const RowList rows = {0, 0}) {
+                                          double &hox, double &hoy, const RowList rows = {0, 0}, const double *stand = nullptr,
+                                          unsigned yields = 0u) {
     const int steps = ip.pred_steps, w = ip.frame_window;
     const float inv_steps = 1.0f / (float)steps;
     const long long NOKEY = 0x7fffffffffffffffLL;
@@ -224,6 +234,10 @@ __device__ __forceinline__ bool first_row(const mpcx_interaction_params &ip, con
                 if (oskip >= 0 && pool >= oskip) pool += 1;                                // skip self
             }
             const double *qq = pred + ((size_t)pool * steps + g) * 4 + 2 * co;
+            if constexpr (PREC) {
+                const double *qs = stand + (size_t)pool * 4 + 2 * co;
+                qq = ((yields >> o) & 1u) ? qs : qq;                                       // a select, not a branch: one load either way
+            }
             ox[u] = qq[0]; oy[u] = qq[1];
         }
 #pragma unroll
@@ -327,13 +341,14 @@ __device__ __forceinline__ int earliest_pose(const mpcx_interaction_params &ip, 
 
 // s_ego: ego disc centres of the `na` predicted poses; pred: obstacle disc centres [pool][steps][2][2]; (rem, rcs, n): the detailed path and
 // cos/sin of its yaw.  Returns the index of the earliest conflicting pose on the detailed path (and its x,y) or -1 (None).
-template <bool SCENE = false>
+template <bool SCENE = false, bool PREC = false>
 __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)[4], int na, const double *pred,
                               int ooff, int nobs, int oskip, const double *rem, const double *rcs, int n,
                               double (*s_box)[4], int lane, double &hx, double &hy,
                               bool boxes_ready = false,          // s_box already holds the runs' boxes (mpcx_interaction_params.plan_box)
                               const double *pdisc = nullptr,     // disc centres of the poses of `rem` (mpcx_interaction_params.path_disc + 4 * row of rem[0]) or nullptr
-                              const RowList rows = {0, 0}        // SCENE: the window offsets of the nobs present rows
+                              const RowList rows = {0, 0},       // SCENE: the window offsets of the nobs present rows
+                              const double *stand = nullptr, unsigned yields = 0u     // PREC: the standing records and who yields, by rank
                               ) {
     const Within within(2.0 * ip.radius);
     const double slack = within.md * (1.0 + 1e-9) + 1e-9;      // conservative: never culls a pair within md
@@ -342,7 +357,7 @@ __device__ int first_conflict(const mpcx_interaction_params &ip, double (*s_ego)
     if (!boxes_ready) run_boxes(s_ego, na, F, SL, slack, s_box, lane);
     __syncthreads();
     double ox, oy;
-    if (!first_row<SCENE>(ip, within, s_ego, na, F, SL, s_box, pred, ooff, nobs, oskip, lane, ox, oy, rows)) return -1;
+    if (!first_row<SCENE, PREC>(ip, within, s_ego, na, F, SL, s_box, pred, ooff, nobs, oskip, lane, ox, oy, rows, stand, yields)) return -1;
     const int first = earliest_pose(ip, within, ox, oy, rem, rcs, pdisc, n, lane);
     hx = rem[3 * first]; hy = rem[3 * first + 1];
     return first;
@@ -764,13 +779,37 @@ __device__ __forceinline__ unsigned long long present_rows(const InterArgs &a, i
     return __ballot(in && r != own && gone == 0);
 }
 
+// right of way (mpcx_precedence): which of those rows YIELD to the agent -- present, not its own, and with a precedence word larger than its
+// own row's -- as a bit per window offset: a second ballot, one more word load per lane (the own row's word is one wave-uniform load).
+// An agent without an own row (own outside the pool) has nobody yield to it.
+__device__ __forceinline__ unsigned long long yielding_rows(const InterArgs &a, int lane, int cnt, int off, int own, unsigned long long present) {
+    const int r = off + lane;
+    const bool in = lane < cnt && r >= 0 && r < a.n_rows;
+    const bool has_own = own >= 0 && own < a.n_rows;
+    const int32_t w = a.prec[in ? r : 0], wo = a.prec[has_own ? own : 0];          // clamped addresses, selected afterwards
+    return __ballot(in && has_own && w > wo) & present;
+}
+// ... by RANK in the list of present rows (bit o = the o-th present row yields), as first_row's candidates are numbered: <= MPCX_MAX_OBS bits
+__device__ __forceinline__ unsigned yields_by_rank(unsigned long long present, unsigned long long yielding) {
+    unsigned out = 0u;
+    for (unsigned long long m = yielding; m; m &= m - 1) {
+        const int k = __ffsll((long long)m) - 1;
+        out |= 1u << __popcll(present & ((1ull << k) - 1ull));
+    }
+    return out;
+}
+
 // RETIRE: the closed loop with retirement at the goal (mpcx_retire).  A template parameter, not a null test, as predict_kernel<MAPPED>:
 // the launch without retirement runs the code it ran before there was any.
 // SCENE (with RETIRE only): departure (mpcx_scene).  The obstacle list is the list of PRESENT rows of the window, built once per agent, and
 // first_row walks nobs = its length candidates' worth of rows: a window with departed cars is less work.  The other two instantiations
 // are the code they were.
-template <bool RETIRE, bool SCENE = false>
+// PREC (with RETIRE and SCENE only): right of way (mpcx_precedence).  The present rows that yield to the agent are a second ballot, and
+// first_row loads their candidates from the standing records instead of the predictions; nothing else reads an obstacle's prediction
+// (earliest_pose and cut_index work from the hit's disc position and the agent's own path).  The other three are the code they were.
+template <bool RETIRE, bool SCENE = false, bool PREC = false>
 __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
+    static_assert(!PREC || (RETIRE && SCENE), "precedence lives on a scene");
     // a retired agent: nothing is read, written or filed -- its outputs stay as its last driven step left them, and an agent that is
     // not filed is never solved (predict_kernel has packed its pool row all the same: to the others it is a parked car)
     if constexpr (RETIRE) { if (a.done[blockIdx.x] != 0) return; }
@@ -799,11 +838,15 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     if (a.prev_save && lane == 0) a.prev_save[p] = kprev;
     int nobs;
     RowList rows = {0, 0};
+    unsigned yields = 0u;
     if constexpr (SCENE) {
         const int cnt = a.obs_cnt[p];
         const unsigned long long present = present_rows(a, p, lane, cnt, a.obs_off[p], a.obs_skip ? a.obs_skip[p] : -1);     // wave-uniform
         nobs = cnt > WAVE ? MPCX_MAX_OBS + 1 : __popcll(present);       // (beyond one ballot, or too many: locate() leaves with -2)
         if (nobs <= MPCX_MAX_OBS) rows = RowList::of(present);
+        if constexpr (PREC) {
+            if (nobs <= MPCX_MAX_OBS) yields = yields_by_rank(present, yielding_rows(a, lane, cnt, a.obs_off[p], a.obs_skip ? a.obs_skip[p] : -1, present));
+        }
     } else
         nobs = a.obs_cnt[p] - ((a.obs_skip && a.obs_skip[p] >= 0) ? 1 : 0);
     const double *cumtab = ip.path_cum ? ip.path_cum + poff : nullptr;
@@ -831,11 +874,19 @@ __global__ __launch_bounds__(64, 5) void interaction_kernel(InterArgs a) {
     const int ooff = a.obs_off[p], oskip = a.obs_skip ? a.obs_skip[p] : -1;
     double hx, hy;
     const double *pdisc = ip.plan_cnt ? ip.path_disc + 4 * prow : nullptr;     // disc centres of trajectory_full[tidx:] from the host's table
-    const int first = first_conflict<SCENE>(ip, s_ego, na, a.pred, ooff, nobs, oskip, e.rem, rcs, e.n, s_box, lane, hx, hy, from_plan, pdisc, rows);
+    const int first = first_conflict<SCENE, PREC>(ip, s_ego, na, a.pred, ooff, nobs, oskip, e.rem, rcs, e.n, s_box, lane, hx, hy, from_plan, pdisc, rows,
+                                                  a.stand, yields);
     if (first < 0) { leave(a, p, lane, kprev, len, -1); return; }
     finish(a, p, lane, kprev, first, hx, hy, cut_index(ip, path, poff, len, tidx, tidx + first, hx, hy, lane));
 }
 
+// The right-of-way instantiations (predict_kernel<·, true, true>, interaction_kernel<true, true, true>) live in a translation unit of their
+// own, mpcx_interaction_prec.hip, which includes this file for the templates alone (MPCX_INTERACTION_TEMPLATES_ONLY): this file keeps the
+// kernels it had.  Launchers defined there:
+void launch_predict_stand(bool mapped, int lanes, hipStream_t st, const PredArgs &pa);
+void launch_interaction_prec(int P, size_t lds, hipStream_t st, const InterArgs &ia);
+
+#ifndef MPCX_INTERACTION_TEMPLATES_ONLY
 // ------------------------------------------------------------------------------------------------------------
 // check_collision_moving_cars on EXPLICIT trajectories (the reference's own signature, collision_avoidance.py:66):
 // the caller has already resampled the ego and predicted the obstacles (mpc_intersection.py:110-122).
@@ -884,9 +935,11 @@ __global__ __launch_bounds__(64) void moving_collision_kernel(MovArgs a) {
                                      a.path + 3 * (size_t)a.path_off[p], a.path_cs + 2 * (size_t)a.path_off[p], n, s_box, lane, hx, hy);
     if (lane == 0) { a.hit_idx[p] = first; a.hit_xy[2 * p] = first < 0 ? 0.0 : hx; a.hit_xy[2 * p + 1] = first < 0 ? 0.0 : hy; }
 }
+#endif  // MPCX_INTERACTION_TEMPLATES_ONLY
 
 }  // namespace mpcx
 
+#ifndef MPCX_INTERACTION_TEMPLATES_ONLY
 
 extern "C" int32_t mpcx_interaction_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P,
                                           const double *state, const double *path_xyyaw, const double *path_cs,
@@ -910,18 +963,21 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     if (ip->pred_steps < 1 || ip->pred_steps > MPCX_PRED_STEPS_MAX || ip->frame_window < 0 || !(ip->dt > 0) || !(ip->L > 0))
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: pred_steps outside 1..%d or bad dt/L/frame_window", MPCX_PRED_STEPS_MAX);
     if (x.absent && (!x.done || n_obs_pool < 1)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: a scene without retirement or without a pool");
+    if ((x.prec || x.stand) && (!x.absent || !x.prec || !x.stand)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: precedence without a scene, or without one of prec and stand");
     { int32_t rc = mpcx_ensure_pred(ctx, (size_t)(n_obs_pool > 0 ? n_obs_pool : 1) * ip->pred_steps * 4); if (rc != MPCX_OK) return rc; }
     if (n_obs_pool > 0 && x.pack_state && x.ego_row) {
         // closed loop with scripted traffic: only the rows that hold an agent or an actor are predicted (the others are outside every window)
         const int lanes = x.n_ego + x.n_actors;
         mpcx::PredArgs pa{*ip, lanes, n_obs_pool, obs6, ctx->pred, x.pack_state, x.pack_applied, const_cast<double *>(obs6),
-                          x.ego_row, x.actor_row, x.n_ego, x.absent};
-        if (x.absent) hipLaunchKernelGGL((mpcx::predict_kernel<true, true>), dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
+                          x.ego_row, x.actor_row, x.n_ego, x.absent, x.stand};
+        if (x.prec) mpcx::launch_predict_stand(true, lanes, ctx->stream, pa);
+        else if (x.absent) hipLaunchKernelGGL((mpcx::predict_kernel<true, true>), dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
         else hipLaunchKernelGGL(mpcx::predict_kernel<true>, dim3((lanes + 63) / 64), dim3(64), 0, ctx->stream, pa);
     } else if (n_obs_pool > 0) {
         mpcx::PredArgs pa{*ip, n_obs_pool, n_obs_pool, obs6, ctx->pred, x.pack_state, x.pack_applied, x.pack_state ? const_cast<double *>(obs6) : nullptr,
-                          nullptr, nullptr, 0, x.absent};
-        if (x.absent) hipLaunchKernelGGL((mpcx::predict_kernel<false, true>), dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
+                          nullptr, nullptr, 0, x.absent, x.stand};
+        if (x.prec) mpcx::launch_predict_stand(false, n_obs_pool, ctx->stream, pa);
+        else if (x.absent) hipLaunchKernelGGL((mpcx::predict_kernel<false, true>), dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
         else hipLaunchKernelGGL(mpcx::predict_kernel<false>, dim3((n_obs_pool + 63) / 64), dim3(64), 0, ctx->stream, pa);
     }
     // capacity: max_path_len path points (0 = MPCX_MAX_REMAINING; never below 512), rounded up to whole wavefronts; the LDS that
@@ -938,8 +994,9 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     mpcx::InterArgs ia{*ip, P, state, path_xyyaw, path_cs, path_off, path_len, prev_cut_len, ctx->pred,
                        obs_off, obs_cnt, obs_skip, traj_idx, hit_idx, hit_xy, cut_len, max_rem, fcap, x.prev_save,
                        x.bin_hint, x.bin_hint ? ctx->bins : nullptr, x.bin_hint ? ctx->bins + MPCX_ORDER_COPIES * MPCX_ORDER_BINS : nullptr,
-                       x.key_prev, x.near, x.done, x.absent, n_obs_pool};
-    if (x.absent) hipLaunchKernelGGL((mpcx::interaction_kernel<true, true>), dim3(P), dim3(64), lds, ctx->stream, ia);
+                       x.key_prev, x.near, x.done, x.absent, n_obs_pool, x.prec, x.stand};
+    if (x.prec) mpcx::launch_interaction_prec(P, lds, ctx->stream, ia);
+    else if (x.absent) hipLaunchKernelGGL((mpcx::interaction_kernel<true, true>), dim3(P), dim3(64), lds, ctx->stream, ia);
     else if (x.done) hipLaunchKernelGGL(mpcx::interaction_kernel<true>, dim3(P), dim3(64), lds, ctx->stream, ia);
     else hipLaunchKernelGGL(mpcx::interaction_kernel<false>, dim3(P), dim3(64), lds, ctx->stream, ia);
     return mpcx_check_launch(ctx, "interaction kernels");
@@ -975,3 +1032,4 @@ extern "C" int32_t mpcx_moving_collision_batch(mpcx_ctx *ctx, const mpcx_interac
     hipLaunchKernelGGL(mpcx::moving_collision_kernel, dim3(P), dim3(64), 0, ctx->stream, ma);
     return mpcx_check_launch(ctx, "moving collision kernels");
 }
+#endif  // MPCX_INTERACTION_TEMPLATES_ONLY

@@ -6,7 +6,8 @@
 // host synchronisation or host arithmetic in between.  With retirement at the goal (mpcx_retire) the step ends with retire_kernel, and an agent
 // that has arrived is skipped by every stage but the pool pack; with a scene (mpcx_scene) its arrival also takes it out of everybody
 // else's obstacle list; with admission (mpcx_admit) the step begins with the two launches that let waiting agents in; with respawn
-// (mpcx_respawn) it ends with respawn_kernel, which resets an arrived agent's slot for the next vehicle of its stream.  Every stage is the kernel behind the per-stage C entry
+// (mpcx_respawn) it ends with respawn_kernel, which resets an arrived agent's slot for the next vehicle of its stream; with right of way
+// (mpcx_precedence) the conflict search shows an agent the cars that yield to it as standing cars.  Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
 #include "mpcx_common.h"
@@ -72,9 +73,12 @@ static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cu
 // rt: routes or nullptr = none (then exactly the launches of a step with respawn, with the same arguments).  With them respawn_route_kernel
 // takes respawn_kernel's place -- the same number of launches --: the reset also writes the next vehicle's route into c->path_off / c->path_len
 // and its own start pose and index, which every stage of the next step reads afresh.
+// pc: right of way or nullptr = none (then exactly the launches of a step with routes, with the same arguments).  With it the prediction also
+// stores the standing records and the conflict search runs its PREC instantiation; in MPCX_PRECEDENCE_ENTRY one more launch,
+// precedence_stamp_kernel, follows the admission stage -- before the prediction, so an agent admitted in this step is seen with its word.
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                             const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc, const mpcx_admit *ad,
-                            const mpcx_respawn *rs, const mpcx_routes *rt) {
+                            const mpcx_respawn *rs, const mpcx_routes *rt, const mpcx_precedence *pc) {
     const int P = c->P;
     const int32_t *done = r ? r->done : nullptr;
     int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
@@ -86,6 +90,10 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         rc = mpcx_admit_enqueue(ctx, ip, P, c->state, c->obs_off, c->obs_cnt, c->obs_skip, r->done, sc->n_rows, sc->absent, na, c->actors,
                                 c->actor_state, c->tape, c->tape_rows, c->actor_row, ad);
         if (rc != MPCX_OK) return rc;
+        if (pc && pc->mode == MPCX_PRECEDENCE_ENTRY) {      // (validated: ENTRY has admission)
+            rc = mpcx_precedence_enqueue(ctx, P, c->obs_off, c->obs_skip, ad, pc);
+            if (rc != MPCX_OK) return rc;
+        }
     }
     // the warm-start rollout of this step needs only the states and the previous solution: it runs on the side stream BESIDE the pool pack,
     // the prediction and the conflict search (a chain of T dependent sincos / tan per agent, 35-45 us) and is joined by the window selection
@@ -101,6 +109,7 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     ix.bin_hint = binned ? c->iters : nullptr;
     ix.done = done;
     ix.absent = sc ? sc->absent : nullptr;
+    if (pc) { ix.prec = pc->prec; ix.stand = pc->stand; }       // (validated: a scene)
     if (speed) ix.key_prev = c->cut_len;        // "the cut moved" = the stop index moved
     if (c->exchange == MPCX_SHARD_AGENTS) {
         // agent-sharded layout: this rank's rows travel to every rank, every rank assembles the whole pool (one RCCL all-gather)
@@ -171,7 +180,8 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
 
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                                const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, const mpcx_admit *admit,
-                               const mpcx_respawn *respawn, const mpcx_routes *routes, int32_t n_steps, int32_t use_graph) {
+                               const mpcx_respawn *respawn, const mpcx_routes *routes, const mpcx_precedence *precedence, int32_t n_steps,
+                               int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
@@ -220,6 +230,11 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         cap = (cap + 63) / 64 * 64;
         const int32_t trc = mpcx_routes_validate(ctx, routes, respawn, c->path_off, c->path_len, cap);
         if (trc != MPCX_OK) return trc;
+    }
+    if (mpcx_precedence_absent(precedence)) precedence = nullptr;
+    if (precedence) {   // refused before anything is launched, whatever n_steps is
+        const int32_t prc = mpcx_precedence_validate(ctx, precedence, scene, admit);
+        if (prc != MPCX_OK) return prc;
     }
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
@@ -291,7 +306,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes);
+            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -301,7 +316,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_routes) + sizeof(mpcx_interaction_params) +
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_routes) + sizeof(mpcx_precedence) + sizeof(mpcx_interaction_params) +
                   sizeof(mpcx_mpc_params) + 10 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
@@ -320,6 +335,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     o += sizeof *respawn;
     if (routes) memcpy(key + o, routes, sizeof *routes);     // (zeros = no routes: a graph captured with respawn_kernel)
     o += sizeof *routes;
+    if (precedence) memcpy(key + o, precedence, sizeof *precedence);     // (zeros = no precedence: a graph captured without its instantiations)
+    o += sizeof *precedence;
     memcpy(key + o, &ctx->admit_tab, sizeof ctx->admit_tab); o += sizeof ctx->admit_tab;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
@@ -340,7 +357,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes);
+        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -357,35 +374,35 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_admit(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, const mpcx_admit *admit, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_respawn(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
@@ -399,5 +416,13 @@ extern "C" int32_t mpcx_closed_loop_run_routes(mpcx_ctx *ctx, const mpcx_interac
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                const mpcx_routes *routes, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, n_steps, use_graph);
+    return mpcx_closed_loop_run_precedence(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_precedence(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                                   const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                                   const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
+                                                   const mpcx_routes *routes, const mpcx_precedence *precedence, int32_t n_steps,
+                                                   int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, precedence, n_steps, use_graph);
 }

@@ -616,7 +616,7 @@ class Context:
                         log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None,
                         retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None,
                         admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None,
-                        routes: Optional['_lib.RoutesC'] = None):
+                        routes: Optional['_lib.RoutesC'] = None, precedence: Optional['_lib.PrecedenceC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
@@ -628,9 +628,16 @@ class Context:
         respawn: a _lib.RespawnC -- respawn: an arrived agent's slot is reset for the next vehicle of its stream and handed back to the
         admission gate (mpcx_closed_loop_run_respawn; refused without admit); None = a departed slot stays empty.
         routes: a _lib.RoutesC -- every vehicle of a slot takes its own route from its own start pose (mpcx_closed_loop_run_routes; refused
-        without respawn); None = a slot keeps its route."""
+        without respawn); None = a slot keeps its route.
+        precedence: a _lib.PrecedenceC -- right of way: an agent sees the present rows whose word is larger than its own as standing cars
+        (mpcx_closed_loop_run_precedence; refused without scene, and in ENTRY mode without admit); None = everybody yields to everybody."""
         cip = ip.to_c()
-        if routes is not None:
+        ref = lambda s: None if s is None else C.byref(s)
+        if precedence is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_precedence(self._ctx, C.byref(cip), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
+                                                               ref(admit), ref(respawn), ref(routes), C.byref(precedence), int(n_steps),
+                                                               1 if graph else 0))
+        elif routes is not None:
             self._chk(self.lib.mpcx_closed_loop_run_routes(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
                                                            None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
                                                            None if scene is None else C.byref(scene), None if admit is None else C.byref(admit),
@@ -664,11 +671,13 @@ class Context:
 
     @_ordered
     def admit_step(self, ip: InteractionParams, state, obs_off, obs_cnt, obs_skip, done, absent, admit: '_lib.AdmitC', actors=None,
-                   actor_state=None, actor_row=None, tape=None):
+                   actor_state=None, actor_row=None, tape=None, precedence: Optional['_lib.PrecedenceC'] = None):
         """mpcx_admit_step_batch: ONE step's admission as the closed loop enqueues it at the head of a step.  done (P) and absent (pool
         rows) are the retirement and scene words, int32, updated in place; admit: a _lib.AdmitC naming caller-owned device buffers (wait and
         entered_step: P int32, clock: 1 int32).  actors / actor_state / actor_row / tape: scripted cars as traffic_step takes them; they
-        are read, not stepped."""
+        are read, not stepped.
+        precedence: a _lib.PrecedenceC -- mpcx_admit_step_batch_precedence: in ENTRY mode the entry-order stamp follows the admission, as
+        at the head of a closed-loop step with right of way."""
         Pn = int(state.shape[0])
         self._want(state, torch.float64, (Pn, 4), 'state'); self._want(done, torch.int32, (Pn,), 'done')
         self._want(absent, torch.int32, (absent.shape[0],), 'absent')
@@ -682,11 +691,15 @@ class Context:
             if tape is not None:
                 self._want(tape, torch.float64, (tape.shape[0], 6), 'tape')
         cip = ip.to_c()
-        self._chk(self.lib.mpcx_admit_step_batch(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip), _ptr(done),
-                                                 int(absent.shape[0]), _ptr(absent), n, _ptr(actors) if n else None,
-                                                 _ptr(actor_state) if n else None, _ptr(tape) if n else None,
-                                                 0 if (tape is None or not n) else int(tape.shape[0]), _ptr(actor_row) if n else None,
-                                                 C.byref(admit)))
+        args = (self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip), _ptr(done),
+                int(absent.shape[0]), _ptr(absent), n, _ptr(actors) if n else None,
+                _ptr(actor_state) if n else None, _ptr(tape) if n else None,
+                0 if (tape is None or not n) else int(tape.shape[0]), _ptr(actor_row) if n else None,
+                C.byref(admit))
+        if precedence is not None:
+            self._chk(self.lib.mpcx_admit_step_batch_precedence(*args, C.byref(precedence)))
+            return
+        self._chk(self.lib.mpcx_admit_step_batch(*args))
 
     @_ordered
     def respawn_step(self, state, applied, u_sol, traj_idx, target_ind, cut_len, iters, obs_skip, n_obs_pool: int, retire: '_lib.RetireC',
