@@ -21,7 +21,8 @@
  *     mpcx_closed_loop_run_scene; letting vehicles in on a schedule is admission: mpcx_admit, mpcx_closed_loop_run_admit; re-using a
  *     departed agent's slot for the next vehicle is respawn: mpcx_respawn, mpcx_closed_loop_run_respawn.  Who yields to whom at the crossing is
  *     right of way: mpcx_precedence, mpcx_closed_loop_run_precedence.  A route per vehicle of such a slot is mpcx_routes,
- *     mpcx_closed_loop_run_routes; mpcx_episode_summary reduces the episode table per instance and route.
+ *     mpcx_closed_loop_run_routes; mpcx_episode_summary reduces the episode table per instance and route.  Holding agents at the stop
+ *     lines of a signalised crossing is mpcx_signals, mpcx_closed_loop_run_signals.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -733,6 +734,60 @@ int32_t mpcx_admit_step_batch_precedence(mpcx_ctx *ctx, const mpcx_interaction_p
                                          int32_t n_actors, const mpcx_traffic_actor *actors /*n_actors*/, const double *actor_state /*n_actors,4*/,
                                          const double *tape /*rows,6 or NULL*/, int64_t tape_rows, const int32_t *actor_row /*n_actors*/,
                                          const mpcx_admit *admit, const mpcx_precedence *precedence /*or NULL*/);
+
+/* ---- traffic signals: agents are held at stop lines.  A signalised crossing separates conflicting movements in time, and a car that must
+ * wait does so at a stop line outside the crossing.  The reference holds an ego by ending its path in front of a conflict
+ * (tmp_trajectory = trajectory_full[:cutoff_idx]); a red light is a conflict at a known point of the agent's own path, so the rule is one
+ * small stage directly behind the conflict search (signal_kernel, csrc/mpcx_signal.hip; the rule is csrc/mpcx_signal_core.h) that
+ * shortens cut_len -- the cut length, or the stop index in MPCX_STOP_SPEED -- and touches nothing else.
+ * Stop lines are a property of PATH POINTS, two int32 tables parallel to the descriptor's path tables: path_stop[i] is the route-local
+ * index s of the next stop-line point at or after point i (-1: none ahead), path_group[i] that line's signal group (0 .. n_groups - 1,
+ * n_groups <= MPCX_SIGNAL_GROUPS_MAX = 16).  Plans -- a table, so that a sweep of signal timings runs as one batch --: plan_cycle[n_plans]
+ * (steps, >= 1), plan_amber[n_plans] (steps, >= 0), plan_green[n_plans][n_groups][2] = (green_from in [0, cycle), green_len >= 0, with
+ * green_len + amber <= cycle), plan_of[P] the plan of agent q.  The clock is one word per agent, tick[P]: agent q's lane reads t = tick[q]
+ * reduced into [0, cycle) and writes back t + 1 wrapped at cycle, in every step whether the agent drives or not; an offset is the initial
+ * tick.  Light of group g at t: u = t - green_from (+ cycle if negative); GREEN if u < green_len, AMBER if u < green_len + amber, else RED.
+ * Per agent q after the tick: done[q] (retirement) -> held[q] = 0 and nothing else.  With i = path_off[q] + traj_idx[q] (traj_idx as this
+ * step's conflict search left it), s = path_stop[i], g = path_group[i] the agent is FREE (held[q] = 0) with no line ahead (s < 0), on or
+ * past the line (traj_idx[q] >= s) or with a defective entry (i outside [0, n_points), g or plan_of[q] out of range, s >= path_len[q]).
+ * Otherwise GREEN: free; RED: held[q] = 1; AMBER: held[q] = 2 if held[q] was nonzero already or if the car can stop,
+ * (s - traj_idx[q]) * dl >= v * v / (2 * brake) with v = state[q][2], else free.  held is in-out (the decision in amber is sticky) and
+ * zero-initialised by the caller.  A held agent gets cut_len[q] = min(cut_len[q], s): its path ends on the point before the line.
+ * hit_idx and hit_xy stay the conflict search's.  The defining property: a step with signals equals the step without them in which, for
+ * every held agent, the cut length / stop index the conflict search produced is replaced by its minimum with s before the window stage.
+ * (The conflict search has filed the agent in the QP work queue under a key computed from the cut before this stage: that affects the
+ * queue order only, never a result.  In speed mode a stop index equal to 999 reads as "no stop", as in the reference.)
+ * The struct travels beside the descriptor (no other struct changes size); the cached graph's key covers it by value.  signals = NULL or
+ * an all-zero struct: mpcx_closed_loop_run_precedence itself -- the same launches with the same arguments.  MPCX_E_INVALID
+ * ("signals: ...") before anything is launched, whatever n_steps is: a NULL pointer; n_groups outside 1..16; n_plans < 1 or n_points < 1;
+ * brake not finite or not positive; a plan with cycle < 1, amber < 0, green_from outside [0, cycle), green_len < 0 or green_len + amber >
+ * cycle (the three plan tables are read back once per call; the per-agent and per-point tables are not -- the kernel's own tests cover
+ * them); the agent-sharded layout; more than one linearisation pass.  Works with scripted traffic, the run log, retirement, scene,
+ * admission, respawn, routes, precedence, both stop modes and use_graph, and needs none of them. */
+#define MPCX_SIGNAL_GROUPS_MAX 16
+typedef struct {
+    const int32_t *path_stop;    /* n_points: route-local index of the next stop line at or after this path point, -1 = none ahead */
+    const int32_t *path_group;   /* n_points: that line's signal group */
+    const int32_t *plan_cycle;   /* n_plans: cycle length in steps, >= 1 */
+    const int32_t *plan_amber;   /* n_plans: amber length in steps, >= 0 */
+    const int32_t *plan_green;   /* n_plans x n_groups x 2: (green_from, green_len) */
+    const int32_t *plan_of;      /* P: the plan of agent q */
+    int32_t *tick;               /* P, caller-owned, in-out: the agent's clock */
+    int32_t *held;               /* P, caller-owned, in-out, zero-initialised: 0 free, 1 held at red, 2 held at amber */
+    double brake;                /* the deceleration (> 0, m/s^2) an agent is trusted to stop with in amber */
+    int32_t n_points, n_plans, n_groups, reserved;   /* reserved: 0 */
+} mpcx_signals;
+int32_t mpcx_closed_loop_run_signals(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                     const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                     const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                     const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                     const mpcx_routes *routes /*or NULL*/, const mpcx_precedence *precedence /*or NULL*/,
+                                     const mpcx_signals *signals /*or NULL*/, int32_t n_steps, int32_t use_graph);
+/* one step's signal stage alone (what mpcx_closed_loop_run_signals enqueues between the conflict search and the window stage): cut_len is
+ * the conflict search's output of this step, in-out; done: mpcx_retire::done or NULL.  The struct is checked as above. */
+int32_t mpcx_signal_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
+                               const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
+                               const int32_t *done /*P or NULL*/, const mpcx_signals *signals);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

@@ -97,6 +97,18 @@ PRECEDENCE_WINDOW = 64                          # MPCX_PRECEDENCE_WINDOW: the en
 PRECEDENCE_MAX_STEP = (2 ** 31 - 1 - (PRECEDENCE_WINDOW - 1)) // PRECEDENCE_WINDOW      # the largest entered_step whose word fits
 
 
+class SignalsC(C.Structure):
+    """mirror of mpcx_signals (include/mpcx.h): traffic signals; every pointer is a device address -- path_stop / path_group (n_points int32),
+    plan_cycle / plan_amber (n_plans int32), plan_green (n_plans x n_groups x 2 int32), plan_of / tick / held (P int32)"""
+    _fields_ = [('path_stop', C.c_void_p), ('path_group', C.c_void_p), ('plan_cycle', C.c_void_p), ('plan_amber', C.c_void_p),
+                ('plan_green', C.c_void_p), ('plan_of', C.c_void_p), ('tick', C.c_void_p), ('held', C.c_void_p), ('brake', C.c_double),
+                ('n_points', C.c_int32), ('n_plans', C.c_int32), ('n_groups', C.c_int32), ('reserved', C.c_int32)]
+
+
+SIGNAL_GROUPS_MAX = 16                          # MPCX_SIGNAL_GROUPS_MAX
+HELD_FREE, HELD_RED, HELD_AMBER = 0, 1, 2       # mpcx_signals.held
+
+
 # the words of an episode record (ep_i32[q][g][0..6]; word 7 is 0, with routes the episode's route: EPISODE_ROUTE_WORD; ep_f64[q][g][0], one
 # reserved)
 EPISODE_I32 = ('entered', 'arrived', 'steps_driven', 'row_end', 'contact_step', 'flags', 'due')
@@ -167,7 +179,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
            'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
            'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
-           'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence']
+           'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence',
+           'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch']
 
 
 def load():
@@ -272,5 +285,11 @@ def load():
     lib.mpcx_admit_step_batch_precedence.restype = i32
     lib.mpcx_admit_step_batch_precedence.argtypes = [vp, C.POINTER(InteractionParamsC), i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp,
                                                      C.c_int64, vp, C.POINTER(AdmitC), C.POINTER(PrecedenceC)]
+    lib.mpcx_closed_loop_run_signals.restype = i32
+    lib.mpcx_closed_loop_run_signals.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                 C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                 C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC), i32, i32]
+    lib.mpcx_signal_step_batch.restype = i32
+    lib.mpcx_signal_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC)]
     _lib = lib
     return lib

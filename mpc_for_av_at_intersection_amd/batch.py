@@ -30,6 +30,9 @@ approach arm; episode_routes() and movement_summary() read the run per movement,
 `give_way(order)` is RIGHT OF WAY: every pool row has a precedence word, and an agent sees the cars whose word is larger than its own as
 standing cars at their present pose -- which ends the mutual wait of yield-to-everybody at the crossing; order='entry' is first come, first
 served, stamped on the device as vehicles are admitted.
+`signalise(plans)` puts TRAFFIC SIGNALS on the crossing: stop lines are a property of path points (stop_lines()), a plan gives every signal
+group its green within a cycle (two_phase_plan()), and one more small launch behind the conflict search holds an agent whose light is red
+-- or amber, if it can still stop -- at its line by cutting its path there; a table of plans runs a sweep of timings as one batch.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -340,6 +343,10 @@ class IntersectionBatch:
         self.prec: Optional[torch.Tensor] = None             # give_way(): int32 (pool rows,), the precedence words, a smaller word goes first
         self.stand: Optional[torch.Tensor] = None            # ... float64 (pool rows, 4), the standing records (scratch)
         self._precedence = None
+        self.tick: Optional[torch.Tensor] = None             # signalise(): int32 (P,), every agent's signal clock
+        self.held: Optional[torch.Tensor] = None             # ... int32 (P,), 0 free, 1 held at red, 2 held at amber
+        self._signals = None
+        self._signal_tabs = None                             # ... the device tables the struct names (kept alive here)
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -632,6 +639,66 @@ class IntersectionBatch:
         self._precedence = None
         self._desc = None
 
+    def signalise(self, plans, plan_of=None, stop=None, group=None, offset=None, brake: Optional[float] = None):
+        """TRAFFIC SIGNALS (mpcx_closed_loop_run_signals).  One more small launch behind the conflict search holds an agent at its stop
+        line while its light is red -- or amber, if it can still stop with `brake` or was held already --: the agent's path is cut on the point
+        before the line (speed mode: its stop index is lowered to the line), exactly what the conflict search does in front of a conflict, so
+        every later stage does the right thing; a conflict cut in front of the line is kept.
+        plans: one plan or a sequence of plans, each dict(cycle, amber, green) with green of shape (n_groups, 2) = (green_from, green_len)
+        per signal group, in steps (two_phase_plan() builds one); plan_of: the plan of every instance (B,) or agent (B, A) / (P,), default
+        plan 0 -- a sweep of timings runs as one batch.  stop, group: the per-path-point tables (default: stop_lines() of the batch's
+        routes).  offset: the initial signal clock per instance (B,) or agent (B, A) / (P,), default 0.  brake: default abs(MAX_DECEL) of the
+        batch's parameters.
+        Allocates `tick`, `held` (zero) and the tables and drops the cached descriptor.  Needs none of the other options and works with all
+        of them; unsignalise() switches it off."""
+        if isinstance(plans, dict):
+            plans = [plans]
+        plans = list(plans)
+        if not plans:
+            raise ValueError('signalise: at least one plan')
+        green = [np.asarray(pl['green'], dtype=np.int64) for pl in plans]
+        if any(g.ndim != 2 or g.shape != green[0].shape or g.shape[1] != 2 for g in green):
+            raise ValueError('signalise: every plan\'s green has shape (n_groups, 2), the same n_groups in all plans')
+        n_groups = int(green[0].shape[0])
+        if not 1 <= n_groups <= _lib.SIGNAL_GROUPS_MAX:
+            raise ValueError('signalise: %d signal groups, 1 .. %d' % (n_groups, _lib.SIGNAL_GROUPS_MAX))
+        n_points = int(self.path.shape[0])
+        if stop is None or group is None:
+            if stop is not None or group is not None:
+                raise ValueError('signalise: give both stop and group, or neither')
+            routes = [self._route_table[self._route_offs[k]:self._route_offs[k + 1]] for k in range(len(self._route_offs) - 1)]
+            stop, group = stop_lines(routes)
+        stop, group = np.asarray(stop), np.asarray(group)
+        if stop.shape != (n_points,) or group.shape != (n_points,):
+            raise ValueError('signalise: stop and group hold one word per path point (%d)' % n_points)
+
+        def per_agent(v, name, default):
+            if v is None:
+                return np.full(self.P, default, dtype=np.int64)
+            v = np.asarray(v)
+            if not np.issubdtype(v.dtype, np.integer) or v.shape not in ((self.B,), (self.B, self.A), (self.P,)):
+                raise ValueError('signalise: %s is an integer array of shape (B,) = (%d,), (B, A) or (P,)' % (name, self.B))
+            return (np.repeat(v, self.A) if v.shape == (self.B,) and self.B != self.P else v.reshape(-1)).astype(np.int64)
+        plan_of, offset = per_agent(plan_of, 'plan_of', 0), per_agent(offset, 'offset', 0)
+        brake = abs(float(self.params.max_decel)) if brake is None else float(brake)
+        c = self.ctx
+        tabs = dict(path_stop=c.i32(stop), path_group=c.i32(group), plan_cycle=c.i32(np.array([int(pl['cycle']) for pl in plans])),
+                    plan_amber=c.i32(np.array([int(pl['amber']) for pl in plans])), plan_green=c.i32(np.stack(green)), plan_of=c.i32(plan_of))
+        self.tick = c.i32(offset)
+        self.held = torch.zeros(self.P, dtype=torch.int32, device=c.device)
+        self._signal_tabs = tabs
+        self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), tabs['plan_cycle'].data_ptr(),
+                                      tabs['plan_amber'].data_ptr(), tabs['plan_green'].data_ptr(), tabs['plan_of'].data_ptr(),
+                                      self.tick.data_ptr(), self.held.data_ptr(), brake, n_points, len(plans), n_groups, 0)
+        self._desc = None
+        c.synchronize()
+
+    def unsignalise(self):
+        """switch the signals off and nothing else: the batch enqueues exactly the launches of one that never had them (`tick` and `held`
+        keep what they hold and are no longer read or written)"""
+        self._signals = None
+        self._desc = None
+
     def stop_respawning(self):
         """switch respawn off and nothing else: the batch enqueues exactly the launches of one with admission alone.  Vehicles in flight
         finish (and stay departed), waiting ones still enter; `served` and the episode table keep what they hold.  Routing goes with it: a
@@ -781,7 +848,7 @@ class IntersectionBatch:
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
                                  retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes,
-                                 precedence=self._precedence)
+                                 precedence=self._precedence, signals=self._signals)
         self.steps_done += n_steps
 
     def step(self):
@@ -828,6 +895,8 @@ class IntersectionBatch:
         c.interaction(self.ip, self.state, self.path, self.path_cs, self.path_off, self.path_len,
                       self.prev_len if speed else self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self.obs_skip,
                       self.traj_idx, out=self.inter)
+        if self._signals is not None:       # the signal stage: between the conflict search and the window stage, as in the loop
+            c.signal_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals)
         # the previous solution (zeros where the last solve failed or on the first step) is the warm start
         for it in range(self.lin_passes):       # lib/mpc.py:226-237: from the second pass on the previous pass's speeds space the window
             if speed:       # the whole path + the stop index (mpcx_mpc_prepare_batch_stop).  len_seen is a side effect the NEXT step
@@ -870,16 +939,63 @@ class IntersectionBatch:
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         if self._precedence is not None:     # the precedence word of every pool row (a smaller word goes first)
             out['precedence'] = self.prec.cpu().numpy().copy()
+        if self._signals is not None:        # 0 free, 1 held at red, 2 held at amber, as the last step's signal stage left it
+            out['held'] = self.held.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:
         """speed mode: the agents' stop indices of the last step in the reference's own terms (the `cutoff_idx` of
         mpc_intersection_new_ref.py:122-139): the conflict search's cut index where it found a conflict, _lib.NO_STOP (999) where it
-        did not (synchronises).  The device keeps the path length for "no conflict" -- a stop index nothing reaches."""
+        did not (synchronises).  The device keeps the path length for "no conflict" -- a stop index nothing reaches.  With signals on, an
+        agent held at its stop line (held != 0) reports its stop index too: the line, or a conflict in front of it."""
         if self.stop_mode != 'speed':
             raise MpcxError('stop_index(): the batch runs with stop_mode=%r' % self.stop_mode)
         self.ctx.synchronize()
-        return np.where(self.inter['hit_idx'].cpu().numpy() >= 0, self.inter['cut_len'].cpu().numpy(), _lib.NO_STOP).astype(np.int32)
+        stops = self.inter['hit_idx'].cpu().numpy() >= 0
+        if self._signals is not None:
+            stops = stops | (self.held.cpu().numpy() != 0)
+        return np.where(stops, self.inter['cut_len'].cpu().numpy(), _lib.NO_STOP).astype(np.int32)
+
+
+def stop_lines(routes, half_width: float = 12.0, setback: float = 6.0):
+    """The two per-path-point tables of IntersectionBatch.signalise for `routes` (a list of (n, 3) paths, concatenated in order as the batch
+    concatenates them): (path_stop, path_group), int32, one word per path point.  The crossing is the square max(|x|, |y|) <= half_width
+    about the origin (the stock crossing: distance_center 12).  The stop line of a route is the last point that lies at least `setback`
+    metres of arc before the route's first point inside the square; path_stop of every point up to and including the line is the line's
+    route-local index, -1 behind it (and everywhere on a route that starts inside the square, never enters it or has no such point).  The
+    signal group is the approach arm minus one, taken from the route's first point: 0 = from the south (y most negative; arm 1 of the stock
+    scenario), 1 = from the west (arm 2), 2 = from the north (arm 3), 3 = from the east (arm 4).  path_group is the group on every point
+    that has a line ahead, 0 elsewhere.  Pure numpy: no GPU, no state."""
+    stop, group = [], []
+    for r in routes:
+        r = np.asarray(r, dtype=np.float64)
+        n = len(r)
+        st, gr = np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        inside = np.flatnonzero(np.maximum(np.abs(r[:, 0]), np.abs(r[:, 1])) <= half_width)
+        if n and len(inside) and inside[0] > 0:
+            arc = np.concatenate([[0.0], np.cumsum(np.hypot(np.diff(r[:, 0]), np.diff(r[:, 1])))])
+            ok = np.flatnonzero(arc[:inside[0]] <= arc[inside[0]] - setback)
+            if len(ok):
+                x0, y0 = r[0, 0], r[0, 1]
+                arm = (0 if y0 < 0 else 2) if abs(y0) >= abs(x0) else (1 if x0 < 0 else 3)
+                st[:ok[-1] + 1] = ok[-1]
+                gr[:ok[-1] + 1] = arm
+        stop.append(st); group.append(gr)
+    if not stop:
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+    return np.concatenate(stop), np.concatenate(group)
+
+
+def two_phase_plan(cycle: int, green: int, amber: int) -> dict:
+    """A two-phase plan for the four signal groups of stop_lines(): dict(cycle, amber, green (4, 2)).  Groups 0 and 2 (arms 1 and 3, the
+    south-north road) share the first phase, green from step 0; groups 1 and 3 (arms 2 and 4) share the second, green from step cycle // 2;
+    each green lasts `green` steps and is followed by `amber` steps of amber.  What is left of a half cycle is the all-red gap that clears
+    the crossing: cycle // 2 - green - amber >= 0 steps."""
+    cycle, green, amber = int(cycle), int(green), int(amber)
+    half = cycle // 2
+    if cycle < 2 or green < 0 or amber < 0 or green + amber > half:
+        raise ValueError('two_phase_plan: green + amber = %d + %d must fit half a cycle of %d steps' % (green, amber, cycle))
+    return dict(cycle=cycle, amber=amber, green=np.array([[0, green], [half, green], [0, green], [half, green]], dtype=np.int32))
 
 
 def entry_schedule(route_of_agent, routes, start_index, mean_headway_steps: float, seed: int) -> np.ndarray:
