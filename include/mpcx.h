@@ -381,6 +381,16 @@ int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, c
  * print per run: solver failures; plus iteration counts): out4 = (agent-steps, interior-point iterations, failed solves, max iterations).
  * Synchronises the context's stream. */
 int32_t mpcx_closed_loop_stats(mpcx_ctx *ctx, int64_t *out4 /*host*/, int32_t reset);
+/* the QP work queue as the last step of mpcx_closed_loop_run with P agents left it (for tests of the queue's order): order[i] = the agent
+ * in place i of the queue, keyslot[p] = (queue key << 24 | slot) under which the conflict search filed agent p (stale for an agent that was
+ * not filed in that step).  Both host arrays of P words.  MPCX_E_INVALID if no closed loop has built a queue for at least P agents.
+ * Synchronises the context's stream. */
+int32_t mpcx_closed_loop_queue(mpcx_ctx *ctx, int32_t P, int32_t *order /*host, P*/, int32_t *keyslot /*host, P*/);
+/* the obstacle prediction the last conflict search on this context worked from (for tests of the prediction): out[row][frame][disc][x, y],
+ * rows x steps x 2 x 2 doubles, for the first `rows` pool rows and the pred_steps = `steps` of that call.  A row that was not predicted
+ * (absent, or outside every window under scripted traffic) holds what an earlier call left.  MPCX_E_INVALID if no prediction that large
+ * has been made.  Synchronises the context's stream. */
+int32_t mpcx_interaction_prediction(mpcx_ctx *ctx, int32_t rows, int32_t steps, double *out /*host, rows*steps*4*/);
 
 /* ---- the run log: what the reference's own loop produces ABOUT a run -- HistorySimulation's rows (lib/simulation.py:58-88 with
  * get_current_xref_deviation, lib/mpc.py:301-308), the end of the loop (mpc.is_goal, lib/mpc.py:310-326; mpc_intersection.py:97-98) --

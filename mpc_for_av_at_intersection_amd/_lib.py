@@ -180,7 +180,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
            'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
            'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence',
-           'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch']
+           'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction']
 
 
 def load():
@@ -238,6 +238,8 @@ def load():
     lib.mpcx_comm_destroy.restype = i32; lib.mpcx_comm_destroy.argtypes = [vp]
     lib.mpcx_allgather_states.restype = i32; lib.mpcx_allgather_states.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.mpcx_closed_loop_stats.restype = i32; lib.mpcx_closed_loop_stats.argtypes = [vp, C.POINTER(C.c_int64), i32]
+    lib.mpcx_closed_loop_queue.restype = i32; lib.mpcx_closed_loop_queue.argtypes = [vp, i32, vp, vp]
+    lib.mpcx_interaction_prediction.restype = i32; lib.mpcx_interaction_prediction.argtypes = [vp, i32, i32, vp]
     lib.mpcx_traffic_step_batch.restype = i32; lib.mpcx_traffic_step_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int64, vp, i32, vp]
     lib.mpcx_record_step_batch.restype = i32
     lib.mpcx_record_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 12 + [i32] + [vp] * 4 + [C.POINTER(RunLogC)]

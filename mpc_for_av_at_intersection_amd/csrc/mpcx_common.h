@@ -318,6 +318,28 @@ __device__ __forceinline__ T wave_min_i(T v) {
     return v;
 }
 
+// A recurrence acc_i = f(acc_{i-1}, term_i) over the G consecutive lanes of a group (G a power of two, lane j of the group holds term_j),
+// evaluated strictly in index order: every lane runs the whole chain on shuffled terms -- the same operations on the same operands as one
+// lane walking it alone, so the same bits -- and keeps the value of its own index.  Returns acc_j; leaves acc = acc_{G-1} in every lane,
+// the carry into the group's next G indices.  What is expensive per index (sincos, tan, divide) goes into the terms, one index per lane;
+// only f, an addition or so, is serial.  SAME: the term is the same in every lane (no shuffle).
+template <int G, bool SAME = false, class F>
+__device__ __forceinline__ double group_chain(double &acc, double term, int j, F f) {
+    double mine = acc;
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+        acc = f(acc, SAME ? term : __shfl(term, i, G));
+        mine = i == j ? acc : mine;
+    }
+    return mine;
+}
+// the value the previous index left: lane j - 1's, or `first` in lane 0 of the group
+template <int G>
+__device__ __forceinline__ double group_prev(double v, double first, int j) {
+    const double up = __shfl_up(v, 1, G);
+    return j == 0 ? first : up;
+}
+
 // trajectories.py:11-37: centre (ex, ey) of the disc at (cx, cy) in the frame of a pose at (px, py) whose heading has cos / sin (c, s)
 __device__ __forceinline__ void disc_centre(double px, double py, double c, double s, double cx, double cy, double &ex, double &ey) {
     ex = __dadd_rn(__dadd_rn(__dmul_rn(c, cx), -__dmul_rn(s, cy)), px);

@@ -1006,6 +1006,17 @@ int32_t mpcx_ensure_pred(mpcx_ctx *ctx, size_t need) {
     return mpcx_grow(ctx, (void **)&ctx->pred, &ctx->pred_cap, need * sizeof(double), "the prediction scratch");
 }
 
+extern "C" int32_t mpcx_interaction_prediction(mpcx_ctx *ctx, int32_t rows, int32_t steps, double *out) {
+    if (!ctx || !out || rows < 0 || steps < 1 || steps > MPCX_PRED_STEPS_MAX) return MPCX_E_INVALID;
+    const size_t bytes = (size_t)rows * steps * 4 * sizeof(double);
+    if (!ctx->pred || ctx->pred_cap < bytes)
+        return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_prediction: no prediction of %d rows x %d frames has been made on this context", rows, steps);
+    if (rows == 0) return MPCX_OK;
+    if (hipMemcpyAsync(out, ctx->pred, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return mpcx_fail(ctx, MPCX_E_LAUNCH, "interaction_prediction: copy failed");
+    return MPCX_OK;
+}
+
 extern "C" int32_t mpcx_moving_collision_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P,
                                                const double *ego_xyyaw, const double *ego_cs, const int32_t *ego_off,
                                                const int32_t *ego_len, const double *path_xyyaw, const double *path_cs,

@@ -1,12 +1,12 @@
 // mpcx_prepare.hip -- reference window, warm-start rollout and plant update, batched.
 //
 // Replaces (paths relative to /root/reference/main):
-//   lib/mpc.py:86-109   _calc_ref_trajectory      -> ref_window_kernel  (one wavefront per instance)
+//   lib/mpc.py:86-109   _calc_ref_trajectory      -> ref_window_kernel  (a run of T + 1 lanes per instance)
 //   lib/trajectories.py:100-126 calc_nearest_index_in_direction (inside the above)
-//   lib/mpc.py:112-126  _predict_motion            -> rollout_kernel     (one thread per instance)
+//   lib/mpc.py:112-126  _predict_motion            -> rollout_kernel     (a group of lanes per instance)
 //   lib/simulation.py:35-47 Simulation.step + bicycle/main.py:28-41      -> plant_kernel / rollout
 // Arithmetic follows the reference's operation order; products are kept un-fused (-ffp-contract is
-// irrelevant here because every product/sum below goes through __dmul_rn/__dadd_rn where order matters).
+// irrelevant to the window's gathers; the plant's Euler updates are fused multiply-adds, see plant_euler).
 #include "mpcx_common.h"
 #include <cmath>
 
@@ -42,91 +42,146 @@ struct RefArgs {
 
 // RETIRE: the closed loop with retirement at the goal (mpcx_retire) -- a template parameter, not a null test: the launch without
 // retirement runs the code it ran before there was any
+//
+// A wavefront takes WIN_AGENTS consecutive agents, a workgroup PREP_WAVES wavefronts.  (Until this layout every agent had a wavefront of
+// its own, which summed the 16 x 64 queue counters again -- 134 MB of L2 reads per launch for a 4-KB table -- and then used T + 1 of its
+// 64 lanes.)  Three parts:
+//  1. per agent, lane i = agent b0 + i: its scalars, its place in the queue order, the nearest-index hint;
+//  2. the agents whose hint misses: calc_nearest_index_in_direction by the whole wavefront, one agent at a time;
+//  3. the windows, floor(64 / (T + 1)) agents per pass, each on a run of T + 1 lanes of its own.
+constexpr int PREP_WAVES = 4;
+constexpr int WIN_AGENTS = 8;
+static_assert(WIN_AGENTS <= WAVE, "one lane per agent in parts 1 and 2");
 template <bool RETIRE>
-__device__ __forceinline__ void ref_window_block(const RefArgs &a, int b) {
-    const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(64 * PREP_WAVES) void ref_window_kernel(RefArgs a) {
+    // s_first[q][k] = the place in the queue of the first agent with key k that counted in copy q of the bins: the agents with a larger
+    // key (suffix sums over the bins) + those with the same key in a lower copy.  Built once per workgroup
+    __shared__ int s_first[MPCX_ORDER_COPIES][MPCX_ORDER_BINS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int T = a.p.T, W = T + 1;
-    if (a.order) {
-        // lane k holds bin k.  Agents with a larger key come first (suffix sums over the bins by shuffles), then the agents of the same key
-        // that counted in a lower copy of the bins, then the slot the conflict search drew
-        static_assert(MPCX_ORDER_BINS == 64, "one bin per lane");
-        const int mine = b % MPCX_ORDER_COPIES;
-        int c = 0, lower = 0;
-#pragma unroll
-        for (int q = 0; q < MPCX_ORDER_COPIES; q++) {
-            const int v = a.bin_cnt[q * MPCX_ORDER_BINS + lane];
-            c += v;
-            lower += q < mine ? v : 0;
-        }
-        int sfx = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_down(sfx, d); sfx += lane + d < 64 ? o : 0; }
-        if constexpr (RETIRE) {
-            // lane 0's suffix sum is the sum of all bins over all copies = the agents the conflict search filed = the length of this step's
-            // queue.  The first wavefront of the launch leaves it for the solve, whether its own agent is retired or not
-            if (b == 0 && lane == 0) *a.queue_len = sfx;
-            if (a.done[b] != 0) return;       // retired: no place in the order, no output, len_seen untouched
-        }
-        const int ks = a.keyslot[b];
-        const int first = __shfl(sfx - c + lower, ks >> 24);
-        if (lane == 0) a.order[first + (ks & 0xFFFFFF)] = b;
-    }
-    const double *path = a.path + 3 * (size_t)a.path_off[b];
-    const double *pv = a.path_v ? a.path_v + (size_t)a.path_off[b] : nullptr;   // mpc_with_speed.py:103-104
-    const int n = a.path_len[b];
+    const int b0 = ((int)blockIdx.x * PREP_WAVES + wave) * WIN_AGENTS;
+    const int nag = a.B - b0 < WIN_AGENTS ? a.B - b0 : WIN_AGENTS;       // agents of this wavefront (<= 0: none, it only keeps the barrier)
+    // ---- part 1: lane i < nag holds agent b0 + i (the other lanes read agent 0 and write nothing)
+    const bool own = lane < nag;
+    const int b = own ? b0 + lane : 0;
+    bool gone = !own;
+    if constexpr (RETIRE) gone = gone || a.done[b] != 0;       // retired: no place in the order, no output, len_seen untouched
+    const int off = a.path_off[b], n = a.path_len[b];
     const double x = a.state[4 * b], y = a.state[4 * b + 1], v = a.state[4 * b + 2];
-    int start = a.target_ind[b];
+    const int start = a.target_ind[b];
+    // (everything an agent reads is asked for here, in front of the barrier: one round trip to memory instead of one per dependent step)
+    const int ks = a.order ? a.keyslot[b] : 0;
+    const int hs = a.near ? a.near[3 * b] : -1, hm = a.near ? a.near[3 * b + 1] : -1, hl = a.near ? a.near[3 * b + 2] : -1;
+    const int hint = a.near ? a.near_tidx[b] : -1;
+    const int stop_at = a.stop_idx ? a.stop_idx[b] : MPCX_NO_STOP;
+    if (a.order) {
+        static_assert(MPCX_ORDER_BINS == 64, "one bin per lane");
+        if (wave == 0) {        // lane k holds bin k
+            int cnt[MPCX_ORDER_COPIES], c = 0;
+#pragma unroll
+            for (int q = 0; q < MPCX_ORDER_COPIES; q++) { cnt[q] = a.bin_cnt[q * MPCX_ORDER_BINS + lane]; c += cnt[q]; }
+            int sfx = c;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_down(sfx, d); sfx += lane + d < 64 ? o : 0; }
+            // lane 0's suffix sum is the sum of all bins over all copies = the agents the conflict search filed = the length of this step's
+            // queue.  The first wavefront of the launch leaves it for the solve
+            if constexpr (RETIRE) { if (blockIdx.x == 0 && lane == 0) *a.queue_len = sfx; }
+            int first = sfx - c;
+#pragma unroll
+            for (int q = 0; q < MPCX_ORDER_COPIES; q++) { s_first[q][lane] = first; first += cnt[q]; }
+        }
+        __syncthreads();
+        if (!gone)              // ... then the slot the conflict search drew
+            a.order[s_first[b % MPCX_ORDER_COPIES][(ks >> 24) & (MPCX_ORDER_BINS - 1)] + (ks & 0xFFFFFF)] = b;
+    }
     // The three nearest points of path[start .. n) are those of the conflict search's scan over path[hs .. len) whenever this range lies
     // inside that one (start >= hs) and holds all three (the three smallest of a set are the three smallest of every subset that contains
     // them; ties go to the lower index in both; the answer is a function of their absolute indices): then the answer is the conflict
     // search's and the scan is skipped.  Else (an earlier start, a cut in front of one of the three, an ego that did not advance): scan.
-    int s;
-    const int hs = a.near ? a.near[3 * b] : -1, hm = a.near ? a.near[3 * b + 1] : -1, hl = a.near ? a.near[3 * b + 2] : -1;
-    if (hm >= 0 && start >= hs && hl >= start && hm < n) s = a.near_tidx[b];
-    else s = (start < 0 || n <= 0) ? -1 : nearest_index_in_direction(path, n, start, x, y, lane);
-    if (lane == 0) a.target_ind[b] = s;
+    int s = -1;
+    bool scan = false;
+    if (!gone) {
+        if (hm >= 0 && start >= hs && hl >= start && hm < n) s = hint;
+        else scan = !(start < 0 || n <= 0);
+    }
+    // ---- part 2: the scans, wave-cooperative, under a wave-uniform condition
+    for (unsigned long long todo = __ballot(scan); todo; todo &= todo - 1) {
+        const int i = __ffsll((long long)todo) - 1;
+        const int r = nearest_index_in_direction(a.path + 3 * (size_t)__shfl(off, i), __shfl(n, i), __shfl(start, i), __shfl(x, i), __shfl(y, i), lane);
+        s = lane == i ? r : s;
+    }
     int stop = 0x7fffffff;
-    if (a.stop_idx) {
-        const int c = a.stop_idx[b];
-        stop = c == MPCX_NO_STOP ? stop : c;
-        if (a.len_seen && lane == 0) a.len_seen[b] = n;
+    if (!gone) {
+        a.target_ind[b] = s;
+        stop = stop_at == MPCX_NO_STOP ? stop : stop_at;
+        if (a.stop_idx && a.len_seen) a.len_seen[b] = n;
     }
-    double *xr = a.xref + (size_t)b * 4 * W;
-    uint8_t *re = a.re + (size_t)b * W;
-    if (s < 0) {  // reference raised: leave a defined (zero) window, caller sees target_ind = -1
-        if (lane <= T) { xr[lane] = 0; xr[W + lane] = 0; xr[2 * W + lane] = 0; xr[3 * W + lane] = 0; re[lane] = 0; }
-        return;
-    }
-    // mpc.py:95-100: ov = max(v, 10/3.6); travel = cumsum(|ov|*dt); idx = min(rint(travel/dl) + s, n-1)
-    // from the second of MAX_ITER linearisation passes on, ov = the previous pass's speeds (mpc.py:226-237)
-    const double ov = v > 10.0 / 3.6 ? v : 10.0 / 3.6;
-    const double step = __dmul_rn(fabs(ov), a.p.dt);
-    const double *ovp = a.ov ? a.ov + (size_t)b * a.ov_stride : nullptr;
-    if (lane <= T) {
+    // ---- part 3: lane = (agent g of the pass, window point t)
+    const int G = 64 / W;
+    const int g = lane / W, t = lane - g * W;
+    for (int base = 0; base < nag; base += G) {
+        const int i = base + g;
+        const bool on = g < G && i < nag;
+        const int from = on ? i : 0;
+        const bool skip = __shfl((int)gone, from) != 0;
+        const int si = __shfl(s, from), ni = __shfl(n, from), oi = __shfl(off, from), stopi = __shfl(stop, from);
+        const double vi = __shfl(v, from);
+        if (!on || skip) continue;
+        const int bi = b0 + i;
+        const double *path = a.path + 3 * (size_t)oi;
+        const double *pv = a.path_v ? a.path_v + (size_t)oi : nullptr;   // mpc_with_speed.py:103-104
+        double *xr = a.xref + (size_t)bi * 4 * W;
+        uint8_t *re = a.re + (size_t)bi * W;
+        if (si < 0) {  // reference raised: leave a defined (zero) window, caller sees target_ind = -1
+            xr[t] = 0; xr[W + t] = 0; xr[2 * W + t] = 0; xr[3 * W + t] = 0; re[t] = 0;
+            continue;
+        }
+        // mpc.py:95-100: ov = max(v, 10/3.6); travel = cumsum(|ov|*dt); idx = min(rint(travel/dl) + s, n-1)
+        // from the second of MAX_ITER linearisation passes on, ov = the previous pass's speeds (mpc.py:226-237)
+        const double ov = vi > 10.0 / 3.6 ? vi : 10.0 / 3.6;
+        const double step = __dmul_rn(fabs(ov), a.p.dt);
+        const double *ovp = a.ov ? a.ov + (size_t)bi * a.ov_stride : nullptr;
         double travel = ovp ? __dmul_rn(fabs(ovp[0]), a.p.dt) : step;                       // np.cumsum: sequential adds
-        for (int k = 1; k <= lane; k++) travel = __dadd_rn(travel, ovp ? __dmul_rn(fabs(ovp[k]), a.p.dt) : step);
-        long long idx = (long long)rint(__ddiv_rn(travel, a.dl)) + s;
-        if (idx > n - 1) idx = n - 1;
-        xr[0 * W + lane] = path[3 * idx];
-        xr[1 * W + lane] = path[3 * idx + 1];
-        xr[2 * W + lane] = idx >= stop ? 0.0 : (pv ? pv[idx] : a.v_ref);
-        xr[3 * W + lane] = path[3 * idx + 2];
-        re[lane] = (idx == n - 1);
+        for (int k = 1; k <= t; k++) travel = __dadd_rn(travel, ovp ? __dmul_rn(fabs(ovp[k]), a.p.dt) : step);
+        long long idx = (long long)rint(__ddiv_rn(travel, a.dl)) + si;
+        if (idx > ni - 1) idx = ni - 1;
+        xr[0 * W + t] = path[3 * idx];
+        xr[1 * W + t] = path[3 * idx + 1];
+        xr[2 * W + t] = idx >= stopi ? 0.0 : (pv ? pv[idx] : a.v_ref);
+        xr[3 * W + t] = path[3 * idx + 2];
+        re[t] = (idx == ni - 1);
     }
 }
 
-// simulation.py:35-47 + bicycle/main.py:28-41
+// simulation.py:35-47 + bicycle/main.py:28-41.  The pieces of one step; plant_step puts them together for one lane, rollout_kernel
+// spreads them over a group of lanes.  Both evaluate these very expressions.  An Euler update acc + rate * dt is ONE fused multiply-add:
+// that is what hipcc's default contraction has always made of it here (HIP's __dadd_rn / __dmul_rn are plain operators that fuse after
+// inlining), and the results are compared bit for bit with that.  It is written out, with contraction off for everything else, so that
+// the grouping of the operations cannot change it
+__device__ __forceinline__ double plant_tan(const mpcx_mpc_params &p, double delta) {          // tan of the clamped steering angle
+    return tan(fmax(fmin(delta, p.max_steer), -p.max_steer));
+}
+__device__ __forceinline__ double plant_rate_xy(double v, double cs) {      // d/dt of x (cs = cos th) or y (cs = sin th)
+#pragma clang fp contract(off)
+    return v * cs;
+}
+__device__ __forceinline__ double plant_rate_th(const mpcx_mpc_params &p, double v, double tn) {      // d/dt of th
+#pragma clang fp contract(off)
+    return (v / p.L) * tn;
+}
+__device__ __forceinline__ double plant_euler(const mpcx_mpc_params &p, double acc, double rate) { return fma(rate, p.dt, acc); }
+__device__ __forceinline__ double plant_speed(const mpcx_mpc_params &p, double v, double a) {      // the speed after a step
+    return fmax(fmin(plant_euler(p, v, a), p.max_speed), p.min_speed);
+}
 __device__ __forceinline__ void plant_step(const mpcx_mpc_params &p, double &x, double &y, double &v, double &th,
                                            double a, double delta) {
-    delta = fmax(fmin(delta, p.max_steer), -p.max_steer);
+    const double tn = plant_tan(p, delta);
     double s, c;
     sincos(th, &s, &c);
-    const double xd = __dmul_rn(v, c), yd = __dmul_rn(v, s), td = __dmul_rn(__ddiv_rn(v, p.L), tan(delta));
-    x = __dadd_rn(x, __dmul_rn(xd, p.dt));
-    y = __dadd_rn(y, __dmul_rn(yd, p.dt));
-    th = __dadd_rn(th, __dmul_rn(td, p.dt));
-    v = __dadd_rn(v, __dmul_rn(a, p.dt));
-    v = fmax(fmin(v, p.max_speed), p.min_speed);
+    x = plant_euler(p, x, plant_rate_xy(v, c));
+    y = plant_euler(p, y, plant_rate_xy(v, s));
+    th = plant_euler(p, th, plant_rate_th(p, v, tn));
+    v = plant_speed(p, v, a);
 }
 
 struct RollArgs {
@@ -137,57 +192,69 @@ struct RollArgs {
     const int32_t *done;    // retirement (read by the RETIRE instantiation only): the row of an agent with done[b] != 0 is neither computed nor written
 };
 
-// Rollout of 64 instances by one wavefront (lane = instance: the reference's operation order, one dependent chain of T x (sincos, tan,
-// divide) per instance), results staged in LDS and written as ONE contiguous run: the 64 instances' xbar rows are adjacent in memory
-// (64 x 4 x (T+1) doubles).  Until round 3 every lane stored its doubles straight to memory, 8 bytes at a 4 (T+1) x 8-byte lane stride,
-// each its own write transaction: 165 MB of write traffic for 45 MB of output.
-// (round 4: the staging buffer is dynamic LDS sized for the horizon in use -- 43.5 KB at T = 20 instead of 68 KB for T = 32: this kernel runs
-// beside the conflict search on the side stream, and its two workgroups per CU left that kernel's 6.5-KB workgroups 24 KB of a CU's LDS)
+// Rollout of ROLL_AGENTS instances by one workgroup, a group of ROLL_GROUP lanes per instance, lane j of it the steps t = j, j + ROLL_GROUP,
+// ...: of plant_step's recurrence only the running values v_t (with its clamp), th_t, x_t, y_t are serial (group_chain: every lane of the
+// group walks them in step order); tan of the steering input, the divide in th's increment, sincos(th_t) and the products in x's and
+// y's increments are evaluated once, by the step's own lane.  (One lane per instance walked T dependent sincos + tan + divide: 29 us
+// beside the conflict search, which it cost 7 us.)  Results are staged in LDS and written as ONE contiguous run: the instances' xbar rows
+// are adjacent in memory (ROLL_AGENTS x 4 x (T+1) doubles); straight from the lanes they would be 8-byte stores at four strides.  The
+// staging buffer is dynamic LDS sized for the horizon in use: 43.5 KB at T = 20, 68 KB at T = 32, as much as one lane per instance
+// needed for its 64 instances.  Groups of 4 measured 20.1 us, of 8 26.7, of 16 109, of 32 195: every lane walks the whole chain.
 // RETIRE: a retired agent's xbar row stays as its last driven step left it (its state and inputs are frozen, so the row would come out
 // the same from the step after its arrival on -- but not the same as that last driven step's, which started one state earlier)
+constexpr int ROLL_GROUP = 4, ROLL_BLOCK = 256, ROLL_AGENTS = ROLL_BLOCK / ROLL_GROUP;
+static_assert(WAVE % ROLL_GROUP == 0 && ROLL_BLOCK % WAVE == 0, "whole groups per wavefront");
+inline size_t rollout_lds(int T) { return ROLL_AGENTS * (4 * (size_t)(T + 1) + 1) * sizeof(double); }
 template <bool RETIRE>
-__global__ __launch_bounds__(64) void rollout_kernel(RollArgs a) {
-    extern __shared__ double s_roll[];                   // [64][4 W + 1]; +1: rows of 4 W doubles would sit 8 lanes to a bank group
+__global__ __launch_bounds__(ROLL_BLOCK) void rollout_kernel(RollArgs a) {
+    constexpr int G = ROLL_GROUP;
+    extern __shared__ double s_roll[];                   // [ROLL_AGENTS][4 W + 1]; +1: rows of 4 W doubles would share their banks; it holds the row's "retired" flag
     const int T = a.p.T, W = T + 1;
     const int RS = 4 * W + 1;
-    auto s_x = [&](int lane) -> double * { return s_roll + (size_t)lane * RS; };
-    const int b0 = (int)blockIdx.x * 64;
-    const int n = a.B - b0 < 64 ? a.B - b0 : 64;
-    bool gone = false;
-    if constexpr (RETIRE) gone = threadIdx.x < (unsigned)n && a.done[b0 + (int)threadIdx.x] != 0;
-    if (threadIdx.x < (unsigned)n && !gone) {
-        const int b = b0 + (int)threadIdx.x;
+    auto s_x = [&](int row) -> double * { return s_roll + (size_t)row * RS; };
+    const int b0 = (int)blockIdx.x * ROLL_AGENTS;
+    const int n = a.B - b0 < ROLL_AGENTS ? a.B - b0 : ROLL_AGENTS;
+    const int r = (int)threadIdx.x / G, j = (int)threadIdx.x % G;
+    bool gone = r >= n;
+    if constexpr (RETIRE) gone = gone || a.done[b0 + r] != 0;
+    if (j == 0) s_x(r)[4 * W] = gone ? 1.0 : 0.0;
+    if (!gone) {            // (the same for every lane of a group)
+        const int b = b0 + r;
         double x = a.state[4 * b], y = a.state[4 * b + 1], v = a.state[4 * b + 2], th = a.state[4 * b + 3];
-        double *xb = s_x(threadIdx.x);
-        xb[0] = x; xb[W] = y; xb[2 * W] = v; xb[3 * W] = th;
+        double *xb = s_x(r);
+        if (j == 0) { xb[0] = x; xb[W] = y; xb[2 * W] = v; xb[3 * W] = th; }
         const double *oa = a.u_warm ? a.u_warm + (size_t)b * 2 * T : nullptr;
-        for (int t = 1; t <= T; t++) {
-            const double ai = oa ? oa[t - 1] : 0.0, di = oa ? oa[T + t - 1] : 0.0;   // mpc.py:222-224: zeros when no warm start
-            plant_step(a.p, x, y, v, th, ai, di);
-            xb[t] = x; xb[W + t] = y; xb[2 * W + t] = v; xb[3 * W + t] = th;
+        const auto euler = [&](double acc, double rate) { return plant_euler(a.p, acc, rate); };
+        const auto speed = [&](double vv, double acc) { return plant_speed(a.p, vv, acc); };
+        // x, y, v, th: the state at step t0, the same in every lane of the group; lane j takes the step from t = t0 + j to t + 1
+        for (int t0 = 0; t0 < T; t0 += G) {
+            const int t = t0 + j;
+            const bool in = t < T;
+            const double ai = oa && in ? oa[t] : 0.0, di = oa && in ? oa[T + t] : 0.0;   // mpc.py:222-224: zeros when no warm start
+            const double tn = plant_tan(a.p, di);
+            const double v0 = v, th0 = th;
+            const double vn = group_chain<G>(v, ai, j, speed);                  // v_{t+1}
+            const double vt = group_prev<G>(vn, v0, j);                         // v_t
+            const double thn = group_chain<G>(th, plant_rate_th(a.p, vt, tn), j, euler);
+            const double tht = group_prev<G>(thn, th0, j);
+            double s, c;
+            sincos(tht, &s, &c);
+            const double xn = group_chain<G>(x, plant_rate_xy(vt, c), j, euler);
+            const double yn = group_chain<G>(y, plant_rate_xy(vt, s), j, euler);
+            if (in) { xb[t + 1] = xn; xb[W + t + 1] = yn; xb[2 * W + t + 1] = vn; xb[3 * W + t + 1] = thn; }
         }
     }
     __syncthreads();
     double *out = a.xbar + (size_t)b0 * 4 * W;
-    if constexpr (RETIRE) {
-        const unsigned long long gm = __ballot(gone);       // one wavefront per block: bit l = lane l's agent is retired
-        for (int i = threadIdx.x; i < n * 4 * W; i += blockDim.x)
-            if (!((gm >> (i / (4 * W))) & 1ull)) out[i] = s_x(i / (4 * W))[i % (4 * W)];
-    } else
-        for (int i = threadIdx.x; i < n * 4 * W; i += blockDim.x) out[i] = s_x(i / (4 * W))[i % (4 * W)];
+    for (int i = threadIdx.x; i < n * 4 * W; i += ROLL_BLOCK) {
+        const int row = i / (4 * W);
+        if (!RETIRE || s_x(row)[4 * W] == 0.0) out[i] = s_x(row)[i - row * 4 * W];
+    }
 }
 
-// The two halves of mpc.py:211-239's preparation are independent -- the rollout is a chain of T dependent sincos / tan evaluations per
-// instance (44 us), the window selection a scan of the path (31 us) -- and run BESIDE each other: the rollout on the context's side
-// stream (fork / join by events, capturable into the closed loop's hipGraph), the window selection on the context's stream.  (Until
-// round 3 both were workgroups of one launch; the rollout's 68-KB staging buffer would have been allocated for every workgroup of it.)
-// Window workgroups of four wavefronts = four instances: fewer, larger workgroups to dispatch (57 -> 54 us).
-constexpr int PREP_WAVES = 4;
-template <bool RETIRE>
-__global__ __launch_bounds__(64 * PREP_WAVES) void ref_window_kernel(RefArgs ra) {
-    const int b = (int)blockIdx.x * PREP_WAVES + (threadIdx.x >> 6);
-    if (b < ra.B) ref_window_block<RETIRE>(ra, b);
-}
+// The two halves of mpc.py:211-239's preparation are independent and run BESIDE each other: the rollout on the context's side stream
+// (fork / join by events, capturable into the closed loop's hipGraph), the window selection on the context's stream.  (Until round 3 both
+// were workgroups of one launch; the rollout's staging buffer would have been allocated for every workgroup of it.)
 
 struct PlantArgs {
     mpcx_mpc_params p;
@@ -300,7 +367,8 @@ int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const
     // a rollout forked just now runs beside the window selection and is joined behind it
     if (forked && hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "mpc_prepare_batch: cannot join the side stream");
-    const dim3 wgrid((B + mpcx::PREP_WAVES - 1) / mpcx::PREP_WAVES), wblock(64 * mpcx::PREP_WAVES);
+    constexpr int per_block = mpcx::PREP_WAVES * mpcx::WIN_AGENTS;
+    const dim3 wgrid((B + per_block - 1) / per_block), wblock(64 * mpcx::PREP_WAVES);
     if (retire) hipLaunchKernelGGL(mpcx::ref_window_kernel<true>, wgrid, wblock, 0, ctx->stream, ra);
     else hipLaunchKernelGGL(mpcx::ref_window_kernel<false>, wgrid, wblock, 0, ctx->stream, ra);
     if (!forked && hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) != hipSuccess)
@@ -314,11 +382,11 @@ int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const d
     mpcx::RollArgs ro{ctx->mpc, B, state, u_warm, xbar, done};
     if (hipEventRecord(ctx->ev_fork, ctx->stream) != hipSuccess || hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "mpc_prepare_batch: cannot fork the side stream");
-    const size_t roll_lds = 64 * (4 * (size_t)(ctx->mpc.T + 1) + 1) * sizeof(double);
-    if (done) hipLaunchKernelGGL(mpcx::rollout_kernel<true>, dim3((B + 63) / 64), dim3(64), roll_lds, ctx->side, ro);
-    else hipLaunchKernelGGL(mpcx::rollout_kernel<false>, dim3((B + 63) / 64), dim3(64), roll_lds, ctx->side, ro);
-    // a refused launch is the rollout's failure, not that of whichever call checks the error state next (the staging buffer is above
-    // 64 KB for T >= 31: gfx950 grants up to 160 KB of LDS per workgroup without hipFuncAttributeMaxDynamicSharedMemorySize)
+    const size_t roll_lds = mpcx::rollout_lds(ctx->mpc.T);
+    const dim3 rgrid((B + mpcx::ROLL_AGENTS - 1) / mpcx::ROLL_AGENTS), rblock(mpcx::ROLL_BLOCK);
+    if (done) hipLaunchKernelGGL(mpcx::rollout_kernel<true>, rgrid, rblock, roll_lds, ctx->side, ro);
+    else hipLaunchKernelGGL(mpcx::rollout_kernel<false>, rgrid, rblock, roll_lds, ctx->side, ro);
+    // a refused launch is the rollout's failure, not that of whichever call checks the error state next
     const int32_t rc = mpcx_check_launch(ctx, "rollout_kernel");
     if (rc != MPCX_OK) return rc;
     // the join event right behind the rollout: by the time the context's stream waits for it (in front of the solve) the marker has long
@@ -362,5 +430,18 @@ extern "C" int32_t mpcx_closed_loop_stats(mpcx_ctx *ctx, int64_t *out4, int32_t 
     }
     if (reset && hipMemsetAsync(ctx->stats, 0, h.size() * sizeof(unsigned long long), ctx->stream) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_stats: reset failed");
+    return MPCX_OK;
+}
+
+extern "C" int32_t mpcx_closed_loop_queue(mpcx_ctx *ctx, int32_t P, int32_t *order, int32_t *keyslot) {
+    if (!ctx || !order || !keyslot || P < 0) return MPCX_E_INVALID;
+    const size_t counters = (size_t)MPCX_ORDER_COPIES * MPCX_ORDER_BINS;
+    if (!ctx->order || !ctx->bins || ctx->order_cap < (size_t)P * sizeof(int32_t) || ctx->bins_cap < (counters + (size_t)P) * sizeof(int32_t))
+        return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_queue: no closed loop has built a work queue for %d agents on this context", P);
+    if (P == 0) return MPCX_OK;
+    if (hipMemcpyAsync(order, ctx->order, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(keyslot, ctx->bins + counters, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_queue: copy failed");
     return MPCX_OK;
 }

@@ -801,6 +801,20 @@ class Context:
         self._chk(self.lib.mpcx_closed_loop_stats(self._ctx, out, 1 if reset else 0))
         return dict(agent_steps=int(out[0]), iterations=int(out[1]), failures=int(out[2]), max_iterations=int(out[3]))
 
+    def closed_loop_queue(self, P: int):
+        """mpcx_closed_loop_queue: (order, keyslot), int32 host arrays of P words -- the QP work queue as the last closed-loop step left
+        it and the (key << 24 | slot) every agent was filed under (synchronises)"""
+        order, keyslot = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.int32)
+        self._chk(self.lib.mpcx_closed_loop_queue(self._ctx, int(P), order.ctypes.data, keyslot.ctypes.data))
+        return order, keyslot
+
+    def interaction_prediction(self, rows: int, steps: int):
+        """mpcx_interaction_prediction: the obstacle prediction of the last interaction() / closed-loop step, float64 host array
+        (rows, steps, 2, 2) of disc centres (synchronises)"""
+        out = np.zeros((int(rows), int(steps), 2, 2))
+        self._chk(self.lib.mpcx_interaction_prediction(self._ctx, int(rows), int(steps), out.ctypes.data))
+        return out
+
     @_ordered
     def set_instance_tuning(self, rows: Optional[torch.Tensor]):
         """mpcx_set_instance_tuning: rows (B,16) float64 device tensor (MpcParams.tuning_row per problem) or None to clear.
