@@ -22,7 +22,8 @@
  *     departed agent's slot for the next vehicle is respawn: mpcx_respawn, mpcx_closed_loop_run_respawn.  Who yields to whom at the crossing is
  *     right of way: mpcx_precedence, mpcx_closed_loop_run_precedence.  A route per vehicle of such a slot is mpcx_routes,
  *     mpcx_closed_loop_run_routes; mpcx_episode_summary reduces the episode table per instance and route.  Holding agents at the stop
- *     lines of a signalised crossing is mpcx_signals, mpcx_closed_loop_run_signals.
+ *     lines of a signalised crossing is mpcx_signals, mpcx_closed_loop_run_signals; lights that follow the demand are mpcx_actuation,
+ *     mpcx_closed_loop_run_actuated.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -798,6 +799,67 @@ int32_t mpcx_closed_loop_run_signals(mpcx_ctx *ctx, const mpcx_interaction_param
 int32_t mpcx_signal_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
                                const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
                                const int32_t *done /*P or NULL*/, const mpcx_signals *signals);
+
+/* ---- vehicle-actuated signals: a controller per junction decides the lights from who is waiting.  mpcx_signals with a fixed plan gives an
+ * empty approach its green while the loaded one queues; the controller of a real junction holds a phase at least its minimum green,
+ * extends it while its own detectors are occupied, ends it when they have been empty for a gap, or at a maximum -- but only if somebody
+ * else is waiting -- and skips phases nobody calls.  One launch (actuated_signal_kernel, csrc/mpcx_actuated.hip; the rule is
+ * csrc/mpcx_actuated_core.h) takes the place of signal_kernel: a step with actuation has the launches of a step with signals.  It replaces
+ * the SOURCE OF THE LIGHT and nothing else: the hold at the line is the rule of mpcx_signals, word for word.
+ * A junction is n_per consecutive agents: junction j owns agents [j n_per, (j + 1) n_per), n_per n_junctions = P.  A controller (one timing
+ * set) has n_phases phases (1 .. MPCX_ACTUATION_PHASES_MAX = 8); a table of n_ctrl controllers runs a sweep as one batch:
+ * phase_groups[n_ctrl][n_phases] the bitmask of the signal groups green in the phase, phase_time[n_ctrl][n_phases][3] = (min_green,
+ * max_green, gap) in steps, ctrl_time[n_ctrl][3] = (amber, all_red in steps, detect in path points), ctrl_of[n_junctions] the controller of
+ * junction j.  jstate[n_junctions][4] = (phase, stage, timer, idle), stage 0 GREEN, 1 AMBER, 2 ALL_RED, caller-owned device memory, in-out,
+ * zero-initialised; lights[n_junctions] (out): 2 bits per group, MPCX_SIGNAL_GREEN / AMBER / RED; calls[n_junctions] (out): bit g set when
+ * group g is called this step.
+ * Per junction and step: (1) read (p, stage, timer, idle); a defective word -- p outside [0, n_phases), stage outside 0..2, a negative
+ * timer or idle -- counts as (0, GREEN, 0, 0); a junction whose ctrl_of is out of range has no controller: its agents are free (held = 0),
+ * its jstate is left alone, lights = calls = 0.  (2) the lights of this step from the state as read: GREEN -- the groups of
+ * phase_groups[p] green, all others red; AMBER -- those groups amber, all others red; ALL_RED -- all red.  (3) calls: bit g is set if some
+ * agent q of the junction is not done (done NULL or done[q] == 0), stands on a valid point in front of its line (i = path_off[q] +
+ * traj_idx[q] in [0, n_points), s = path_stop[i] with 0 <= s < path_len[q], traj_idx[q] < s, g = path_group[i] in [0, n_groups)) and inside
+ * the detector, s - traj_idx[q] <= detect.  (4) advance, with D_k = (calls & phase_groups[k]) != 0 and other = some k != p has D_k.
+ * GREEN: timer' = min(timer + 1, max_green), idle' = D_p ? 0 : min(idle + 1, gap); the phase ends if other and timer' >= min_green and
+ * (idle' >= gap or timer' >= max_green), else it rests in green -- a phase nobody contests never ends.  AMBER: timer' = timer + 1, ends at
+ * timer' >= amber; ALL_RED the same with all_red.  Leaving goes GREEN -> AMBER -> ALL_RED -> GREEN of the next phase with timer = idle = 0
+ * on entry; a stage of length 0 is passed through in the same step.  The next phase is the first k in ring order p + 1, p + 2, ... (mod
+ * n_phases, p excluded) with D_k by this step's calls, (p + 1) % n_phases if there is none.  (5) every agent of the junction goes through
+ * steps 2 - 5 of the signal rule with the light of its group taken from lights[j].
+ * With actuation mpcx_signals supplies path_stop, path_group, held, brake, n_points and n_groups; its plan_cycle, plan_amber, plan_green,
+ * plan_of and tick must be NULL and n_plans 0.  actuation = NULL or an all-zero struct: mpcx_closed_loop_run_signals itself -- the same
+ * launches with the same arguments.  No other struct changes size; the cached graph's key covers the struct by value.  MPCX_E_INVALID
+ * ("actuation: ...") before anything is launched, whatever n_steps is: a NULL pointer; actuation without signals, or signals that also
+ * carry a fixed plan; n_per < 1 or n_per n_junctions != P; n_phases outside 1..8; n_ctrl < 1; reserved != 0; a phase mask that is zero or
+ * has bits at or above n_groups; min_green < 0, max_green < 1, min_green > max_green, gap < 1; amber < 0, all_red < 0, detect < 1 (the three
+ * controller tables are read back once per call; the per-junction, per-agent and per-point words are not -- a bad word is never a GPU
+ * fault); signals' own refusals of n_groups, n_points and brake; the agent-sharded layout; more than one linearisation pass. */
+#define MPCX_ACTUATION_PHASES_MAX 8
+#define MPCX_STAGE_GREEN 0
+#define MPCX_STAGE_AMBER 1
+#define MPCX_STAGE_ALL_RED 2
+typedef struct {
+    const int32_t *phase_groups; /* n_ctrl x n_phases: bitmask of the signal groups green in the phase */
+    const int32_t *phase_time;   /* n_ctrl x n_phases x 3: (min_green, max_green, gap), steps */
+    const int32_t *ctrl_time;    /* n_ctrl x 3: (amber, all_red) in steps, detect in path points */
+    const int32_t *ctrl_of;      /* n_junctions: the controller of junction j */
+    int32_t *jstate;             /* n_junctions x 4, caller-owned, in-out, zero-initialised: (phase, stage, timer, idle) */
+    int32_t *lights;             /* n_junctions, out: 2 bits per group */
+    int32_t *calls;              /* n_junctions, out: bit g = group g is called this step */
+    int32_t n_per, n_junctions, n_phases, n_ctrl, reserved;      /* reserved: 0 */
+} mpcx_actuation;
+int32_t mpcx_closed_loop_run_actuated(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                      const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                      const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                      const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                      const mpcx_routes *routes /*or NULL*/, const mpcx_precedence *precedence /*or NULL*/,
+                                      const mpcx_signals *signals /*or NULL*/, const mpcx_actuation *actuation /*or NULL*/, int32_t n_steps,
+                                      int32_t use_graph);
+/* one step's actuated signal stage alone (what mpcx_closed_loop_run_actuated enqueues between the conflict search and the window stage);
+ * the arguments of mpcx_signal_step_batch plus the controller.  Both structs are checked as above. */
+int32_t mpcx_actuated_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
+                                 const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
+                                 const int32_t *done /*P or NULL*/, const mpcx_signals *signals, const mpcx_actuation *actuation);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

@@ -105,7 +105,19 @@ class SignalsC(C.Structure):
                 ('n_points', C.c_int32), ('n_plans', C.c_int32), ('n_groups', C.c_int32), ('reserved', C.c_int32)]
 
 
+class ActuationC(C.Structure):
+    """mirror of mpcx_actuation (include/mpcx.h): vehicle-actuated signals; every pointer is a device address -- phase_groups (n_ctrl x
+    n_phases int32), phase_time (n_ctrl x n_phases x 3 int32), ctrl_time (n_ctrl x 3 int32), ctrl_of / lights / calls (n_junctions int32),
+    jstate (n_junctions x 4 int32)"""
+    _fields_ = [('phase_groups', C.c_void_p), ('phase_time', C.c_void_p), ('ctrl_time', C.c_void_p), ('ctrl_of', C.c_void_p),
+                ('jstate', C.c_void_p), ('lights', C.c_void_p), ('calls', C.c_void_p), ('n_per', C.c_int32), ('n_junctions', C.c_int32),
+                ('n_phases', C.c_int32), ('n_ctrl', C.c_int32), ('reserved', C.c_int32)]
+
+
 SIGNAL_GROUPS_MAX = 16                          # MPCX_SIGNAL_GROUPS_MAX
+ACTUATION_PHASES_MAX = 8                        # MPCX_ACTUATION_PHASES_MAX
+STAGE_GREEN, STAGE_AMBER, STAGE_ALL_RED = 0, 1, 2       # mpcx_actuation.jstate[j][1]
+LIGHT_GREEN, LIGHT_AMBER, LIGHT_RED = 0, 1, 2   # MPCX_SIGNAL_*: two bits per group in mpcx_actuation.lights
 HELD_FREE, HELD_RED, HELD_AMBER = 0, 1, 2       # mpcx_signals.held
 
 
@@ -180,7 +192,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
            'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
            'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence',
-           'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction']
+           'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
+           'mpcx_closed_loop_run_actuated', 'mpcx_actuated_step_batch']
 
 
 def load():
@@ -293,5 +306,12 @@ def load():
                                                  C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC), i32, i32]
     lib.mpcx_signal_step_batch.restype = i32
     lib.mpcx_signal_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC)]
+    lib.mpcx_closed_loop_run_actuated.restype = i32
+    lib.mpcx_closed_loop_run_actuated.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                  C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                  C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
+                                                  C.POINTER(ActuationC), i32, i32]
+    lib.mpcx_actuated_step_batch.restype = i32
+    lib.mpcx_actuated_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(ActuationC)]
     _lib = lib
     return lib

@@ -33,6 +33,9 @@ served, stamped on the device as vehicles are admitted.
 `signalise(plans)` puts TRAFFIC SIGNALS on the crossing: stop lines are a property of path points (stop_lines()), a plan gives every signal
 group its green within a cycle (two_phase_plan()), and one more small launch behind the conflict search holds an agent whose light is red
 -- or amber, if it can still stop -- at its line by cutting its path there; a table of plans runs a sweep of timings as one batch.
+`actuate(controllers)` makes the signals VEHICLE-ACTUATED: every instance is a junction with a controller on the device that holds a phase
+at least its minimum green, extends it while cars approach its lines, ends it after a gap or at a maximum if somebody else waits, and skips
+phases nobody calls (two_phase_controller()); the launch takes the place of the fixed plan's, the hold at the line is the same.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -347,6 +350,10 @@ class IntersectionBatch:
         self.held: Optional[torch.Tensor] = None             # ... int32 (P,), 0 free, 1 held at red, 2 held at amber
         self._signals = None
         self._signal_tabs = None                             # ... the device tables the struct names (kept alive here)
+        self.junction_state: Optional[torch.Tensor] = None   # actuate(): int32 (B, 4), every junction's (phase, stage, timer, idle)
+        self.lights: Optional[torch.Tensor] = None           # ... int32 (B,), the lights of the last step, 2 bits per signal group
+        self.calls: Optional[torch.Tensor] = None            # ... int32 (B,), bit g = group g was called in the last step
+        self._actuation = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -690,13 +697,84 @@ class IntersectionBatch:
         self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), tabs['plan_cycle'].data_ptr(),
                                       tabs['plan_amber'].data_ptr(), tabs['plan_green'].data_ptr(), tabs['plan_of'].data_ptr(),
                                       self.tick.data_ptr(), self.held.data_ptr(), brake, n_points, len(plans), n_groups, 0)
+        self._actuation = None              # (a fixed plan replaces a controller as the source of the lights)
+        self._desc = None
+        c.synchronize()
+
+    def actuate(self, controllers, ctrl_of=None, stop=None, group=None, brake: Optional[float] = None):
+        """VEHICLE-ACTUATED SIGNALS (mpcx_closed_loop_run_actuated).  Every instance is a junction (n_per = A) with a controller on the
+        device: the launch that holds agents at their stop lines first reduces, over the junction's agents, which signal groups have a car
+        within `detect` path points of its line, advances the junction's state machine and takes the lights from it.  A phase is held at
+        least min_green steps, extended while its own groups are called, ended when they have not been for `gap` steps or at max_green --
+        but only if another phase is called --, followed by `amber` steps of amber and `all_red` of red for all; phases nobody calls are
+        skipped.  The hold at the line is signalise()'s, which this call replaces as the source of the lights (and the reverse).
+        controllers: one dict or a sequence of dicts, dict(phases=[[groups], ...], min_green, max_green, gap, amber, all_red, detect), the
+        three per-phase values a scalar or one value per phase, the same number of phases in all (two_phase_controller() builds one);
+        ctrl_of: the controller of every instance (B,), default 0 -- a sweep of timings runs as one batch.  stop, group: the
+        per-path-point tables (default: stop_lines() of the batch's routes).  brake: default abs(MAX_DECEL) of the batch's parameters.
+        Allocates `held`, `junction_state`, `lights`, `calls` (zero) and the tables and drops the cached descriptor; unsignalise()
+        switches it off."""
+        if isinstance(controllers, dict):
+            controllers = [controllers]
+        controllers = list(controllers)
+        if not controllers:
+            raise ValueError('actuate: at least one controller')
+        n_phases = len(controllers[0]['phases'])
+        if not 1 <= n_phases <= _lib.ACTUATION_PHASES_MAX or any(len(ct['phases']) != n_phases for ct in controllers):
+            raise ValueError('actuate: 1 .. %d phases, the same number in all controllers' % _lib.ACTUATION_PHASES_MAX)
+        masks = np.zeros((len(controllers), n_phases), dtype=np.int64)
+        times = np.zeros((len(controllers), n_phases, 3), dtype=np.int64)
+        ctrl = np.zeros((len(controllers), 3), dtype=np.int64)
+        for k, ct in enumerate(controllers):
+            for p, groups in enumerate(ct['phases']):
+                groups = [int(g) for g in groups]
+                if not groups or any(not 0 <= g < _lib.SIGNAL_GROUPS_MAX for g in groups):
+                    raise ValueError('actuate: controller %d phase %d: at least one signal group, each 0 .. %d' % (k, p, _lib.SIGNAL_GROUPS_MAX - 1))
+                masks[k, p] = sum(1 << g for g in set(groups))
+            for col, name in enumerate(('min_green', 'max_green', 'gap')):
+                v = np.asarray(ct[name])
+                if not np.issubdtype(v.dtype, np.integer) or v.shape not in ((), (n_phases,)):
+                    raise ValueError('actuate: controller %d: %s is an integer or one integer per phase' % (k, name))
+                times[k, :, col] = v
+            ctrl[k] = [int(ct['amber']), int(ct['all_red']), int(ct['detect'])]
+        n_points = int(self.path.shape[0])
+        if stop is None or group is None:
+            if stop is not None or group is not None:
+                raise ValueError('actuate: give both stop and group, or neither')
+            routes = [self._route_table[self._route_offs[k]:self._route_offs[k + 1]] for k in range(len(self._route_offs) - 1)]
+            stop, group = stop_lines(routes)
+        stop, group = np.asarray(stop), np.asarray(group)
+        if stop.shape != (n_points,) or group.shape != (n_points,):
+            raise ValueError('actuate: stop and group hold one word per path point (%d)' % n_points)
+        # the signal groups: every group a phase or a path point names (a point with a group beyond the limit is a defective entry: free)
+        n_groups = min(max(int(masks.max()).bit_length(), int(group.max()) + 1 if len(group) else 1), _lib.SIGNAL_GROUPS_MAX)
+        if ctrl_of is None:
+            ctrl_of = np.zeros(self.B, dtype=np.int64)
+        ctrl_of = np.asarray(ctrl_of)
+        if not np.issubdtype(ctrl_of.dtype, np.integer) or ctrl_of.shape != (self.B,):
+            raise ValueError('actuate: ctrl_of is an integer array of shape (B,) = (%d,)' % self.B)
+        brake = abs(float(self.params.max_decel)) if brake is None else float(brake)
+        c = self.ctx
+        tabs = dict(path_stop=c.i32(stop), path_group=c.i32(group), phase_groups=c.i32(masks), phase_time=c.i32(times), ctrl_time=c.i32(ctrl),
+                    ctrl_of=c.i32(ctrl_of))
+        self.held = torch.zeros(self.P, dtype=torch.int32, device=c.device)
+        self.junction_state = torch.zeros((self.B, 4), dtype=torch.int32, device=c.device)
+        self.lights = torch.zeros(self.B, dtype=torch.int32, device=c.device)
+        self.calls = torch.zeros(self.B, dtype=torch.int32, device=c.device)
+        self._signal_tabs = tabs
+        self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), None, None, None, None, None,
+                                      self.held.data_ptr(), brake, n_points, 0, n_groups, 0)
+        self._actuation = _lib.ActuationC(tabs['phase_groups'].data_ptr(), tabs['phase_time'].data_ptr(), tabs['ctrl_time'].data_ptr(),
+                                          tabs['ctrl_of'].data_ptr(), self.junction_state.data_ptr(), self.lights.data_ptr(),
+                                          self.calls.data_ptr(), self.A, self.B, n_phases, len(controllers), 0)
         self._desc = None
         c.synchronize()
 
     def unsignalise(self):
-        """switch the signals off and nothing else: the batch enqueues exactly the launches of one that never had them (`tick` and `held`
-        keep what they hold and are no longer read or written)"""
+        """switch the signals off, fixed or actuated, and nothing else: the batch enqueues exactly the launches of one that never had them
+        (`tick`, `held` and the junction words keep what they hold and are no longer read or written)"""
         self._signals = None
+        self._actuation = None
         self._desc = None
 
     def stop_respawning(self):
@@ -848,7 +926,7 @@ class IntersectionBatch:
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
                                  retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes,
-                                 precedence=self._precedence, signals=self._signals)
+                                 precedence=self._precedence, signals=self._signals, actuation=self._actuation)
         self.steps_done += n_steps
 
     def step(self):
@@ -895,7 +973,9 @@ class IntersectionBatch:
         c.interaction(self.ip, self.state, self.path, self.path_cs, self.path_off, self.path_len,
                       self.prev_len if speed else self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self.obs_skip,
                       self.traj_idx, out=self.inter)
-        if self._signals is not None:       # the signal stage: between the conflict search and the window stage, as in the loop
+        if self._actuation is not None:     # the actuated signal stage, in the place of the signal stage
+            c.actuated_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._actuation)
+        elif self._signals is not None:     # the signal stage: between the conflict search and the window stage, as in the loop
             c.signal_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals)
         # the previous solution (zeros where the last solve failed or on the first step) is the warm start
         for it in range(self.lin_passes):       # lib/mpc.py:226-237: from the second pass on the previous pass's speeds space the window
@@ -941,6 +1021,9 @@ class IntersectionBatch:
             out['precedence'] = self.prec.cpu().numpy().copy()
         if self._signals is not None:        # 0 free, 1 held at red, 2 held at amber, as the last step's signal stage left it
             out['held'] = self.held.cpu().numpy().copy()
+        if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
+            js = self.junction_state.cpu().numpy()
+            out['phase'], out['stage'], out['lights'] = js[:, 0].copy(), js[:, 1].copy(), self.lights.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:
@@ -996,6 +1079,16 @@ def two_phase_plan(cycle: int, green: int, amber: int) -> dict:
     if cycle < 2 or green < 0 or amber < 0 or green + amber > half:
         raise ValueError('two_phase_plan: green + amber = %d + %d must fit half a cycle of %d steps' % (green, amber, cycle))
     return dict(cycle=cycle, amber=amber, green=np.array([[0, green], [half, green], [0, green], [half, green]], dtype=np.int32))
+
+
+def two_phase_controller(min_green: int, max_green: int, gap: int, amber: int, all_red: int, detect: int) -> dict:
+    """An actuated two-phase controller for the four signal groups of stop_lines(), for IntersectionBatch.actuate: phases [[0, 2], [1, 3]]
+    -- the phases of two_phase_plan() --, every phase with the same (min_green, max_green, gap) in steps; `amber` steps of amber and
+    `all_red` steps of red for all between phases; a car calls its group from `detect` path points before its line on."""
+    v = dict(min_green=int(min_green), max_green=int(max_green), gap=int(gap), amber=int(amber), all_red=int(all_red), detect=int(detect))
+    if v['min_green'] < 0 or v['max_green'] < 1 or v['min_green'] > v['max_green'] or v['gap'] < 1 or v['amber'] < 0 or v['all_red'] < 0 or v['detect'] < 1:
+        raise ValueError('two_phase_controller: 0 <= min_green <= max_green, max_green >= 1, gap >= 1, amber >= 0, all_red >= 0, detect >= 1')
+    return dict(phases=[[0, 2], [1, 3]], **v)
 
 
 def entry_schedule(route_of_agent, routes, start_index, mean_headway_steps: float, seed: int) -> np.ndarray:

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1192] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + routes + precedence + signals + parameters the cached graph was captured for
+    unsigned char loop_key[1272] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + routes + precedence + signals + actuation + parameters the cached graph was captured for
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -183,6 +183,13 @@ bool mpcx_signals_absent(const mpcx_signals *s);
 int32_t mpcx_signals_validate(mpcx_ctx *ctx, const mpcx_signals *s, int32_t exchange);
 int32_t mpcx_signal_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
                             const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals);
+// vehicle-actuated signals (mpcx_actuated.hip): "no actuation" test, check of both structs against the run (reads the controller tables back),
+// the launch alone (in the place of mpcx_signal_enqueue)
+bool mpcx_actuation_absent(const mpcx_actuation *s);
+int32_t mpcx_actuation_validate(mpcx_ctx *ctx, const mpcx_actuation *s, const mpcx_signals *sg, int32_t P, int32_t exchange);
+int32_t mpcx_actuated_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
+                              const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals,
+                              const mpcx_actuation *actuation);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -8,7 +8,8 @@
 // else's obstacle list; with admission (mpcx_admit) the step begins with the two launches that let waiting agents in; with respawn
 // (mpcx_respawn) it ends with respawn_kernel, which resets an arrived agent's slot for the next vehicle of its stream; with right of way
 // (mpcx_precedence) the conflict search shows an agent the cars that yield to it as standing cars; with traffic signals (mpcx_signals) one
-// more launch behind the conflict search holds agents at their stop lines.  Every stage is the kernel behind the per-stage C entry
+// more launch behind the conflict search holds agents at their stop lines (mpcx_actuation: its lights follow the demand).
+// Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
 // by one from the host.
 #include "mpcx_common.h"
@@ -81,9 +82,13 @@ static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cu
 // launch, signal_kernel, follows the conflict search: it advances every agent's clock and, for an agent its light holds, lowers c->cut_len
 // (the cut length, the stop index in speed mode) to the agent's stop line before the window stage reads it.  The agent is filed in the QP
 // work queue already, under a key from the cut before this launch: the order of the queue only.
+// av: vehicle-actuated signals or nullptr = none (then exactly the launches of a step with signals, with the same arguments).  With them
+// actuated_signal_kernel stands in the place of signal_kernel -- the same number of launches --: a controller per junction decides the
+// lights from the agents in front of their lines, the hold is signal_kernel's.
 static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                             const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc, const mpcx_admit *ad,
-                            const mpcx_respawn *rs, const mpcx_routes *rt, const mpcx_precedence *pc, const mpcx_signals *sg) {
+                            const mpcx_respawn *rs, const mpcx_routes *rt, const mpcx_precedence *pc, const mpcx_signals *sg,
+                            const mpcx_actuation *av) {
     const int P = c->P;
     const int32_t *done = r ? r->done : nullptr;
     int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
@@ -141,7 +146,8 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
                                   c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len, ix);
     if (rc != MPCX_OK) return rc;
     if (sg) {       // (validated: the local pool, one linearisation pass)
-        rc = mpcx_signal_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, sg);
+        rc = av ? mpcx_actuated_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, sg, av)
+                : mpcx_signal_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, sg);
         if (rc != MPCX_OK) return rc;
     }
     // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
@@ -190,7 +196,7 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                                const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, const mpcx_admit *admit,
                                const mpcx_respawn *respawn, const mpcx_routes *routes, const mpcx_precedence *precedence,
-                               const mpcx_signals *signals, int32_t n_steps, int32_t use_graph) {
+                               const mpcx_signals *signals, const mpcx_actuation *actuation, int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
@@ -246,7 +252,18 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         if (prc != MPCX_OK) return prc;
     }
     if (mpcx_signals_absent(signals)) signals = nullptr;
-    if (signals) {      // refused before anything is launched, whatever n_steps is
+    if (mpcx_actuation_absent(actuation)) actuation = nullptr;
+    mpcx_actuation act;         // by value with its padding zeroed: the cached graph's key
+    memset(&act, 0, sizeof act);
+    if (actuation) {    // refused before anything is launched, whatever n_steps is; checks the signals it draws on too
+        const int32_t arc = mpcx_actuation_validate(ctx, actuation, signals, c->P, c->exchange);
+        if (arc != MPCX_OK) return arc;
+        act.phase_groups = actuation->phase_groups; act.phase_time = actuation->phase_time; act.ctrl_time = actuation->ctrl_time;
+        act.ctrl_of = actuation->ctrl_of; act.jstate = actuation->jstate; act.lights = actuation->lights; act.calls = actuation->calls;
+        act.n_per = actuation->n_per; act.n_junctions = actuation->n_junctions; act.n_phases = actuation->n_phases;
+        act.n_ctrl = actuation->n_ctrl;
+        actuation = &act;
+    } else if (signals) {      // refused before anything is launched, whatever n_steps is
         const int32_t grc = mpcx_signals_validate(ctx, signals, c->exchange);
         if (grc != MPCX_OK) return grc;
     }
@@ -320,7 +337,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
     if (!use_graph) {
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence, signals);
+            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence, signals, actuation);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -330,7 +347,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
     unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_routes) + sizeof(mpcx_precedence) + sizeof(mpcx_signals) + sizeof(mpcx_interaction_params) +
+    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_routes) + sizeof(mpcx_precedence) + sizeof(mpcx_signals) + sizeof(mpcx_actuation) + sizeof(mpcx_interaction_params) +
                   sizeof(mpcx_mpc_params) + 10 * sizeof(void *) <= sizeof key,
                   "loop_key too small");
     memset(key, 0, sizeof key);
@@ -353,6 +370,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     o += sizeof *precedence;
     if (signals) memcpy(key + o, signals, sizeof *signals);  // (zeros = no signals: a graph captured without signal_kernel)
     o += sizeof *signals;
+    if (actuation) memcpy(key + o, actuation, sizeof *actuation);    // (zeros = no actuation: a graph captured with signal_kernel, if any)
+    o += sizeof *actuation;
     memcpy(key + o, &ctx->admit_tab, sizeof ctx->admit_tab); o += sizeof ctx->admit_tab;
     memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
     memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
@@ -373,7 +392,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence, signals);
+        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence, signals, actuation);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
@@ -390,35 +409,35 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
 
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_admit(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, const mpcx_admit *admit, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
 }
 
 extern "C" int32_t mpcx_closed_loop_run_respawn(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
@@ -448,5 +467,13 @@ extern "C" int32_t mpcx_closed_loop_run_signals(mpcx_ctx *ctx, const mpcx_intera
                                                 const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                 const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
                                                 int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, precedence, signals, n_steps, use_graph);
+    return mpcx_closed_loop_run_actuated(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, precedence, signals, nullptr, n_steps, use_graph);
+}
+
+extern "C" int32_t mpcx_closed_loop_run_actuated(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                                 const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                                 const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
+                                                 const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
+                                                 const mpcx_actuation *actuation, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation, n_steps, use_graph);
 }

@@ -25,6 +25,8 @@
 //      else free.  held is in-out, zero-initialised by the caller.
 //   5. held: cut_len[q] = min(cut_len[q], s).  traj_idx < s, so this is the reference's max(traj_agent_idx + 1, cutoff_idx): the path ends
 //      on the point before the line.  A conflict cut shorter than s is kept.
+// The text is in two parts: signal_agent is step 1, "clock and light"; signal_hold is steps 2 - 5, the hold, which takes the light of a group
+// from its caller and is shared with the vehicle-actuated rule (mpcx_actuated_core.h), where a junction's controller supplies the light.
 // Every access is to words of agent q plus the read-only tables: no lane reads a word another lane writes, the outcome does not depend on
 // the order of the lanes, and a replayed hipGraph counts like a plain run.  The stopping distance has no multiply-add to fuse; host builds
 // use -ffp-contract=off all the same.
@@ -34,6 +36,12 @@
 #define MPCX_SIGNAL_GREEN 0
 #define MPCX_SIGNAL_AMBER 1
 #define MPCX_SIGNAL_RED 2
+
+#ifdef __HIPCC__
+#define MPCX_REC_FN_MEMBER __host__ __device__ __forceinline__
+#else
+#define MPCX_REC_FN_MEMBER inline
+#endif
 
 namespace mpcx {
 
@@ -57,7 +65,42 @@ MPCX_REC_FN int signal_light(int32_t cycle, int32_t amber, int32_t green_from, i
     return MPCX_SIGNAL_RED;
 }
 
-// returns held[q] as it is left
+// the light of agent q's group under a fixed plan at t (the "clock and light" half of the rule hands this to the hold)
+struct PlanLight {
+    const mpcx_signals *g;
+    int32_t plan, cycle, t;
+    MPCX_REC_FN_MEMBER int operator()(int32_t grp) const {
+        const int32_t *gr = g->plan_green + 2 * ((size_t)plan * (size_t)g->n_groups + (size_t)grp);
+        return signal_light(cycle, g->plan_amber[plan], gr[0], gr[1], t);
+    }
+};
+
+// steps 2 - 5, THE HOLD, shared by the fixed-time rule and the actuated one (mpcx_actuated_core.h): lit = the agent has a source of light
+// at all (a cycle, a controller), light_of(grp) the light of signal group grp in this step.  Returns held[q] as it is left.
+template <class LightOf>
+MPCX_REC_FN int32_t signal_hold(const SignalArgs &a, int q, bool lit, const LightOf &light_of) {
+    const mpcx_signals &g = a.sg;
+    if (a.done && a.done[q] != 0) { g.held[q] = 0; return 0; }
+    const int32_t ti = a.traj_idx[q];
+    const int64_t i = (int64_t)a.path_off[q] + (int64_t)ti;
+    int32_t held = 0;
+    if (lit && i >= 0 && i < (int64_t)g.n_points) {
+        const int32_t s = g.path_stop[i], grp = g.path_group[i];
+        if (s >= 0 && ti < s && s < a.path_len[q] && grp >= 0 && grp < g.n_groups) {
+            const int light = light_of(grp);
+            if (light == MPCX_SIGNAL_RED) held = 1;
+            else if (light == MPCX_SIGNAL_AMBER) {
+                const double v = a.state[4 * (size_t)q + 2];
+                if (g.held[q] != 0 || (double)(s - ti) * a.dl >= v * v / (2.0 * g.brake)) held = 2;
+            }
+            if (held != 0 && s < a.cut_len[q]) a.cut_len[q] = s;
+        }
+    }
+    g.held[q] = held;
+    return held;
+}
+
+// step 1, CLOCK AND LIGHT, then the hold; returns held[q] as it is left
 MPCX_REC_FN int32_t signal_agent(const SignalArgs &a, int q) {
     const mpcx_signals &g = a.sg;
     const int32_t plan = g.plan_of[q];
@@ -69,25 +112,7 @@ MPCX_REC_FN int32_t signal_agent(const SignalArgs &a, int q) {
         if (t < 0) t += cycle;
         g.tick[q] = t + 1 < cycle ? t + 1 : 0;
     }
-    if (a.done && a.done[q] != 0) { g.held[q] = 0; return 0; }
-    const int32_t ti = a.traj_idx[q];
-    const int64_t i = (int64_t)a.path_off[q] + (int64_t)ti;
-    int32_t held = 0;
-    if (cycle >= 1 && i >= 0 && i < (int64_t)g.n_points) {
-        const int32_t s = g.path_stop[i], grp = g.path_group[i];
-        if (s >= 0 && ti < s && s < a.path_len[q] && grp >= 0 && grp < g.n_groups) {
-            const int32_t *gr = g.plan_green + 2 * ((size_t)plan * (size_t)g.n_groups + (size_t)grp);
-            const int light = signal_light(cycle, g.plan_amber[plan], gr[0], gr[1], t);
-            if (light == MPCX_SIGNAL_RED) held = 1;
-            else if (light == MPCX_SIGNAL_AMBER) {
-                const double v = a.state[4 * (size_t)q + 2];
-                if (g.held[q] != 0 || (double)(s - ti) * a.dl >= v * v / (2.0 * g.brake)) held = 2;
-            }
-            if (held != 0 && s < a.cut_len[q]) a.cut_len[q] = s;
-        }
-    }
-    g.held[q] = held;
-    return held;
+    return signal_hold(a, q, cycle >= 1, PlanLight{&g, plan, cycle, t});
 }
 
 }  // namespace mpcx

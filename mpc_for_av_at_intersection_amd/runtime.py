@@ -617,7 +617,7 @@ class Context:
                         retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None,
                         admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None,
                         routes: Optional['_lib.RoutesC'] = None, precedence: Optional['_lib.PrecedenceC'] = None,
-                        signals: Optional['_lib.SignalsC'] = None):
+                        signals: Optional['_lib.SignalsC'] = None, actuation: Optional['_lib.ActuationC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
@@ -633,10 +633,16 @@ class Context:
         precedence: a _lib.PrecedenceC -- right of way: an agent sees the present rows whose word is larger than its own as standing cars
         (mpcx_closed_loop_run_precedence; refused without scene, and in ENTRY mode without admit); None = everybody yields to everybody.
         signals: a _lib.SignalsC -- traffic signals: one more launch behind the conflict search holds agents at their stop lines
-        (mpcx_closed_loop_run_signals; needs none of the others); None = no signals."""
+        (mpcx_closed_loop_run_signals; needs none of the others); None = no signals.
+        actuation: a _lib.ActuationC -- vehicle-actuated signals: a controller per junction takes the place of the signals' fixed plan
+        (mpcx_closed_loop_run_actuated; refused without signals); None = the signals' own plan."""
         cip = ip.to_c()
         ref = lambda s: None if s is None else C.byref(s)
-        if signals is not None:
+        if actuation is not None:
+            self._chk(self.lib.mpcx_closed_loop_run_actuated(self._ctx, C.byref(cip), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
+                                                             ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals),
+                                                             C.byref(actuation), int(n_steps), 1 if graph else 0))
+        elif signals is not None:
             self._chk(self.lib.mpcx_closed_loop_run_signals(self._ctx, C.byref(cip), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
                                                             ref(admit), ref(respawn), ref(routes), ref(precedence), C.byref(signals),
                                                             int(n_steps), 1 if graph else 0))
@@ -689,6 +695,21 @@ class Context:
             self._want(done, torch.int32, (Pn,), 'done')
         self._chk(self.lib.mpcx_signal_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
                                                   _ptr(cut_len), _ptr(done), C.byref(signals)))
+
+    @_ordered
+    def actuated_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', actuation: '_lib.ActuationC',
+                      done=None):
+        """mpcx_actuated_step_batch: ONE step's actuated signal stage as the closed loop enqueues it in the place of the signal stage.
+        cut_len (P int32) is updated in place, as are the signals' held and the controller's jstate, lights and calls; done: the retirement
+        words (P int32) or None."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('cut_len', cut_len)):
+            self._want(t, torch.int32, (Pn,), name)
+        if done is not None:
+            self._want(done, torch.int32, (Pn,), 'done')
+        self._chk(self.lib.mpcx_actuated_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
+                                                    _ptr(cut_len), _ptr(done), C.byref(signals), C.byref(actuation)))
 
     @_ordered
     def admit_step(self, ip: InteractionParams, state, obs_off, obs_cnt, obs_skip, done, absent, admit: '_lib.AdmitC', actors=None,

@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""What the actuated signal stage costs beside the fixed-time one: the routed respawn batch of scripts/signal_timing.py (instances x 8
+agents on the eight stock routes, the seeded demand of batch.demand_schedule()) in three variants:
+
+    off       no signals
+    plan      signalise(two_phase_plan(cycle, green, amber)): signal_kernel, one lane per agent
+    actuated  actuate(two_phase_controller(...)): actuated_signal_kernel in its place, a lane group of 8 per junction -- the same number of
+              launches per step
+
+The variants alternate within every repetition, after a warm-up run of each; HIP events around the whole run; reported: median and range of
+the time per step.  Then the two stage calls alone (Context.signal_step, Context.actuated_step) on the words of the last runs, `--stage-reps`
+launches back to back between two events: the time of one launch of either kernel.
+
+    python scripts/actuated_timing.py [--reps 3] [--steps 150] [--instances 4096] [--headway 25] [--vehicles 3] [--gap 2.0] [--graph]
+                                      [--cycle 100] [--green 30] [--amber 8] [--min-green 10] [--max-green 60] [--gap-out 5] [--detect 100]
+                                      [--stage-reps 200]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'examples'))
+
+TAGS = ('off', 'plan', 'actuated')
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--steps', type=int, default=150)
+    ap.add_argument('--instances', type=int, default=4096)
+    ap.add_argument('--horizon', type=int, default=13)
+    ap.add_argument('--headway', type=float, default=25.0)
+    ap.add_argument('--vehicles', type=int, default=3)
+    ap.add_argument('--gap', type=float, default=2.0)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--cycle', type=int, default=100)
+    ap.add_argument('--green', type=int, default=30)
+    ap.add_argument('--amber', type=int, default=8)
+    ap.add_argument('--min-green', type=int, default=10)
+    ap.add_argument('--max-green', type=int, default=60)
+    ap.add_argument('--gap-out', type=int, default=5)
+    ap.add_argument('--detect', type=int, default=100)
+    ap.add_argument('--stage-reps', type=int, default=200, help='launches of either stage kernel alone between two events (0: skip)')
+    ap.add_argument('--graph', action='store_true')
+    args = ap.parse_args()
+    import torch
+    from open_intersection_flow import family
+    from mpc_for_av_at_intersection_amd.batch import demand_schedule, stock_routes, two_phase_controller, two_phase_plan
+    from mpc_for_av_at_intersection_amd.runtime import Context
+    ctx = Context(0, stream=torch.cuda.Stream(device=0)) if args.graph else Context(0)
+    routes, dl, cd = stock_routes(ctx)
+    plan = two_phase_plan(args.cycle, args.green, args.amber)
+    ctrl = two_phase_controller(args.min_green, args.max_green, args.gap_out, args.amber, args.cycle // 2 - args.green - args.amber, args.detect)
+
+    def fresh(tag):
+        sim, route = family(ctx, routes, dl, cd, args.instances, args.horizon)
+        sim.retire_at_goal(leave_scene=True)
+        due = demand_schedule(route, routes, np.zeros_like(route), args.headway, args.vehicles, args.seed)
+        sim.respawn_on_schedule(due, gap=args.gap, route=np.repeat(route[:, :, None], args.vehicles, axis=2))
+        if tag == 'plan':
+            sim.signalise(plan)
+        elif tag == 'actuated':
+            sim.actuate(ctrl)
+        return sim
+    res = {'workload': 'open intersection %d x 8, T = %d, headway %.1f, %d vehicles per slot, gap %.1f, seed %d, plan %d / %d / %d, controller '
+                       '%d / %d / %d, detector %d%s' % (args.instances, args.horizon, args.headway, args.vehicles, args.gap, args.seed, args.cycle,
+                                                        args.green, args.amber, args.min_green, args.max_green, args.gap_out, args.detect,
+                                                        ', graph replay' if args.graph else ''),
+           'steps': args.steps}
+    for tag in TAGS:
+        fresh(tag).run(args.steps, args.graph)      # warm-up
+    ctx.synchronize()
+    ms, last = {t: [] for t in TAGS}, {}
+    stream = torch.cuda.current_stream(ctx.device)
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        e1.synchronize()
+        ctx.synchronize()
+        return e0.elapsed_time(e1) / n
+    for _ in range(args.reps):
+        for tag in TAGS:
+            sim = fresh(tag)
+            ctx.synchronize()
+            ms[tag].append(timed(lambda: sim.run(args.steps, args.graph), args.steps))
+            last[tag] = sim
+    for tag in TAGS:
+        m, sim = np.array(ms[tag]), last[tag]
+        res[tag + '_ms_per_step'] = [round(float(v), 4) for v in m]
+        res[tag + '_median_ms_per_step'], res[tag + '_min'], res[tag + '_max'] = round(float(np.median(m)), 4), round(float(m.min()), 4), round(float(m.max()), 4)
+        res[tag + '_served'] = sim.served_count()
+    res['plan_held_at_end'], res['actuated_held_at_end'] = (int((last[t].held != 0).sum().item()) for t in ('plan', 'actuated'))
+    if args.stage_reps > 0:         # either kernel alone on the words its run left (the clocks and junction states move on: harmless here)
+        n = args.stage_reps
+        a, b = last['plan'], last['actuated']
+        cut_a, cut_b = a.inter['cut_len'].clone(), b.inter['cut_len'].clone()
+
+        def plan_stage():
+            for _ in range(n):
+                ctx.signal_step(a.dl, a.state, a.path_off, a.path_len, a.traj_idx, cut_a, a._signals, done=a.done)
+
+        def actuated_stage():
+            for _ in range(n):
+                ctx.actuated_step(b.dl, b.state, b.path_off, b.path_len, b.traj_idx, cut_b, b._signals, b._actuation, done=b.done)
+        plan_stage(); actuated_stage(); ctx.synchronize()      # warm-up
+        us = {'signal_kernel': [], 'actuated_signal_kernel': []}
+        for _ in range(args.reps):
+            us['signal_kernel'].append(1000.0 * timed(plan_stage, n))
+            us['actuated_signal_kernel'].append(1000.0 * timed(actuated_stage, n))
+        for k, v in us.items():
+            res[k + '_us_per_call'] = [round(float(x), 3) for x in v]
+            res[k + '_median_us_per_call'] = round(float(np.median(v)), 3)
+        res['stage_note'] = 'back-to-back stage calls from the host, each with its struct check (the three small tables read back): an upper bound of the launch'
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == '__main__':
+    main()
