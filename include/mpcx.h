@@ -378,6 +378,12 @@ typedef struct {
 } mpcx_closed_loop;
 int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
                              int32_t n_steps, int32_t use_graph);
+/* Step fusion (on by default).  A run of n steps without a graph on the local pool -- no scripted traffic, one linearisation pass, none of
+ * the run log, retirement, scene, admission, respawn, routes, precedence, signals or actuation -- enqueues ONE launch per step for what
+ * belongs to an agent alone: the plant update of the step before, the pack and prediction of its pool row and its warm-start rollout
+ * (head_kernel); the run ends with the last step's plant update in a launch of its own.  Every buffer holds the same bits when the call
+ * returns.  on = 0: the launch sequence without fusion (the rollout on the side stream beside the conflict search), for every run. */
+int32_t mpcx_set_step_fusion(mpcx_ctx *ctx, int32_t on);
 /* run statistics accumulated on the device by every step of mpcx_closed_loop_run since the last reset (what the reference's scripts
  * print per run: solver failures; plus iteration counts): out4 = (agent-steps, interior-point iterations, failed solves, max iterations).
  * Synchronises the context's stream. */

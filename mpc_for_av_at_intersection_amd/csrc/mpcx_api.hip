@@ -120,6 +120,12 @@ int32_t mpcx_set_linearisation_passes(mpcx_ctx *ctx, int32_t passes) {
     return MPCX_OK;
 }
 
+int32_t mpcx_set_step_fusion(mpcx_ctx *ctx, int32_t on) {
+    if (!ctx) return MPCX_E_INVALID;
+    ctx->step_fusion = on != 0;
+    return MPCX_OK;
+}
+
 int32_t mpcx_profile_qp(mpcx_ctx *ctx, int32_t enable) {
     if (!ctx) return MPCX_E_INVALID;
     ctx->prof_qp = enable != 0;

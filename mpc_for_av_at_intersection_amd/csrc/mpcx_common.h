@@ -41,6 +41,7 @@ struct mpcx_ctx {
     void *multi = nullptr;      // scratch of mpcx_expand_multi_batch and mpcx_astar_batch (segment descriptors + block tables)
     size_t multi_cap = 0;
     int qp_solver = 0;          // 0 = automatic, 1 = condensed (one wavefront per QP), 2 = stage-structured (mpcx_set_qp_solver)
+    bool step_fusion = true;    // mpcx_closed_loop_run takes plant, prediction and rollout in one launch where it can (mpcx_set_step_fusion)
     int lin_passes = 1;         // linearisation passes per step of mpcx_closed_loop_run (lib/mpc.py MAX_ITER; mpcx_set_linearisation_passes)
     bool prof_qp = false;       // bracket qp_kernel launches with events (mpcx_profile_qp)
     std::vector<hipEvent_t> prof_ev;   // start/stop pairs recorded so far
@@ -61,6 +62,7 @@ struct mpcx_ctx {
 struct mpcx_interaction_extras {
     // local pool: the prediction kernel packs the pool rows from the agents' states and applied inputs itself (no launch of its own)
     const double *pack_state = nullptr, *pack_applied = nullptr;
+    bool predicted = false;             // the pool rows are packed and predicted already, in stream order (head_kernel): no prediction launch
     // ... with scripted traffic in the pool: agent q is packed into row ego_row[q], and the n_actors rows actor_row[] (written by
     // traffic_kernel just before) are predicted as they stand; nullptr: row q is agent q
     const int32_t *ego_row = nullptr, *actor_row = nullptr;
@@ -86,6 +88,7 @@ struct mpcx_window_extras {
     bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
     const int32_t *near = nullptr, *tidx = nullptr;   // mpcx_interaction_extras::near and the conflict search's updated traj_idx
     bool rollout_forked = false;        // the rollout of this step is in flight on the side stream already (mpcx_rollout_fork)
+    bool rollout_done = false;          // ... or xbar is written already, in stream order (head_kernel): nothing is forked and nothing joined
     // mpcx_mpc_prepare_batch_stop: the stop index per agent (nullptr: none, the two below are not read), the speed reference in front of
     // it and where the window kernel leaves the path length it saw
     const int32_t *stop_idx = nullptr;
@@ -116,6 +119,8 @@ int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const
 int32_t mpcx_qp_enqueue(mpcx_ctx *ctx, int32_t B, const double *x0, const double *xref, const double *xbar, const uint8_t *reaches_end,
                       const double *u_warm, double *x_out, double *u_out, int32_t *status, int32_t *iters, double *kkt, const mpcx_qp_order &ord);   // mpcx_qp.hip
 int32_t mpcx_plant_enqueue(mpcx_ctx *ctx, int32_t B, double *state, double *u, const int32_t *status, double *applied, const mpcx_plant_extras &x);   // mpcx_prepare.hip
+int32_t mpcx_head_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, double *state, double *applied, double *u,
+                          const int32_t *status, const int32_t *iters, double *xbar, double *obs6, bool plant, bool reset_bins);                   // mpcx_prepare.hip
 
 int32_t mpcx_fail(mpcx_ctx *ctx, int32_t code, const char *fmt, ...);
 int32_t mpcx_check_launch(mpcx_ctx *ctx, const char *what);

@@ -13,6 +13,7 @@
 // reach, and the FIRST ROW IN THE REFERENCE'S ORDER is recovered as the minimum of an integer key over all hits
 // (bit-exact index outputs).
 #include "mpcx_common.h"
+#include "mpcx_predict_core.h"
 
 namespace mpcx {
 
@@ -22,12 +23,6 @@ constexpr bool FORCE_EXACT = true;
 #else
 constexpr bool FORCE_EXACT = false;
 #endif
-
-// trajectories.py:11-37: the two disc centres (x, y, x, y) of a pose at (px, py) whose heading has cos / sin (c, s)
-__device__ __forceinline__ void pose_discs(const mpcx_interaction_params &ip, double px, double py, double c, double s, double *out) {
-#pragma unroll
-    for (int d = 0; d < 2; d++) disc_centre(px, py, c, s, ip.circle_centers[2 * d], ip.circle_centers[2 * d + 1], out[2 * d], out[2 * d + 1]);
-}
 
 struct PredArgs {
     mpcx_interaction_params ip;
@@ -50,7 +45,7 @@ struct PredArgs {
     double *stand;
 };
 
-// moving_obstacles_prediction.py:21-28: v is updated BEFORE yaw; disc centres as trajectories.py:11-37
+// moving_obstacles_prediction.py:21-28, one lane per pool row (predict_row, mpcx_predict_core.h)
 template <bool MAPPED, bool SCENE = false, bool STAND = false>
 __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
     int o = blockIdx.x * blockDim.x + threadIdx.x;
@@ -73,20 +68,7 @@ __global__ __launch_bounds__(256) void predict_kernel(PredArgs a) {
         x = s6[0]; y = s6[1]; v = s6[2]; yaw = s6[3]; acc = s6[4]; steer = s6[5];
     }
     if constexpr (SCENE) { if (a.absent[o] != 0) return; }       // (0 <= o < n_pool = the mask's length, checked by the host)
-    const double tn = tan(steer);
-    const double dt = a.ip.dt;
-    double s, c;
-    sincos(yaw, &s, &c);
-    if constexpr (STAND) pose_discs(a.ip, x, y, c, s, a.stand + 4 * (size_t)o);
-    double *out = a.pred + (size_t)o * a.ip.pred_steps * 4;
-    for (int k = 0; k < a.ip.pred_steps; k++) {
-        x = __dadd_rn(x, __dmul_rn(__dmul_rn(v, c), dt));
-        y = __dadd_rn(y, __dmul_rn(__dmul_rn(v, s), dt));
-        v = __dadd_rn(v, __dmul_rn(acc, dt));
-        yaw = __dadd_rn(yaw, __dmul_rn(__dmul_rn(__ddiv_rn(v, a.ip.L), tn), dt));
-        sincos(yaw, &s, &c);
-        pose_discs(a.ip, x, y, c, s, out + 4 * k);
-    }
+    predict_row<STAND>(a.ip, x, y, v, yaw, acc, steer, STAND ? a.stand + 4 * (size_t)o : nullptr, a.pred + (size_t)o * a.ip.pred_steps * 4);
 }
 
 struct InterArgs {
@@ -965,7 +947,9 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     if (x.absent && (!x.done || n_obs_pool < 1)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: a scene without retirement or without a pool");
     if ((x.prec || x.stand) && (!x.absent || !x.prec || !x.stand)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: precedence without a scene, or without one of prec and stand");
     { int32_t rc = mpcx_ensure_pred(ctx, (size_t)(n_obs_pool > 0 ? n_obs_pool : 1) * ip->pred_steps * 4); if (rc != MPCX_OK) return rc; }
-    if (n_obs_pool > 0 && x.pack_state && x.ego_row) {
+    if (x.predicted) {
+        // (the head of the closed loop's step has packed and predicted the pool already)
+    } else if (n_obs_pool > 0 && x.pack_state && x.ego_row) {
         // closed loop with scripted traffic: only the rows that hold an agent or an actor are predicted (the others are outside every window)
         const int lanes = x.n_ego + x.n_actors;
         mpcx::PredArgs pa{*ip, lanes, n_obs_pool, obs6, ctx->pred, x.pack_state, x.pack_applied, const_cast<double *>(obs6),

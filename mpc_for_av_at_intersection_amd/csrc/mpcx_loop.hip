@@ -11,7 +11,8 @@
 // more launch behind the conflict search holds agents at their stop lines (mpcx_actuation: its lights follow the demand).
 // Every stage is the kernel behind the per-stage C entry
 // point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
-// by one from the host.
+// by one from the host.  With step fusion (mpcx_set_step_fusion, enqueue_fused_run) a run without any of the optional stages takes the plant
+// update of the step before, the pool pack, the prediction and the rollout in one launch per step: the same bits in every buffer.
 #include "mpcx_common.h"
 #include <cmath>
 #include <cstring>
@@ -193,6 +194,48 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     return rc;
 }
 
+// A run of n_steps with step fusion (mpcx_set_step_fusion; closed_loop_run decides where it applies: the local pool, no scripted traffic, one
+// linearisation pass, no optional stage): per step ONE launch for what belongs to an agent alone -- the plant update of the step before
+// (from the second step of the run on), the pack and prediction of its pool row, its warm-start rollout -- then the conflict search, the
+// window selection and the solve with the arguments enqueue_step gives them; the last step's plant update ends the run in a launch of its
+// own.  Nothing runs on the side stream and neither event is touched.  The buffers hold the bits enqueue_step leaves.
+static int32_t enqueue_fused_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_closed_loop_opts *o,
+                                 int32_t n_steps) {
+    const int P = c->P;
+    const bool speed = o->stop_mode == MPCX_STOP_SPEED;
+    const bool binned = P < (1 << 24);
+    int32_t rc;
+    for (int s = 0; s < n_steps; s++) {
+        ctx->bins_clean = false;        // until the plant update of this step is enqueued
+        rc = mpcx_head_enqueue(ctx, ip, P, c->state, c->applied, c->u_sol, c->status, c->iters, c->xbar, c->obs6, s > 0, binned);
+        if (rc != MPCX_OK) return rc;
+        mpcx_interaction_extras ix;
+        ix.prev_save = ctx->prev_cut;
+        ix.near = near_hints(ctx, P);
+        ix.bin_hint = binned ? c->iters : nullptr;
+        if (speed) ix.key_prev = c->cut_len;
+        ix.pack_state = c->state; ix.pack_applied = c->applied;
+        ix.predicted = true;
+        rc = mpcx_interaction_enqueue(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
+                                      speed ? o->prev_len : c->cut_len, P, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx,
+                                      c->hit_xy, c->cut_len, ix);
+        if (rc != MPCX_OK) return rc;
+        mpcx_window_extras wx{binned, near_hints(ctx, P), c->traj_idx, true};
+        wx.rollout_done = true;
+        if (speed) { wx.stop_idx = c->cut_len; wx.v_ref = o->v_ref; wx.len_seen = o->prev_len; }
+        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
+                                 c->target_ind, nullptr, 4 * (int64_t)(ctx->mpc.T + 1), c->xref, c->reaches_end, c->xbar, wx);
+        if (rc != MPCX_OK) return rc;
+        const mpcx_qp_order ord{binned, c->iters, c->cut_len, ctx->prev_cut, nullptr};
+        rc = mpcx_qp_enqueue(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol, c->status, c->iters, c->kkt, ord);
+        if (rc != MPCX_OK) return rc;
+    }
+    const mpcx_plant_extras px{c->iters, binned, nullptr};
+    rc = mpcx_plant_enqueue(ctx, P, c->state, c->u_sol, c->status, c->applied, px);
+    if (rc == MPCX_OK) ctx->bins_clean = binned;
+    return rc;
+}
+
 static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
                                const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, const mpcx_admit *admit,
                                const mpcx_respawn *respawn, const mpcx_routes *routes, const mpcx_precedence *precedence,
@@ -336,6 +379,9 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (rc != MPCX_OK) return rc;
 
     if (!use_graph) {
+        if (ctx->step_fusion && c->exchange == 0 && c->n_actors == 0 && ctx->lin_passes == 1 && !log && !retire && !scene && !admit && !respawn &&
+            !routes && !precedence && !signals && !actuation)
+            return enqueue_fused_run(ctx, ip, c, &opt, n_steps);
         for (int s = 0; s < n_steps; s++) {
             rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence, signals, actuation);
             if (rc != MPCX_OK) return rc;

@@ -8,6 +8,7 @@
 // Arithmetic follows the reference's operation order; products are kept un-fused (-ffp-contract is
 // irrelevant to the window's gathers; the plant's Euler updates are fused multiply-adds, see plant_euler).
 #include "mpcx_common.h"
+#include "mpcx_predict_core.h"
 #include <cmath>
 
 namespace mpcx {
@@ -205,6 +206,32 @@ struct RollArgs {
 constexpr int ROLL_GROUP = 4, ROLL_BLOCK = 256, ROLL_AGENTS = ROLL_BLOCK / ROLL_GROUP;
 static_assert(WAVE % ROLL_GROUP == 0 && ROLL_BLOCK % WAVE == 0, "whole groups per wavefront");
 inline size_t rollout_lds(int T) { return ROLL_AGENTS * (4 * (size_t)(T + 1) + 1) * sizeof(double); }
+// one agent's rollout from (x, y, v, th) by its group of lanes (j = the lane's place in the group) into its staging row xb[4 W];
+// oa = its warm start (T accelerations | T steering angles) or nullptr = zeros
+__device__ __forceinline__ void rollout_group(const mpcx_mpc_params &p, double x, double y, double v, double th, const double *oa, int j, double *xb) {
+    constexpr int G = ROLL_GROUP;
+    const int T = p.T, W = T + 1;
+    if (j == 0) { xb[0] = x; xb[W] = y; xb[2 * W] = v; xb[3 * W] = th; }
+    const auto euler = [&](double acc, double rate) { return plant_euler(p, acc, rate); };
+    const auto speed = [&](double vv, double acc) { return plant_speed(p, vv, acc); };
+    // x, y, v, th: the state at step t0, the same in every lane of the group; lane j takes the step from t = t0 + j to t + 1
+    for (int t0 = 0; t0 < T; t0 += G) {
+        const int t = t0 + j;
+        const bool in = t < T;
+        const double ai = oa && in ? oa[t] : 0.0, di = oa && in ? oa[T + t] : 0.0;   // mpc.py:222-224: zeros when no warm start
+        const double tn = plant_tan(p, di);
+        const double v0 = v, th0 = th;
+        const double vn = group_chain<G>(v, ai, j, speed);                  // v_{t+1}
+        const double vt = group_prev<G>(vn, v0, j);                         // v_t
+        const double thn = group_chain<G>(th, plant_rate_th(p, vt, tn), j, euler);
+        const double tht = group_prev<G>(thn, th0, j);
+        double s, c;
+        sincos(tht, &s, &c);
+        const double xn = group_chain<G>(x, plant_rate_xy(vt, c), j, euler);
+        const double yn = group_chain<G>(y, plant_rate_xy(vt, s), j, euler);
+        if (in) { xb[t + 1] = xn; xb[W + t + 1] = yn; xb[2 * W + t + 1] = vn; xb[3 * W + t + 1] = thn; }
+    }
+}
 template <bool RETIRE>
 __global__ __launch_bounds__(ROLL_BLOCK) void rollout_kernel(RollArgs a) {
     constexpr int G = ROLL_GROUP;
@@ -221,28 +248,7 @@ __global__ __launch_bounds__(ROLL_BLOCK) void rollout_kernel(RollArgs a) {
     if (!gone) {            // (the same for every lane of a group)
         const int b = b0 + r;
         double x = a.state[4 * b], y = a.state[4 * b + 1], v = a.state[4 * b + 2], th = a.state[4 * b + 3];
-        double *xb = s_x(r);
-        if (j == 0) { xb[0] = x; xb[W] = y; xb[2 * W] = v; xb[3 * W] = th; }
-        const double *oa = a.u_warm ? a.u_warm + (size_t)b * 2 * T : nullptr;
-        const auto euler = [&](double acc, double rate) { return plant_euler(a.p, acc, rate); };
-        const auto speed = [&](double vv, double acc) { return plant_speed(a.p, vv, acc); };
-        // x, y, v, th: the state at step t0, the same in every lane of the group; lane j takes the step from t = t0 + j to t + 1
-        for (int t0 = 0; t0 < T; t0 += G) {
-            const int t = t0 + j;
-            const bool in = t < T;
-            const double ai = oa && in ? oa[t] : 0.0, di = oa && in ? oa[T + t] : 0.0;   // mpc.py:222-224: zeros when no warm start
-            const double tn = plant_tan(a.p, di);
-            const double v0 = v, th0 = th;
-            const double vn = group_chain<G>(v, ai, j, speed);                  // v_{t+1}
-            const double vt = group_prev<G>(vn, v0, j);                         // v_t
-            const double thn = group_chain<G>(th, plant_rate_th(a.p, vt, tn), j, euler);
-            const double tht = group_prev<G>(thn, th0, j);
-            double s, c;
-            sincos(tht, &s, &c);
-            const double xn = group_chain<G>(x, plant_rate_xy(vt, c), j, euler);
-            const double yn = group_chain<G>(y, plant_rate_xy(vt, s), j, euler);
-            if (in) { xb[t + 1] = xn; xb[W + t + 1] = yn; xb[2 * W + t + 1] = vn; xb[3 * W + t + 1] = thn; }
-        }
+        rollout_group(a.p, x, y, v, th, a.u_warm ? a.u_warm + (size_t)b * 2 * T : nullptr, j, s_x(r));
     }
     __syncthreads();
     double *out = a.xbar + (size_t)b0 * 4 * W;
@@ -271,6 +277,24 @@ struct PlantArgs {
     const int32_t *done;                // retirement or nullptr: the lane of an agent with done[b] != 0 leaves state, applied and u alone and feeds no statistics
 };
 
+// the run statistics of the 64 agents of one wavefront (lane = agent b; in: it drove this step, it = its iteration count, bad: its solve
+// failed) are added to the wavefront's slot, b / 64
+__device__ __forceinline__ void plant_stats(unsigned long long *stats, int b, bool in, int it, bool bad) {
+    int s_it = it, s_bad = bad ? 1 : 0, s_n = in ? 1 : 0, s_mx = it;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        s_it += __shfl_xor(s_it, d, WAVE); s_bad += __shfl_xor(s_bad, d, WAVE); s_n += __shfl_xor(s_n, d, WAVE);
+        const int o = __shfl_xor(s_mx, d, WAVE); s_mx = o > s_mx ? o : s_mx;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        // one slot of four counters per wavefront, touched by that wavefront only (steps are ordered by the stream): no atomics --
+        // 2048 atomics on four hot words made this 5-us kernel a 22-us one
+        unsigned long long *w = stats + 4 * (size_t)(b >> 6);
+        w[0] += (unsigned long long)s_n; w[1] += (unsigned long long)s_it; w[2] += (unsigned long long)s_bad;
+        if ((unsigned long long)s_mx > w[3]) w[3] = (unsigned long long)s_mx;
+    }
+}
+
 // MPC.step's tail (mpc.py:294-297) + Simulation.step
 __global__ __launch_bounds__(256) void plant_kernel(PlantArgs a) {
     if (a.zero_bins && blockIdx.x == 0) {
@@ -281,21 +305,7 @@ __global__ __launch_bounds__(256) void plant_kernel(PlantArgs a) {
     const bool gone = a.done && b < a.B && a.done[b] != 0;
     if (a.has_stats) {          // run statistics (mpcx_closed_loop_stats)
         const bool in = b < a.B && !gone;
-        const int it = in ? a.iters[b] : 0;
-        const int bad = (in && a.status[b] != MPCX_QP_OPTIMAL) ? 1 : 0;
-        int s_it = it, s_bad = bad, s_n = in ? 1 : 0, s_mx = it;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            s_it += __shfl_xor(s_it, d, WAVE); s_bad += __shfl_xor(s_bad, d, WAVE); s_n += __shfl_xor(s_n, d, WAVE);
-            const int o = __shfl_xor(s_mx, d, WAVE); s_mx = o > s_mx ? o : s_mx;
-        }
-        if ((threadIdx.x & 63) == 0) {
-            // one slot of four counters per wavefront, touched by that wavefront only (steps are ordered by the stream): no atomics --
-            // 2048 atomics on four hot words made this 5-us kernel a 22-us one
-            unsigned long long *w = a.stats + 4 * (size_t)(b >> 6);
-            w[0] += (unsigned long long)s_n; w[1] += (unsigned long long)s_it; w[2] += (unsigned long long)s_bad;
-            if ((unsigned long long)s_mx > w[3]) w[3] = (unsigned long long)s_mx;
-        }
+        plant_stats(a.stats, b, in, in ? a.iters[b] : 0, in && a.status[b] != MPCX_QP_OPTIMAL);
     }
     if (b >= a.B || gone) return;
     const int T = a.p.T;
@@ -310,6 +320,96 @@ __global__ __launch_bounds__(256) void plant_kernel(PlantArgs a) {
     double x = a.state[4 * b], y = a.state[4 * b + 1], v = a.state[4 * b + 2], th = a.state[4 * b + 3];
     plant_step(a.p, x, y, v, th, ai, di);
     a.state[4 * b] = x; a.state[4 * b + 1] = y; a.state[4 * b + 2] = v; a.state[4 * b + 3] = th;
+}
+
+struct HeadArgs {
+    mpcx_mpc_params p;
+    mpcx_interaction_params ip;
+    int B;
+    double *state, *applied, *u;      // u: the previous solution, the rollout's warm start
+    double *xbar, *obs6, *pred;       // the pool (row q = agent q) and the prediction scratch [B][pred_steps][2][2]
+    // PLANT only: what plant_kernel gets (PlantArgs) for the step before
+    const int32_t *status, *iters;
+    const mpcx_qp_tuning *tune;
+    unsigned long long *stats;
+    int32_t *zero_bins, *zero_ticket;
+};
+
+// The head of a closed-loop step in ONE launch: what belongs to agent q alone and reads nothing but q's own state, applied inputs and
+// previous solution -- the plant update of the step before (PLANT; plant_kernel), the pack and the prediction of pool row q
+// (predict_kernel<false>) and the warm-start rollout of agent q (rollout_kernel<false>).  The rollout is over before the conflict search
+// starts: no side stream, no fork, no join, and one dependent launch boundary instead of two.
+// A workgroup takes ROLL_AGENTS = 64 agents: wavefronts 0..3 are rollout_kernel's workgroup (a group of ROLL_GROUP lanes per agent), wavefront
+// 4 is predict_kernel's and plant_kernel's wavefront (a lane per agent).  The two serial chains (pred_steps dependent sincos, T / ROLL_GROUP
+// chain steps) sit in different wavefronts and run beside each other.  PLANT: EVERY lane takes its agent's plant step in registers (one tan,
+// one sincos) from the old state; the lanes of wavefront 4 alone store state, applied, the reset warm start and the statistics -- behind
+// the workgroup's one barrier, in front of which every lane has loaded what it needs of the old values.  A rollout group whose agent's
+// solve failed takes zeros for the warm start that wavefront 4 resets: it never loads it.  No workgroup waits for another.
+// Every wavefront of the rollout writes its own 16 agents' rows to LDS and copies them out itself (one contiguous run of 16 x 4 W doubles):
+// it waits for nobody, wavefront 4's chain included.
+constexpr int HEAD_BLOCK = ROLL_BLOCK + WAVE;
+static_assert(ROLL_AGENTS == WAVE, "the prediction wavefront holds the workgroup's agents one per lane; its statistics slot is plant_kernel's");
+template <bool PLANT>
+__global__ __launch_bounds__(HEAD_BLOCK) void head_kernel(HeadArgs a) {
+    constexpr int G = ROLL_GROUP;
+    extern __shared__ double s_roll[];                   // [ROLL_AGENTS][4 W + 1], rollout_kernel's rows (the spare word keeps them off each other's banks)
+    const int T = a.p.T, W = T + 1;
+    const int RS = 4 * W + 1;
+    const int tid = (int)threadIdx.x;
+    const bool pred_wave = tid >= ROLL_BLOCK;
+    const int b0 = (int)blockIdx.x * ROLL_AGENTS;
+    const int n = a.B - b0 < ROLL_AGENTS ? a.B - b0 : ROLL_AGENTS;
+    const int r = pred_wave ? tid - ROLL_BLOCK : tid / G, j = tid % G;
+    const bool in = r < n;
+    const int b = b0 + (in ? r : 0);        // (the lanes without an agent read the workgroup's first and write nothing)
+    double x = a.state[4 * b], y = a.state[4 * b + 1], v = a.state[4 * b + 2], th = a.state[4 * b + 3];
+    double di = 0.0, ai = 0.0;              // the inputs applied to reach (x, y, v, th): (steer, accel)
+    bool failed = false;
+    if constexpr (PLANT) {
+        if (a.zero_bins && blockIdx.x == 0) {
+            for (int i = tid; i < MPCX_ORDER_COPIES * MPCX_ORDER_BINS; i += HEAD_BLOCK) a.zero_bins[i] = 0;
+            if (tid < MPCX_TICKET_WORDS) a.zero_ticket[tid] = 0;
+        }
+        // plant_kernel's expressions for the step before, in every lane
+        failed = a.status[b] != MPCX_QP_OPTIMAL;
+        const int it = pred_wave && in ? a.iters[b] : 0;
+        di = a.applied[2 * b];
+        if (!failed) { di = a.u[(size_t)b * 2 * T + T]; ai = a.u[(size_t)b * 2 * T]; }
+        else { ai = a.p.max_decel; if (a.tune) ai = a.tune[b].max_decel; }      // (as a ?: of the two the kernel argument went to a stack slot)
+        plant_step(a.p, x, y, v, th, ai, di);
+        __syncthreads();        // every lane holds what it needs of the old state, applied and u: now they may be overwritten
+        if (pred_wave) {
+            plant_stats(a.stats, b0 + r, in, it, in && failed);
+            if (in) {
+                if (failed) for (int t = 0; t < 2 * T; t++) a.u[(size_t)b * 2 * T + t] = 0.0;   // warm start reset, mpc.py:222-224
+                a.applied[2 * b] = di; a.applied[2 * b + 1] = ai;
+                a.state[4 * b] = x; a.state[4 * b + 1] = y; a.state[4 * b + 2] = v; a.state[4 * b + 3] = th;
+            }
+        }
+    } else if (pred_wave) {
+        di = a.applied[2 * b]; ai = a.applied[2 * b + 1];
+    }
+    if (pred_wave) {
+        if (!in) return;
+        // predict_kernel<false> with the pool pack: MovingObstacle*.get() = (x, y, v, yaw, a, steer)
+        double *row = a.obs6 + 6 * (size_t)b;
+        row[0] = x; row[1] = y; row[2] = v; row[3] = th; row[4] = ai; row[5] = di;
+        predict_row<false>(a.ip, x, y, v, th, ai, di, nullptr, a.pred + (size_t)b * a.ip.pred_steps * 4);
+        return;
+    }
+    if (in) rollout_group(a.p, x, y, v, th, failed ? nullptr : a.u + (size_t)b * 2 * T, j, s_roll + (size_t)r * RS);
+    // the rows of this wavefront's agents were written by its own lanes: LDS serves a wavefront's accesses in order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    constexpr int ROWS = WAVE / G;
+    const int lane = tid & 63, r0 = (tid >> 6) * ROWS;
+    const int nr = n - r0 < ROWS ? n - r0 : ROWS;       // (<= 0: a wavefront without agents)
+    double *out = a.xbar + (size_t)(b0 + r0) * 4 * W;
+    for (int i = lane; i < nr * 4 * W; i += WAVE) {
+        const int row = i / (4 * W);
+        out[i] = s_roll[(size_t)(r0 + row) * RS + (i - row * 4 * W)];
+    }
 }
 
 }  // namespace mpcx
@@ -358,6 +458,13 @@ int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const
         return mpcx_fail(ctx, MPCX_E_INVALID, "mpc_prepare_batch: retirement needs the queue order built beside the window selection");
     // the rollout may already be in flight: mpcx_closed_loop_run forks it at the start of the step, beside the conflict search
     const bool forked = x.rollout_forked;
+    if (x.rollout_done) {       // xbar is written already, by a launch in front of this one on the context's stream: no side stream, no events
+        constexpr int per_block = mpcx::PREP_WAVES * mpcx::WIN_AGENTS;
+        const dim3 wgrid((B + per_block - 1) / per_block), wblock(64 * mpcx::PREP_WAVES);
+        if (retire) hipLaunchKernelGGL(mpcx::ref_window_kernel<true>, wgrid, wblock, 0, ctx->stream, ra);
+        else hipLaunchKernelGGL(mpcx::ref_window_kernel<false>, wgrid, wblock, 0, ctx->stream, ra);
+        return mpcx_check_launch(ctx, "prepare kernels");
+    }
     if (!forked) {
         int32_t rc = mpcx_rollout_fork(ctx, B, state, u_warm, xbar, x.done);
         if (rc != MPCX_OK) return rc;
@@ -394,6 +501,26 @@ int32_t mpcx_rollout_fork(mpcx_ctx *ctx, int32_t B, const double *state, const d
     if (hipEventRecord(ctx->ev_join, ctx->side) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "mpc_prepare_batch: cannot record the join event");
     return MPCX_OK;
+}
+
+// the head of a closed-loop step (head_kernel): plant = it also takes the plant step of the step before, with the statistics, and -- reset_bins --
+// zeroes the queue bins and the ticket, as mpcx_plant_enqueue would have.  Local pool without scripted traffic only: obs6 row q is agent q
+int32_t mpcx_head_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, double *state, double *applied, double *u,
+                          const int32_t *status, const int32_t *iters, double *xbar, double *obs6, bool plant, bool reset_bins) {
+    if (!ctx || !ip || P <= 0 || !state || !applied || !u || !status || !iters || !xbar || !obs6 || !ctx->pred || !ctx->stats)
+        return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null pointer at the head of a step");
+    if (ctx->pred_cap < (size_t)P * ip->pred_steps * 4 * sizeof(double) || ctx->stats_slots < ((size_t)P + 63) / 64)
+        return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: the prediction scratch or the statistics are too small for %d agents", P);
+    if (ctx->tune && ctx->tune_rows != P)
+        return mpcx_fail(ctx, MPCX_E_INVALID, "plant_step_batch: %d tuning rows are set but the batch has %d agents", ctx->tune_rows, P);
+    const bool rz = plant && reset_bins && ctx->bins && ctx->ticket;
+    mpcx::HeadArgs ha{ctx->mpc, *ip, P, state, applied, u, xbar, obs6, ctx->pred, status, iters, ctx->tune, ctx->stats,
+                      rz ? ctx->bins : nullptr, rz ? ctx->ticket : nullptr};
+    const size_t lds = mpcx::rollout_lds(ctx->mpc.T);
+    const dim3 grid((P + mpcx::ROLL_AGENTS - 1) / mpcx::ROLL_AGENTS), block(mpcx::HEAD_BLOCK);
+    if (plant) hipLaunchKernelGGL(mpcx::head_kernel<true>, grid, block, lds, ctx->stream, ha);
+    else hipLaunchKernelGGL(mpcx::head_kernel<false>, grid, block, lds, ctx->stream, ha);
+    return mpcx_check_launch(ctx, "head_kernel");
 }
 
 extern "C" int32_t mpcx_plant_step_batch(mpcx_ctx *ctx, int32_t B, double *state, double *u,

@@ -867,6 +867,12 @@ class Context:
         self._chk(self.lib.mpcx_set_linearisation_passes(self._ctx, int(passes)))
         self.lin_passes = int(passes)
 
+    def set_step_fusion(self, on: bool):
+        """mpcx_closed_loop_run without a graph: True (the default) = one launch per step for the plant update of the step before, the
+        prediction and the warm-start rollout, where the run has none of the optional stages; False = a launch each, the rollout on the
+        side stream.  The results are the same bits either way."""
+        self._chk(self.lib.mpcx_set_step_fusion(self._ctx, 1 if on else 0))
+
     def profile_qp(self, enable: bool):
         """bracket every qp_kernel launch with HIP events on the context's stream (mpcx_profile_qp)"""
         self._chk(self.lib.mpcx_profile_qp(self._ctx, 1 if enable else 0))
