@@ -562,12 +562,25 @@ class Context:
     @_ordered
     def moving_collision(self, ip: InteractionParams, ego, ego_cs, ego_off, ego_len, path, path_cs, path_off, path_len,
                          obs, obs_cs, obs_off, obs_cnt, out=None):
-        """mpcx_moving_collision_batch (explicit trajectories). Returns dict(hit_idx, hit_xy)."""
+        """mpcx_moving_collision_batch (explicit trajectories). Returns dict(hit_idx, hit_xy).
+        obs / obs_cs: the obstacle trajectories, ip.pred_steps poses each, as (n, pred_steps, 3) / (n, pred_steps, 2) or with the first two
+        axes flattened; obs_off / obs_cnt count TRAJECTORIES.  The pool size handed to the library is the number of trajectories: it
+        reads pred_steps poses per pool entry, so the number of rows of a flattened table would send it pred_steps times past the end."""
         Pn = ego_off.shape[0]
         if out is None:
             out = dict(hit_idx=torch.empty(Pn, dtype=torch.int32, device=self.device),
                        hit_xy=torch.empty((Pn, 2), dtype=torch.float64, device=self.device))
-        nobs = 0 if obs is None else obs.shape[0]
+        nobs = 0
+        if obs is not None:
+            steps = int(ip.pred_steps)
+            if steps < 1 or obs.dtype != torch.float64 or obs.numel() % (3 * steps) or not obs.is_contiguous():
+                raise MpcxError('moving_collision: obs must be a contiguous float64 table of whole trajectories of pred_steps = %d poses '
+                                '(x, y, yaw), got shape %s' % (steps, tuple(obs.shape)))
+            nobs = obs.numel() // (3 * steps)
+            self._want(obs_cs, torch.float64, None, 'obs_cs')
+            if obs_cs.numel() != 2 * nobs * steps:
+                raise MpcxError('moving_collision: obs_cs must hold cos / sin of every pose of obs (%d x %d x 2), got shape %s'
+                                % (nobs, steps, tuple(obs_cs.shape)))
         cip = ip.to_c()
         self._chk(self.lib.mpcx_moving_collision_batch(self._ctx, C.byref(cip), Pn, _ptr(ego), _ptr(ego_cs), _ptr(ego_off),
                                                        _ptr(ego_len), _ptr(path), _ptr(path_cs), _ptr(path_off), _ptr(path_len),

@@ -15,7 +15,7 @@ by KKT residuals, see DESIGN.md "parity").
 
 Only DATA is written (npz/json): no reference source, bytecode or pickle is copied.
 
-usage:  python tests/golden/make_golden.py [--stage numpy|closedloop|...|horizons|all]
+usage:  python tests/golden/make_golden.py [--stage numpy|closedloop|...|horizons|moving_wide|all]
 """
 import argparse
 import json
@@ -639,6 +639,172 @@ def stage_onedisc():
     _savez('moving_onedisc.npz', hit=np.array(hits), cut=np.array(cuts, dtype=np.int32), circle_centers=one.circle_centers)
 
 
+WIDE_STEPS = (1, 2, 7, 35, 36, 50, 63, 64)
+WIDE_WINDOWS = (0, 3, 20, 40, 70)
+WIDE_CHUNK = 512            # obstacle disc positions the conflict-search kernel holds per pass (8 per lane)
+
+
+def stage_moving_wide():
+    """moving_wide.npz: the moving-car conflict chain of moving/* (same path, same car, same sequence of calls) beyond the stock
+    point 7 obstacles / 35 frames / window 20: 8..16 obstacles, 1..64 predicted frames, windows 0..70.  Two parts, told apart by
+    `kind`: 0 = random cases on the grid WIDE_STEPS x WIDE_WINDOWS, 1..6 = constructed cases (a)..(f) with standing obstacles placed on
+    poses of the ego's own prediction, which fix WHICH obstacle rank holds the first row.  Every answer is the reference's; the
+    asserts below are conditions on those answers (coverage of the fixture), not expectations of them."""
+    import numpy as np
+    from lib.car_dimensions import BicycleModelDimensions
+    from lib.trajectories import resample_curve, car_trajectory_to_collision_point_trajectories
+    from lib.simulation import Simulation
+    from lib.collision_avoidance import check_collision_moving_cars, get_cutoff_curve_by_position_idx
+    from lib.moving_obstacles_prediction import MovingObstaclesPrediction
+    import lib.mpc as rmpc
+
+    rng = np.random.default_rng(20261019)
+    bic = BicycleModelDimensions()
+    full = np.load(os.path.join(HERE, 'mpc_pre.npz'))['path_4_1']
+    dl = float(np.linalg.norm(full[0, :2] - full[1, :2]))
+    margin = 4 * int(np.ceil(bic.radius / dl))
+    assert margin == int(np.load(os.path.join(HERE, 'moving.npz'))['moving/margin'])
+    NMAX = 16
+
+    def ego_prediction(idx, v0):                    # main/scenarios/mpc_intersection.py:110-116
+        traj = full[idx:]
+        if v0 < Simulation.MAX_SPEED:
+            rdl = np.zeros((traj.shape[0],)) + rmpc.MAX_ACCEL
+            rdl = 0.2 * np.minimum(np.cumsum(rdl) + v0, Simulation.MAX_SPEED)
+            return traj, resample_curve(traj, dl=rdl)
+        return traj, resample_curve(traj, dl=0.2 * Simulation.MAX_SPEED)
+
+    def predictions(six, steps):
+        # `steps` frames: the horizon is half a sample short of 0.2 * steps, because np.arange(0, 0.2 * 63, 0.2) has 64 entries
+        # (0.2 * 63 = 12.600000000000001); the frames themselves do not depend on the horizon
+        trajs = [np.vstack(MovingObstaclesPrediction(*s6, sample_time=0.2, car_dimensions=bic).state_prediction(0.2 * steps - 0.1)).T
+                 for s6 in six]
+        assert all(len(t) == steps for t in trajs), (steps, [len(t) for t in trajs])
+        return trajs
+
+    rec = dict(inp=[], obs=[], hit=[], cut=[], nres=[], winner=[], kind=[], rank=[])
+
+    def record(kind, rank, idx, v0, six, steps, window):
+        traj, tres = ego_prediction(idx, v0)
+        trajs = predictions(six, steps)
+        hit = check_collision_moving_cars(bic, tres, traj, trajs, frame_window=window)
+        winner = -1
+        if hit is None:
+            rec['hit'].append([np.nan, np.nan, -1]); rec['cut'].append(len(full))
+        else:
+            cut = max(idx + 1, get_cutoff_curve_by_position_idx(full, hit[0], hit[1]) - margin)
+            rec['hit'].append([hit[0], hit[1], hit[2]]); rec['cut'].append(int(cut))
+            for j in range(len(six)):               # the winner's rank: the shortest prefix of the obstacle list with the full answer
+                if check_collision_moving_cars(bic, tres, traj, trajs[:j + 1], frame_window=window) == hit:
+                    winner = j
+                    break
+            assert winner >= 0
+        pad = np.full((NMAX, 6), np.nan); pad[:len(six)] = six
+        rec['inp'].append([idx, v0, len(six), steps, window]); rec['obs'].append(pad); rec['nres'].append(len(tres))
+        rec['winner'].append(winner); rec['kind'].append(kind); rec['rank'].append(rank)
+        return winner
+
+    # ---------------- random part ----------------
+    grid = 1.0 / 4096           # obstacle states on a binary grid: they are inputs, and the file deflates to a third
+
+    def far_obstacle():
+        p = full[int(rng.integers(0, len(full)))]
+        ang = rng.uniform(-np.pi, np.pi)
+        d = rng.uniform(30, 80)
+        return [p[0] - d * np.cos(ang), p[1] - d * np.sin(ang), rng.uniform(0, 9), rng.uniform(-np.pi, np.pi), rng.uniform(-1, 1), rng.uniform(-0.3, 0.3)]
+
+    def near_obstacle(idx):
+        p = full[int(rng.integers(idx, len(full)))]
+        ang = rng.uniform(-np.pi, np.pi)
+        d = rng.uniform(0, 40)
+        return [p[0] - d * np.cos(ang), p[1] - d * np.sin(ang), rng.uniform(0, 9), ang, rng.uniform(-1, 1), rng.uniform(-0.3, 0.3)]
+
+    for steps in WIDE_STEPS:
+        for window in WIDE_WINDOWS:
+            for k in range(20):
+                idx = int(rng.integers(0, len(full) - 5))
+                v0 = float(rng.uniform(0, 30 / 3.6)) if k % 4 else 30 / 3.6
+                nobs = int(rng.integers(8, NMAX + 1))
+                n_near = 0 if k % 5 == 4 else 3
+                six = np.array([far_obstacle() for _ in range(nobs - n_near)] + [near_obstacle(idx) for _ in range(n_near)])
+                six = np.round(six / grid) * grid
+                record(0, -1, idx, v0, six, steps, window)
+
+    # ---------------- constructed part ----------------
+    def far_row(j):
+        return [300.0 + 10.0 * j, 300.0, 0.0, 0.0, 0.0, 0.0]        # >= 200 m from every path point
+
+    def on_pose(pose, ahead=0.0):
+        return [pose[0] + ahead * np.cos(pose[2]), pose[1] + ahead * np.sin(pose[2]), 0.0, pose[2], 0.0, 0.0]
+
+    def constructed(kind, rank, idx, v0, near, steps):
+        six = np.array([far_row(j) for j in range(NMAX)])
+        for r, row in near.items():
+            six[r] = row
+        return record(kind, rank, idx, v0, six, steps, WIDE_WINDOWS[(rank if rank >= 0 else kind) % len(WIDE_WINDOWS)])
+
+    def first_frame_and_disc(tres, row, steps):
+        """(frame, agent disc) of the first row for ONE standing obstacle, written out plainly (for case (d) only: two obstacles that
+        must share it)"""
+        ag = [t[:, :2] for t in car_trajectory_to_collision_point_trajectories(tres, bic)]
+        ob = [t[:, :2] for t in car_trajectory_to_collision_point_trajectories(predictions([row], steps)[0], bic)]
+        for f in range(max(len(tres), steps)):
+            for ca in range(2):
+                for co in range(2):
+                    if np.linalg.norm(ag[ca][min(f, len(tres) - 1)] - ob[co][min(f, steps - 1)]) <= 2 * bic.radius:
+                        return f, ca
+        return None
+
+    IDX, V0 = 40, 30 / 3.6
+    assert min(np.linalg.norm(full[:, :2] - np.array(far_row(j)[:2]), axis=1).min() for j in range(NMAX)) >= 200.0
+    for steps in (35, 64):
+        _, tres = ego_prediction(IDX, V0)
+        assert len(tres) > 20
+        for r in range(NMAX):                                               # (a)
+            assert constructed(1, r, IDX, V0, {r: on_pose(tres[5])}, steps) == r
+        assert constructed(2, -1, IDX, V0, {0: on_pose(tres[20]), 15: on_pose(tres[3])}, steps) == 15     # (b)
+        assert constructed(3, -1, IDX, V0, {0: on_pose(tres[3]), 15: on_pose(tres[20])}, steps) == 0      # (c)
+        for k in range(6, 20):                                              # (d): a pose where both obstacles meet the same frame and disc first
+            lo, hi = on_pose(tres[k]), on_pose(tres[k], ahead=0.5)
+            if first_frame_and_disc(tres, lo, steps) == first_frame_and_disc(tres, hi, steps) is not None:
+                break
+        else:
+            raise AssertionError('(d): no pose on which both obstacles share their first frame and disc')
+        n0 = len(rec['hit'])
+        assert constructed(4, -1, IDX, V0, {2: lo, 13: hi}, steps) == 2
+        constructed(4, -2, IDX, V0, {13: hi}, steps)                        # rank 13 alone: another answer, so the order is visible
+        assert rec['hit'][n0] != rec['hit'][n0 + 1] and rec['winner'][n0 + 1] == 13
+        idx_e = len(full) - 160                                            # (e): a prediction shorter than the obstacles', conflict on its last pose
+        _, tres_e = ego_prediction(idx_e, V0)
+        assert 5 < len(tres_e) < steps
+        for r in range(NMAX):
+            assert constructed(5, r, idx_e, V0, {r: on_pose(tres_e[-1])}, steps) == r
+    _, tres_f = ego_prediction(0, V0)                                      # (f): a prediction longer than the obstacles'
+    assert len(tres_f) > 30
+    for r in range(NMAX):
+        assert constructed(6, r, 0, V0, {r: on_pose(tres_f[30])}, 2) == r
+
+    # ---------------- coverage conditions (on the reference's outputs) ----------------
+    inp = np.array(rec['inp']); hit = np.array(rec['hit']); kind = np.array(rec['kind']); winner = np.array(rec['winner'], dtype=np.int32)
+    nres = np.array(rec['nres'], dtype=np.int32)
+    steps_, window_ = inp[:, 3].astype(int), inp[:, 4].astype(int)
+    rnd = kind == 0
+    for steps in WIDE_STEPS:
+        for window in WIDE_WINDOWS:
+            cell = rnd & (steps_ == steps) & (window_ == window)
+            n_hit, n_free = int((hit[cell, 2] >= 0).sum()), int((hit[cell, 2] < 0).sum())
+            assert n_hit >= 3 and n_free >= 2, (steps, window, n_hit, n_free)
+    long_hits = rnd & (steps_ >= 35) & (hit[:, 2] >= 0)
+    late = long_hits & (winner * steps_ * 2 >= WIDE_CHUNK)
+    assert late.sum() >= 0.25 * long_hits.sum(), (int(late.sum()), int(long_hits.sum()))
+    assert (nres[rnd] < steps_[rnd]).any() and (nres[rnd] == steps_[rnd]).any() and (nres[rnd] > steps_[rnd]).any()
+    print('moving_wide: %d random cases (%d hits; steps >= 35: %d hits, %d with the winner in a later chunk), %d constructed'
+          % (rnd.sum(), (hit[rnd, 2] >= 0).sum(), long_hits.sum(), late.sum(), (~rnd).sum()))
+    _savez_stable('moving_wide.npz', **{'in': inp, 'obs': np.array(rec['obs']), 'hit': hit, 'cut': np.array(rec['cut'], dtype=np.int32),
+                                        'nres': nres, 'winner_rank': winner, 'kind': np.array(kind, dtype=np.int32),
+                                        'rank': np.array(rec['rank'], dtype=np.int32), 'margin': np.array(margin)})
+
+
 def stage_traffic():
     """scripted actors of main/lib/moving_obstacles.py: get()/step() tapes for every class and branch"""
     import contextlib
@@ -794,7 +960,7 @@ def stage_worlds():
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
-    ap.add_argument('--stage', default='numpy', choices=['numpy', 'closedloop', 'closedloop_iter2', 'onedisc', 'traffic', 'worlds', 'horizons', 'all'])
+    ap.add_argument('--stage', default='numpy', choices=['numpy', 'closedloop', 'closedloop_iter2', 'onedisc', 'traffic', 'worlds', 'horizons', 'moving_wide', 'all'])
     a = ap.parse_args()
     _enter_reference()
     if a.stage in ('numpy', 'all'):
@@ -811,3 +977,5 @@ if __name__ == '__main__':
         stage_worlds()
     if a.stage in ('horizons', 'all'):          # reads the paths of mpc_pre.npz: after stage_numpy
         stage_horizons()
+    if a.stage in ('moving_wide', 'all'):       # reads the path of mpc_pre.npz and the margin of moving.npz: after stage_numpy
+        stage_moving_wide()

@@ -175,3 +175,47 @@ def replay_all_on_oracle(sim, before, after, threads=16, tol=2e-7, dead=None):
     worst = float(diff[ok].max()) if ok.any() else 0.0
     assert worst < tol, (worst, int(diff[ok].argmax()))
     return worst, int((~same_count).sum()), int((~ok).sum())
+
+
+WIDE_CHUNK = 512        # obstacle disc positions the conflict-search kernel holds per pass of its candidate loop (8 per lane)
+WIDE_KINDS = {1: 'a', 2: 'b', 3: 'c', 4: 'd', 5: 'e', 6: 'f'}      # moving_wide.npz: `kind` of the constructed cases (0 = random)
+
+
+def wide_cases():
+    """moving_wide.npz (make_golden.py --stage moving_wide) as a dict of arrays: idx, v0, nobs, steps, window split out of `in`, + the rest"""
+    g = gold('moving_wide.npz')
+    out = {k: g[k] for k in g.files}
+    cols = out.pop('in')
+    out['v0'] = cols[:, 1]
+    for j, k in ((0, 'idx'), (2, 'nobs'), (3, 'steps'), (4, 'window')):
+        out[k] = cols[:, j].astype(np.int32)
+    return out
+
+
+def wide_coverage(w):
+    """The conditions make_golden.py asserted when it recorded moving_wide.npz, from the stored arrays alone (a regenerated fixture cannot
+    lose them quietly).  Returns (hits at steps >= 35, those whose winner's candidates start in a later chunk) of the random part."""
+    rnd, hit = w['kind'] == 0, w['hit'][:, 2] >= 0
+    cells = sorted(set(zip(w['steps'][rnd].tolist(), w['window'][rnd].tolist())))
+    assert cells == [(s, f) for s in (1, 2, 7, 35, 36, 50, 63, 64) for f in (0, 3, 20, 40, 70)]
+    for s, f in cells:
+        cell = rnd & (w['steps'] == s) & (w['window'] == f)
+        assert cell.sum() == 20 and (hit & cell).sum() >= 3 and (~hit & cell).sum() >= 2, (s, f)
+    assert w['nobs'][rnd].min() == 8 and w['nobs'][rnd].max() == 16 and (w['nobs'][~rnd] == 16).all()
+    assert ((w['winner_rank'] >= 0) == hit).all() and (w['winner_rank'] < w['nobs']).all()
+    long_hits = rnd & hit & (w['steps'] >= 35)
+    late = long_hits & (w['winner_rank'] * w['steps'] * 2 >= WIDE_CHUNK)
+    assert 4 * late.sum() >= long_hits.sum(), (int(late.sum()), int(long_hits.sum()))
+    for rel in (np.less, np.equal, np.greater):
+        assert rel(w['nres'][rnd], w['steps'][rnd]).any()
+    k, r, win = w['kind'], w['rank'], w['winner_rank']
+    for steps in (35, 64):
+        at = w['steps'] == steps
+        for kind in (1, 5):                                     # (a), (e): the winner is the one near obstacle, at every rank
+            assert sorted(r[at & (k == kind)].tolist()) == list(range(16)) and (win[at & (k == kind)] == r[at & (k == kind)]).all()
+        assert win[at & (k == 2)].tolist() == [15] and win[at & (k == 3)].tolist() == [0]            # (b), (c)
+        assert win[at & (k == 4)].tolist() == [2, 13]           # (d): both near obstacles, then rank 13 alone
+        assert (w['nres'][at & (k == 5)] < steps).all()         # (e): the ego's prediction is the shorter one
+    f = k == 6
+    assert (w['steps'][f] == 2).all() and sorted(r[f].tolist()) == list(range(16)) and (win[f] == r[f]).all() and (w['nres'][f] > 30).all()
+    return int(long_hits.sum()), int(late.sum())

@@ -1,0 +1,361 @@
+"""GPU tests of the conflict search (first_row of csrc/mpcx_interaction.hip, shared by interaction_kernel and moving_collision_kernel)
+away from the one point the other files pin it at -- at most 7 obstacles, 35 predicted frames, a window of 20.
+
+Against tests/golden/moving_wide.npz, recorded from the reference (make_golden.py --stage moving_wide): 8..16 obstacles per ego, 1..64
+frames, windows 0..70, so that the candidate loop takes up to four passes of 512 obstacle disc positions and the first row often belongs
+to a later pass; and constructed cases (a)..(f) that fix which obstacle rank wins.  Both entry points, every index bit for bit.  Then the
+closed loop with 16 obstacles per ego (15 agents + 2 scripted cars; 12 agents) replayed on the CPU oracle, and the scene and right-of-way
+instantiations with more than ten present rows, where the packed row list spills into its second word and yielding ranks reach 10..15."""
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+from tests import helpers as H
+from tests import precedence_helpers as PH
+
+pytestmark = pytest.mark.gpu
+
+STEPS = (1, 2, 7, 35, 36, 50, 63, 64)
+WINDOWS = (0, 3, 20, 40, 70)
+DT, MAX_SPEED = 0.2, 30.0 / 3.6
+
+
+@pytest.fixture(scope='module')
+def ctx():
+    from mpc_for_av_at_intersection_amd.runtime import Context
+    c = Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope='module')
+def wide(ctx):
+    """the fixture, the path and its tables on the device, the oracle's ego predictions (what the reference's caller resamples)"""
+    from oracle import oracle_py as orc
+    w = H.wide_cases()
+    full = H.gold('mpc_pre.npz')['path_4_1']
+    w['full'] = full
+    w['cs'] = np.column_stack([np.cos(full[:, 2]), np.sin(full[:, 2])])
+    w['d_full'], w['d_cs'] = ctx.f64(full), ctx.f64(w['cs'])
+    w['ego'] = []
+    for k in range(len(w['idx'])):
+        traj = full[int(w['idx'][k]):]
+        w['ego'].append(orc.resample_curve(traj, H.ego_resample_dl(len(traj), w['v0'][k])))
+        assert len(w['ego'][k]) == w['nres'][k]
+    w['plans'] = {}
+    return w
+
+
+def _params(w, steps, window, **kw):
+    from mpc_for_av_at_intersection_amd.runtime import InteractionParams
+    car = H.car()
+    return InteractionParams(pred_steps=int(steps), frame_window=int(window), cutoff_margin=int(w['margin']), L=car['L'], radius=car['radius'],
+                             circle_centers=np.array(car['circle_centers']).ravel(), **kw)
+
+
+def _tables(ctx, w, steps):
+    """path_cum / path_first_within / plan for the single path, as IntersectionBatch builds them for its route table (the plan is made
+    for `steps` predicted frames: the kernel takes it only where plan_steps == pred_steps)"""
+    from mpc_for_av_at_intersection_amd.runtime import path_first_within, path_plan, path_tables
+    if steps not in w['plans']:
+        full, offs = w['full'], [0, len(w['full'])]
+        car = H.car()
+        if 'cum' not in w:
+            cum, err = path_tables(full, offs)
+            w['cum'], w['cum_err'], w['pfw'] = ctx.f64(cum), err, ctx.i32(path_first_within(full, offs))
+        pl = path_plan(full, w['cs'], offs, DT, MAX_SPEED, np.array(car['circle_centers']).ravel(), car['radius'], int(steps))
+        assert (pl['cnt'] > 0).any()
+        w['plans'][steps] = dict(pl, cnt=ctx.i32(pl['cnt']), disc=ctx.f64(pl['disc']), box=ctx.f64(pl['box']), path_disc=ctx.f64(pl['path_disc']))
+    return dict(path_cum=w['cum'], path_cum_err=w['cum_err'], path_first_within=w['pfw'], plan=w['plans'][steps])
+
+
+def _cells(w, sel):
+    """the cases `sel` grouped by (steps, window): one launch per group"""
+    keys = sorted(set(zip(w['steps'][sel].tolist(), w['window'][sel].tolist())))
+    return [(s, f, sel[(w['steps'][sel] == s) & (w['window'][sel] == f)]) for s, f in keys]
+
+
+def _pool(w, ks):
+    nobs = w['nobs'][ks]
+    pool = np.concatenate([w['obs'][k][:w['nobs'][k]] for k in ks])
+    off = np.concatenate([[0], np.cumsum(nobs)[:-1]]).astype(np.int32)         # ragged: every case has its own run of the pool
+    return pool, off, nobs.astype(np.int32)
+
+
+def _interaction(ctx, w, sel, tables=False):
+    """mpcx_interaction_batch on the cases `sel` -> dict(hit_idx, hit_xy, cut_len, traj_idx), rows in the order of sel"""
+    n_path = len(w['full'])
+    out = {k: [] for k in ('hit_idx', 'hit_xy', 'cut_len', 'traj_idx', 'k')}
+    for steps, window, ks in _cells(w, sel):
+        n = len(ks)
+        ip = _params(w, steps, window, **(_tables(ctx, w, steps) if tables else {}))
+        idx = w['idx'][ks]
+        state = np.zeros((n, 4)); state[:, 0] = w['full'][idx, 0]; state[:, 1] = w['full'][idx, 1]; state[:, 2] = w['v0'][ks]
+        pool, off, nobs = _pool(w, ks)
+        tidx = ctx.i32(idx)
+        # prev_cut_len = idx + 1: the previous path collapsed onto the agent, so traj_idx is NOT advanced (the fixture fixes idx)
+        r = ctx.interaction(ip, ctx.f64(state), w['d_full'], w['d_cs'], ctx.i32(np.zeros(n)), ctx.i32(np.full(n, n_path)), ctx.i32(idx + 1),
+                            ctx.f64(pool), ctx.i32(off), ctx.i32(nobs), None, tidx)
+        ctx.synchronize()
+        for k in ('hit_idx', 'hit_xy', 'cut_len'):
+            out[k].append(r[k].cpu().numpy())
+        out['traj_idx'].append(tidx.cpu().numpy()); out['k'].append(ks)
+    return _in_order(out, sel)
+
+
+def _moving(ctx, w, sel, flat=True):
+    """mpcx_moving_collision_batch on the cases `sel`: the ego is the oracle's resampled prediction, the obstacles are
+    ctx.predict_obstacles of the six-vectors (flat: as a (trajectories x frames, 3) table, else (trajectories, frames, 3)), the detailed path
+    is full[idx:] -> dict(hit_idx, hit_xy)"""
+    n_path = len(w['full'])
+    out = {k: [] for k in ('hit_idx', 'hit_xy', 'k')}
+    L = H.car()['L']
+    for steps, window, ks in _cells(w, sel):
+        ego = np.concatenate([w['ego'][k][:, :3] for k in ks])
+        ego_len = np.array([len(w['ego'][k]) for k in ks], dtype=np.int32)
+        ego_off = np.concatenate([[0], np.cumsum(ego_len)[:-1]]).astype(np.int32)
+        pool, off, nobs = _pool(w, ks)
+        pred = ctx.predict_obstacles(ctx.f64(pool), int(steps), DT, L)
+        ctx.synchronize()
+        assert tuple(pred.shape) == (len(pool), steps, 3)
+        poses = pred.cpu().numpy().reshape(-1, 3)
+        shape = (-1,) if flat else (len(pool), int(steps))
+        idx = w['idx'][ks]
+        r = ctx.moving_collision(_params(w, steps, window), ctx.f64(ego), ctx.f64(np.column_stack([np.cos(ego[:, 2]), np.sin(ego[:, 2])])),
+                                 ctx.i32(ego_off), ctx.i32(ego_len), w['d_full'], w['d_cs'], ctx.i32(idx), ctx.i32(n_path - idx),
+                                 ctx.f64(poses.reshape(shape + (3,))), ctx.f64(np.column_stack([np.cos(poses[:, 2]), np.sin(poses[:, 2])]).reshape(shape + (2,))),
+                                 ctx.i32(off), ctx.i32(nobs))          # (obs_off / obs_cnt count obstacles: `steps` poses each)
+        ctx.synchronize()
+        for k in ('hit_idx', 'hit_xy'):
+            out[k].append(r[k].cpu().numpy())
+        out['k'].append(ks)
+    return _in_order(out, sel)
+
+
+def _in_order(out, sel):
+    ks = np.concatenate(out.pop('k'))
+    assert sorted(ks.tolist()) == sorted(sel.tolist())
+    pos = {int(k): i for i, k in enumerate(ks)}
+    take = np.array([pos[int(k)] for k in sel])
+    return {name: np.concatenate(v)[take] for name, v in out.items()}
+
+
+def _equals_reference(w, sel, got, what):
+    """every output the entry point has, bit for bit the fixture's; the failure names the cases"""
+    gh = w['hit'][sel]
+    want = dict(hit_idx=gh[:, 2].astype(np.int32), cut_len=w['cut'][sel], traj_idx=w['idx'][sel])
+    for name in ('hit_idx', 'cut_len', 'traj_idx'):
+        if name in got:
+            bad = np.flatnonzero(got[name] != want[name])
+            assert len(bad) == 0, '%s: %s differs from the reference in %d of %d cases, first (case, steps, window, nobs, winner rank, got, want): %s' % (
+                what, name, len(bad), len(sel), [(int(sel[i]), int(w['steps'][sel[i]]), int(w['window'][sel[i]]), int(w['nobs'][sel[i]]),
+                                                  int(w['winner_rank'][sel[i]]), int(got[name][i]), int(want[name][i])) for i in bad[:5]])
+    m = want['hit_idx'] >= 0
+    assert np.array_equal(got['hit_xy'][m], gh[m, :2]), what
+    late = int((m & (w['winner_rank'][sel] * w['steps'][sel] * 2 >= H.WIDE_CHUNK)).sum())
+    return len(sel), int(m.sum()), late
+
+
+def _random_cases(w, steps):
+    return np.flatnonzero((w['kind'] == 0) & (w['steps'] == steps))
+
+
+@pytest.mark.parametrize('steps', STEPS)
+def test_interaction_wide_vs_reference(ctx, wide, steps):
+    """mpcx_interaction_batch (predict_kernel + interaction_kernel) on the 100 random cases of this frame count, one call per window, the
+    pool ragged: hit index, hit position, cut length and traj_idx bitwise the reference's.  Twice: with the plain path, and with the
+    arc-length table, the first-within table and the ego plan (made for this frame count) that IntersectionBatch hands the kernel."""
+    sel = _random_cases(wide, steps)
+    assert len(sel) == 20 * len(WINDOWS) and sorted(set(wide['window'][sel].tolist())) == list(WINDOWS)
+    for tables in (False, True):
+        n, hits, late = _equals_reference(wide, sel, _interaction(ctx, wide, sel, tables), 'interaction, %d frames, tables %s' % (steps, tables))
+        print('interaction, %d frames, tables %s: %d cases, %d hits, %d with the winner in a later chunk' % (steps, tables, n, hits, late))
+
+
+@pytest.mark.parametrize('steps', STEPS)
+def test_moving_collision_wide_vs_reference(ctx, wide, steps):
+    """mpcx_moving_collision_batch (explicit trajectories: pose_disc_kernel + moving_collision_kernel) on the same cases: hit index and
+    position bitwise the reference's"""
+    sel = _random_cases(wide, steps)
+    n, hits, late = _equals_reference(wide, sel, _moving(ctx, wide, sel), 'moving_collision, %d frames' % steps)
+    print('moving_collision, %d frames: %d cases, %d hits, %d with the winner in a later chunk' % (steps, n, hits, late))
+
+
+def test_moving_collision_pool_counts_trajectories(ctx, wide):
+    """Context.moving_collision hands the library the number of obstacle TRAJECTORIES whichever way the table is shaped (the library reads
+    pred_steps poses per pool entry: with the rows of a flattened table as the pool size it read pred_steps times past the end of the
+    table -- found by the test above at 35 frames), and refuses a table that is not whole trajectories"""
+    from mpc_for_av_at_intersection_amd.runtime import MpcxError
+    sel = np.flatnonzero(wide['kind'] == 2)
+    a, b = _moving(ctx, wide, sel), _moving(ctx, wide, sel, flat=False)
+    _equals_reference(wide, sel, b, 'moving_collision, (n, frames, 3) table')
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    one = ctx.i32([0])
+    z = lambda *shape: ctx.f64(np.zeros(shape))
+    for obs, cs in ((z(34, 3), z(34, 2)), (z(35, 3), z(34, 2))):
+        with pytest.raises(MpcxError):
+            ctx.moving_collision(_params(wide, 35, 20), z(4, 3), z(4, 2), one, ctx.i32([4]), wide['d_full'], wide['d_cs'], one, ctx.i32([10]),
+                                 obs, cs, one, ctx.i32([1]))
+
+
+@pytest.mark.parametrize('case', sorted(H.WIDE_KINDS.values()))
+def test_constructed_chunk_order(ctx, wide, case):
+    """The constructed cases, 16 obstacles each, all but one or two far away, the near ones standing on poses of the ego's own prediction;
+    35 and 64 frames = 3 and 4 passes of the candidate loop ((f): 2 frames).  Through both entry points, bitwise the reference's.
+    (a) one near obstacle at every rank 0..15: the winner's candidates visit every pass
+    (b) rank 0 on ego pose 20, rank 15 on pose 3: the last pass must win with the earlier frame
+    (c) rank 0 on pose 3, rank 15 on pose 20: the first pass's answer must survive the later ones (the narrowed run limit is live)
+    (d) ranks 2 and 13 meet the same ego frame and disc first, 0.5 m apart: the lower rank's row comes first (and rank 13 alone)
+    (e) as (a) on the LAST pose of an ego prediction shorter than the obstacles': the padded ego tail
+    (f) as (a) with 2 obstacle frames and the conflict on ego pose 30: the padded obstacle tail"""
+    kind = {v: k for k, v in H.WIDE_KINDS.items()}[case]
+    sel = np.flatnonzero(wide['kind'] == kind)
+    assert len(sel) == {'a': 32, 'b': 2, 'c': 2, 'd': 4, 'e': 32, 'f': 16}[case] and (wide['hit'][sel, 2] >= 0).all()
+    runs = [('interaction', _interaction(ctx, wide, sel)), ('interaction with tables', _interaction(ctx, wide, sel, True)),
+            ('moving_collision', _moving(ctx, wide, sel))]
+    for what, got in runs:
+        n, hits, late = _equals_reference(wide, sel, got, '(%s) %s' % (case, what))
+        print('(%s) %s: %d cases, %d with the winner in a later chunk' % (case, what, n, late))
+
+
+# ---------------------------------------------------------------- the closed loop at the obstacle limit
+T = 13
+SEED = 0        # on the CPU oracle alone (scene_helpers.OracleLoop on the same layout and scripted cars): in steps 10..12 of every instance of
+                # scripted_traffic_batch(B=4, A=15, K=2, T=13, seed=0) 14 egos have a conflict and one has none, every solve succeeds -- with
+                # and without the three hidden rows and the right of way below (seeds 1 and 2 have instances where every ego has a conflict)
+
+
+@pytest.fixture(scope='module')
+def stock(ctx):
+    from mpc_for_av_at_intersection_amd.batch import stock_routes
+    return stock_routes(ctx)
+
+
+def _traffic_batch(c, stock):
+    from mpc_for_av_at_intersection_amd.batch import scripted_traffic_batch
+    routes, dl, cd = stock
+    return scripted_traffic_batch(c, B=4, A=15, K=2, T=T, seed=SEED, routes=routes, dl=dl, cd=cd)
+
+
+def _replay_egos(sim, before, after, absent=None, prec=None):
+    """Every driving ego of the step before -> after on the oracle (oracle_py.agent_step, as tests/test_gpu_traffic.py replays its mixed
+    batch): the obstacles are the rows of its pool window except its own and the absent ones, in order, as the device wrote them for this
+    step -- the agents' rows checked against the state and controls before the step --, with right of way the yielding rows standing
+    (precedence_helpers.view).  Integer decisions and status identical, u and x within 2e-7 (helpers.replay_all_on_oracle's bar).
+    Returns (worst difference, hit indices, present rows per ego, yielding ranks per ego)."""
+    from oracle import oracle_py as orc
+    po = orc.MpcParams(**{f.name: getattr(sim.params, f.name) for f in dataclasses.fields(orc.MpcParams)})
+    tab = sim.path.cpu().numpy(); off = sim.path_off.cpu().numpy(); ln = sim.path_len.cpu().numpy()
+    o_off, o_cnt, o_skip = (t.cpu().numpy() for t in (sim.obs_off, sim.obs_cnt, sim.obs_skip))
+    centers = np.asarray(sim.ip.circle_centers).reshape(2, 2)
+    pool = after['obs6']
+    packed = np.column_stack([before['state'], before['applied'][:, 1], before['applied'][:, 0]])
+    assert np.array_equal(pool[sim.ego_row.cpu().numpy()], packed)
+    absent = np.zeros(len(pool), np.int32) if absent is None else absent
+    worst, hits, n_present, ranks = 0.0, [], [], []
+    for p in range(sim.P):
+        if 'done' in before and before['done'][p]:
+            continue
+        present = [r for r in range(o_off[p], o_off[p] + o_cnt[p]) if r != o_skip[p] and not absent[r]]
+        rows = pool[present] if prec is None else PH.view(pool, present, prec[o_skip[p]], prec)
+        r = orc.agent_step(po, tab[off[p]:off[p] + ln[p]], sim.dl, before['state'][p], rows, int(before['traj_idx'][p]), int(before['prev_cut'][p]),
+                           int(before['target_ind'][p]), before['u'][p], centers, sim.ip.radius, sim.ip.cutoff_margin)
+        want_hit = -1 if r['hit'] is None else int(r['hit'][2])
+        got = (after['traj_idx'][p], after['cut_len'][p], after['target_ind'][p], after['hit_idx'][p], after['status'][p])
+        assert (r['traj_idx'], r['cut'], r['target_ind'], want_hit, r['sol'].status) == got, (p, len(present), r['traj_idx'], r['cut'], r['target_ind'], want_hit, got)
+        assert r['sol'].status == 0, p
+        worst = max(worst, float(np.abs(r['sol'].u - after['u'][p]).max()), float(np.abs(r['sol'].x - after['x'][p]).max()))
+        hits.append(want_hit); n_present.append(len(present))
+        ranks.append([] if prec is None else [i for i, q in enumerate(present) if prec[q] > prec[o_skip[p]]])
+    assert worst < 2e-7, worst
+    return worst, np.array(hits), np.array(n_present), ranks
+
+
+def _same_snapshots(a, b, what):
+    assert sorted(a) == sorted(b), what
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), (what, k)
+
+
+def test_closed_loop_with_sixteen_obstacles(ctx, stock):
+    """scripted_traffic_batch(B=4, A=15, K=2, T=13): every ego sees 14 other egos + 2 scripted cars = MPCX_MAX_OBS obstacles, 16 x 35 x 2 =
+    1120 candidates = three passes of the candidate loop in every step; and synthetic_batch(B=4, A=12, T=13): 11 obstacles, two passes.  Ten
+    burn-in steps, then three steps replayed on the oracle, every ego: integer decisions and status identical, solutions within 2e-7.  Not
+    vacuous: egos with a conflict and egos without.  run(1) = step_staged() bit for bit over the same 13 steps."""
+    from mpc_for_av_at_intersection_amd import _lib
+    from mpc_for_av_at_intersection_amd.batch import synthetic_batch
+    routes, dl, cd = stock
+    sim, staged = _traffic_batch(ctx, stock), _traffic_batch(ctx, stock)
+    assert ((sim.obs_cnt - 1).cpu().numpy() == _lib.MAX_OBS).all() and sim.ip.pred_steps == 35 and sim.ip.frame_window == 20
+    sim.run(10)
+    sim.check()
+    hits, worst = [], 0.0
+    for _ in range(3):
+        before = sim.snapshot()
+        sim.run(1)
+        w, h, n_present, _ = _replay_egos(sim, before, sim.snapshot())
+        assert (n_present == 16).all()
+        worst = max(worst, w); hits.append(h)
+    hits = np.concatenate(hits)
+    print('15 agents + 2 scripted cars: %d ego-steps on the oracle, %d with a conflict, %d without, worst |GPU - oracle| %.2e'
+          % (len(hits), (hits >= 0).sum(), (hits == -1).sum(), worst))
+    assert (hits >= 0).any() and (hits == -1).any()
+    for _ in range(13):
+        staged.step_staged()
+    _same_snapshots(sim.snapshot(), staged.snapshot(), '15 agents + 2 scripted cars: run(1) vs step_staged()')
+
+    sim, staged = (synthetic_batch(ctx, B=4, A=12, T=T, seed=SEED, routes=routes, dl=dl, cd=cd) for _ in range(2))
+    sim.run(10)
+    sim.check()
+    hits = []
+    for _ in range(3):
+        before = sim.snapshot()
+        sim.run(1)
+        after = sim.snapshot()
+        worst, _, failed = H.replay_all_on_oracle(sim, before, after)
+        assert failed == 0
+        hits.append(after['hit_idx'])
+    hits = np.concatenate(hits)
+    print('12 agents: %d ego-steps on the oracle, %d with a conflict, %d without, worst |GPU - oracle| %.2e' % (len(hits), (hits >= 0).sum(), (hits == -1).sum(), worst))
+    assert (hits >= 0).any() and (hits == -1).any()
+    for _ in range(13):
+        staged.step_staged()
+    _same_snapshots(sim.snapshot(), staged.snapshot(), '12 agents: run(1) vs step_staged()')
+
+
+def test_scene_and_right_of_way_with_more_than_ten_present_rows(ctx, stock):
+    """The same 15 + 2 batch with departure (retire_at_goal(leave_scene=True)) and, in every instance, the rows of agents 2, 7 and 13 preset
+    absent: ranks 1, 6 and 12 of the window of the instance's agent 0.  Every other ego then has 13 present rows -- more than the ten
+    entries of the row list's first word -- and the ranks behind a hidden row shift across the boundary of the two words; the three hidden
+    agents still drive (ghosts) and have 14.  Eight steps from the start, every one replayed on the oracle with each ego's list of present
+    rows as its obstacle window.  Then the same with right of way, fixed words as tests/test_gpu_precedence.py gives them: word = agent
+    index in instances 0 and 2, reversed in 1 and 3, so that the agents with the smallest words see yielding rows of rank 10 and more;
+    replayed with the yielding rows standing.  That both conditions occur is asserted from the host-side masks."""
+    order = np.array([np.arange(15), np.arange(15)[::-1], np.arange(15), np.arange(15)[::-1]])
+    for prec in (False, True):
+        sim = _traffic_batch(ctx, stock)
+        sim.retire_at_goal(leave_scene=True)
+        stride = 17
+        hidden = np.array([b * stride + a for b in range(4) for a in (2, 7, 13)])
+        assert np.array_equal(sim.ego_row.cpu().numpy().reshape(4, 15), np.arange(4)[:, None] * stride + np.arange(15)[None, :])
+        sim.absent[torch.as_tensor(hidden, device=sim.absent.device)] = 1
+        if prec:
+            sim.give_way(order=order)
+        worst, hits, over_ten, rank_ten, differs = 0.0, [], 0, 0, 0
+        for _ in range(8):
+            before = sim.snapshot()
+            sim.run(1)
+            after = sim.snapshot()
+            assert not before['done'].any() and np.array_equal(np.flatnonzero(before['absent']), hidden)
+            w, h, n_present, ranks = _replay_egos(sim, before, after, before['absent'], before['precedence'] if prec else None)
+            assert sorted(set(n_present.tolist())) == [13, 14] and (n_present == 13).sum() == 48
+            worst = max(worst, w); hits.append(h)
+            over_ten += int((n_present > 10).sum())
+            rank_ten += sum(1 for r in ranks for i in r if i >= 10)
+        hits = np.concatenate(hits)
+        print('%s: %d ego-steps on the oracle (%d with a conflict, %d without), %d present-row lists longer than 10, %d yielding ranks >= 10, '
+              'worst |GPU - oracle| %.2e' % ('right of way' if prec else 'scene', len(hits), (hits >= 0).sum(), (hits == -1).sum(), over_ten, rank_ten, worst))
+        assert over_ten == len(hits) and (hits >= 0).any() and (hits == -1).any()
+        assert (rank_ten > 0) == prec
