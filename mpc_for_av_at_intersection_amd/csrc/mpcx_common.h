@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1272] = {};    // descriptor + run log + options + retirement + scene + admission + respawn + routes + precedence + signals + actuation + parameters the cached graph was captured for
+    unsigned char loop_key[1272] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)

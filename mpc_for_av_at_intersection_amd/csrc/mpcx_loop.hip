@@ -3,15 +3,9 @@
 // path kept whole and the speed reference zeroed from the conflict on):
 // n_steps x [scripted traffic rows -> pool pack -> predict -> conflict search + path cut -> reference window ->
 // rollout -> QP -> plant (-> run-log record, iff a log is attached)], enqueued back to back on the context's stream (optionally as a replayed hipGraph), no
-// host synchronisation or host arithmetic in between.  With retirement at the goal (mpcx_retire) the step ends with retire_kernel, and an agent
-// that has arrived is skipped by every stage but the pool pack; with a scene (mpcx_scene) its arrival also takes it out of everybody
-// else's obstacle list; with admission (mpcx_admit) the step begins with the two launches that let waiting agents in; with respawn
-// (mpcx_respawn) it ends with respawn_kernel, which resets an arrived agent's slot for the next vehicle of its stream; with right of way
-// (mpcx_precedence) the conflict search shows an agent the cars that yield to it as standing cars; with traffic signals (mpcx_signals) one
-// more launch behind the conflict search holds agents at their stop lines (mpcx_actuation: its lights follow the demand).
-// Every stage is the kernel behind the per-stage C entry
-// point, called with the very buffers the descriptor names, so a run is bit-identical to driving the stages one
-// by one from the host.  With step fusion (mpcx_set_step_fusion, enqueue_fused_run) a run without any of the optional stages takes the plant
+// host synchronisation or host arithmetic in between.  mpcx::LoopStages lists the optional stages: the launches each adds, what it needs.
+// Every stage is the kernel behind the per-stage C entry point, called with the very buffers the descriptor names, so a run is bit-identical
+// to driving the stages one by one from the host.  With step fusion (mpcx_set_step_fusion, enqueue_fused_run) a run without any of the optional stages takes the plant
 // update of the step before, the pool pack, the prediction and the rollout in one launch per step: the same bits in every buffer.
 #include "mpcx_common.h"
 #include <cmath>
@@ -36,7 +30,87 @@ __global__ __launch_bounds__(256) void pack_pool_kernel(PackArgs a) {
     o[5] = a.applied[2 * q];
 }
 
+// What the caller of an entry point passed beside the descriptor, in the order the entry points grew; nullptr = nothing.
+struct LoopArgs {
+    const mpcx_run_log *log; const mpcx_closed_loop_opts *opts; const mpcx_retire *retire; const mpcx_scene *scene; const mpcx_admit *admit;
+    const mpcx_respawn *respawn; const mpcx_routes *routes; const mpcx_precedence *precedence; const mpcx_signals *signals;
+    const mpcx_actuation *actuation;
+};
+
+// The optional stages of a run, checked (check_stages): a pointer is nullptr where the stage is off -- NULL and what the stage's own
+// mpcx_*_absent calls "none" are the same run --, and a step without a stage is exactly the launches of a step that never heard of it, with
+// the same arguments.
+struct LoopStages {
+    // the run log: mpcx_record_enqueue behind the plant update, one row per agent from the buffers as the step leaves them (the pool still
+    // holds the rows this step's conflict search saw)
+    const mpcx_run_log *log = nullptr;
+    // by value: nullptr and a cut-mode struct, whatever its other fields say, are the same run.  MPCX_STOP_SPEED changes three arguments of
+    // a step and no launch: the conflict search reads the length of the previous tmp_trajectory from prev_len (0 before the batch's first
+    // step, the path length afterwards -- the window kernel sets it, device memory, so a replayed graph sees it change), its cut index in
+    // c->cut_len is the window stage's stop index over the whole path, and the record stage tests the goal against the whole path.
+    mpcx_closed_loop_opts opts = {};
+    // retirement at the goal: retire_kernel behind the record stage (so the arrival step's row logs the controls really applied).  Every
+    // stage gets retire->done: the conflict search returns at once for a retired agent and does not file it, the window stage gives it no
+    // place in the order and leaves the length of the queue in a spare word of ctx->ticket (the plant kernel zeroes it with the others),
+    // both solvers draw tickets up to that length, the rollout, the plant and the record stage skip the agent.  Its pool row is still packed
+    // from its frozen state and zero controls, and the scripted cars step as ever.  Refused with more than one linearisation pass.
+    const mpcx_retire *retire = nullptr;
+    // departure, no launch of its own; needs retirement and the local pool.  The prediction skips absent pool rows, the conflict search runs
+    // its SCENE instantiation on the list of present rows, the record stage's clearance leaves absent rows out, and retire_kernel sets
+    // absent[obs_skip[q]] for an agent that arrives -- the last launch of the step, so the others see the car gone from the next step on.
+    const mpcx_scene *scene = nullptr;
+    // admission: the step BEGINS with the two launches of mpcx_admit.hip; needs a scene.  A waiting agent (done[q] = 1, its own row absent)
+    // that is due and whose start pose is clear has both words cleared before the rollout is forked -- the side stream's rollout already
+    // reads done --, so every stage of this step drives and sees it.
+    const mpcx_admit *admit = nullptr;
+    // respawn: the step ENDS with respawn_kernel, behind retire_kernel; needs admission.  An agent that has arrived leaves an episode record
+    // and, while its slot has vehicles left, is reset to the first step of a fresh batch and waits for the gate (wait >= 0).  The next
+    // step's rollout is forked after this launch in stream order.
+    const mpcx_respawn *respawn = nullptr;
+    // routes: respawn_route_kernel in respawn_kernel's place; needs respawn and the descriptor's own path_off / path_len.  The reset also
+    // writes the next vehicle's route into them and its own start pose and index, which every stage of the next step reads afresh.
+    const mpcx_routes *routes = nullptr;
+    // right of way, needs a scene: the prediction also stores the standing records and the conflict search runs its PREC instantiation.  In
+    // MPCX_PRECEDENCE_ENTRY, which needs admission, precedence_stamp_kernel follows the admission stage -- before the prediction, so an
+    // agent admitted in this step is seen with its word.
+    const mpcx_precedence *precedence = nullptr;
+    // traffic signals: signal_kernel between the conflict search and the window stage; needs the local pool and one linearisation pass.  It
+    // advances every agent's clock and, for an agent its light holds, lowers c->cut_len (the cut length, the stop index in speed mode) to
+    // the agent's stop line before the window stage reads it.  The agent is filed in the QP work queue already, under a key from the cut
+    // before this launch: the order of the queue only.
+    const mpcx_signals *signals = nullptr;
+    // vehicle-actuated signals: actuated_signal_kernel in signal_kernel's place; needs signals.  A controller per junction decides the
+    // lights from the agents in front of their lines, the hold is signal_kernel's.  By value with its padding zeroed (all zeros where
+    // `actuated` is false): the cached graph's key takes it as it stands.
+    mpcx_actuation actuation;
+    bool actuated = false;
+
+    LoopStages() { memset(&actuation, 0, sizeof actuation); }
+    // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated; }
+    bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
+    const int32_t *done() const { return retire ? retire->done : nullptr; }
+};
+
+// Everything the cached one-step graph was captured for (ctx->loop_key): a run whose key differs in any byte captures afresh.  Filled after
+// a memset, so padding and the struct of a stage that is off are zeros.
+struct LoopKey {
+    mpcx_closed_loop desc;
+    mpcx_run_log log; mpcx_closed_loop_opts opts; mpcx_retire retire; mpcx_scene scene; mpcx_admit admit; mpcx_respawn respawn;
+    mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation;
+    mpcx_interaction_params ip;
+    mpcx_mpc_params mpc;
+    const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
+    int qp_solver, lin_passes;          // the captured launch is the solver chosen at capture time
+};
+static_assert(sizeof(LoopKey) <= sizeof(mpcx_ctx::loop_key), "loop_key too small");
+
+// the bytes of *src, or the zeros already there for a stage that is off
+template <class T> static void key_put(T &dst, const T *src) { if (src) memcpy(&dst, src, sizeof dst); }
+
 }  // namespace mpcx
+using mpcx::LoopArgs;
+using mpcx::LoopStages;
 
 // the agents' pool rows (device) lie inside the pool; who: what the message starts with
 static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego_row, int32_t pool_rows, const char *who = "closed_loop_run") {
@@ -52,76 +126,140 @@ static int32_t mpcx_loop_check_rows(mpcx_ctx *ctx, int32_t P, const int32_t *ego
 // the second part of ctx->prev_cut: 3 ints per agent that the conflict search leaves for the window selection (mpcx_interaction_extras::near)
 static int32_t *near_hints(const mpcx_ctx *ctx, int32_t P) { return ctx->prev_cut + P; }
 
-// log: the run log's descriptor or nullptr = none (then exactly the launches of a step without one)
-// o: the options (never nullptr here).  MPCX_STOP_SPEED changes three arguments of a step and no launch: the conflict search reads the length
-// of the previous tmp_trajectory from o->prev_len (0 before the batch's first step, the path length afterwards -- the window kernel sets it,
-// device memory, so a replayed graph sees it change), its cut index in c->cut_len is the window stage's stop index over the whole path, and
-// the record stage tests the goal against the whole path.
-// r: retirement at the goal or nullptr = none (then exactly the launches of a step without it, with the same arguments).  With it every
-// stage gets r->done: the conflict search returns at once for a retired agent and does not file it, the window stage gives it no place in
-// the order and leaves the length of the queue in a spare word of ctx->ticket (the plant kernel zeroes it with the others), both solvers
-// draw tickets up to that length, the rollout, the plant and the record stage skip the agent, and retire_kernel ends the step.  The pool
-// row of a retired agent is still packed (by predict_kernel, or by pack_pool_kernel in the agent-sharded layout) from its frozen state and
-// zero controls, and the scripted cars step as ever.
-// sc: the scene (departure) or nullptr = none (then exactly the launches of a step with retirement alone, with the same arguments).  With it
-// the prediction skips absent pool rows, the conflict search runs its SCENE instantiation on the list of present rows, the record stage's
-// clearance leaves absent rows out, and retire_kernel sets absent[obs_skip[q]] for an agent that arrives -- the last launch of the step,
-// so the others see the car gone from the next step on.
-// ad: admission or nullptr = none (then exactly the launches of a step with a scene, with the same arguments).  With it the step BEGINS with the
-// two launches of mpcx_admit.hip: a waiting agent (done[q] = 1, its own row absent) that is due and whose start pose is clear has both words
-// cleared before the rollout is forked -- the side stream's rollout already reads done --, so every stage of this step drives and sees it.
-// rs: respawn or nullptr = none (then exactly the launches of a step with admission, with the same arguments).  With it the step ENDS with
-// respawn_kernel, after retire_kernel: an agent that has arrived leaves an episode record and, while its slot has vehicles left, is reset to
-// the first step of a fresh batch and waits for the gate (wait >= 0).  The next step's rollout is forked after this launch in stream order.
-// rt: routes or nullptr = none (then exactly the launches of a step with respawn, with the same arguments).  With them respawn_route_kernel
-// takes respawn_kernel's place -- the same number of launches --: the reset also writes the next vehicle's route into c->path_off / c->path_len
-// and its own start pose and index, which every stage of the next step reads afresh.
-// pc: right of way or nullptr = none (then exactly the launches of a step with routes, with the same arguments).  With it the prediction also
-// stores the standing records and the conflict search runs its PREC instantiation; in MPCX_PRECEDENCE_ENTRY one more launch,
-// precedence_stamp_kernel, follows the admission stage -- before the prediction, so an agent admitted in this step is seen with its word.
-// sg: traffic signals or nullptr = none (then exactly the launches of a step with right of way, with the same arguments).  With them one more
-// launch, signal_kernel, follows the conflict search: it advances every agent's clock and, for an agent its light holds, lowers c->cut_len
-// (the cut length, the stop index in speed mode) to the agent's stop line before the window stage reads it.  The agent is filed in the QP
-// work queue already, under a key from the cut before this launch: the order of the queue only.
-// av: vehicle-actuated signals or nullptr = none (then exactly the launches of a step with signals, with the same arguments).  With them
-// actuated_signal_kernel stands in the place of signal_kernel -- the same number of launches --: a controller per junction decides the
-// lights from the agents in front of their lines, the hold is signal_kernel's.
-static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                            const mpcx_closed_loop_opts *o, const mpcx_retire *r, const mpcx_scene *sc, const mpcx_admit *ad,
-                            const mpcx_respawn *rs, const mpcx_routes *rt, const mpcx_precedence *pc, const mpcx_signals *sg,
-                            const mpcx_actuation *av) {
+// the counting sort of the work queue rides in the kernels of the step (the slot of an agent has 24 bits)
+static bool binned(int32_t P) { return P < (1 << 24); }
+
+// The stage set of a run from what the caller passed; refused before anything is launched, whatever n_steps is.
+static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopArgs &a, LoopStages *st) {
+    if (a.opts && a.opts->stop_mode != MPCX_STOP_CUT) {
+        if (a.opts->stop_mode != MPCX_STOP_SPEED)
+            return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: unknown stop mode %d (MPCX_STOP_CUT or MPCX_STOP_SPEED)", a.opts->stop_mode);
+        if (!std::isfinite(a.opts->v_ref)) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: MPCX_STOP_SPEED with a speed reference v_ref that is not finite");
+        if (!a.opts->prev_len) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: MPCX_STOP_SPEED needs prev_len (P zero-initialised int32)");
+        st->opts.stop_mode = MPCX_STOP_SPEED; st->opts.v_ref = a.opts->v_ref; st->opts.prev_len = a.opts->prev_len;
+    }
+    int32_t rc = MPCX_OK;
+    if (!mpcx_record_absent(a.log)) st->log = a.log;
+    if (st->log && (rc = mpcx_record_validate(ctx, st->log, c->obs_skip)) != MPCX_OK) return rc;
+    if (!mpcx_retire_absent(a.retire)) st->retire = a.retire;
+    if (st->retire && (rc = mpcx_retire_validate(ctx, st->retire, c->P)) != MPCX_OK) return rc;
+    if (!mpcx_scene_absent(a.scene)) {
+        st->scene = a.scene;
+        const bool traffic = c->n_actors > 0;
+        const size_t rows = traffic ? (size_t)(c->pool_rows > 0 ? c->pool_rows : 0) : (size_t)c->P;
+        rc = mpcx_scene_validate(ctx, st->scene, st->retire, c->exchange, rows, c->obs_skip);
+        if (rc == MPCX_OK && c->P > 0) rc = mpcx_loop_check_rows(ctx, c->P, c->obs_skip, st->scene->n_rows, "scene");
+        if (rc != MPCX_OK) return rc;
+    }
+    if (!mpcx_admit_absent(a.admit)) st->admit = a.admit;
+    if (st->admit && (rc = mpcx_admit_validate(ctx, st->admit, st->retire, st->scene, c->exchange)) != MPCX_OK) return rc;
+    if (!mpcx_respawn_absent(a.respawn)) st->respawn = a.respawn;
+    if (st->respawn && (rc = mpcx_respawn_validate(ctx, st->respawn, st->admit)) != MPCX_OK) return rc;
+    if (!mpcx_routes_absent(a.routes)) {
+        st->routes = a.routes;
+        // the longest route the conflict search handles: max_path_len as mpcx_interaction_enqueue rounds it
+        int32_t cap = ip->max_path_len > 0 ? ip->max_path_len : MPCX_MAX_REMAINING;
+        if (cap < 512) cap = 512;
+        cap = (cap + 63) / 64 * 64;
+        rc = mpcx_routes_validate(ctx, st->routes, st->respawn, c->path_off, c->path_len, cap);
+        if (rc != MPCX_OK) return rc;
+    }
+    if (!mpcx_precedence_absent(a.precedence)) st->precedence = a.precedence;
+    if (st->precedence && (rc = mpcx_precedence_validate(ctx, st->precedence, st->scene, st->admit)) != MPCX_OK) return rc;
+    if (!mpcx_signals_absent(a.signals)) st->signals = a.signals;
+    if (!mpcx_actuation_absent(a.actuation)) {      // checks the signals it draws on too
+        rc = mpcx_actuation_validate(ctx, a.actuation, st->signals, c->P, c->exchange);
+        if (rc != MPCX_OK) return rc;
+        mpcx_actuation &act = st->actuation;
+        act.phase_groups = a.actuation->phase_groups; act.phase_time = a.actuation->phase_time; act.ctrl_time = a.actuation->ctrl_time;
+        act.ctrl_of = a.actuation->ctrl_of; act.jstate = a.actuation->jstate; act.lights = a.actuation->lights; act.calls = a.actuation->calls;
+        act.n_per = a.actuation->n_per; act.n_junctions = a.actuation->n_junctions; act.n_phases = a.actuation->n_phases;
+        act.n_ctrl = a.actuation->n_ctrl;
+        st->actuated = true;
+    } else if (st->signals) {
+        rc = mpcx_signals_validate(ctx, st->signals, c->exchange);
+    }
+    return rc;
+}
+
+// The middle of a step, the same on both paths: the conflict search (-> the signal stage) -> lin_passes x (reference window -> solve).
+// ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
+// in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
+static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopStages &st,
+                                        mpcx_interaction_extras ix, int32_t pool_rows, bool rollout_done) {
     const int P = c->P;
-    const int32_t *done = r ? r->done : nullptr;
-    int32_t *queue_len = r ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
-    const bool speed = o->stop_mode == MPCX_STOP_SPEED;
+    const bool speed = st.speed(), bins = binned(P);
+    const int32_t *done = st.done();
+    int32_t *queue_len = st.retire ? ctx->ticket + MPCX_TICKET_QUEUE_LEN : nullptr;
+    // the conflict search leaves the cut lengths of the previous step in ctx->prev_cut (the queue of the QP kernel puts the agents whose
+    // cut moved at the front) and files every agent under its work-queue key (previous iteration count + "the cut moved"): hard problems first.  The window
+    // selection then writes the queue order and the plant kernel resets bins and ticket, so the counting sort costs no launch of its own.
+    ix.prev_save = ctx->prev_cut;
+    ix.near = near_hints(ctx, P);
+    ix.bin_hint = bins ? c->iters : nullptr;
+    ix.done = done;
+    ix.absent = st.scene ? st.scene->absent : nullptr;
+    if (st.precedence) { ix.prec = st.precedence->prec; ix.stand = st.precedence->stand; }
+    if (speed) ix.key_prev = c->cut_len;        // "the cut moved" = the stop index moved
+    int32_t rc = mpcx_interaction_enqueue(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
+                                          speed ? st.opts.prev_len : c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows,
+                                          c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len, ix);
+    if (rc != MPCX_OK) return rc;
+    if (st.signals) {
+        rc = st.actuated ? mpcx_actuated_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, &st.actuation)
+                         : mpcx_signal_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals);
+        if (rc != MPCX_OK) return rc;
+    }
+    // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
+    // previous pass's speeds (row 2 of its x) and the rollout uses its inputs.  (Where a pass fails the reference crashes in the next
+    // one -- zip over None; here the next pass starts from the untouched warm start, as after a failed step.)
+    const int Wd = ctx->mpc.T + 1;
+    for (int pass = 0; pass < ctx->lin_passes; pass++) {
+        const bool first = pass == 0;
+        // the first pass writes the queue order and joins the rollout of this step; a later one forks its own
+        mpcx_window_extras wx{bins && first, near_hints(ctx, P), c->traj_idx, first};
+        wx.rollout_done = rollout_done;
+        if (speed) { wx.stop_idx = c->cut_len; wx.v_ref = st.opts.v_ref; wx.len_seen = st.opts.prev_len; }
+        wx.done = done; wx.queue_len = queue_len;
+        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
+                                 c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar, wx);
+        if (rc != MPCX_OK) return rc;
+        // (further linearisation passes build their order in line, from the iteration counts of the pass before)
+        const mpcx_qp_order ord{bins && first, c->iters, c->cut_len, ctx->prev_cut, queue_len};
+        rc = mpcx_qp_enqueue(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol, c->status, c->iters, c->kkt, ord);
+        if (rc != MPCX_OK) return rc;
+    }
+    return MPCX_OK;
+}
+
+// the plant update in a launch of its own; it leaves the queue bins and the ticket zeroed for the next step
+static int32_t enqueue_plant(mpcx_ctx *ctx, const mpcx_closed_loop *c, const int32_t *done) {
+    const mpcx_plant_extras px{c->iters, binned(c->P), done};
+    const int32_t rc = mpcx_plant_enqueue(ctx, c->P, c->state, c->u_sol, c->status, c->applied, px);
+    if (rc == MPCX_OK) ctx->bins_clean = binned(c->P);
+    return rc;
+}
+
+static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopStages &st) {
+    const int P = c->P;
+    const bool speed = st.speed();
     ctx->bins_clean = false;        // until the plant kernel of this step is enqueued
     int32_t rc, pool_rows = P;
-    if (ad) {       // (validated: a scene, retirement, the local pool)
+    if (st.admit) {
         const int32_t na = c->n_actors > 0 ? c->n_actors : 0;
-        rc = mpcx_admit_enqueue(ctx, ip, P, c->state, c->obs_off, c->obs_cnt, c->obs_skip, r->done, sc->n_rows, sc->absent, na, c->actors,
-                                c->actor_state, c->tape, c->tape_rows, c->actor_row, ad);
+        rc = mpcx_admit_enqueue(ctx, ip, P, c->state, c->obs_off, c->obs_cnt, c->obs_skip, st.retire->done, st.scene->n_rows, st.scene->absent, na,
+                                c->actors, c->actor_state, c->tape, c->tape_rows, c->actor_row, st.admit);
         if (rc != MPCX_OK) return rc;
-        if (pc && pc->mode == MPCX_PRECEDENCE_ENTRY) {      // (validated: ENTRY has admission)
-            rc = mpcx_precedence_enqueue(ctx, P, c->obs_off, c->obs_skip, ad, pc);
+        if (st.precedence && st.precedence->mode == MPCX_PRECEDENCE_ENTRY) {
+            rc = mpcx_precedence_enqueue(ctx, P, c->obs_off, c->obs_skip, st.admit, st.precedence);
             if (rc != MPCX_OK) return rc;
         }
     }
     // the warm-start rollout of this step needs only the states and the previous solution: it runs on the side stream BESIDE the pool pack,
     // the prediction and the conflict search (a chain of T dependent sincos / tan per agent, 35-45 us) and is joined by the window selection
-    rc = mpcx_rollout_fork(ctx, P, c->state, c->u_sol, c->xbar, done);
+    rc = mpcx_rollout_fork(ctx, P, c->state, c->u_sol, c->xbar, st.done());
     if (rc != MPCX_OK) return rc;
-    // the conflict search leaves the cut lengths of the previous step in ctx->prev_cut (the queue of the QP kernel puts the agents whose
-    // cut moved at the front) and files every agent under its work-queue key (previous iteration count + "the cut moved"): hard problems first.  The window
-    // selection then writes the queue order and the plant kernel resets bins and ticket, so the counting sort costs no launch of its own.
-    const bool binned = P < (1 << 24);
     mpcx_interaction_extras ix;
-    ix.prev_save = ctx->prev_cut;
-    ix.near = near_hints(ctx, P);
-    ix.bin_hint = binned ? c->iters : nullptr;
-    ix.done = done;
-    ix.absent = sc ? sc->absent : nullptr;
-    if (pc) { ix.prec = pc->prec; ix.stand = pc->stand; }       // (validated: a scene)
-    if (speed) ix.key_prev = c->cut_len;        // "the cut moved" = the stop index moved
     if (c->exchange == MPCX_SHARD_AGENTS) {
         // agent-sharded layout: this rank's rows travel to every rank, every rank assembles the whole pool (one RCCL all-gather)
         mpcx::PackArgs pa{P, c->state, c->applied, c->obs_local};
@@ -142,174 +280,58 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
             pool_rows = c->pool_rows;
         }
     }
-    rc = mpcx_interaction_enqueue(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
-                                  speed ? o->prev_len : c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows, c->obs6,
-                                  c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len, ix);
+    rc = enqueue_search_and_solve(ctx, ip, c, st, ix, pool_rows, false);
     if (rc != MPCX_OK) return rc;
-    if (sg) {       // (validated: the local pool, one linearisation pass)
-        rc = av ? mpcx_actuated_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, sg, av)
-                : mpcx_signal_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, sg);
-        if (rc != MPCX_OK) return rc;
-    }
-    // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
-    // previous pass's speeds (row 2 of its x) and the rollout uses its inputs.  (Where a pass fails the reference crashes in the next
-    // one -- zip over None; here the next pass starts from the untouched warm start, as after a failed step.)
-    const int Wd = ctx->mpc.T + 1;
-    for (int pass = 0; pass < ctx->lin_passes; pass++) {
-        const bool first = pass == 0;
-        // the first pass writes the queue order and joins the rollout forked above; a later one forks its own
-        mpcx_window_extras wx{binned && first, near_hints(ctx, P), c->traj_idx, first};
-        if (speed) { wx.stop_idx = c->cut_len; wx.v_ref = o->v_ref; wx.len_seen = o->prev_len; }
-        wx.done = done; wx.queue_len = queue_len;       // (retirement is refused with more than one pass or without bins)
-        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
-                                 c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar, wx);
-        if (rc != MPCX_OK) return rc;
-        // (further linearisation passes build their order in line, from the iteration counts of the pass before)
-        const mpcx_qp_order ord{binned && first, c->iters, c->cut_len, ctx->prev_cut, queue_len};
-        rc = mpcx_qp_enqueue(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol, c->status, c->iters, c->kkt, ord);
-        if (rc != MPCX_OK) return rc;
-    }
-    const mpcx_plant_extras px{c->iters, binned, done};
-    rc = mpcx_plant_enqueue(ctx, P, c->state, c->u_sol, c->status, c->applied, px);
-    if (rc == MPCX_OK) ctx->bins_clean = binned;
+    rc = enqueue_plant(ctx, c, st.done());
     if (rc != MPCX_OK) return rc;
-    // the run log: one row per agent from the buffers as the step leaves them; the pool still holds the rows this step's conflict search saw
-    if (log) {
+    if (st.log) {
         rc = mpcx_record_enqueue(ctx, ip, P, c->state, c->applied, c->x_sol, c->path_xyyaw, c->path_off, c->path_len, c->target_ind, c->cut_len,
-                                 c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, log,
-                                 speed ? c->path_len : nullptr, done, sc ? sc->absent : nullptr);
+                                 c->traj_idx, c->hit_idx, c->status, c->iters, pool_rows, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, st.log,
+                                 speed ? c->path_len : nullptr, st.done(), st.scene ? st.scene->absent : nullptr);
         if (rc != MPCX_OK) return rc;
     }
-    // retirement: the goal test of the record stage (len(cx) = cut_len, the whole path in speed mode), after it, so that the arrival
-    // step's row logs the controls really applied
-    if (r) rc = mpcx_retire_enqueue(ctx, P, c->state, c->applied, c->path_xyyaw, c->path_off, c->path_len, c->target_ind,
-                                    speed ? c->path_len : c->cut_len, r, sc, c->obs_skip);
+    // the goal test of the record stage (len(cx) = cut_len, the whole path in speed mode)
+    if (st.retire) rc = mpcx_retire_enqueue(ctx, P, c->state, c->applied, c->path_xyyaw, c->path_off, c->path_len, c->target_ind,
+                                            speed ? c->path_len : c->cut_len, st.retire, st.scene, c->obs_skip);
     if (rc != MPCX_OK) return rc;
-    if (rs && rt)   // (validated: respawn, and the descriptor's own path_off / path_len)
+    if (st.respawn && st.routes)
         rc = mpcx_route_enqueue(ctx, P, c->state, c->applied, c->u_sol, c->traj_idx, c->target_ind, c->cut_len, c->iters,
-                                speed ? o->prev_len : nullptr, c->obs_skip, sc->n_rows, log, r, ad, rs, rt);
-    else if (rs)    // (validated: admission, and with it a scene and retirement)
+                                speed ? st.opts.prev_len : nullptr, c->obs_skip, st.scene->n_rows, st.log, st.retire, st.admit, st.respawn, st.routes);
+    else if (st.respawn)
         rc = mpcx_respawn_enqueue(ctx, P, c->state, c->applied, c->u_sol, c->traj_idx, c->target_ind, c->cut_len, c->iters,
-                                  speed ? o->prev_len : nullptr, c->obs_skip, sc->n_rows, log, r, ad, rs);
+                                  speed ? st.opts.prev_len : nullptr, c->obs_skip, st.scene->n_rows, st.log, st.retire, st.admit, st.respawn);
     return rc;
 }
 
 // A run of n_steps with step fusion (mpcx_set_step_fusion; closed_loop_run decides where it applies: the local pool, no scripted traffic, one
 // linearisation pass, no optional stage): per step ONE launch for what belongs to an agent alone -- the plant update of the step before
-// (from the second step of the run on), the pack and prediction of its pool row, its warm-start rollout -- then the conflict search, the
-// window selection and the solve with the arguments enqueue_step gives them; the last step's plant update ends the run in a launch of its
-// own.  Nothing runs on the side stream and neither event is touched.  The buffers hold the bits enqueue_step leaves.
-static int32_t enqueue_fused_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_closed_loop_opts *o,
+// (from the second step of the run on), the pack and prediction of its pool row, its warm-start rollout -- then the middle of a step as
+// enqueue_step has it; the last step's plant update ends the run in a launch of its own.  Nothing runs on the side stream and neither
+// event is touched.  The buffers hold the bits enqueue_step leaves.
+static int32_t enqueue_fused_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopStages &st,
                                  int32_t n_steps) {
     const int P = c->P;
-    const bool speed = o->stop_mode == MPCX_STOP_SPEED;
-    const bool binned = P < (1 << 24);
-    int32_t rc;
     for (int s = 0; s < n_steps; s++) {
         ctx->bins_clean = false;        // until the plant update of this step is enqueued
-        rc = mpcx_head_enqueue(ctx, ip, P, c->state, c->applied, c->u_sol, c->status, c->iters, c->xbar, c->obs6, s > 0, binned);
+        int32_t rc = mpcx_head_enqueue(ctx, ip, P, c->state, c->applied, c->u_sol, c->status, c->iters, c->xbar, c->obs6, s > 0, binned(P));
         if (rc != MPCX_OK) return rc;
         mpcx_interaction_extras ix;
-        ix.prev_save = ctx->prev_cut;
-        ix.near = near_hints(ctx, P);
-        ix.bin_hint = binned ? c->iters : nullptr;
-        if (speed) ix.key_prev = c->cut_len;
         ix.pack_state = c->state; ix.pack_applied = c->applied;
         ix.predicted = true;
-        rc = mpcx_interaction_enqueue(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
-                                      speed ? o->prev_len : c->cut_len, P, c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx,
-                                      c->hit_xy, c->cut_len, ix);
-        if (rc != MPCX_OK) return rc;
-        mpcx_window_extras wx{binned, near_hints(ctx, P), c->traj_idx, true};
-        wx.rollout_done = true;
-        if (speed) { wx.stop_idx = c->cut_len; wx.v_ref = o->v_ref; wx.len_seen = o->prev_len; }
-        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
-                                 c->target_ind, nullptr, 4 * (int64_t)(ctx->mpc.T + 1), c->xref, c->reaches_end, c->xbar, wx);
-        if (rc != MPCX_OK) return rc;
-        const mpcx_qp_order ord{binned, c->iters, c->cut_len, ctx->prev_cut, nullptr};
-        rc = mpcx_qp_enqueue(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol, c->status, c->iters, c->kkt, ord);
+        rc = enqueue_search_and_solve(ctx, ip, c, st, ix, P, true);
         if (rc != MPCX_OK) return rc;
     }
-    const mpcx_plant_extras px{c->iters, binned, nullptr};
-    rc = mpcx_plant_enqueue(ctx, P, c->state, c->u_sol, c->status, c->applied, px);
-    if (rc == MPCX_OK) ctx->bins_clean = binned;
-    return rc;
+    return enqueue_plant(ctx, c, nullptr);
 }
 
-static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const mpcx_run_log *log,
-                               const mpcx_closed_loop_opts *opts, const mpcx_retire *retire, const mpcx_scene *scene, const mpcx_admit *admit,
-                               const mpcx_respawn *respawn, const mpcx_routes *routes, const mpcx_precedence *precedence,
-                               const mpcx_signals *signals, const mpcx_actuation *actuation, int32_t n_steps, int32_t use_graph) {
+static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopArgs &args,
+                               int32_t n_steps, int32_t use_graph) {
     if (!ctx) return MPCX_E_INVALID;
     if (!ctx->have_mpc) return mpcx_fail(ctx, MPCX_E_INVALID, "mpcx_set_mpc_params has not been called");
     if (!ip || !c || n_steps < 0 || c->P < 0) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: null descriptor or negative count");
-    // the options as the graph's key holds them: nullptr and a cut-mode struct, whatever its other fields say, are the same run
-    mpcx_closed_loop_opts opt = {};
-    if (opts && opts->stop_mode != MPCX_STOP_CUT) {     // refused before anything is launched, whatever n_steps is
-        if (opts->stop_mode != MPCX_STOP_SPEED)
-            return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: unknown stop mode %d (MPCX_STOP_CUT or MPCX_STOP_SPEED)", opts->stop_mode);
-        if (!std::isfinite(opts->v_ref)) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: MPCX_STOP_SPEED with a speed reference v_ref that is not finite");
-        if (!opts->prev_len) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: MPCX_STOP_SPEED needs prev_len (P zero-initialised int32)");
-        opt.stop_mode = MPCX_STOP_SPEED; opt.v_ref = opts->v_ref; opt.prev_len = opts->prev_len;
-    }
-    if (mpcx_record_absent(log)) log = nullptr;
-    if (log) {          // refused before anything is launched, whatever n_steps is
-        const int32_t lrc = mpcx_record_validate(ctx, log, c->obs_skip);
-        if (lrc != MPCX_OK) return lrc;
-    }
-    if (mpcx_retire_absent(retire)) retire = nullptr;
-    if (retire) {       // refused before anything is launched, whatever n_steps is
-        const int32_t rrc = mpcx_retire_validate(ctx, retire, c->P);
-        if (rrc != MPCX_OK) return rrc;
-    }
-    if (mpcx_scene_absent(scene)) scene = nullptr;
-    if (scene) {        // refused before anything is launched, whatever n_steps is
-        const bool traffic = c->n_actors > 0;
-        const size_t rows = traffic ? (size_t)(c->pool_rows > 0 ? c->pool_rows : 0) : (size_t)c->P;
-        int32_t src = mpcx_scene_validate(ctx, scene, retire, c->exchange, rows, c->obs_skip);
-        if (src == MPCX_OK && c->P > 0) src = mpcx_loop_check_rows(ctx, c->P, c->obs_skip, scene->n_rows, "scene");
-        if (src != MPCX_OK) return src;
-    }
-    if (mpcx_admit_absent(admit)) admit = nullptr;
-    if (admit) {        // refused before anything is launched, whatever n_steps is
-        const int32_t arc = mpcx_admit_validate(ctx, admit, retire, scene, c->exchange);
-        if (arc != MPCX_OK) return arc;
-    }
-    if (mpcx_respawn_absent(respawn)) respawn = nullptr;
-    if (respawn) {      // refused before anything is launched, whatever n_steps is
-        const int32_t prc = mpcx_respawn_validate(ctx, respawn, admit);
-        if (prc != MPCX_OK) return prc;
-    }
-    if (mpcx_routes_absent(routes)) routes = nullptr;
-    if (routes) {       // refused before anything is launched, whatever n_steps is
-        // the longest route the conflict search handles: max_path_len as mpcx_interaction_enqueue rounds it
-        int32_t cap = ip->max_path_len > 0 ? ip->max_path_len : MPCX_MAX_REMAINING;
-        if (cap < 512) cap = 512;
-        cap = (cap + 63) / 64 * 64;
-        const int32_t trc = mpcx_routes_validate(ctx, routes, respawn, c->path_off, c->path_len, cap);
-        if (trc != MPCX_OK) return trc;
-    }
-    if (mpcx_precedence_absent(precedence)) precedence = nullptr;
-    if (precedence) {   // refused before anything is launched, whatever n_steps is
-        const int32_t prc = mpcx_precedence_validate(ctx, precedence, scene, admit);
-        if (prc != MPCX_OK) return prc;
-    }
-    if (mpcx_signals_absent(signals)) signals = nullptr;
-    if (mpcx_actuation_absent(actuation)) actuation = nullptr;
-    mpcx_actuation act;         // by value with its padding zeroed: the cached graph's key
-    memset(&act, 0, sizeof act);
-    if (actuation) {    // refused before anything is launched, whatever n_steps is; checks the signals it draws on too
-        const int32_t arc = mpcx_actuation_validate(ctx, actuation, signals, c->P, c->exchange);
-        if (arc != MPCX_OK) return arc;
-        act.phase_groups = actuation->phase_groups; act.phase_time = actuation->phase_time; act.ctrl_time = actuation->ctrl_time;
-        act.ctrl_of = actuation->ctrl_of; act.jstate = actuation->jstate; act.lights = actuation->lights; act.calls = actuation->calls;
-        act.n_per = actuation->n_per; act.n_junctions = actuation->n_junctions; act.n_phases = actuation->n_phases;
-        act.n_ctrl = actuation->n_ctrl;
-        actuation = &act;
-    } else if (signals) {      // refused before anything is launched, whatever n_steps is
-        const int32_t grc = mpcx_signals_validate(ctx, signals, c->exchange);
-        if (grc != MPCX_OK) return grc;
-    }
+    LoopStages st;
+    int32_t rc = check_stages(ctx, ip, c, args, &st);
+    if (rc != MPCX_OK) return rc;
     if (n_steps == 0 || c->P == 0) return MPCX_OK;
     if (!c->state || !c->applied || !c->obs6 || !c->path_xyyaw || !c->path_cs || !c->path_off || !c->path_len ||
         !c->obs_off || !c->obs_cnt || !c->traj_idx || !c->target_ind || !c->hit_idx || !c->cut_len || !c->hit_xy ||
@@ -333,7 +355,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     }
     // everything that allocates (or reads back) happens before the first launch (and outside any capture)
     const size_t pool_rows = c->n_actors > 0 ? (size_t)c->pool_rows : (size_t)c->P * (c->exchange == MPCX_SHARD_AGENTS ? (size_t)ctx->comm_world : 1);
-    int32_t rc = mpcx_ensure_pred(ctx, pool_rows * ip->pred_steps * 4);
+    rc = mpcx_ensure_pred(ctx, pool_rows * ip->pred_steps * 4);
     if (rc != MPCX_OK) return rc;
     if (c->n_actors > 0) {
         rc = mpcx_traffic_validate(ctx, c->n_actors, c->actors, c->tape, c->tape_rows, c->actor_row, c->pool_rows);
@@ -343,8 +365,8 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     }
     rc = mpcx_ensure_ticket(ctx);
     if (rc != MPCX_OK) return rc;
-    if (admit) {
-        rc = mpcx_admit_prepare(ctx, (size_t)scene->n_rows);
+    if (st.admit) {
+        rc = mpcx_admit_prepare(ctx, (size_t)st.scene->n_rows);
         if (rc != MPCX_OK) return rc;
     }
     {
@@ -379,11 +401,10 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (rc != MPCX_OK) return rc;
 
     if (!use_graph) {
-        if (ctx->step_fusion && c->exchange == 0 && c->n_actors == 0 && ctx->lin_passes == 1 && !log && !retire && !scene && !admit && !respawn &&
-            !routes && !precedence && !signals && !actuation)
-            return enqueue_fused_run(ctx, ip, c, &opt, n_steps);
+        if (ctx->step_fusion && c->exchange == 0 && c->n_actors == 0 && ctx->lin_passes == 1 && st.none())
+            return enqueue_fused_run(ctx, ip, c, st, n_steps);
         for (int s = 0; s < n_steps; s++) {
-            rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence, signals, actuation);
+            rc = enqueue_step(ctx, ip, c, st);
             if (rc != MPCX_OK) return rc;
         }
         return MPCX_OK;
@@ -392,44 +413,17 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     if (!ctx->stream) return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: graph replay needs a non-default stream");
     if (ctx->prof_qp)       // the event pairs of mpcx_profile_qp cannot be recorded inside a replayed graph: say so instead of reporting 0 launches
         return mpcx_fail(ctx, MPCX_E_INVALID, "closed_loop_run: mpcx_profile_qp is on; the QP launches of a replayed graph are not bracketed by events -- run without graph or switch the hook off");
-    unsigned char key[sizeof ctx->loop_key];
-    static_assert(sizeof(mpcx_closed_loop) + sizeof(mpcx_run_log) + sizeof(mpcx_closed_loop_opts) + sizeof(mpcx_retire) + sizeof(mpcx_scene) + sizeof(mpcx_admit) + sizeof(mpcx_respawn) + sizeof(mpcx_routes) + sizeof(mpcx_precedence) + sizeof(mpcx_signals) + sizeof(mpcx_actuation) + sizeof(mpcx_interaction_params) +
-                  sizeof(mpcx_mpc_params) + 10 * sizeof(void *) <= sizeof key,
-                  "loop_key too small");
-    memset(key, 0, sizeof key);
-    size_t o = 0;
-    memcpy(key + o, c, sizeof *c); o += sizeof *c;
-    if (log) memcpy(key + o, log, sizeof *log);     // (zeros = no log: a graph captured without the record stage)
-    o += sizeof *log;
-    memcpy(key + o, &opt, sizeof opt); o += sizeof opt;
-    if (retire) memcpy(key + o, retire, sizeof *retire);     // (zeros = no retirement: a graph captured without it)
-    o += sizeof *retire;
-    if (scene) memcpy(key + o, scene, sizeof *scene);        // (zeros = no scene: a graph captured without departure)
-    o += sizeof *scene;
-    if (admit) memcpy(key + o, admit, sizeof *admit);        // (zeros = no admission: a graph captured without its two launches)
-    o += sizeof *admit;
-    if (respawn) memcpy(key + o, respawn, sizeof *respawn);  // (zeros = no respawn: a graph captured without its launch)
-    o += sizeof *respawn;
-    if (routes) memcpy(key + o, routes, sizeof *routes);     // (zeros = no routes: a graph captured with respawn_kernel)
-    o += sizeof *routes;
-    if (precedence) memcpy(key + o, precedence, sizeof *precedence);     // (zeros = no precedence: a graph captured without its instantiations)
-    o += sizeof *precedence;
-    if (signals) memcpy(key + o, signals, sizeof *signals);  // (zeros = no signals: a graph captured without signal_kernel)
-    o += sizeof *signals;
-    if (actuation) memcpy(key + o, actuation, sizeof *actuation);    // (zeros = no actuation: a graph captured with signal_kernel, if any)
-    o += sizeof *actuation;
-    memcpy(key + o, &ctx->admit_tab, sizeof ctx->admit_tab); o += sizeof ctx->admit_tab;
-    memcpy(key + o, ip, sizeof *ip); o += sizeof *ip;
-    memcpy(key + o, &ctx->mpc, sizeof ctx->mpc); o += sizeof ctx->mpc;
-    memcpy(key + o, &ctx->pred, sizeof ctx->pred); o += sizeof ctx->pred;
-    memcpy(key + o, &ctx->tune, sizeof ctx->tune); o += sizeof ctx->tune;
-    memcpy(key + o, &ctx->order, sizeof ctx->order); o += sizeof ctx->order;
-    memcpy(key + o, &ctx->prev_cut, sizeof ctx->prev_cut); o += sizeof ctx->prev_cut;
-    memcpy(key + o, &ctx->bins, sizeof ctx->bins); o += sizeof ctx->bins;
-    memcpy(key + o, &ctx->qp_solver, sizeof ctx->qp_solver); o += sizeof ctx->qp_solver;      // the captured launch is the solver chosen at capture time
-    memcpy(key + o, &ctx->lin_passes, sizeof ctx->lin_passes); o += sizeof ctx->lin_passes;
-    memcpy(key + o, &ctx->stats, sizeof ctx->stats);
-    if (!ctx->loop_exec || memcmp(key, ctx->loop_key, sizeof key) != 0) {
+    mpcx::LoopKey key;
+    memset(&key, 0, sizeof key);
+    using mpcx::key_put;
+    key_put(key.desc, c); key_put(key.ip, ip); key_put(key.mpc, &ctx->mpc);
+    key_put(key.log, st.log); key_put(key.retire, st.retire); key_put(key.scene, st.scene); key_put(key.admit, st.admit);
+    key_put(key.respawn, st.respawn); key_put(key.routes, st.routes); key_put(key.precedence, st.precedence); key_put(key.signals, st.signals);
+    key.opts = st.opts; key.actuation = st.actuation;
+    key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
+    key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;
+    key.qp_solver = ctx->qp_solver; key.lin_passes = ctx->lin_passes;
+    if (!ctx->loop_exec || memcmp(&key, ctx->loop_key, sizeof key) != 0) {
         if (ctx->loop_exec) {
             (void)hipStreamSynchronize(ctx->stream);
             (void)hipGraphExecDestroy(ctx->loop_exec);
@@ -438,14 +432,14 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
             return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipStreamBeginCapture failed");
-        rc = enqueue_step(ctx, ip, c, log, &opt, retire, scene, admit, respawn, routes, precedence, signals, actuation);
+        rc = enqueue_step(ctx, ip, c, st);
         hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
         if (rc != MPCX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess || !graph) return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: stream capture failed: %s", hipGetErrorString(e));
         e = hipGraphInstantiate(&ctx->loop_exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) { ctx->loop_exec = nullptr; return mpcx_fail(ctx, MPCX_E_LAUNCH, "closed_loop_run: hipGraphInstantiate: %s", hipGetErrorString(e)); }
-        memcpy(ctx->loop_key, key, sizeof key);
+        memcpy(ctx->loop_key, &key, sizeof key);
     }
     for (int s = 0; s < n_steps; s++)
         if (hipGraphLaunch(ctx->loop_exec, ctx->stream) != hipSuccess)
@@ -453,73 +447,65 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     return MPCX_OK;
 }
 
+// The entry points: each names the stages it has parameters for, in LoopArgs' order; the rest are off.
+
 extern "C" int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                         int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_logged(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_opts(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                              const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_retire(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_scene(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_admit(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                               const mpcx_scene *scene, const mpcx_admit *admit, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, nullptr, nullptr, nullptr, nullptr, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_respawn(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                 const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                 const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                 int32_t n_steps, int32_t use_graph) {
-    return mpcx_closed_loop_run_routes(ctx, ip, c, log, opts, retire, scene, admit, respawn, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_routes(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                const mpcx_routes *routes, int32_t n_steps, int32_t use_graph) {
-    return mpcx_closed_loop_run_precedence(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_precedence(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                    const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                    const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                    const mpcx_routes *routes, const mpcx_precedence *precedence, int32_t n_steps,
                                                    int32_t use_graph) {
-    return mpcx_closed_loop_run_signals(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, precedence, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_signals(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                 const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                 const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                 const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
                                                 int32_t n_steps, int32_t use_graph) {
-    return mpcx_closed_loop_run_actuated(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, precedence, signals, nullptr, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals}, n_steps, use_graph);
 }
-
 extern "C" int32_t mpcx_closed_loop_run_actuated(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
                                                  const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
                                                  const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
                                                  const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
                                                  const mpcx_actuation *actuation, int32_t n_steps, int32_t use_graph) {
-    return closed_loop_run(ctx, ip, c, log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation, n_steps, use_graph);
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation}, n_steps, use_graph);
 }

@@ -649,51 +649,11 @@ class Context:
         (mpcx_closed_loop_run_signals; needs none of the others); None = no signals.
         actuation: a _lib.ActuationC -- vehicle-actuated signals: a controller per junction takes the place of the signals' fixed plan
         (mpcx_closed_loop_run_actuated; refused without signals); None = the signals' own plan."""
-        cip = ip.to_c()
         ref = lambda s: None if s is None else C.byref(s)
-        if actuation is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_actuated(self._ctx, C.byref(cip), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
-                                                             ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals),
-                                                             C.byref(actuation), int(n_steps), 1 if graph else 0))
-        elif signals is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_signals(self._ctx, C.byref(cip), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
-                                                            ref(admit), ref(respawn), ref(routes), ref(precedence), C.byref(signals),
-                                                            int(n_steps), 1 if graph else 0))
-        elif precedence is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_precedence(self._ctx, C.byref(cip), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
-                                                               ref(admit), ref(respawn), ref(routes), C.byref(precedence), int(n_steps),
-                                                               1 if graph else 0))
-        elif routes is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_routes(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
-                                                           None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
-                                                           None if scene is None else C.byref(scene), None if admit is None else C.byref(admit),
-                                                           None if respawn is None else C.byref(respawn), C.byref(routes), int(n_steps),
-                                                           1 if graph else 0))
-        elif respawn is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_respawn(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
-                                                            None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
-                                                            None if scene is None else C.byref(scene), None if admit is None else C.byref(admit),
-                                                            C.byref(respawn), int(n_steps), 1 if graph else 0))
-        elif admit is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_admit(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
-                                                          None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
-                                                          None if scene is None else C.byref(scene), C.byref(admit), int(n_steps),
-                                                          1 if graph else 0))
-        elif scene is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_scene(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
-                                                          None if opts is None else C.byref(opts), None if retire is None else C.byref(retire),
-                                                          C.byref(scene), int(n_steps), 1 if graph else 0))
-        elif retire is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_retire(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
-                                                           None if opts is None else C.byref(opts), C.byref(retire), int(n_steps),
-                                                           1 if graph else 0))
-        elif opts is not None:
-            self._chk(self.lib.mpcx_closed_loop_run_opts(self._ctx, C.byref(cip), C.byref(desc), None if log is None else C.byref(log),
-                                                         C.byref(opts), int(n_steps), 1 if graph else 0))
-        elif log is None:
-            self._chk(self.lib.mpcx_closed_loop_run(self._ctx, C.byref(cip), C.byref(desc), int(n_steps), 1 if graph else 0))
-        else:
-            self._chk(self.lib.mpcx_closed_loop_run_logged(self._ctx, C.byref(cip), C.byref(desc), C.byref(log), int(n_steps), 1 if graph else 0))
+        # (the widest entry point: NULL is "none" for every stage, and the narrower ones are that call with NULLs)
+        self._chk(self.lib.mpcx_closed_loop_run_actuated(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
+                                                         ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals), ref(actuation),
+                                                         int(n_steps), 1 if graph else 0))
 
     @_ordered
     def signal_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', done=None):
