@@ -113,6 +113,8 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
                                const double *path_cs, const int32_t *path_off, const int32_t *path_len, const int32_t *prev_cut_len,
                                int32_t n_obs_pool, const double *obs6, const int32_t *obs_off, const int32_t *obs_cnt, const int32_t *obs_skip,
                                int32_t *traj_idx, int32_t *hit_idx, double *hit_xy, int32_t *cut_len, const mpcx_interaction_extras &x);   // mpcx_interaction.hip
+// the path points that launch makes room for: ip->max_path_len (0 = MPCX_MAX_REMAINING; never below 512) rounded up to a multiple of 64
+int32_t mpcx_interaction_capacity(const mpcx_interaction_params *ip);                                                                    // mpcx_interaction.hip
 int32_t mpcx_window_enqueue(mpcx_ctx *ctx, int32_t B, const double *state, const double *u_warm, const double *path_xyyaw, const double *path_v,
                           const int32_t *path_off, const int32_t *path_len, double dl, int32_t *target_ind, const double *ov, int64_t ov_stride,
                           double *xref, uint8_t *reaches_end, double *xbar, const mpcx_window_extras &x);                                   // mpcx_prepare.hip

@@ -1,9 +1,8 @@
 // mpcx_interaction_prec.hip -- the right-of-way instantiations of the conflict search's kernels (mpcx_precedence): predict_kernel<·, true, true>
 // (STAND: every predicted row also leaves its standing record) and interaction_kernel<true, true, true> (PREC: the present rows that yield to
-// the agent are seen through their standing records).  The templates are mpcx_interaction.hip's, included for the templates alone; the
-// instantiations are kept apart so that mpcx_interaction.hip holds exactly the kernels it held before there was precedence.
-#define MPCX_INTERACTION_TEMPLATES_ONLY
-#include "mpcx_interaction.hip"
+// the agent are seen through their standing records).  The templates are mpcx_interaction_parts.h's; the instantiations are kept apart, here
+// and nowhere else, so that mpcx_interaction.hip holds exactly the kernels it held before there was precedence.
+#include "mpcx_interaction_parts.h"
 
 namespace mpcx {
 

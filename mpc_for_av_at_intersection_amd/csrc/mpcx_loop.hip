@@ -157,11 +157,8 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (st->respawn && (rc = mpcx_respawn_validate(ctx, st->respawn, st->admit)) != MPCX_OK) return rc;
     if (!mpcx_routes_absent(a.routes)) {
         st->routes = a.routes;
-        // the longest route the conflict search handles: max_path_len as mpcx_interaction_enqueue rounds it
-        int32_t cap = ip->max_path_len > 0 ? ip->max_path_len : MPCX_MAX_REMAINING;
-        if (cap < 512) cap = 512;
-        cap = (cap + 63) / 64 * 64;
-        rc = mpcx_routes_validate(ctx, st->routes, st->respawn, c->path_off, c->path_len, cap);
+        // (the longest route the conflict search handles is its launch's capacity)
+        rc = mpcx_routes_validate(ctx, st->routes, st->respawn, c->path_off, c->path_len, mpcx_interaction_capacity(ip));
         if (rc != MPCX_OK) return rc;
     }
     if (!mpcx_precedence_absent(a.precedence)) st->precedence = a.precedence;

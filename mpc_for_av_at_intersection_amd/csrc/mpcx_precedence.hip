@@ -1,6 +1,6 @@
 // mpcx_precedence.hip -- right of way in the device-resident closed loop: the struct's checks and the entry-order stamp of
 // MPCX_PRECEDENCE_ENTRY.  The rule of the stamp is mpcx_precedence_core.h; the rule the words stand for is applied by the PREC instantiations
-// of predict_kernel and interaction_kernel (mpcx_interaction.hip).
+// of predict_kernel and interaction_kernel (mpcx_interaction_parts.h; instantiated in mpcx_interaction_prec.hip).
 // precedence_stamp_kernel: one launch right after the admission stage, one lane per agent, one store per agent in the scene.  No LDS, no
 // scratch.  Everything it reads is device memory the step itself maintains, so a replayed hipGraph stamps like a plain run.
 #include "mpcx_common.h"

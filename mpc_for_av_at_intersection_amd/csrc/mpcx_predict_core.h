@@ -1,4 +1,4 @@
-// mpcx_predict_core.h -- the prediction of one pool row, shared by predict_kernel (mpcx_interaction.hip) and head_kernel (mpcx_prepare.hip):
+// mpcx_predict_core.h -- the prediction of one pool row, shared by predict_kernel (mpcx_interaction_parts.h) and head_kernel (mpcx_prepare.hip):
 // both evaluate these very expressions, in this spelling, so both leave the same bits.
 #pragma once
 #include "mpcx_common.h"

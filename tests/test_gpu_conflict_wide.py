@@ -1,4 +1,4 @@
-"""GPU tests of the conflict search (first_row of csrc/mpcx_interaction.hip, shared by interaction_kernel and moving_collision_kernel)
+"""GPU tests of the conflict search (first_row of csrc/mpcx_interaction_parts.h, shared by interaction_kernel and moving_collision_kernel)
 away from the one point the other files pin it at -- at most 7 obstacles, 35 predicted frames, a window of 20.
 
 Against tests/golden/moving_wide.npz, recorded from the reference (make_golden.py --stage moving_wide): 8..16 obstacles per ego, 1..64

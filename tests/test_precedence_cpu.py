@@ -165,8 +165,8 @@ def test_stamp_kernel_needs_no_scratch():
 
 def test_right_of_way_instantiations():
     """P5.  mpcx_interaction_prec.hip holds exactly the three right-of-way instantiations -- predict_kernel<false / true, true, true> and
-    interaction_kernel<true, true, true> --, none with scratch, spills or static LDS; the conflict search keeps five wavefronts per SIMD
-    within 96 VGPRs"""
+    interaction_kernel<true, true, true> -- of the templates in mpcx_interaction_parts.h, none with scratch, spills or static LDS; the
+    conflict search keeps five wavefronts per SIMD within 96 VGPRs"""
     use = _usage('mpcx_interaction_prec.hip')
     want = ('predict_kernelILb0ELb1ELb1EEE', 'predict_kernelILb1ELb1ELb1EEE', 'interaction_kernelILb1ELb1ELb1EEE')
     assert len(use) == 3 and all(sum(w in n for n in use) == 1 for w in want), sorted(use)
