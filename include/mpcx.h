@@ -23,7 +23,7 @@
  *     right of way: mpcx_precedence, mpcx_closed_loop_run_precedence.  A route per vehicle of such a slot is mpcx_routes,
  *     mpcx_closed_loop_run_routes; mpcx_episode_summary reduces the episode table per instance and route.  Holding agents at the stop
  *     lines of a signalised crossing is mpcx_signals, mpcx_closed_loop_run_signals; lights that follow the demand are mpcx_actuation,
- *     mpcx_closed_loop_run_actuated.
+ *     mpcx_closed_loop_run_actuated; a speed advised ahead of a red light of a fixed plan is mpcx_advice, mpcx_closed_loop_run_advised.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -379,7 +379,7 @@ typedef struct {
 int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
                              int32_t n_steps, int32_t use_graph);
 /* Step fusion (on by default).  A run of n steps without a graph on the local pool -- no scripted traffic, one linearisation pass, none of
- * the run log, retirement, scene, admission, respawn, routes, precedence, signals or actuation -- enqueues ONE launch per step for what
+ * the run log, retirement, scene, admission, respawn, routes, precedence, signals, actuation or advice -- enqueues ONE launch per step for what
  * belongs to an agent alone: the plant update of the step before, the pack and prediction of its pool row and its warm-start rollout
  * (head_kernel); the run ends with the last step's plant update in a launch of its own.  Every buffer holds the same bits when the call
  * returns.  on = 0: the launch sequence without fusion (the rollout on the side stream beside the conflict search), for every run. */
@@ -866,6 +866,49 @@ int32_t mpcx_closed_loop_run_actuated(mpcx_ctx *ctx, const mpcx_interaction_para
 int32_t mpcx_actuated_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
                                  const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
                                  const int32_t *done /*P or NULL*/, const mpcx_signals *signals, const mpcx_actuation *actuation);
+
+/* ---- signal-aware approach speed: agents are advised ahead of a red light.  In MPCX_STOP_SPEED a hold only zeroes the speed reference
+ * from the stop line on; the path stays whole and the position reference keeps pulling the car forward, so it reaches its line at speed,
+ * brakes late and creeps over.  The plan is a table in device memory: an agent can know when its light turns green.  One launch per step
+ * (advise_kernel, csrc/mpcx_advise.hip; the rule is csrc/mpcx_advise_core.h) between the window stage and the QP caps row 2 of the agent's
+ * xref -- the speed reference over the window -- at the speed with which it reaches its line as the light turns green, and touches nothing
+ * else.  The hold of mpcx_signals stays as it is, the safety net behind the advice; a held agent IS advised.
+ * For agent q, with traj_idx, cut_len, tick and held as the signal stage of this step left them:  (1) NO ADVICE, advised[q] = 0.0 and xref
+ * untouched: done[q] != 0; plan_of[q] out of range or cycle < 1; any "free" condition of the hold -- with i = path_off[q] + traj_idx[q]: i
+ * outside [0, n_points), s = path_stop[i] < 0, traj_idx[q] >= s, s >= path_len[q], the group out of range --; cut_len[q] < s (a conflict
+ * stops the agent before its line); d > reach with d = (double)(s - traj_idx[q]) * dl.  (2) t0 = tick[q] - 1 (+ cycle if negative): the
+ * clock value the signal stage used this step.  (3) k_c = ceil(d / (v_cruise * dt)), an integer clamped to 2^30, dt the context's MPC
+ * time step: the earliest arrival; u = (t0 + k_c - green_from) mod cycle, non-negative; u < green_len: arrival on green at cruise speed, no
+ * advice.  (4) else w = cycle - u, k_t = k_c + w + lead, v = d / ((double)k_t * dt), advised[q] = max(v, v_min).  (5) every entry of row 2
+ * of agent q's xref (T + 1 doubles at xref + (4 q + 2)(T + 1)) becomes fmin(entry, advised[q]): the zeros of the stop profile stay zero.
+ * The result is bit-identical between a host build of the rule and the device and does not depend on the order of the lanes.
+ * advice = NULL or an all-zero struct: mpcx_closed_loop_run_actuated itself -- the same launches with the same arguments.  No other struct
+ * changes size; the cached graph's key covers the struct by value.  MPCX_E_INVALID ("advice: ...") before anything is launched, whatever
+ * n_steps is: advised NULL; n_rows != P; v_cruise, v_min or reach not finite or not positive; v_min > v_cruise; lead < 0; no signals, or
+ * signals without a fixed plan; actuation on (a controller decides the lights step by step: there is no plan to look ahead into); a stop
+ * mode other than MPCX_STOP_SPEED (in cut mode the speed reference is 0 and the stage would silently do nothing); the signals' own
+ * refusals.  The struct has no padding: two int32 close its 40 bytes. */
+typedef struct {
+    double *advised;             /* n_rows = P, caller-owned, out: the speed advised to agent q in the last step, 0.0 = none */
+    double v_cruise;             /* the speed the earliest arrival is computed with (> 0, m/s) */
+    double v_min;                /* advice is never below this (> 0, <= v_cruise, m/s) */
+    double reach;                /* only agents within this distance of their line are advised (> 0, m) */
+    int32_t lead, n_rows;        /* lead: steps of margin added to the wait (>= 0); n_rows: P */
+} mpcx_advice;
+/* the widest entry point: mpcx_closed_loop_run_actuated with the advice stage */
+int32_t mpcx_closed_loop_run_advised(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                     const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                     const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                     const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                     const mpcx_routes *routes /*or NULL*/, const mpcx_precedence *precedence /*or NULL*/,
+                                     const mpcx_signals *signals /*or NULL*/, const mpcx_actuation *actuation /*or NULL*/,
+                                     const mpcx_advice *advice /*or NULL*/, int32_t n_steps, int32_t use_graph);
+/* one step's advice stage alone (what mpcx_closed_loop_run_advised enqueues between the window stage and the QP): xref is the window
+ * stage's output of this step (P x 4 x (T + 1), T the context's horizon), row 2 of it in-out; done: mpcx_retire::done or NULL.  Both
+ * structs are checked as above (the caller vouches for the stop mode: xref is that of mpcx_mpc_prepare_batch_stop). */
+int32_t mpcx_advise_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const int32_t *path_off /*P*/, const int32_t *path_len /*P*/,
+                               const int32_t *traj_idx /*P*/, const int32_t *cut_len /*P*/, const int32_t *done /*P or NULL*/,
+                               const mpcx_signals *signals, const mpcx_advice *advice, double *xref /*P,4,T+1*/);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

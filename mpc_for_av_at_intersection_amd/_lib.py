@@ -114,6 +114,12 @@ class ActuationC(C.Structure):
                 ('n_phases', C.c_int32), ('n_ctrl', C.c_int32), ('reserved', C.c_int32)]
 
 
+class AdviceC(C.Structure):
+    """mirror of mpcx_advice (include/mpcx.h): signal-aware approach speed; advised (n_rows = P float64, out) is a device address"""
+    _fields_ = [('advised', C.c_void_p), ('v_cruise', C.c_double), ('v_min', C.c_double), ('reach', C.c_double), ('lead', C.c_int32),
+                ('n_rows', C.c_int32)]
+
+
 SIGNAL_GROUPS_MAX = 16                          # MPCX_SIGNAL_GROUPS_MAX
 ACTUATION_PHASES_MAX = 8                        # MPCX_ACTUATION_PHASES_MAX
 STAGE_GREEN, STAGE_AMBER, STAGE_ALL_RED = 0, 1, 2       # mpcx_actuation.jstate[j][1]
@@ -193,7 +199,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
            'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence',
            'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
-           'mpcx_closed_loop_run_actuated', 'mpcx_actuated_step_batch']
+           'mpcx_closed_loop_run_actuated', 'mpcx_actuated_step_batch', 'mpcx_closed_loop_run_advised', 'mpcx_advise_step_batch']
 
 
 def load():
@@ -314,5 +320,12 @@ def load():
                                                   C.POINTER(ActuationC), i32, i32]
     lib.mpcx_actuated_step_batch.restype = i32
     lib.mpcx_actuated_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(ActuationC)]
+    lib.mpcx_closed_loop_run_advised.restype = i32
+    lib.mpcx_closed_loop_run_advised.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                 C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                 C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
+                                                 C.POINTER(ActuationC), C.POINTER(AdviceC), i32, i32]
+    lib.mpcx_advise_step_batch.restype = i32
+    lib.mpcx_advise_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(AdviceC), vp]
     _lib = lib
     return lib

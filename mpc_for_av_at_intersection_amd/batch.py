@@ -36,6 +36,9 @@ group its green within a cycle (two_phase_plan()), and one more small launch beh
 `actuate(controllers)` makes the signals VEHICLE-ACTUATED: every instance is a junction with a controller on the device that holds a phase
 at least its minimum green, extends it while cars approach its lines, ends it after a gap or at a maximum if somebody else waits, and skips
 phases nobody calls (two_phase_controller()); the launch takes the place of the fixed plan's, the hold at the line is the same.
+`advise_speed()` is SIGNAL-AWARE APPROACH SPEED for a signalised batch in speed mode: an agent that would reach its stop line on red at cruise
+speed gets the speed with which it reaches the line as the light turns green as a cap on its speed reference (one launch between the
+window stage and the QP); the hold stays the safety net behind it.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -354,6 +357,8 @@ class IntersectionBatch:
         self.lights: Optional[torch.Tensor] = None           # ... int32 (B,), the lights of the last step, 2 bits per signal group
         self.calls: Optional[torch.Tensor] = None            # ... int32 (B,), bit g = group g was called in the last step
         self._actuation = None
+        self.advised: Optional[torch.Tensor] = None          # advise_speed(): float64 (P,), the speed advised in the last step, 0 = none
+        self._advice = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -701,6 +706,32 @@ class IntersectionBatch:
         self._desc = None
         c.synchronize()
 
+    def advise_speed(self, v_min: float = 1.0, lead: int = 1, reach: float = 60.0, v_cruise: Optional[float] = None):
+        """SIGNAL-AWARE APPROACH SPEED (mpcx_closed_loop_run_advised), for a batch in speed mode under signalise().  In speed mode a red
+        light zeroes the speed reference from the stop line on while the position reference keeps pulling the car forward: it reaches the
+        line at speed, brakes late and creeps over.  With advice an agent within `reach` metres of its line that would arrive on red at
+        v_cruise (default: the batch's v_ref) has its speed reference capped at the speed with which it arrives `lead` steps after the
+        light turns green, never below v_min: one more launch between the window stage and the QP.  The hold at the line is unchanged.
+        Allocates `advised` (zero) and drops the cached descriptor; stop_advising() switches it off, as does unsignalise()."""
+        if self.stop_mode != 'speed':
+            raise ValueError('advise_speed: the batch runs with stop_mode=%r; advice caps the speed reference of stop_mode=\'speed\'' % self.stop_mode)
+        if self._signals is None or self._actuation is not None:
+            raise ValueError('advise_speed: needs signalise() -- a fixed plan to look ahead into (actuate() decides the lights step by step)')
+        v_cruise = float(self.v_ref) if v_cruise is None else float(v_cruise)
+        v_min, reach, lead = float(v_min), float(reach), int(lead)
+        if not (np.isfinite([v_cruise, v_min, reach]).all() and v_cruise > 0 and v_min > 0 and reach > 0 and v_min <= v_cruise and lead >= 0):
+            raise ValueError('advise_speed: 0 < v_min <= v_cruise, reach > 0, all finite, lead >= 0')
+        self.advised = torch.zeros(self.P, dtype=torch.float64, device=self.ctx.device)
+        self._advice = _lib.AdviceC(self.advised.data_ptr(), v_cruise, v_min, reach, lead, self.P)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def stop_advising(self):
+        """switch the advice off and nothing else: the batch enqueues exactly the launches of one that never had it (`advised` keeps what
+        it holds and is no longer written)"""
+        self._advice = None
+        self._desc = None
+
     def actuate(self, controllers, ctrl_of=None, stop=None, group=None, brake: Optional[float] = None):
         """VEHICLE-ACTUATED SIGNALS (mpcx_closed_loop_run_actuated).  Every instance is a junction (n_per = A) with a controller on the
         device: the launch that holds agents at their stop lines first reduces, over the junction's agents, which signal groups have a car
@@ -767,14 +798,16 @@ class IntersectionBatch:
         self._actuation = _lib.ActuationC(tabs['phase_groups'].data_ptr(), tabs['phase_time'].data_ptr(), tabs['ctrl_time'].data_ptr(),
                                           tabs['ctrl_of'].data_ptr(), self.junction_state.data_ptr(), self.lights.data_ptr(),
                                           self.calls.data_ptr(), self.A, self.B, n_phases, len(controllers), 0)
+        self._advice = None                 # (there is no plan left to look ahead into)
         self._desc = None
         c.synchronize()
 
     def unsignalise(self):
-        """switch the signals off, fixed or actuated, and nothing else: the batch enqueues exactly the launches of one that never had them
+        """switch the signals off, fixed or actuated -- and the advice that draws on them -- and nothing else: the batch enqueues exactly the launches of one that never had them
         (`tick`, `held` and the junction words keep what they hold and are no longer read or written)"""
         self._signals = None
         self._actuation = None
+        self._advice = None                 # (advice looks ahead into the signals' plan)
         self._desc = None
 
     def stop_respawning(self):
@@ -926,7 +959,7 @@ class IntersectionBatch:
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
                                  retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes,
-                                 precedence=self._precedence, signals=self._signals, actuation=self._actuation)
+                                 precedence=self._precedence, signals=self._signals, actuation=self._actuation, advice=self._advice)
         self.steps_done += n_steps
 
     def step(self):
@@ -984,6 +1017,9 @@ class IntersectionBatch:
                 c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.path_len, self.dl, self.target_ind, out=self.pre,
                           path_v=self.path_v, x_prev=self.sol['x'] if it else None, stop_idx=self.inter['cut_len'], v_ref=self.v_ref,
                           len_seen=self.prev_len)
+                if self._advice is not None:    # the advice stage: between the window stage and the QP, as in the loop
+                    c.advise_step(self.dl, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._advice,
+                                  self.pre['xref'])
             else:
                 c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.inter['cut_len'], self.dl, self.target_ind, out=self.pre,
                           path_v=self.path_v, x_prev=self.sol['x'] if it else None)
@@ -1021,6 +1057,8 @@ class IntersectionBatch:
             out['precedence'] = self.prec.cpu().numpy().copy()
         if self._signals is not None:        # 0 free, 1 held at red, 2 held at amber, as the last step's signal stage left it
             out['held'] = self.held.cpu().numpy().copy()
+        if self._advice is not None:         # the speed advised to every agent in the last step, 0 = none
+            out['advised'] = self.advised.cpu().numpy().copy()
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
             js = self.junction_state.cpu().numpy()
             out['phase'], out['stage'], out['lights'] = js[:, 0].copy(), js[:, 1].copy(), self.lights.cpu().numpy().copy()

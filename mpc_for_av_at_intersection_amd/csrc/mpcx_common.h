@@ -197,6 +197,13 @@ int32_t mpcx_actuation_validate(mpcx_ctx *ctx, const mpcx_actuation *s, const mp
 int32_t mpcx_actuated_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
                               const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals,
                               const mpcx_actuation *actuation);
+// signal-aware approach speed (mpcx_advise.hip): "no advice" test, check of the struct against the run (the signals it draws on are
+// checked by mpcx_signals_validate), the launch alone (between the window stage and the QP)
+bool mpcx_advice_absent(const mpcx_advice *s);
+int32_t mpcx_advise_validate(mpcx_ctx *ctx, const mpcx_advice *s, const mpcx_signals *sg, bool actuated, bool speed, int32_t P);
+int32_t mpcx_advise_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const int32_t *path_off, const int32_t *path_len, const int32_t *traj_idx,
+                            const int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals, const mpcx_advice *advice,
+                            double *xref);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

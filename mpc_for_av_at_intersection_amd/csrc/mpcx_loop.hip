@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void pack_pool_kernel(PackArgs a) {
 struct LoopArgs {
     const mpcx_run_log *log; const mpcx_closed_loop_opts *opts; const mpcx_retire *retire; const mpcx_scene *scene; const mpcx_admit *admit;
     const mpcx_respawn *respawn; const mpcx_routes *routes; const mpcx_precedence *precedence; const mpcx_signals *signals;
-    const mpcx_actuation *actuation;
+    const mpcx_actuation *actuation; const mpcx_advice *advice;
 };
 
 // The optional stages of a run, checked (check_stages): a pointer is nullptr where the stage is off -- NULL and what the stage's own
@@ -84,10 +84,14 @@ struct LoopStages {
     // `actuated` is false): the cached graph's key takes it as it stands.
     mpcx_actuation actuation;
     bool actuated = false;
+    // signal-aware approach speed: advise_kernel between the window stage and the QP; needs signals under a fixed plan (no actuation) and
+    // MPCX_STOP_SPEED.  It caps row 2 of c->xref for an agent that would reach its stop line on red and writes advice->advised; the QP
+    // reads the capped window.  Signals allow one linearisation pass, so there is one window stage to follow.
+    const mpcx_advice *advice = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -97,7 +101,7 @@ struct LoopStages {
 struct LoopKey {
     mpcx_closed_loop desc;
     mpcx_run_log log; mpcx_closed_loop_opts opts; mpcx_retire retire; mpcx_scene scene; mpcx_admit admit; mpcx_respawn respawn;
-    mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation;
+    mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -176,10 +180,16 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     } else if (st->signals) {
         rc = mpcx_signals_validate(ctx, st->signals, c->exchange);
     }
+    if (rc != MPCX_OK) return rc;
+    if (!mpcx_advice_absent(a.advice)) {            // (the signals it draws on are checked above)
+        rc = mpcx_advise_validate(ctx, a.advice, st->signals, st->actuated, st->speed(), c->P);
+        if (rc == MPCX_OK) st->advice = a.advice;
+    }
     return rc;
 }
 
-// The middle of a step, the same on both paths: the conflict search (-> the signal stage) -> lin_passes x (reference window -> solve).
+// The middle of a step, the same on both paths: the conflict search (-> the signal stage) -> lin_passes x (reference window (-> the advice
+// stage) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
 static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopStages &st,
@@ -221,6 +231,10 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
         rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
                                  c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar, wx);
         if (rc != MPCX_OK) return rc;
+        if (st.advice) {
+            rc = mpcx_advise_enqueue(ctx, P, c->dl, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, st.advice, c->xref);
+            if (rc != MPCX_OK) return rc;
+        }
         // (further linearisation passes build their order in line, from the iteration counts of the pass before)
         const mpcx_qp_order ord{bins && first, c->iters, c->cut_len, ctx->prev_cut, queue_len};
         rc = mpcx_qp_enqueue(ctx, P, c->state, c->xref, c->xbar, c->reaches_end, c->u_sol, c->x_sol, c->u_sol, c->status, c->iters, c->kkt, ord);
@@ -416,6 +430,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.desc, c); key_put(key.ip, ip); key_put(key.mpc, &ctx->mpc);
     key_put(key.log, st.log); key_put(key.retire, st.retire); key_put(key.scene, st.scene); key_put(key.admit, st.admit);
     key_put(key.respawn, st.respawn); key_put(key.routes, st.routes); key_put(key.precedence, st.precedence); key_put(key.signals, st.signals);
+    key_put(key.advice, st.advice);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;
@@ -505,4 +520,11 @@ extern "C" int32_t mpcx_closed_loop_run_actuated(mpcx_ctx *ctx, const mpcx_inter
                                                  const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
                                                  const mpcx_actuation *actuation, int32_t n_steps, int32_t use_graph) {
     return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation}, n_steps, use_graph);
+}
+extern "C" int32_t mpcx_closed_loop_run_advised(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                                const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                                const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
+                                                const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
+                                                const mpcx_actuation *actuation, const mpcx_advice *advice, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation, advice}, n_steps, use_graph);
 }

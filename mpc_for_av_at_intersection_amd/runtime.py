@@ -630,7 +630,8 @@ class Context:
                         retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None,
                         admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None,
                         routes: Optional['_lib.RoutesC'] = None, precedence: Optional['_lib.PrecedenceC'] = None,
-                        signals: Optional['_lib.SignalsC'] = None, actuation: Optional['_lib.ActuationC'] = None):
+                        signals: Optional['_lib.SignalsC'] = None, actuation: Optional['_lib.ActuationC'] = None,
+                        advice: Optional['_lib.AdviceC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
@@ -648,12 +649,15 @@ class Context:
         signals: a _lib.SignalsC -- traffic signals: one more launch behind the conflict search holds agents at their stop lines
         (mpcx_closed_loop_run_signals; needs none of the others); None = no signals.
         actuation: a _lib.ActuationC -- vehicle-actuated signals: a controller per junction takes the place of the signals' fixed plan
-        (mpcx_closed_loop_run_actuated; refused without signals); None = the signals' own plan."""
+        (mpcx_closed_loop_run_actuated; refused without signals); None = the signals' own plan.
+        advice: a _lib.AdviceC -- signal-aware approach speed: one more launch between the window stage and the QP caps the speed reference
+        of an agent that would reach its stop line on red (mpcx_closed_loop_run_advised; refused without signals under a fixed plan, with
+        actuation and outside speed mode); None = no advice."""
         ref = lambda s: None if s is None else C.byref(s)
         # (the widest entry point: NULL is "none" for every stage, and the narrower ones are that call with NULLs)
-        self._chk(self.lib.mpcx_closed_loop_run_actuated(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
-                                                         ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals), ref(actuation),
-                                                         int(n_steps), 1 if graph else 0))
+        self._chk(self.lib.mpcx_closed_loop_run_advised(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
+                                                        ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals), ref(actuation),
+                                                        ref(advice), int(n_steps), 1 if graph else 0))
 
     @_ordered
     def signal_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', done=None):
@@ -683,6 +687,22 @@ class Context:
             self._want(done, torch.int32, (Pn,), 'done')
         self._chk(self.lib.mpcx_actuated_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
                                                     _ptr(cut_len), _ptr(done), C.byref(signals), C.byref(actuation)))
+
+    @_ordered
+    def advise_step(self, dl: float, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', advice: '_lib.AdviceC', xref, done=None):
+        """mpcx_advise_step_batch: ONE step's advice stage as the closed loop enqueues it between the window stage and the QP, in speed mode.
+        xref (P, 4, T + 1 float64: the window stage's output of this step) has row 2 of every advised agent capped in place, and the
+        struct's advised is written; traj_idx and cut_len (P int32) as the signal stage left them; done: the retirement words or None."""
+        if self.params is None:
+            raise MpcxError('advise_step: set_mpc_params has not been called (the stage sizes the window from the horizon)')
+        Pn = int(xref.shape[0])
+        self._want(xref, torch.float64, (Pn, 4, self.params.T + 1), 'xref')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('cut_len', cut_len)):
+            self._want(t, torch.int32, (Pn,), name)
+        if done is not None:
+            self._want(done, torch.int32, (Pn,), 'done')
+        self._chk(self.lib.mpcx_advise_step_batch(self._ctx, Pn, float(dl), _ptr(path_off), _ptr(path_len), _ptr(traj_idx), _ptr(cut_len),
+                                                  _ptr(done), C.byref(signals), C.byref(advice), _ptr(xref)))
 
     @_ordered
     def admit_step(self, ip: InteractionParams, state, obs_off, obs_cnt, obs_skip, done, absent, admit: '_lib.AdmitC', actors=None,
