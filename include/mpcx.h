@@ -24,6 +24,8 @@
  *     mpcx_closed_loop_run_routes; mpcx_episode_summary reduces the episode table per instance and route.  Holding agents at the stop
  *     lines of a signalised crossing is mpcx_signals, mpcx_closed_loop_run_signals; lights that follow the demand are mpcx_actuation,
  *     mpcx_closed_loop_run_actuated; a speed advised ahead of a red light of a fixed plan is mpcx_advice, mpcx_closed_loop_run_advised.
+ *     Connected agents, seen by the others on their last MPC solution instead of on their last controls, are mpcx_intent,
+ *     mpcx_closed_loop_run_intent.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -379,7 +381,7 @@ typedef struct {
 int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
                              int32_t n_steps, int32_t use_graph);
 /* Step fusion (on by default).  A run of n steps without a graph on the local pool -- no scripted traffic, one linearisation pass, none of
- * the run log, retirement, scene, admission, respawn, routes, precedence, signals, actuation or advice -- enqueues ONE launch per step for what
+ * the run log, retirement, scene, admission, respawn, routes, precedence, signals, actuation, advice or shared plans -- enqueues ONE launch per step for what
  * belongs to an agent alone: the plant update of the step before, the pack and prediction of its pool row and its warm-start rollout
  * (head_kernel); the run ends with the last step's plant update in a launch of its own.  Every buffer holds the same bits when the call
  * returns.  on = 0: the launch sequence without fusion (the rollout on the side stream beside the conflict search), for every run. */
@@ -909,6 +911,51 @@ int32_t mpcx_closed_loop_run_advised(mpcx_ctx *ctx, const mpcx_interaction_param
 int32_t mpcx_advise_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const int32_t *path_off /*P*/, const int32_t *path_len /*P*/,
                                const int32_t *traj_idx /*P*/, const int32_t *cut_len /*P*/, const int32_t *done /*P or NULL*/,
                                const mpcx_signals *signals, const mpcx_advice *advice, double *xref /*P,4,T+1*/);
+
+/* ---- shared plans: a connected agent is predicted from its last MPC solution.  The prediction stage is the reference's
+ * MovingObstaclesPrediction: the controls applied in the last step, held for pred_steps frames -- right for a scripted car, which has no
+ * plan, wrong for an MPC agent, whose plan of one step ago (u_sol, still resident when the prediction runs) already holds its braking in
+ * front of a cut path, a stop line or an advised speed.  One launch per step (intent_kernel, csrc/mpcx_intent.hip; the rule is
+ * csrc/mpcx_intent_core.h) between the prediction and the conflict search overwrites the frames of a sharing agent's OWN pool row
+ * r = obs_skip[q] with its plan re-rolled through the prediction's model, and touches no other row.
+ * For agent q: row r is left as the prediction stage wrote it and frames[q] = 0 if share[q] == 0; done[q] != 0; absent[r] != 0;
+ * status[q] != MPCX_QP_OPTIMAL (the plant applied max_decel and zeroed the warm start: the constant prediction is then the truth).
+ * Otherwise, from (x, y, v, yaw) = state[q], frame k = 0 .. pred_steps - 1 takes acc = u_sol[q][0][j], steer = u_sol[q][1][j],
+ * j = min(k + 1, T - 1) (column 0 was applied in the step just taken; beyond the plan the last column is held), and the prediction's
+ * updates in its order: x += (v cos yaw) dt; y += (v sin yaw) dt; v += acc dt; yaw += ((v / L) tan steer) dt (v is not clamped); then
+ * the two disc centres of the pose; frames[q] = pred_steps.  Bit for bit on the device: a plan whose columns j >= 1 all equal the
+ * applied controls, and any plan with T = 1, leave the prediction stage's own frames.
+ * intent = NULL or an all-zero struct: mpcx_closed_loop_run_advised itself -- the same launches with the same arguments.  No other struct
+ * changes size; the cached graph's key covers the struct by value.  A run with the stage on does not take step fusion.  MPCX_E_INVALID
+ * ("intent: ...") before anything is launched, whatever n_steps is: share or frames NULL; n_rows != P; no pool or no obs_skip; an
+ * obs_skip[q] outside the pool (read back once); exchange == MPCX_SHARD_AGENTS (the other ranks' rows arrive without their plans).
+ * The struct has no padding: two int32 close its 24 bytes. */
+typedef struct {
+    const int32_t *share;        /* n_rows = P, caller-owned: nonzero = agent q shares its plan */
+    int32_t *frames;             /* n_rows = P, caller-owned, out: frames of agent q's row taken from its plan in the last step (pred_steps or 0) */
+    int32_t n_rows;              /* P */
+    int32_t reserved;            /* 0 */
+} mpcx_intent;
+/* the widest entry point: mpcx_closed_loop_run_advised with the shared-plans stage */
+int32_t mpcx_closed_loop_run_intent(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                    const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                    const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                    const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                    const mpcx_routes *routes /*or NULL*/, const mpcx_precedence *precedence /*or NULL*/,
+                                    const mpcx_signals *signals /*or NULL*/, const mpcx_actuation *actuation /*or NULL*/,
+                                    const mpcx_advice *advice /*or NULL*/, const mpcx_intent *intent /*or NULL*/, int32_t n_steps,
+                                    int32_t use_graph);
+/* mpcx_interaction_batch with the shared-plans stage between its prediction and its conflict search: u_sol (P x 2 x T, T the context's
+ * horizon) and status (P) are the previous solve's; done (P) and absent (n_obs_pool) may be NULL and are read by the stage alone.  The
+ * struct is checked as above (an all-zero or NULL struct is refused here: the call exists for the stage); obs_skip is required. */
+int32_t mpcx_interaction_batch_intent(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P,
+                                      const double *state /*P,4*/, const double *path_xyyaw, const double *path_cs,
+                                      const int32_t *path_off /*P*/, const int32_t *path_len /*P*/, const int32_t *prev_cut_len /*P or NULL*/,
+                                      int32_t n_obs_pool, const double *obs6 /*NOBS,6*/, const int32_t *obs_off /*P*/,
+                                      const int32_t *obs_cnt /*P*/, const int32_t *obs_skip /*P*/,
+                                      int32_t *traj_idx /*P in-out*/, int32_t *hit_idx /*P*/, double *hit_xy /*P,2*/, int32_t *cut_len /*P*/,
+                                      const double *u_sol /*P,2,T*/, const int32_t *status /*P*/, const int32_t *done /*P or NULL*/,
+                                      const int32_t *absent /*NOBS or NULL*/, const mpcx_intent *intent);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

@@ -120,6 +120,12 @@ class AdviceC(C.Structure):
                 ('n_rows', C.c_int32)]
 
 
+class IntentC(C.Structure):
+    """mirror of mpcx_intent (include/mpcx.h): shared plans; share (n_rows = P int32, nonzero = the agent shares its plan) and frames
+    (n_rows int32, out) are device addresses"""
+    _fields_ = [('share', C.c_void_p), ('frames', C.c_void_p), ('n_rows', C.c_int32), ('reserved', C.c_int32)]
+
+
 SIGNAL_GROUPS_MAX = 16                          # MPCX_SIGNAL_GROUPS_MAX
 ACTUATION_PHASES_MAX = 8                        # MPCX_ACTUATION_PHASES_MAX
 STAGE_GREEN, STAGE_AMBER, STAGE_ALL_RED = 0, 1, 2       # mpcx_actuation.jstate[j][1]
@@ -199,7 +205,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
            'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence',
            'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
-           'mpcx_closed_loop_run_actuated', 'mpcx_actuated_step_batch', 'mpcx_closed_loop_run_advised', 'mpcx_advise_step_batch']
+           'mpcx_closed_loop_run_actuated', 'mpcx_actuated_step_batch', 'mpcx_closed_loop_run_advised', 'mpcx_advise_step_batch',
+           'mpcx_closed_loop_run_intent', 'mpcx_interaction_batch_intent']
 
 
 def load():
@@ -327,5 +334,13 @@ def load():
                                                  C.POINTER(ActuationC), C.POINTER(AdviceC), i32, i32]
     lib.mpcx_advise_step_batch.restype = i32
     lib.mpcx_advise_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(AdviceC), vp]
+    lib.mpcx_closed_loop_run_intent.restype = i32
+    lib.mpcx_closed_loop_run_intent.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
+                                                C.POINTER(ActuationC), C.POINTER(AdviceC), C.POINTER(IntentC), i32, i32]
+    lib.mpcx_interaction_batch_intent.restype = i32
+    lib.mpcx_interaction_batch_intent.argtypes = ([vp, C.POINTER(InteractionParamsC), i32] + [vp] * 6 + [i32] + [vp] * 8 + [vp] * 4 +
+                                                  [C.POINTER(IntentC)])
     _lib = lib
     return lib

@@ -359,6 +359,9 @@ class IntersectionBatch:
         self._actuation = None
         self.advised: Optional[torch.Tensor] = None          # advise_speed(): float64 (P,), the speed advised in the last step, 0 = none
         self._advice = None
+        self.share: Optional[torch.Tensor] = None            # share_plans(): int32 (P,), nonzero = the agent shares its plan
+        self.shared_frames: Optional[torch.Tensor] = None    # ... int32 (P,), frames of the agent's row taken from its plan in the last step
+        self._intent = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -732,6 +735,36 @@ class IntersectionBatch:
         self._advice = None
         self._desc = None
 
+    def share_plans(self, share=None):
+        """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
+        it applied in the last step, held for pred_steps frames -- the reference's prediction of a scripted car.  A sharing agent is seen
+        on the plan it solved one step ago instead (its braking in front of a cut path, a stop line or an advised speed is in there): one
+        more launch between the prediction and the conflict search re-rolls that plan into the agent's own pool row.  share: None = every
+        agent; else a bool or int array of P, nonzero = the agent shares (mixed fleets).  An agent whose last solve failed, that is retired
+        or whose row is out of the scene is predicted as ever.  Allocates `shared_frames` (zero) and drops the cached descriptor;
+        keep_plans_private() switches it off."""
+        if callable(self.exchange) or self.exchange == 'rccl':
+            raise MpcxError('share_plans: not with an agent-sharded exchange (the other ranks\' rows arrive without their plans)')
+        if share is None:
+            flags = np.ones(self.P, np.int32)
+        else:
+            flags = np.asarray(share)
+            if flags.shape != (self.P,) or flags.dtype.kind not in 'biu':
+                raise ValueError('share_plans: share must be a bool or int array of P = %d, got shape %s dtype %s' % (self.P, flags.shape, flags.dtype))
+            flags = (flags != 0).astype(np.int32)
+        dev = self.ctx.device
+        self.share = torch.from_numpy(np.ascontiguousarray(flags)).to(dev)
+        self.shared_frames = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        self._intent = _lib.IntentC(self.share.data_ptr(), self.shared_frames.data_ptr(), self.P, 0)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def keep_plans_private(self):
+        """switch the shared plans off and nothing else: the batch enqueues exactly the launches of one that never shared (`shared_frames`
+        keeps what it holds and is no longer written)"""
+        self._intent = None
+        self._desc = None
+
     def actuate(self, controllers, ctrl_of=None, stop=None, group=None, brake: Optional[float] = None):
         """VEHICLE-ACTUATED SIGNALS (mpcx_closed_loop_run_actuated).  Every instance is a junction (n_per = A) with a controller on the
         device: the launch that holds agents at their stop lines first reduces, over the junction's agents, which signal groups have a car
@@ -943,6 +976,8 @@ class IntersectionBatch:
         if self._retire is not None and self.lin_passes > 1:
             raise MpcxError('retirement at the goal with lin_passes = %d: the later linearisation passes build their work queue without '
                             'the retired mask (MPCX_E_INVALID); keep_driving() or lin_passes = 1' % self.lin_passes)
+        if self._intent is not None and (callable(self.exchange) or self.exchange == 'rccl'):
+            raise MpcxError('shared plans with an agent-sharded exchange: the other ranks\' rows arrive without their plans; keep_plans_private()')
         if callable(self.exchange):          # rehearsal exchange (torch.distributed): the host moves the rows between stages
             if self._retire is not None:
                 raise MpcxError('retirement at the goal%s with a callable exchange: it steps through step_staged(), whose per-stage entry '
@@ -959,7 +994,8 @@ class IntersectionBatch:
         self._claim_context()
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
                                  retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes,
-                                 precedence=self._precedence, signals=self._signals, actuation=self._actuation, advice=self._advice)
+                                 precedence=self._precedence, signals=self._signals, actuation=self._actuation, advice=self._advice,
+                                 intent=self._intent)
         self.steps_done += n_steps
 
     def step(self):
@@ -980,6 +1016,8 @@ class IntersectionBatch:
         if self._retire is not None:
             raise MpcxError('step_staged() with retirement at the goal%s: the per-stage entry points have no retired mask; run() or keep_driving()'
                             % (' and admission' if self._admit is not None else ''))
+        if self._intent is not None and self.obs_local is not None:
+            raise MpcxError('step_staged() with shared plans in the agent-sharded layout: the other ranks\' rows arrive without their plans')
         c = self.ctx
         self._claim_context()
         # what MovingObstacle*.get() would return for every agent: (x, y, v, yaw, a, steer)
@@ -1005,7 +1043,7 @@ class IntersectionBatch:
         speed = self.stop_mode == 'speed'
         c.interaction(self.ip, self.state, self.path, self.path_cs, self.path_off, self.path_len,
                       self.prev_len if speed else self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self.obs_skip,
-                      self.traj_idx, out=self.inter)
+                      self.traj_idx, out=self.inter, intent=self._intent, u_sol=self.sol['u'], status=self.sol['status'])
         if self._actuation is not None:     # the actuated signal stage, in the place of the signal stage
             c.actuated_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._actuation)
         elif self._signals is not None:     # the signal stage: between the conflict search and the window stage, as in the loop
@@ -1059,6 +1097,8 @@ class IntersectionBatch:
             out['held'] = self.held.cpu().numpy().copy()
         if self._advice is not None:         # the speed advised to every agent in the last step, 0 = none
             out['advised'] = self.advised.cpu().numpy().copy()
+        if self._intent is not None:         # frames of every agent's own row taken from its plan in the last step (pred_steps or 0)
+            out['shared_frames'] = self.shared_frames.cpu().numpy().copy()
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
             js = self.junction_state.cpu().numpy()
             out['phase'], out['stage'], out['lights'] = js[:, 0].copy(), js[:, 1].copy(), self.lights.cpu().numpy().copy()

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1272] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1296] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -59,6 +59,14 @@ struct mpcx_ctx {
 
 // The stages of a step.  Each is the whole of the C entry point of the same name (checks included) plus one struct of what only
 // mpcx_closed_loop_run passes: default-constructed = the stand-alone call.
+// what the shared-plans launch reads beside the conflict search's own arguments (state, obs_skip, the pool and its prediction)
+struct mpcx_intent_launch {
+    const double *u_sol = nullptr;      // P x 2 x T, the previous step's solution
+    const int32_t *status = nullptr;    // P, of that solution
+    const int32_t *done = nullptr;      // P or nullptr
+    const int32_t *absent = nullptr;    // pool rows or nullptr
+    mpcx_intent in = {};
+};
 struct mpcx_interaction_extras {
     // local pool: the prediction kernel packs the pool rows from the agents' states and applied inputs itself (no launch of its own)
     const double *pack_state = nullptr, *pack_applied = nullptr;
@@ -83,6 +91,9 @@ struct mpcx_interaction_extras {
     // predicted row's standing record, and an agent sees the present rows whose word is larger than its own row's through that record
     const int32_t *prec = nullptr;
     double *stand = nullptr;
+    // shared plans (mpcx_intent.hip; nullptr: off): one more launch between the prediction and the conflict search re-rolls the plans of the
+    // sharing agents into their own pool rows
+    const mpcx_intent_launch *intent = nullptr;
 };
 struct mpcx_window_extras {
     bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
@@ -204,6 +215,12 @@ int32_t mpcx_advise_validate(mpcx_ctx *ctx, const mpcx_advice *s, const mpcx_sig
 int32_t mpcx_advise_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const int32_t *path_off, const int32_t *path_len, const int32_t *traj_idx,
                             const int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals, const mpcx_advice *advice,
                             double *xref);
+// shared plans (mpcx_intent.hip): "no sharing" test, check of the struct against the run (reads obs_skip back), the launch alone (between
+// the prediction and the conflict search, inside mpcx_interaction_enqueue)
+bool mpcx_intent_absent(const mpcx_intent *s);
+int32_t mpcx_intent_validate(mpcx_ctx *ctx, const mpcx_intent *s, int32_t P, int32_t exchange, int32_t pool_rows, const int32_t *obs_skip);
+int32_t mpcx_intent_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const int32_t *obs_skip,
+                            int32_t n_obs_pool, const mpcx_intent_launch &x);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -129,6 +129,10 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
                           nullptr, nullptr, 0, x.absent, x.stand};
         mpcx::launch_predict(false, n_obs_pool, ctx->stream, pa, x);
     }
+    if (x.intent) {     // shared plans: the sharing agents' own rows are re-rolled from their plans before anybody searches them
+        const int32_t rc = mpcx_intent_enqueue(ctx, ip, P, state, obs_skip, n_obs_pool, *x.intent);
+        if (rc != MPCX_OK) return rc;
+    }
     // capacity (mpcx_interaction_capacity): the LDS that holds the cumulative lengths of max_rem path points later holds the ego discs of
     // max_rem / 4 - 32 resampled poses and the runs' boxes.
     // The kernel hides its memory latency with resident wavefronts (17 -> 11 blocks per CU costs 36 %), so the LDS follows the

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void pack_pool_kernel(PackArgs a) {
 struct LoopArgs {
     const mpcx_run_log *log; const mpcx_closed_loop_opts *opts; const mpcx_retire *retire; const mpcx_scene *scene; const mpcx_admit *admit;
     const mpcx_respawn *respawn; const mpcx_routes *routes; const mpcx_precedence *precedence; const mpcx_signals *signals;
-    const mpcx_actuation *actuation; const mpcx_advice *advice;
+    const mpcx_actuation *actuation; const mpcx_advice *advice; const mpcx_intent *intent;
 };
 
 // The optional stages of a run, checked (check_stages): a pointer is nullptr where the stage is off -- NULL and what the stage's own
@@ -88,10 +88,14 @@ struct LoopStages {
     // MPCX_STOP_SPEED.  It caps row 2 of c->xref for an agent that would reach its stop line on red and writes advice->advised; the QP
     // reads the capped window.  Signals allow one linearisation pass, so there is one window stage to follow.
     const mpcx_advice *advice = nullptr;
+    // shared plans: intent_kernel between the prediction and the conflict search (inside mpcx_interaction_enqueue); needs the local pool and
+    // obs_skip.  It overwrites the predicted frames of a sharing agent's own pool row with its plan of the step before (c->u_sol, which no
+    // stage has touched yet) re-rolled through the prediction's model, and writes intent->frames.  Never with step fusion: none() is false.
+    const mpcx_intent *intent = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -101,7 +105,7 @@ struct LoopStages {
 struct LoopKey {
     mpcx_closed_loop desc;
     mpcx_run_log log; mpcx_closed_loop_opts opts; mpcx_retire retire; mpcx_scene scene; mpcx_admit admit; mpcx_respawn respawn;
-    mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice;
+    mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice; mpcx_intent intent;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -184,6 +188,12 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (!mpcx_advice_absent(a.advice)) {            // (the signals it draws on are checked above)
         rc = mpcx_advise_validate(ctx, a.advice, st->signals, st->actuated, st->speed(), c->P);
         if (rc == MPCX_OK) st->advice = a.advice;
+    }
+    if (rc != MPCX_OK) return rc;
+    if (!mpcx_intent_absent(a.intent)) {
+        const int32_t rows = c->n_actors > 0 ? c->pool_rows : c->P;
+        rc = mpcx_intent_validate(ctx, a.intent, c->P, c->exchange, c->obs6 ? rows : 0, c->obs_skip);
+        if (rc == MPCX_OK) st->intent = a.intent;
     }
     return rc;
 }
@@ -271,6 +281,12 @@ static int32_t enqueue_step(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     rc = mpcx_rollout_fork(ctx, P, c->state, c->u_sol, c->xbar, st.done());
     if (rc != MPCX_OK) return rc;
     mpcx_interaction_extras ix;
+    mpcx_intent_launch plans;
+    if (st.intent) {        // the previous step's solution and its status, as they stand at the head of this step
+        plans.u_sol = c->u_sol; plans.status = c->status; plans.done = st.done(); plans.absent = st.scene ? st.scene->absent : nullptr;
+        plans.in = *st.intent;
+        ix.intent = &plans;
+    }
     if (c->exchange == MPCX_SHARD_AGENTS) {
         // agent-sharded layout: this rank's rows travel to every rank, every rank assembles the whole pool (one RCCL all-gather)
         mpcx::PackArgs pa{P, c->state, c->applied, c->obs_local};
@@ -430,7 +446,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.desc, c); key_put(key.ip, ip); key_put(key.mpc, &ctx->mpc);
     key_put(key.log, st.log); key_put(key.retire, st.retire); key_put(key.scene, st.scene); key_put(key.admit, st.admit);
     key_put(key.respawn, st.respawn); key_put(key.routes, st.routes); key_put(key.precedence, st.precedence); key_put(key.signals, st.signals);
-    key_put(key.advice, st.advice);
+    key_put(key.advice, st.advice); key_put(key.intent, st.intent);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;
@@ -527,4 +543,12 @@ extern "C" int32_t mpcx_closed_loop_run_advised(mpcx_ctx *ctx, const mpcx_intera
                                                 const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
                                                 const mpcx_actuation *actuation, const mpcx_advice *advice, int32_t n_steps, int32_t use_graph) {
     return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation, advice}, n_steps, use_graph);
+}
+extern "C" int32_t mpcx_closed_loop_run_intent(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                               const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                               const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
+                                               const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
+                                               const mpcx_actuation *actuation, const mpcx_advice *advice, const mpcx_intent *intent,
+                                               int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation, advice, intent}, n_steps, use_graph);
 }

@@ -535,8 +535,12 @@ class Context:
 
     @_ordered
     def interaction(self, ip: InteractionParams, state, path, path_cs, path_off, path_len, prev_cut_len,
-                    obs6, obs_off, obs_cnt, obs_skip, traj_idx, out=None):
-        """mpcx_interaction_batch. traj_idx updated in place. Returns dict(hit_idx, hit_xy, cut_len)."""
+                    obs6, obs_off, obs_cnt, obs_skip, traj_idx, out=None, intent: Optional['_lib.IntentC'] = None, u_sol=None, status=None,
+                    done=None, absent=None):
+        """mpcx_interaction_batch. traj_idx updated in place. Returns dict(hit_idx, hit_xy, cut_len).
+        intent: a _lib.IntentC -- mpcx_interaction_batch_intent: the shared-plans stage runs between the prediction and the conflict search
+        on u_sol (P, 2, T float64) and status (P int32) of the previous solve; done (P int32) and absent (pool rows int32) are read by that
+        stage alone and may be None."""
         Pn = state.shape[0]
         i32 = torch.int32
         self._want(state, torch.float64, (Pn, 4), 'state')
@@ -553,6 +557,21 @@ class Context:
                        hit_xy=torch.empty((Pn, 2), dtype=torch.float64, device=self.device),
                        cut_len=torch.empty(Pn, dtype=i32, device=self.device))
         cip = ip.to_c()
+        if intent is not None:
+            if u_sol is None or status is None:
+                raise MpcxError('interaction: intent needs u_sol and status (the previous solve)')
+            self._want(u_sol, torch.float64, None if self.params is None else (Pn, 2, self.params.T), 'u_sol')
+            self._want(status, i32, (Pn,), 'status')
+            if done is not None:
+                self._want(done, i32, (Pn,), 'done')
+            if absent is not None:
+                self._want(absent, i32, (nobs,), 'absent')
+            self._chk(self.lib.mpcx_interaction_batch_intent(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(path), _ptr(path_cs),
+                                                             _ptr(path_off), _ptr(path_len), _ptr(prev_cut_len), nobs, _ptr(obs6),
+                                                             _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip), _ptr(traj_idx),
+                                                             _ptr(out['hit_idx']), _ptr(out['hit_xy']), _ptr(out['cut_len']),
+                                                             _ptr(u_sol), _ptr(status), _ptr(done), _ptr(absent), C.byref(intent)))
+            return out
         self._chk(self.lib.mpcx_interaction_batch(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(path), _ptr(path_cs),
                                                   _ptr(path_off), _ptr(path_len), _ptr(prev_cut_len), nobs, _ptr(obs6),
                                                   _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip), _ptr(traj_idx),
@@ -631,7 +650,7 @@ class Context:
                         admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None,
                         routes: Optional['_lib.RoutesC'] = None, precedence: Optional['_lib.PrecedenceC'] = None,
                         signals: Optional['_lib.SignalsC'] = None, actuation: Optional['_lib.ActuationC'] = None,
-                        advice: Optional['_lib.AdviceC'] = None):
+                        advice: Optional['_lib.AdviceC'] = None, intent: Optional['_lib.IntentC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
@@ -652,12 +671,15 @@ class Context:
         (mpcx_closed_loop_run_actuated; refused without signals); None = the signals' own plan.
         advice: a _lib.AdviceC -- signal-aware approach speed: one more launch between the window stage and the QP caps the speed reference
         of an agent that would reach its stop line on red (mpcx_closed_loop_run_advised; refused without signals under a fixed plan, with
-        actuation and outside speed mode); None = no advice."""
+        actuation and outside speed mode); None = no advice.
+        intent: a _lib.IntentC -- shared plans: one more launch between the prediction and the conflict search predicts a sharing agent from
+        its last MPC solution instead of its last controls (mpcx_closed_loop_run_intent; refused in the agent-sharded layout); None = every
+        agent is predicted from its last controls."""
         ref = lambda s: None if s is None else C.byref(s)
         # (the widest entry point: NULL is "none" for every stage, and the narrower ones are that call with NULLs)
-        self._chk(self.lib.mpcx_closed_loop_run_advised(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
-                                                        ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals), ref(actuation),
-                                                        ref(advice), int(n_steps), 1 if graph else 0))
+        self._chk(self.lib.mpcx_closed_loop_run_intent(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
+                                                       ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals), ref(actuation),
+                                                       ref(advice), ref(intent), int(n_steps), 1 if graph else 0))
 
     @_ordered
     def signal_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', done=None):
