@@ -25,7 +25,8 @@
  *     lines of a signalised crossing is mpcx_signals, mpcx_closed_loop_run_signals; lights that follow the demand are mpcx_actuation,
  *     mpcx_closed_loop_run_actuated; a speed advised ahead of a red light of a fixed plan is mpcx_advice, mpcx_closed_loop_run_advised.
  *     Connected agents, seen by the others on their last MPC solution instead of on their last controls, are mpcx_intent,
- *     mpcx_closed_loop_run_intent.
+ *     mpcx_closed_loop_run_intent.  An unsignalised crossing whose manager admits only compatible movements is mpcx_reservation,
+ *     mpcx_closed_loop_run_reserved.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -381,7 +382,7 @@ typedef struct {
 int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
                              int32_t n_steps, int32_t use_graph);
 /* Step fusion (on by default).  A run of n steps without a graph on the local pool -- no scripted traffic, one linearisation pass, none of
- * the run log, retirement, scene, admission, respawn, routes, precedence, signals, actuation, advice or shared plans -- enqueues ONE launch per step for what
+ * the run log, retirement, scene, admission, respawn, routes, precedence, signals, actuation, advice, shared plans or reservations -- enqueues ONE launch per step for what
  * belongs to an agent alone: the plant update of the step before, the pack and prediction of its pool row and its warm-start rollout
  * (head_kernel); the run ends with the last step's plant update in a launch of its own.  Every buffer holds the same bits when the call
  * returns.  on = 0: the launch sequence without fusion (the rollout on the side stream beside the conflict search), for every run. */
@@ -956,6 +957,73 @@ int32_t mpcx_interaction_batch_intent(mpcx_ctx *ctx, const mpcx_interaction_para
                                       int32_t *traj_idx /*P in-out*/, int32_t *hit_idx /*P*/, double *hit_xy /*P,2*/, int32_t *cut_len /*P*/,
                                       const double *u_sol /*P,2,T*/, const int32_t *status /*P*/, const int32_t *done /*P or NULL*/,
                                       const int32_t *absent /*NOBS or NULL*/, const mpcx_intent *intent);
+
+/* ---- crossing reservations: a manager per junction admits only compatible movements.  Signals, fixed or actuated, separate PHASES and
+ * leave the turns inside a phase to the conflict search; an unsignalised crossing of connected vehicles is run by a manager that admits a
+ * car only if its MOVEMENT conflicts with no movement that holds the crossing, first come, first served, while the others wait at their
+ * stop lines.  One launch (reserve_kernel, csrc/mpcx_reserve.hip; the rule is csrc/mpcx_reserve_core.h) takes the place of signal_kernel /
+ * actuated_signal_kernel: a third source of "may I enter" beside the fixed plan and the controller; the hold at the line is the rule of
+ * mpcx_signals, word for word, with GREEN for an agent that holds a reservation and RED for one that does not.  No amber.
+ * The movement of an agent is the signal group of its stop line (path_group).  A junction is n_per consecutive agents, n_per <= 64:
+ * junction j owns agents [j n_per, (j + 1) n_per), n_per n_junctions = P.  Tables: path_exit[n_points] the route-local index e at which a
+ * vehicle on this point has left the crossing, -1 if no crossing lies ahead or under the point; conflict[n_groups], bit h of word g set
+ * when movements g and h may not hold the crossing together (symmetric, no diagonal); lane[n_groups], bit h of word g set when they queue
+ * in the same approach lane (symmetric, bit g of word g set); mgr_time[n_mgr][2] = (detect in path points, patience in steps);
+ * mgr_of[n_junctions] the manager of junction j -- a table of managers runs a sweep as one batch.  State, caller-owned device memory:
+ * grant[P] in-out, zero-initialised (0, or 1 = the agent holds a reservation); since[P] in-out, initialised to -1 (the clock value of the
+ * agent's first request); clock[n_junctions] in-out, zero-initialised; occupied[n_junctions] out (the movements that hold the crossing);
+ * queued[n_junctions] out (the requesters denied this step).
+ * Per junction and step: (1) t = clock[j], a negative word counts as 0; clock[j] = t + 1.  A junction whose mgr_of is out of range has no
+ * manager: its agents are free (held = 0), grant, since and clock are left alone, occupied = queued = 0.  (2) every agent q, with ti =
+ * traj_idx[q] as this step's conflict search left it, i = path_off[q] + ti, s = path_stop[i], g = path_group[i], e = path_exit[i]: OUT
+ * (grant = 0, since = -1) if done[q] != 0, i outside [0, n_points), e < 0, e > path_len[q], ti >= e, g outside [0, n_groups), or ti < s
+ * with s >= path_len[q]; INSIDE (grant = 1, it occupies g whatever grant was; since is left alone) if not OUT and (s < 0 or ti >= s);
+ * otherwise APPROACH: with grant != 0 it occupies g (a grant is never revoked; grant and since are left alone), without one and with
+ * s - ti <= detect it REQUESTS, since = since >= 0 ? since : t, otherwise since = -1.  (3) occ = OR of 1 << g over the occupying agents.
+ * (4) the requesters in ascending order of (since, min(s - ti, 65535), index within the junction), from ahead = blocked = 0: a requester of
+ * movement g is granted (grant = 1, occ |= 1 << g) if (conflict[g] & (occ | blocked)) == 0 and (lane[g] & ahead) == 0; otherwise it is
+ * denied, ahead |= 1 << g, and if it is aged, (int64) t - since >= patience, also blocked |= 1 << g.  patience = 0 is strict first come,
+ * first served; a large patience lets later compatible cars pass a waiting one; any finite patience rules out starvation.  (5)
+ * occupied[j] = occ, queued[j] = the number denied.  (6) every agent goes through steps 2 - 5 of the signal rule: an APPROACH agent
+ * without a grant, requesting or not, gets held = 1 and cut_len = min(cut_len, s); everybody else is free.
+ * In MPCX_STOP_SPEED the soft stop can roll a held car over its line; it then counts as INSIDE and occupies its movement.
+ * With reservations mpcx_signals supplies path_stop, path_group, held, brake, n_points and n_groups; its plan_cycle, plan_amber,
+ * plan_green, plan_of and tick must be NULL and n_plans 0.  reservation = NULL or an all-zero struct: mpcx_closed_loop_run_intent itself
+ * -- the same launches with the same arguments.  No other struct changes size; the cached graph's key covers the struct by value (it has
+ * no padding: four int32 close its 96 bytes).  MPCX_E_INVALID ("reservation: ...") before anything is launched, whatever n_steps is: a
+ * NULL pointer or a nonzero reserved word; reservations without signals, with a fixed plan, with actuation or with advice; n_per outside
+ * 1..64 or n_per n_junctions != P; n_mgr < 1, detect < 1 or patience < 0; conflict not symmetric, with a diagonal bit or with bits at or
+ * above n_groups; lane without its own bit, not symmetric or with bits at or above n_groups (conflict, lane and mgr_time are read back
+ * once per call; the per-agent, per-junction and per-point words are not -- a bad word is data, never a GPU fault); the signals' own
+ * refusals of n_groups, n_points and brake; the agent-sharded layout; more than one linearisation pass. */
+#define MPCX_RESERVE_PER_MAX 64
+typedef struct {
+    const int32_t *path_exit;    /* n_points: route-local index at which a vehicle on this point has left the crossing, -1 = none */
+    const int32_t *conflict;     /* n_groups: bit h of word g = movements g and h may not hold the crossing together */
+    const int32_t *lane;         /* n_groups: bit h of word g = movements g and h queue in the same approach lane */
+    const int32_t *mgr_time;     /* n_mgr x 2: (detect in path points, patience in steps) */
+    const int32_t *mgr_of;       /* n_junctions: the manager of junction j */
+    int32_t *grant;              /* P, caller-owned, in-out, zero-initialised: 1 = the agent holds a reservation */
+    int32_t *since;              /* P, caller-owned, in-out, initialised to -1: the clock value of the agent's first request */
+    int32_t *clock;              /* n_junctions, caller-owned, in-out, zero-initialised */
+    int32_t *occupied;           /* n_junctions, out: the mask of movements that hold the crossing */
+    int32_t *queued;             /* n_junctions, out: the number of requesters denied this step */
+    int32_t n_per, n_junctions, n_mgr, reserved;     /* reserved: 0 */
+} mpcx_reservation;
+/* the widest entry point: mpcx_closed_loop_run_intent with the reservation stage */
+int32_t mpcx_closed_loop_run_reserved(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *cl,
+                                      const mpcx_run_log *log /*or NULL*/, const mpcx_closed_loop_opts *opts /*or NULL*/,
+                                      const mpcx_retire *retire /*or NULL*/, const mpcx_scene *scene /*or NULL*/,
+                                      const mpcx_admit *admit /*or NULL*/, const mpcx_respawn *respawn /*or NULL*/,
+                                      const mpcx_routes *routes /*or NULL*/, const mpcx_precedence *precedence /*or NULL*/,
+                                      const mpcx_signals *signals /*or NULL*/, const mpcx_actuation *actuation /*or NULL*/,
+                                      const mpcx_advice *advice /*or NULL*/, const mpcx_intent *intent /*or NULL*/,
+                                      const mpcx_reservation *reservation /*or NULL*/, int32_t n_steps, int32_t use_graph);
+/* one step's reservation stage alone (what mpcx_closed_loop_run_reserved enqueues between the conflict search and the window stage); the
+ * arguments of mpcx_signal_step_batch plus the reservation.  Both structs are checked as above. */
+int32_t mpcx_reserve_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
+                                const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
+                                const int32_t *done /*P or NULL*/, const mpcx_signals *signals, const mpcx_reservation *reservation);
 
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes

@@ -126,7 +126,17 @@ class IntentC(C.Structure):
     _fields_ = [('share', C.c_void_p), ('frames', C.c_void_p), ('n_rows', C.c_int32), ('reserved', C.c_int32)]
 
 
+class ReservationC(C.Structure):
+    """mirror of mpcx_reservation (include/mpcx.h): crossing reservations; every pointer is a device address -- path_exit (n_points int32),
+    conflict / lane (n_groups int32), mgr_time (n_mgr x 2 int32), mgr_of / clock / occupied / queued (n_junctions int32), grant / since
+    (P int32)"""
+    _fields_ = [('path_exit', C.c_void_p), ('conflict', C.c_void_p), ('lane', C.c_void_p), ('mgr_time', C.c_void_p), ('mgr_of', C.c_void_p),
+                ('grant', C.c_void_p), ('since', C.c_void_p), ('clock', C.c_void_p), ('occupied', C.c_void_p), ('queued', C.c_void_p),
+                ('n_per', C.c_int32), ('n_junctions', C.c_int32), ('n_mgr', C.c_int32), ('reserved', C.c_int32)]
+
+
 SIGNAL_GROUPS_MAX = 16                          # MPCX_SIGNAL_GROUPS_MAX
+RESERVE_PER_MAX = 64                            # MPCX_RESERVE_PER_MAX: agents per junction under reservations
 ACTUATION_PHASES_MAX = 8                        # MPCX_ACTUATION_PHASES_MAX
 STAGE_GREEN, STAGE_AMBER, STAGE_ALL_RED = 0, 1, 2       # mpcx_actuation.jstate[j][1]
 LIGHT_GREEN, LIGHT_AMBER, LIGHT_RED = 0, 1, 2   # MPCX_SIGNAL_*: two bits per group in mpcx_actuation.lights
@@ -206,7 +216,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence',
            'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
            'mpcx_closed_loop_run_actuated', 'mpcx_actuated_step_batch', 'mpcx_closed_loop_run_advised', 'mpcx_advise_step_batch',
-           'mpcx_closed_loop_run_intent', 'mpcx_interaction_batch_intent']
+           'mpcx_closed_loop_run_intent', 'mpcx_interaction_batch_intent', 'mpcx_closed_loop_run_reserved', 'mpcx_reserve_step_batch']
 
 
 def load():
@@ -342,5 +352,13 @@ def load():
     lib.mpcx_interaction_batch_intent.restype = i32
     lib.mpcx_interaction_batch_intent.argtypes = ([vp, C.POINTER(InteractionParamsC), i32] + [vp] * 6 + [i32] + [vp] * 8 + [vp] * 4 +
                                                   [C.POINTER(IntentC)])
+    lib.mpcx_closed_loop_run_reserved.restype = i32
+    lib.mpcx_closed_loop_run_reserved.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
+                                                  C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
+                                                  C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
+                                                  C.POINTER(ActuationC), C.POINTER(AdviceC), C.POINTER(IntentC), C.POINTER(ReservationC),
+                                                  i32, i32]
+    lib.mpcx_reserve_step_batch.restype = i32
+    lib.mpcx_reserve_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(ReservationC)]
     _lib = lib
     return lib

@@ -39,6 +39,9 @@ phases nobody calls (two_phase_controller()); the launch takes the place of the 
 `advise_speed()` is SIGNAL-AWARE APPROACH SPEED for a signalised batch in speed mode: an agent that would reach its stop line on red at cruise
 speed gets the speed with which it reaches the line as the light turns green as a cap on its speed reference (one launch between the
 window stage and the QP); the hold stays the safety net behind it.
+`reserve(managers)` runs the crossing UNSIGNALISED BY RESERVATION: every instance is a junction with a manager on the device that admits a
+car only if its movement (movement_lines()) conflicts with no movement that holds the crossing (movement_conflicts()), first come, first
+served; everybody else waits at its stop line.  The launch takes the place of the signals', the hold at the line is the same.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -362,6 +365,12 @@ class IntersectionBatch:
         self.share: Optional[torch.Tensor] = None            # share_plans(): int32 (P,), nonzero = the agent shares its plan
         self.shared_frames: Optional[torch.Tensor] = None    # ... int32 (P,), frames of the agent's row taken from its plan in the last step
         self._intent = None
+        self.granted: Optional[torch.Tensor] = None          # reserve(): int32 (P,), 1 = the agent holds a reservation of the crossing
+        self.since: Optional[torch.Tensor] = None            # ... int32 (P,), the junction clock at the agent's first request, -1 = none
+        self.junction_clock: Optional[torch.Tensor] = None   # ... int32 (B,), every junction's clock
+        self.occupied: Optional[torch.Tensor] = None         # ... int32 (B,), the movements that held the crossing in the last step
+        self.queued: Optional[torch.Tensor] = None           # ... int32 (B,), the requesters denied in the last step
+        self._reservation = None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -706,6 +715,7 @@ class IntersectionBatch:
                                       tabs['plan_amber'].data_ptr(), tabs['plan_green'].data_ptr(), tabs['plan_of'].data_ptr(),
                                       self.tick.data_ptr(), self.held.data_ptr(), brake, n_points, len(plans), n_groups, 0)
         self._actuation = None              # (a fixed plan replaces a controller as the source of the lights)
+        self._reservation = None            # (... and a junction manager)
         self._desc = None
         c.synchronize()
 
@@ -832,6 +842,77 @@ class IntersectionBatch:
                                           tabs['ctrl_of'].data_ptr(), self.junction_state.data_ptr(), self.lights.data_ptr(),
                                           self.calls.data_ptr(), self.A, self.B, n_phases, len(controllers), 0)
         self._advice = None                 # (there is no plan left to look ahead into)
+        self._reservation = None            # (a controller replaces a junction manager as the source of the hold)
+        self._desc = None
+        c.synchronize()
+
+    def reserve(self, managers, manager_of=None, stop=None, group=None, exit=None, conflict=None, lane=None, brake: Optional[float] = None):
+        """CROSSING RESERVATIONS (mpcx_closed_loop_run_reserved).  Every instance is a junction (n_per = A <= 64) with a manager on the
+        device.  The movement of a car is the signal group of its stop line; a car within `detect` path points of its line requests the
+        crossing, and the launch that holds agents at their stop lines grants the requests in the order of their first request (ties: the
+        nearer car, then the lower agent index): a request is granted if its movement conflicts with no movement that holds the crossing --
+        a car inside it or one that holds a grant -- and no car of its own approach lane has just been denied in front of it.  A denied
+        request that has waited `patience` steps also blocks every later request that conflicts with it: patience 0 is strict first come,
+        first served, patience None (unbounded) lets every compatible car pass a waiting one.  A grant is never revoked; a car gives the
+        crossing back at its exit point.  The hold at the line is signalise()'s, which this call replaces as its source (and the reverse,
+        as with actuate()); advice is dropped.
+        managers: one dict(detect, patience) or a sequence of them; manager_of: the manager of every instance (B,), default 0 -- a sweep
+        runs as one batch.  stop, group, exit: the per-path-point tables (default: movement_lines() of the batch's routes); conflict, lane:
+        one bit mask per movement (default: movement_conflicts() of the batch's routes with the batch's disc model).  brake: unused by the
+        rule (there is no amber), default abs(MAX_DECEL).
+        Allocates `held`, `granted`, `queued`, `occupied`, `junction_clock` (zero), `since` (-1) and the tables and drops the cached
+        descriptor; unsignalise() switches it off."""
+        if isinstance(managers, dict):
+            managers = [managers]
+        managers = list(managers)
+        if not managers:
+            raise ValueError('reserve: at least one manager')
+        if not 1 <= self.A <= _lib.RESERVE_PER_MAX:
+            raise ValueError('reserve: a junction holds 1 .. %d agents, the batch has A = %d' % (_lib.RESERVE_PER_MAX, self.A))
+        big = int(np.iinfo(np.int32).max)
+        times = np.array([[int(m['detect']), big if m.get('patience') is None else int(m['patience'])] for m in managers], dtype=np.int64)
+        if (times[:, 0] < 1).any() or (times[:, 1] < 0).any() or (times > big).any():
+            raise ValueError('reserve: detect >= 1 path point, patience >= 0 steps or None, both int32')
+        n_points = int(self.path.shape[0])
+        routes = [self._route_table[self._route_offs[k]:self._route_offs[k + 1]] for k in range(len(self._route_offs) - 1)]
+        tabs3 = (stop, group, exit)
+        if any(t is None for t in tabs3):
+            if any(t is not None for t in tabs3):
+                raise ValueError('reserve: give stop, group and exit, or none of them')
+            stop, group, exit = movement_lines(routes)
+        stop, group, exit = np.asarray(stop), np.asarray(group), np.asarray(exit)
+        if stop.shape != (n_points,) or group.shape != (n_points,) or exit.shape != (n_points,):
+            raise ValueError('reserve: stop, group and exit hold one word per path point (%d)' % n_points)
+        if conflict is None or lane is None:
+            if conflict is not None or lane is not None:
+                raise ValueError('reserve: give both conflict and lane, or neither')
+            conflict, lane = movement_conflicts(routes, stop, exit, np.asarray(self.ip.circle_centers), float(self.ip.radius))
+        conflict, lane = np.asarray(conflict), np.asarray(lane)
+        n_groups = len(conflict)
+        if conflict.ndim != 1 or lane.shape != conflict.shape or not 1 <= n_groups <= _lib.SIGNAL_GROUPS_MAX:
+            raise ValueError('reserve: conflict and lane hold one word per movement, 1 .. %d movements' % _lib.SIGNAL_GROUPS_MAX)
+        if manager_of is None:
+            manager_of = np.zeros(self.B, dtype=np.int64)
+        manager_of = np.asarray(manager_of)
+        if not np.issubdtype(manager_of.dtype, np.integer) or manager_of.shape != (self.B,):
+            raise ValueError('reserve: manager_of is an integer array of shape (B,) = (%d,)' % self.B)
+        brake = abs(float(self.params.max_decel)) if brake is None else float(brake)
+        c = self.ctx
+        tabs = dict(path_stop=c.i32(stop), path_group=c.i32(group), path_exit=c.i32(exit), conflict=c.i32(conflict), lane=c.i32(lane),
+                    mgr_time=c.i32(times), mgr_of=c.i32(manager_of))
+        zeros = lambda n: torch.zeros(n, dtype=torch.int32, device=c.device)
+        self.held, self.granted = zeros(self.P), zeros(self.P)
+        self.since = torch.full((self.P,), -1, dtype=torch.int32, device=c.device)
+        self.junction_clock, self.occupied, self.queued = zeros(self.B), zeros(self.B), zeros(self.B)
+        self._signal_tabs = tabs
+        self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), None, None, None, None, None,
+                                      self.held.data_ptr(), brake, n_points, 0, n_groups, 0)
+        self._reservation = _lib.ReservationC(tabs['path_exit'].data_ptr(), tabs['conflict'].data_ptr(), tabs['lane'].data_ptr(),
+                                              tabs['mgr_time'].data_ptr(), tabs['mgr_of'].data_ptr(), self.granted.data_ptr(),
+                                              self.since.data_ptr(), self.junction_clock.data_ptr(), self.occupied.data_ptr(),
+                                              self.queued.data_ptr(), self.A, self.B, len(managers), 0)
+        self._actuation = None              # (a junction manager replaces a controller or a plan as the source of the hold)
+        self._advice = None                 # (there is no plan to look ahead into)
         self._desc = None
         c.synchronize()
 
@@ -840,6 +921,7 @@ class IntersectionBatch:
         (`tick`, `held` and the junction words keep what they hold and are no longer read or written)"""
         self._signals = None
         self._actuation = None
+        self._reservation = None
         self._advice = None                 # (advice looks ahead into the signals' plan)
         self._desc = None
 
@@ -995,7 +1077,7 @@ class IntersectionBatch:
         self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
                                  retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes,
                                  precedence=self._precedence, signals=self._signals, actuation=self._actuation, advice=self._advice,
-                                 intent=self._intent)
+                                 intent=self._intent, reservation=self._reservation)
         self.steps_done += n_steps
 
     def step(self):
@@ -1044,7 +1126,9 @@ class IntersectionBatch:
         c.interaction(self.ip, self.state, self.path, self.path_cs, self.path_off, self.path_len,
                       self.prev_len if speed else self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self.obs_skip,
                       self.traj_idx, out=self.inter, intent=self._intent, u_sol=self.sol['u'], status=self.sol['status'])
-        if self._actuation is not None:     # the actuated signal stage, in the place of the signal stage
+        if self._reservation is not None:   # the reservation stage, in the place of the signal stage
+            c.reserve_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._reservation)
+        elif self._actuation is not None:   # the actuated signal stage, in the place of the signal stage
             c.actuated_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._actuation)
         elif self._signals is not None:     # the signal stage: between the conflict search and the window stage, as in the loop
             c.signal_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals)
@@ -1102,6 +1186,9 @@ class IntersectionBatch:
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
             js = self.junction_state.cpu().numpy()
             out['phase'], out['stage'], out['lights'] = js[:, 0].copy(), js[:, 1].copy(), self.lights.cpu().numpy().copy()
+        if self._reservation is not None:    # per agent: its reservation and first request; per junction: the movements on the crossing
+            out['granted'], out['since'] = self.granted.cpu().numpy().copy(), self.since.cpu().numpy().copy()
+            out['occupied'] = self.occupied.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:
@@ -1145,6 +1232,86 @@ def stop_lines(routes, half_width: float = 12.0, setback: float = 6.0):
     if not stop:
         return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
     return np.concatenate(stop), np.concatenate(group)
+
+
+def _arm_of(x: float, y: float) -> int:
+    """the arm a point outside the crossing lies on: 0 south, 1 west, 2 north, 3 east (stop_lines()' signal groups)"""
+    return (0 if y < 0 else 2) if abs(y) >= abs(x) else (1 if x < 0 else 3)
+
+
+def _movement_of(r) -> int:
+    """the movement index 3 (arm - 1) + (turn - 1) of a route, -1 for a route that leaves on the arm it came from: the approach arm from its
+    first point, as in stop_lines(), the exit arm from its last; turn 1 / 2 / 3 = the exit arm is the next clockwise / the opposite one /
+    the next anticlockwise as seen from above (south -> west -> north -> east is clockwise)"""
+    arm, out = _arm_of(r[0, 0], r[0, 1]), _arm_of(r[-1, 0], r[-1, 1])
+    turn = (out - arm) % 4
+    return 3 * arm + turn - 1 if turn else -1
+
+
+def movement_lines(routes, half_width: float = 12.0, setback: float = 6.0, clear: float = 4.0):
+    """The three per-path-point tables of IntersectionBatch.reserve for `routes` (a list of (n, 3) paths, concatenated in order):
+    (path_stop, path_group, path_exit), int32, one word per path point.  path_stop is that of stop_lines().  The exit point of a route is
+    the first point at least `clear` metres of arc behind its last point inside the crossing square (the route's length if it ends before
+    that); path_exit of every point before it is its route-local index, -1 from it on (and everywhere on a route that never enters the
+    square or leaves on the arm it came from).  path_group of every point before the exit is the route's MOVEMENT, 3 (arm - 1) + (turn - 1)
+    with the approach arm as in stop_lines() and turn 1 / 2 / 3 = the exit arm, taken from the route's last point, is the next clockwise /
+    the opposite / the next anticlockwise one as seen from above -- the stock scenario's (start position, turn indicator) --, 0 elsewhere.
+    Pure numpy: no GPU, no state."""
+    stop, _ = stop_lines(routes, half_width, setback)
+    group, exits = [], []
+    for r in routes:
+        r = np.asarray(r, dtype=np.float64)
+        n = len(r)
+        gr, ex = np.zeros(n, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+        inside = np.flatnonzero(np.maximum(np.abs(r[:, 0]), np.abs(r[:, 1])) <= half_width) if n else np.zeros(0, dtype=np.int64)
+        mv = _movement_of(r) if n else -1
+        if len(inside) and mv >= 0:
+            arc = np.concatenate([[0.0], np.cumsum(np.hypot(np.diff(r[:, 0]), np.diff(r[:, 1])))])
+            ok = np.flatnonzero(arc >= arc[inside[-1]] + clear)
+            e = int(ok[0]) if len(ok) else n
+            ex[:e] = e
+            gr[:e] = mv
+        group.append(gr); exits.append(ex)
+    if not group:
+        return stop, np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+    return stop, np.concatenate(group), np.concatenate(exits)
+
+
+def movement_conflicts(routes, stop, exit, circle_centers, radius: float, margin: float = 1.0):
+    """The two movement tables of IntersectionBatch.reserve for `routes` with the tables of movement_lines(): (conflict, lane), int32, one
+    word per movement of a four-arm crossing (12).  Two movements of different arms conflict (bit h of conflict[g] and bit g of conflict[h])
+    if some disc centre of a route of the one, over its points [stop, exit) -- from its line, or its first point if it has none, to its
+    exit --, comes within 2 radius + margin of some disc centre of a route of the other.  Movements of the same arm share a lane (lane[g] =
+    the three movements of g's arm) and never conflict.  circle_centers: the discs' offsets along the vehicle's axis (2,), or (x, y)
+    offsets in the vehicle's frame (2, 2) as the interaction parameters hold them.  Pure numpy: no GPU, no state."""
+    cc = np.asarray(circle_centers, dtype=np.float64).reshape(-1)
+    cc = np.column_stack([cc, np.zeros_like(cc)]) if cc.size == 2 else cc.reshape(-1, 2)
+    stop, exit = np.asarray(stop), np.asarray(exit)
+    swept = {}
+    off = 0
+    for r in routes:
+        r = np.asarray(r, dtype=np.float64)
+        n = len(r)
+        mv = _movement_of(r) if n else -1
+        if n and mv >= 0 and exit[off] >= 0:
+            pts = r[max(int(stop[off]), 0):int(exit[off])]
+            cs, sn = np.cos(pts[:, 2]), np.sin(pts[:, 2])
+            discs = np.concatenate([np.column_stack([pts[:, 0] + ox * cs - oy * sn, pts[:, 1] + ox * sn + oy * cs]) for ox, oy in cc])
+            swept.setdefault(mv, []).append(discs)
+        off += n
+    conflict = np.zeros(12, dtype=np.int64)
+    lane = np.array([7 << 3 * (g // 3) for g in range(12)], dtype=np.int64)
+    reach = 2.0 * float(radius) + float(margin)
+    for g in swept:
+        for h in swept:
+            if g // 3 == h // 3 or h < g:
+                continue
+            a, b = np.concatenate(swept[g]), np.concatenate(swept[h])
+            d2 = ((a[:, None, :] - b[None, :, :]) ** 2).sum(axis=2)
+            if len(a) and len(b) and d2.min() <= reach * reach:
+                conflict[g] |= 1 << h
+                conflict[h] |= 1 << g
+    return conflict.astype(np.int32), lane.astype(np.int32)
 
 
 def two_phase_plan(cycle: int, green: int, amber: int) -> dict:

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1296] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1392] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
@@ -221,6 +221,14 @@ bool mpcx_intent_absent(const mpcx_intent *s);
 int32_t mpcx_intent_validate(mpcx_ctx *ctx, const mpcx_intent *s, int32_t P, int32_t exchange, int32_t pool_rows, const int32_t *obs_skip);
 int32_t mpcx_intent_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const int32_t *obs_skip,
                             int32_t n_obs_pool, const mpcx_intent_launch &x);
+// crossing reservations (mpcx_reserve.hip): "no reservations" test, check of both structs against the run (reads conflict, lane and mgr_time
+// back), the launch alone (in the place of mpcx_signal_enqueue / mpcx_actuated_enqueue)
+bool mpcx_reservation_absent(const mpcx_reservation *s);
+int32_t mpcx_reservation_validate(mpcx_ctx *ctx, const mpcx_reservation *s, const mpcx_signals *sg, int32_t P, int32_t exchange, bool actuated,
+                                  bool advised);
+int32_t mpcx_reserve_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
+                             const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals,
+                             const mpcx_reservation *reservation);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

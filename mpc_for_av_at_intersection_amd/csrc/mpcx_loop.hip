@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void pack_pool_kernel(PackArgs a) {
 struct LoopArgs {
     const mpcx_run_log *log; const mpcx_closed_loop_opts *opts; const mpcx_retire *retire; const mpcx_scene *scene; const mpcx_admit *admit;
     const mpcx_respawn *respawn; const mpcx_routes *routes; const mpcx_precedence *precedence; const mpcx_signals *signals;
-    const mpcx_actuation *actuation; const mpcx_advice *advice; const mpcx_intent *intent;
+    const mpcx_actuation *actuation; const mpcx_advice *advice; const mpcx_intent *intent; const mpcx_reservation *reservation;
 };
 
 // The optional stages of a run, checked (check_stages): a pointer is nullptr where the stage is off -- NULL and what the stage's own
@@ -92,10 +92,13 @@ struct LoopStages {
     // obs_skip.  It overwrites the predicted frames of a sharing agent's own pool row with its plan of the step before (c->u_sol, which no
     // stage has touched yet) re-rolled through the prediction's model, and writes intent->frames.  Never with step fusion: none() is false.
     const mpcx_intent *intent = nullptr;
+    // crossing reservations: reserve_kernel in signal_kernel's place; needs signals without a plan, and neither actuation nor advice.  A
+    // manager per junction admits an agent only if its movement conflicts with none that holds the crossing; the hold is signal_kernel's.
+    const mpcx_reservation *reserve = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -105,7 +108,7 @@ struct LoopStages {
 struct LoopKey {
     mpcx_closed_loop desc;
     mpcx_run_log log; mpcx_closed_loop_opts opts; mpcx_retire retire; mpcx_scene scene; mpcx_admit admit; mpcx_respawn respawn;
-    mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice; mpcx_intent intent;
+    mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice; mpcx_intent intent; mpcx_reservation reservation;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -172,7 +175,12 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (!mpcx_precedence_absent(a.precedence)) st->precedence = a.precedence;
     if (st->precedence && (rc = mpcx_precedence_validate(ctx, st->precedence, st->scene, st->admit)) != MPCX_OK) return rc;
     if (!mpcx_signals_absent(a.signals)) st->signals = a.signals;
-    if (!mpcx_actuation_absent(a.actuation)) {      // checks the signals it draws on too
+    if (!mpcx_reservation_absent(a.reservation)) {  // checks the signals it draws on too, and refuses a controller or advice beside it
+        rc = mpcx_reservation_validate(ctx, a.reservation, st->signals, c->P, c->exchange, !mpcx_actuation_absent(a.actuation),
+                                       !mpcx_advice_absent(a.advice));
+        if (rc != MPCX_OK) return rc;
+        st->reserve = a.reservation;
+    } else if (!mpcx_actuation_absent(a.actuation)) {      // checks the signals it draws on too
         rc = mpcx_actuation_validate(ctx, a.actuation, st->signals, c->P, c->exchange);
         if (rc != MPCX_OK) return rc;
         mpcx_actuation &act = st->actuation;
@@ -223,7 +231,8 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
                                           c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len, ix);
     if (rc != MPCX_OK) return rc;
     if (st.signals) {
-        rc = st.actuated ? mpcx_actuated_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, &st.actuation)
+        rc = st.reserve  ? mpcx_reserve_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, st.reserve)
+           : st.actuated ? mpcx_actuated_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, &st.actuation)
                          : mpcx_signal_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals);
         if (rc != MPCX_OK) return rc;
     }
@@ -446,7 +455,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.desc, c); key_put(key.ip, ip); key_put(key.mpc, &ctx->mpc);
     key_put(key.log, st.log); key_put(key.retire, st.retire); key_put(key.scene, st.scene); key_put(key.admit, st.admit);
     key_put(key.respawn, st.respawn); key_put(key.routes, st.routes); key_put(key.precedence, st.precedence); key_put(key.signals, st.signals);
-    key_put(key.advice, st.advice); key_put(key.intent, st.intent);
+    key_put(key.advice, st.advice); key_put(key.intent, st.intent); key_put(key.reservation, st.reserve);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;
@@ -551,4 +560,13 @@ extern "C" int32_t mpcx_closed_loop_run_intent(mpcx_ctx *ctx, const mpcx_interac
                                                const mpcx_actuation *actuation, const mpcx_advice *advice, const mpcx_intent *intent,
                                                int32_t n_steps, int32_t use_graph) {
     return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation, advice, intent}, n_steps, use_graph);
+}
+extern "C" int32_t mpcx_closed_loop_run_reserved(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c,
+                                                 const mpcx_run_log *log, const mpcx_closed_loop_opts *opts, const mpcx_retire *retire,
+                                                 const mpcx_scene *scene, const mpcx_admit *admit, const mpcx_respawn *respawn,
+                                                 const mpcx_routes *routes, const mpcx_precedence *precedence, const mpcx_signals *signals,
+                                                 const mpcx_actuation *actuation, const mpcx_advice *advice, const mpcx_intent *intent,
+                                                 const mpcx_reservation *reservation, int32_t n_steps, int32_t use_graph) {
+    return closed_loop_run(ctx, ip, c, {log, opts, retire, scene, admit, respawn, routes, precedence, signals, actuation, advice, intent, reservation},
+                           n_steps, use_graph);
 }

@@ -650,7 +650,8 @@ class Context:
                         admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None,
                         routes: Optional['_lib.RoutesC'] = None, precedence: Optional['_lib.PrecedenceC'] = None,
                         signals: Optional['_lib.SignalsC'] = None, actuation: Optional['_lib.ActuationC'] = None,
-                        advice: Optional['_lib.AdviceC'] = None, intent: Optional['_lib.IntentC'] = None):
+                        advice: Optional['_lib.AdviceC'] = None, intent: Optional['_lib.IntentC'] = None,
+                        reservation: Optional['_lib.ReservationC'] = None):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
         log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
         opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
@@ -674,12 +675,16 @@ class Context:
         actuation and outside speed mode); None = no advice.
         intent: a _lib.IntentC -- shared plans: one more launch between the prediction and the conflict search predicts a sharing agent from
         its last MPC solution instead of its last controls (mpcx_closed_loop_run_intent; refused in the agent-sharded layout); None = every
-        agent is predicted from its last controls."""
+        agent is predicted from its last controls.
+        reservation: a _lib.ReservationC -- crossing reservations: a manager per junction takes the place of the signals' fixed plan and
+        admits only compatible movements (mpcx_closed_loop_run_reserved; refused without signals, with a plan, actuation or advice); None =
+        no reservations."""
         ref = lambda s: None if s is None else C.byref(s)
         # (the widest entry point: NULL is "none" for every stage, and the narrower ones are that call with NULLs)
-        self._chk(self.lib.mpcx_closed_loop_run_intent(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire), ref(scene),
-                                                       ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals), ref(actuation),
-                                                       ref(advice), ref(intent), int(n_steps), 1 if graph else 0))
+        self._chk(self.lib.mpcx_closed_loop_run_reserved(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire),
+                                                         ref(scene), ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals),
+                                                         ref(actuation), ref(advice), ref(intent), ref(reservation), int(n_steps),
+                                                         1 if graph else 0))
 
     @_ordered
     def signal_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', done=None):
@@ -709,6 +714,21 @@ class Context:
             self._want(done, torch.int32, (Pn,), 'done')
         self._chk(self.lib.mpcx_actuated_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
                                                     _ptr(cut_len), _ptr(done), C.byref(signals), C.byref(actuation)))
+
+    @_ordered
+    def reserve_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', reservation: '_lib.ReservationC',
+                     done=None):
+        """mpcx_reserve_step_batch: ONE step's reservation stage as the closed loop enqueues it in the place of the signal stage.
+        cut_len (P int32) is updated in place, as are the signals' held and the reservation's grant, since, clock, occupied and queued; done:
+        the retirement words (P int32) or None."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('cut_len', cut_len)):
+            self._want(t, torch.int32, (Pn,), name)
+        if done is not None:
+            self._want(done, torch.int32, (Pn,), 'done')
+        self._chk(self.lib.mpcx_reserve_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
+                                                   _ptr(cut_len), _ptr(done), C.byref(signals), C.byref(reservation)))
 
     @_ordered
     def advise_step(self, dl: float, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', advice: '_lib.AdviceC', xref, done=None):
