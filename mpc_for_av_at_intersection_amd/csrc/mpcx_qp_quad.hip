@@ -17,6 +17,8 @@ struct GroupCx {
     static constexpr int LQ = LQ_, SPL = SPL_;
     static constexpr bool JERK = JERK_;       // the five-state problem of lib/mpc_jerk.py (mpcx_mpc_params.model)
     static_assert(LQ == 8, "groups of 8 lanes");
+    // a plain copy of the predictor's row pass (mpcx_qp_stage.h; DESIGN 4.1 has the counts and timings)
+    static constexpr int PLAIN_PASSES = mpcx_stage::PLAIN_C;
     int q, lane;
     lds_double *sh;                       // s [SPL*8][64], lam [SPL*8][64], gains [SPL*8][64], spare [2*SPL][64]
     // row_shl:1 / row_shr:1 = value of lane q+1 / q-1.

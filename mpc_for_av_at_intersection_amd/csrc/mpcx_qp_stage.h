@@ -22,6 +22,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 #include "mpcx.h"
 #include "mpcx_qp_consts.h"
 
@@ -41,6 +42,19 @@ namespace mpcx_stage {
 //   6: v_{t+1} <= vmax   7: -v_{t+1} <= -vmin
 enum { ROWS = 8 };
 
+// Plain rounds.  The row passes serve three kinds of round with one text: an ordinary iteration, the trial round and the polish
+// round; the flags that tell them apart cost selects on every row visit.  In a round in which NO lane of the wavefront is in a
+// trial or polish round those flags are constants (pa = false, ipm = true), and a policy may ask for a second copy of a row pass
+// compiled with them folded: Cx::PLAIN_PASSES is a mask of the passes that get one.  Both copies are the same text on the same
+// operands in the same order, and a copy is kept only if the compiler also groups its FMAs as in the generic text (checked on the
+// GPU, bit for bit), so a problem's numbers do not depend on the path its rounds took.  Only the predictor's row pass (C) has one:
+// the plain copies of pass A and of the corrector's pass (D) came out with other FMA groupings -- last bits moved -- and that of
+// the multiplier step raised the kernel's scratch (DESIGN 4.1 has every pass's numbers).  A policy without the member (the host
+// build) runs the generic text only.
+enum { PLAIN_C = 1 };
+template <class Cx, class = void> struct plain_passes : std::integral_constant<int, 0> {};
+template <class Cx> struct plain_passes<Cx, std::void_t<decltype(Cx::PLAIN_PASSES)>> : std::integral_constant<int, Cx::PLAIN_PASSES> {};
+
 struct Problem {            // one QP (pointers to that problem's rows of the batch arrays)
     const double *x0, *xref, *xbar, *u_warm;   // u_warm may be null
     const uint8_t *re;
@@ -52,6 +66,13 @@ template <class Cx, class Src>
 MPCX_HD void solve_queue(Cx &cx, Src &src) {
     constexpr int LQ = Cx::LQ, SPL = Cx::SPL;
     constexpr bool JERK = Cx::JERK;
+    constexpr int PASSES = plain_passes<Cx>::value;
+    // a row pass is a generic lambda over std::bool_constant<PLAIN>: this runs its plain copy if the policy asked for one and the
+    // round is plain (the same for every lane of the wavefront), the generic text otherwise
+    auto by_round = [](auto has_plain, bool plain_round, auto &&pass) {
+        if constexpr (decltype(has_plain)::value) { if (plain_round) pass(std::true_type{}); else pass(std::false_type{}); }
+        else pass(std::false_type{});
+    };
     const int q = cx.q;
     mpcx_mpc_params P = src.params();       // weights / limits may be replaced per problem by fetch(); T, dt, L never change
     int pbi = 0;                            // index of the group's problem: its pointers are rebuilt where they are needed (set-up, hand-in)
@@ -750,9 +771,14 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         prev_of(DA1, DAp);
         double al = 1.0, c1 = 0.0, c2 = 0.0;
         bool viol = false;              // trial / polish: the predictor's end point is no KKT point (a row violated, a multiplier negative)
-        const bool ipm = !(trial || polish);
-        const double veps = trial ? 0.0 : MPCX_POLISH_EPS_G;
+        // The round is plain from here to its end if no lane is in a trial or polish round now: the refill (trial) and the exit tests
+        // (polish, pinit) are behind us, and what the step sets (polish for the next round) is read by no pass of this round.
+        const bool plain_round = !cx.any(trial || polish || pinit);
         // per row, recomputed from (s, lam, u, x) wherever needed instead of being kept: rp = s + gap, d = lam / s
+        by_round(std::bool_constant<(PASSES & PLAIN_C) != 0>{}, plain_round, [&](auto plain) {
+        constexpr bool PLAIN = decltype(plain)::value;
+        const bool polish_r = !PLAIN && polish, ipm_r = PLAIN || !(trial || polish);
+        const double veps = trial ? 0.0 : MPCX_POLISH_EPS_G;
         MPCX_UNROLL
         for (int ls = 0; ls < SPL; ls++) {
             double sv[ROWS], lv[ROWS];
@@ -760,20 +786,22 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             MPCX_UNROLL
             for (int r = 0; r < ROWS; r++) {
                 const bool on = row_on(ls, r);
-                const bool pa = polish & (sv[r] < 0.0);
+                const bool pa = polish_r & (sv[r] < 0.0);
                 const double sa = fabs(sv[r]);
                 const double s = pa ? lv[r] * (1.0 / MPCX_POLISH_RHO) : sa;
-                const double l = (pa | (on & ipm)) ? lv[r] : 0.0;
+                const double l = (pa | (on & ipm_r)) ? lv[r] : 0.0;
                 const double gap = row_gap(ls, r, Dprev[ls]), dir = row_dir(r, DA0[ls], DA1[ls], DAp[ls], EA2[ls]);
                 const double rp = on ? s + gap : 0.0;
                 const double d = l * cx.rcp(s);
                 const double dsa = on ? -rp - dir : 0.0;
                 const double dla = -l - d * dsa;
                 // the end point of a trial / polish round: rows outside the active set must hold, the new multipliers of the rows inside it
-                // (lam + dla = lam + rho gap') must not be negative
-                const bool o_in = l + dla < -MPCX_POLISH_EPS_L, o_out = !(gap + dir <= veps);      // (both evaluated: no branch per row)
-                viol = viol | (pa & o_in) | (!pa & on & o_out);
-                (void)sa;
+                // (lam + dla = lam + rho gap') must not be negative.  A plain round has no such end point to check.
+                if constexpr (!PLAIN) {
+                    const bool o_in = l + dla < -MPCX_POLISH_EPS_L, o_out = !(gap + dir <= veps);      // (both evaluated: no branch per row)
+                    viol = viol | (pa & o_in) | (!pa & on & o_out);
+                }
+                (void)sa; (void)veps;
                 // ratio tests: any value <= the exact ratio is a valid step bound, the 0.001 margin of MPCX_STEP_FRACTION is 12 orders above rcp_fast's error
                 al = fmin(al, (on && dsa < 0.0) ? -s * cx.rcp_fast(dsa) : 1.0);
                 al = fmin(al, (on && dla < 0.0) ? -l * cx.rcp_fast(dla) : 1.0);
@@ -781,6 +809,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 c2 += dsa * dla;
             }
         }
+        });
         const double alpha_aff = cx.gmin(al);
         // A trial group goes through the rest of the round with its multipliers still taken as zero: the corrector's right-hand side is
         // then the predictor's, the second forward sweep repeats the first, and the ordinary step below -- at full length, if no row
