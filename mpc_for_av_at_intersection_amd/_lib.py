@@ -2,6 +2,7 @@
 missing or no GPU is usable the loaders below raise."""
 import ctypes as C
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPCX_LIB: developer override (another build of the same sources, such as the MPCX_INTER_FORCE_EXACT one); the product is libmpcx.so
@@ -203,20 +204,95 @@ COMM_ID_BYTES = 128
 SHARD_INSTANCES, SHARD_AGENTS = 1, 2
 
 
-EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mpcx_set_mpc_params',
-           'mpcx_qp_solve_batch', 'mpcx_mpc_prepare_batch', 'mpcx_search_model_create', 'mpcx_search_model_destroy',
-           'mpcx_expand_batch', 'mpcx_interaction_batch', 'mpcx_moving_collision_batch', 'mpcx_plant_step_batch',
-           'mpcx_transform_batch', 'mpcx_cutoff_index_batch', 'mpcx_predict_obstacles_batch', 'mpcx_selftest_wave_ops', 'mpcx_selftest_mfma',
-           'mpcx_closed_loop_run', 'mpcx_profile_qp', 'mpcx_profile_qp_read', 'mpcx_set_instance_tuning', 'mpcx_set_qp_solver', 'mpcx_qp_set_order_hint', 'mpcx_expand_multi_batch',
+class Stage(NamedTuple):
+    """one optional stage of the device closed loop, as the Python layer knows it"""
+    key: str                    # the keyword of Context.closed_loop_run, and IntersectionBatch's attribute `_<key>` (log: `log.c`)
+    struct: type                # the ctypes mirror of ...
+    c_name: str                 # ... this struct of include/mpcx.h
+    suffix: str                 # mpcx_closed_loop_run_<suffix>: the entry point that introduced it
+    doc: str                    # its paragraph of Context.closed_loop_run's docstring
+    dependents: tuple = ()      # the stages that live on it: switched off with it (direct ones; stage_dependents() takes the closure)
+    entry_dependents: tuple = ()    # ... and those that do so only while right of way is by order of entry (PRECEDENCE_ENTRY)
+
+
+# THE list of the loop's stages on the Python side, in the order of LoopArgs (csrc/mpcx_loop.hip) and of the entry points' parameters: the
+# prototypes of load(), the keywords of Context.closed_loop_run and what IntersectionBatch passes and tears down are all read from it
+STAGES = (
+    Stage('log', RunLogC, 'mpcx_run_log', 'logged',
+          'a _lib.RunLogC -- every step then ends with the run log\'s record stage (mpcx_closed_loop_run_logged).'),
+    Stage('opts', ClosedLoopOptsC, 'mpcx_closed_loop_opts', 'opts',
+          'a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.'),
+    Stage('retire', RetireC, 'mpcx_retire', 'retire',
+          'a _lib.RetireC -- agents are retired at their goal (mpcx_closed_loop_run_retire); None = they are driven on.', ('scene',)),
+    Stage('scene', SceneC, 'mpcx_scene', 'scene',
+          'a _lib.SceneC -- departure: pool rows with absent != 0 are out of the scene and an arrival sets the agent\'s own word '
+          '(mpcx_closed_loop_run_scene; refused without retire); None = arrived cars stay in the scene.', ('admit', 'precedence')),
+    Stage('admit', AdmitC, 'mpcx_admit', 'admit',
+          'a _lib.AdmitC -- admission: waiting agents enter on their schedule once their start pose is clear (mpcx_closed_loop_run_admit; '
+          'refused without scene); None = everybody is in from the start.', ('respawn',), ('precedence',)),
+    Stage('respawn', RespawnC, 'mpcx_respawn', 'respawn',
+          'a _lib.RespawnC -- respawn: an arrived agent\'s slot is reset for the next vehicle of its stream and handed back to the '
+          'admission gate (mpcx_closed_loop_run_respawn; refused without admit); None = a departed slot stays empty.', ('routes',)),
+    Stage('routes', RoutesC, 'mpcx_routes', 'routes',
+          'a _lib.RoutesC -- every vehicle of a slot takes its own route from its own start pose (mpcx_closed_loop_run_routes; refused '
+          'without respawn); None = a slot keeps its route.'),
+    Stage('precedence', PrecedenceC, 'mpcx_precedence', 'precedence',
+          'a _lib.PrecedenceC -- right of way: an agent sees the present rows whose word is larger than its own as standing cars '
+          '(mpcx_closed_loop_run_precedence; refused without scene, and in ENTRY mode without admit); None = everybody yields to everybody.'),
+    Stage('signals', SignalsC, 'mpcx_signals', 'signals',
+          'a _lib.SignalsC -- traffic signals: one more launch behind the conflict search holds agents at their stop lines '
+          '(mpcx_closed_loop_run_signals; needs none of the others); None = no signals.', ('actuation', 'reservation', 'advice')),
+    Stage('actuation', ActuationC, 'mpcx_actuation', 'actuated',
+          'a _lib.ActuationC -- vehicle-actuated signals: a controller per junction takes the place of the signals\' fixed plan '
+          '(mpcx_closed_loop_run_actuated; refused without signals); None = the signals\' own plan.'),
+    Stage('advice', AdviceC, 'mpcx_advice', 'advised',
+          'a _lib.AdviceC -- signal-aware approach speed: one more launch between the window stage and the QP caps the speed reference '
+          'of an agent that would reach its stop line on red (mpcx_closed_loop_run_advised; refused without signals under a fixed plan, with '
+          'actuation and outside speed mode); None = no advice.'),
+    Stage('intent', IntentC, 'mpcx_intent', 'intent',
+          'a _lib.IntentC -- shared plans: one more launch between the prediction and the conflict search predicts a sharing agent from '
+          'its last MPC solution instead of its last controls (mpcx_closed_loop_run_intent; refused in the agent-sharded layout); None = every '
+          'agent is predicted from its last controls.'),
+    Stage('reservation', ReservationC, 'mpcx_reservation', 'reserved',
+          'a _lib.ReservationC -- crossing reservations: a manager per junction takes the place of the signals\' fixed plan and '
+          'admits only compatible movements (mpcx_closed_loop_run_reserved; refused without signals, with a plan, actuation or advice); None = '
+          'no reservations.'),
+)
+STAGE_KEYS = tuple(st.key for st in STAGES)
+# rung k of the ladder takes the first k stages' structs; Context.closed_loop_run calls the last with NULL for what is off
+LOOP_ENTRY_POINTS = ['mpcx_closed_loop_run'] + ['mpcx_closed_loop_run_' + st.suffix for st in STAGES]
+
+
+def stage_dependents(key: str, entry_order: bool = False) -> set:
+    """every stage that is switched off with stage `key` (itself not included); entry_order: right of way is on in PRECEDENCE_ENTRY mode"""
+    st = STAGES[STAGE_KEYS.index(key)]
+    out = set()
+    for k in st.dependents + (st.entry_dependents if entry_order else ()):
+        out |= {k} | stage_dependents(k, entry_order)
+    return out
+
+
+def stage_structs(stages: dict) -> list:
+    """the keyword arguments of Context.closed_loop_run as the widest entry point takes them: one struct or None per stage, in order"""
+    unknown = sorted(set(stages) - set(STAGE_KEYS))
+    if unknown:
+        raise TypeError('closed_loop_run() got an unexpected keyword argument %s: the stages are %s'
+                        % (', '.join(map(repr, unknown)), ', '.join(STAGE_KEYS)))
+    return [stages.get(k) for k in STAGE_KEYS]
+
+
+EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mpcx_set_mpc_params', 'mpcx_qp_solve_batch',
+           'mpcx_mpc_prepare_batch', 'mpcx_search_model_create', 'mpcx_search_model_destroy', 'mpcx_expand_batch',
+           'mpcx_interaction_batch', 'mpcx_moving_collision_batch', 'mpcx_plant_step_batch', 'mpcx_transform_batch',
+           'mpcx_cutoff_index_batch', 'mpcx_predict_obstacles_batch', 'mpcx_selftest_wave_ops', 'mpcx_selftest_mfma', 'mpcx_profile_qp',
+           'mpcx_profile_qp_read', 'mpcx_set_instance_tuning', 'mpcx_set_qp_solver', 'mpcx_qp_set_order_hint', 'mpcx_expand_multi_batch',
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
-           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_set_step_fusion', 'mpcx_astar_batch', 'mpcx_traffic_step_batch',
-           'mpcx_record_step_batch', 'mpcx_closed_loop_run_logged', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
-           'mpcx_closed_loop_run_opts', 'mpcx_closed_loop_run_retire', 'mpcx_closed_loop_run_scene', 'mpcx_closed_loop_run_admit',
-           'mpcx_admit_step_batch', 'mpcx_closed_loop_run_respawn', 'mpcx_respawn_step_batch', 'mpcx_closed_loop_run_routes',
-           'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary', 'mpcx_closed_loop_run_precedence', 'mpcx_admit_step_batch_precedence',
-           'mpcx_closed_loop_run_signals', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
-           'mpcx_closed_loop_run_actuated', 'mpcx_actuated_step_batch', 'mpcx_closed_loop_run_advised', 'mpcx_advise_step_batch',
-           'mpcx_closed_loop_run_intent', 'mpcx_interaction_batch_intent', 'mpcx_closed_loop_run_reserved', 'mpcx_reserve_step_batch']
+           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_set_step_fusion', 'mpcx_astar_batch',
+           'mpcx_traffic_step_batch', 'mpcx_record_step_batch', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
+           'mpcx_admit_step_batch', 'mpcx_respawn_step_batch', 'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary',
+           'mpcx_admit_step_batch_precedence', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
+           'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
+           'mpcx_reserve_step_batch'] + LOOP_ENTRY_POINTS
 
 
 def load():
@@ -261,8 +337,10 @@ def load():
     lib.mpcx_predict_obstacles_batch.argtypes = [vp, i32, i32, C.c_double, C.c_double, vp, vp]
     lib.mpcx_selftest_wave_ops.restype = i32; lib.mpcx_selftest_wave_ops.argtypes = [vp, vp, vp]
     lib.mpcx_selftest_mfma.restype = i32; lib.mpcx_selftest_mfma.argtypes = [vp, vp, vp, vp]
-    lib.mpcx_closed_loop_run.restype = i32
-    lib.mpcx_closed_loop_run.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), i32, i32]
+    for k, name in enumerate(LOOP_ENTRY_POINTS):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC)] + [C.POINTER(st.struct) for st in STAGES[:k]] + [i32, i32]
     lib.mpcx_profile_qp.restype = i32; lib.mpcx_profile_qp.argtypes = [vp, i32]
     lib.mpcx_profile_qp_read.restype = i32
     lib.mpcx_profile_qp_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
@@ -280,84 +358,33 @@ def load():
     lib.mpcx_traffic_step_batch.restype = i32; lib.mpcx_traffic_step_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int64, vp, i32, vp]
     lib.mpcx_record_step_batch.restype = i32
     lib.mpcx_record_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 12 + [i32] + [vp] * 4 + [C.POINTER(RunLogC)]
-    lib.mpcx_closed_loop_run_logged.restype = i32
-    lib.mpcx_closed_loop_run_logged.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC), i32, i32]
     lib.mpcx_mpc_prepare_batch_stop.restype = i32
     lib.mpcx_mpc_prepare_batch_stop.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp, C.c_int64, vp, C.c_double, vp, vp, vp, vp]
     lib.mpcx_record_step_batch_goal.restype = i32
     lib.mpcx_record_step_batch_goal.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 12 + [i32] + [vp] * 5 + [C.POINTER(RunLogC)]
-    lib.mpcx_closed_loop_run_opts.restype = i32
-    lib.mpcx_closed_loop_run_opts.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                              C.POINTER(ClosedLoopOptsC), i32, i32]
-    lib.mpcx_closed_loop_run_retire.restype = i32
-    lib.mpcx_closed_loop_run_retire.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), i32, i32]
-    lib.mpcx_closed_loop_run_scene.restype = i32
-    lib.mpcx_closed_loop_run_scene.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                               C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), i32, i32]
-    lib.mpcx_closed_loop_run_admit.restype = i32
-    lib.mpcx_closed_loop_run_admit.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                               C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC), i32, i32]
     lib.mpcx_admit_step_batch.restype = i32
     lib.mpcx_admit_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, C.c_int64, vp,
                                           C.POINTER(AdmitC)]
-    lib.mpcx_closed_loop_run_respawn.restype = i32
-    lib.mpcx_closed_loop_run_respawn.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                 C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                 C.POINTER(RespawnC), i32, i32]
     lib.mpcx_respawn_step_batch.restype = i32
     lib.mpcx_respawn_step_batch.argtypes = [vp, i32] + [vp] * 9 + [i32, C.POINTER(RunLogC), C.POINTER(RetireC), C.POINTER(AdmitC),
                                                                    C.POINTER(RespawnC)]
-    lib.mpcx_closed_loop_run_routes.restype = i32
-    lib.mpcx_closed_loop_run_routes.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                C.POINTER(RespawnC), C.POINTER(RoutesC), i32, i32]
     lib.mpcx_respawn_step_batch_routes.restype = i32
     lib.mpcx_respawn_step_batch_routes.argtypes = [vp, i32] + [vp] * 9 + [i32, C.POINTER(RunLogC), C.POINTER(RetireC), C.POINTER(AdmitC),
                                                                           C.POINTER(RespawnC), C.POINTER(RoutesC), i32]
     lib.mpcx_episode_summary.restype = i32
     lib.mpcx_episode_summary.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.mpcx_closed_loop_run_precedence.restype = i32
-    lib.mpcx_closed_loop_run_precedence.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                    C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                    C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), i32, i32]
     lib.mpcx_admit_step_batch_precedence.restype = i32
     lib.mpcx_admit_step_batch_precedence.argtypes = [vp, C.POINTER(InteractionParamsC), i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp,
                                                      C.c_int64, vp, C.POINTER(AdmitC), C.POINTER(PrecedenceC)]
-    lib.mpcx_closed_loop_run_signals.restype = i32
-    lib.mpcx_closed_loop_run_signals.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                 C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                 C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC), i32, i32]
     lib.mpcx_signal_step_batch.restype = i32
     lib.mpcx_signal_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC)]
-    lib.mpcx_closed_loop_run_actuated.restype = i32
-    lib.mpcx_closed_loop_run_actuated.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                  C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                  C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
-                                                  C.POINTER(ActuationC), i32, i32]
     lib.mpcx_actuated_step_batch.restype = i32
     lib.mpcx_actuated_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(ActuationC)]
-    lib.mpcx_closed_loop_run_advised.restype = i32
-    lib.mpcx_closed_loop_run_advised.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                 C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                 C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
-                                                 C.POINTER(ActuationC), C.POINTER(AdviceC), i32, i32]
     lib.mpcx_advise_step_batch.restype = i32
     lib.mpcx_advise_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(AdviceC), vp]
-    lib.mpcx_closed_loop_run_intent.restype = i32
-    lib.mpcx_closed_loop_run_intent.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
-                                                C.POINTER(ActuationC), C.POINTER(AdviceC), C.POINTER(IntentC), i32, i32]
     lib.mpcx_interaction_batch_intent.restype = i32
     lib.mpcx_interaction_batch_intent.argtypes = ([vp, C.POINTER(InteractionParamsC), i32] + [vp] * 6 + [i32] + [vp] * 8 + [vp] * 4 +
                                                   [C.POINTER(IntentC)])
-    lib.mpcx_closed_loop_run_reserved.restype = i32
-    lib.mpcx_closed_loop_run_reserved.argtypes = [vp, C.POINTER(InteractionParamsC), C.POINTER(ClosedLoopC), C.POINTER(RunLogC),
-                                                  C.POINTER(ClosedLoopOptsC), C.POINTER(RetireC), C.POINTER(SceneC), C.POINTER(AdmitC),
-                                                  C.POINTER(RespawnC), C.POINTER(RoutesC), C.POINTER(PrecedenceC), C.POINTER(SignalsC),
-                                                  C.POINTER(ActuationC), C.POINTER(AdviceC), C.POINTER(IntentC), C.POINTER(ReservationC),
-                                                  i32, i32]
     lib.mpcx_reserve_step_batch.restype = i32
     lib.mpcx_reserve_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(ReservationC)]
     _lib = lib

@@ -59,6 +59,13 @@ RUN_LOG_MAX_BYTES = 1 << 30     # attach_log refuses a larger log unless told ot
 EPISODE_DTYPE = np.dtype([(n, '<i4') for n in ('slot', 'generation', 'due', 'entered', 'arrived', 'steps_driven', 'delay')] + [('contact', '?'),
                          ('min_clearance', '<f8'), ('row_begin', '<i4'), ('row_end', '<i4')])
 MOVEMENT_DTYPE = np.dtype([(n, '<i8') for n in _lib.SUMMARY_I64] + [('min_clearance', '<f8')])
+# IntersectionBatch.snapshot(): stage -> (key, attribute) of the device words it adds while the stage is on.  precedence: the word of every
+# pool row; held: 0 free, 1 at red, 2 at amber; advised: the speed advised in the last step, 0 = none; shared_frames: frames of the agent's
+# own row taken from its plan in the last step; granted, since: per agent; occupied: per junction, the movements on the crossing
+_SNAPSHOT_WORDS = {'retire': (('done', 'done'), ('steps_driven', 'steps_driven')), 'scene': (('absent', 'absent'),),
+                   'admit': (('wait', 'wait'), ('entered_step', 'entered_step')), 'respawn': (('served', 'served'),),
+                   'precedence': (('precedence', 'prec'),), 'signals': (('held', 'held'),), 'advice': (('advised', 'advised'),),
+                   'intent': (('shared_frames', 'shared_frames'),), 'reservation': (('granted', 'granted'), ('since', 'since'), ('occupied', 'occupied'))}
 
 
 class RunLog:
@@ -401,6 +408,18 @@ class IntersectionBatch:
         self._desc = None
         return log
 
+    def _stage_structs(self) -> dict:
+        """the struct of every stage of _lib.STAGES as the batch stands, None = off: the keywords of Context.closed_loop_run"""
+        return {k: (None if self.log is None else self.log.c) if k == 'log' else getattr(self, '_' + k) for k in _lib.STAGE_KEYS}
+
+    def _off(self, *stages):
+        """switch the named stages off, and with each the stages that live on it (_lib.stage_dependents); drops the cached descriptor"""
+        entry = self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY
+        for k in stages:
+            for d in {k} | _lib.stage_dependents(k, entry):
+                setattr(self, '_' + d, None)
+        self._desc = None
+
     def _goal_now(self, goal_dis: float, stop_speed: float) -> np.ndarray:
         """mpc.is_goal (lib/mpc.py:310-326) on the host for every agent as the batch stands: the test at the top of the reference's next
         loop iteration (RunLog.reset() makes the same one for goal_step = 0).  Before the first step only a path of fewer than 5 points
@@ -448,18 +467,14 @@ class IntersectionBatch:
         if there.any():
             self.applied[torch.as_tensor(there, device=self.ctx.device)] = 0.0
         self._retire = _lib.RetireC(self.done.data_ptr(), self.steps_driven.data_ptr(), goal_dis, stop_speed)
-        self.absent, self._scene = None, None
-        self._admit = None                  # (admission lives on a scene: enter_on_schedule() after this call)
-        self._respawn = None                # (... and respawn on admission)
-        self._routes = None
-        self._precedence = None             # (right of way lives on a scene too: give_way() after this call)
+        self.absent = None
+        self._off('scene')                  # (... and what lives on it: enter_on_schedule(), give_way() after this call)
         if leave_scene:
             rows = int(self.obs6.shape[0])
             self.absent = torch.zeros(rows, dtype=torch.int32, device=self.ctx.device)
             if there.any():
                 self.absent[self.obs_skip.long()[torch.as_tensor(there, device=self.ctx.device)]] = 1
             self._scene = _lib.SceneC(self.absent.data_ptr(), rows, 0)
-        self._desc = None
         self.ctx.synchronize()
 
     def keep_driving(self):
@@ -468,13 +483,7 @@ class IntersectionBatch:
         scene goes with it: every car, departed or hidden, is visible again from the next step on (`absent` keeps what it holds and is
         no longer read).  Admission goes with it too: agents still waiting are driven from where they stand, from the next step on -- and
         respawn with admission: no slot is reset any more"""
-        self._retire = None
-        self._scene = None
-        self._admit = None
-        self._respawn = None
-        self._routes = None
-        self._precedence = None             # (right of way lives on the scene)
-        self._desc = None
+        self._off('retire')
 
     def enter_on_schedule(self, wait, gap: float = 0.0):
         """ADMISSION (mpcx_closed_loop_run_admit), the counterpart of departure: agent q with wait[q] >= 0 is taken out of the scene now
@@ -507,21 +516,14 @@ class IntersectionBatch:
         self.clock = torch.zeros(1, dtype=torch.int32, device=self.ctx.device)
         self.scheduled_step = np.maximum(w, 0)
         self._admit = _lib.AdmitC(self.wait.data_ptr(), self.entered_step.data_ptr(), self.clock.data_ptr(), 0, gap)
-        self._respawn = None                # (a new schedule and a new clock: respawn_on_schedule() sets both up itself)
-        self._routes = None
-        self._desc = None
+        self._off('respawn')                # (a new schedule and a new clock: respawn_on_schedule() sets both up itself)
         self.ctx.synchronize()
 
     def enter_now(self):
         """switch admission off and nothing else: the batch enqueues exactly the launches of one that never had it.  Agents still waiting
         stay outside the scene (retired, their rows absent); `wait`, `entered_step` and `clock` keep what they hold.  Respawn lives on admission
         and is switched off with it, and routing with respawn"""
-        self._admit = None
-        self._respawn = None
-        self._routes = None
-        if self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY:
-            self._precedence = None         # (the order of entry is admission's: give_way(order=<array>) keeps a fixed order)
-        self._desc = None
+        self._off('admit')                  # (the order of entry is admission's: give_way(order=<array>) keeps a fixed order)
 
     def respawn_on_schedule(self, due, gap: float = 0.0, route=None, start_index=None):
         """RESPAWN (mpcx_closed_loop_run_respawn): every slot (agent index q) serves a stream of G vehicles, all on the slot's route from the
@@ -660,8 +662,40 @@ class IntersectionBatch:
     def yield_to_everyone(self):
         """switch right of way off and nothing else: the batch enqueues exactly the launches of one that never had it, and every agent
         yields to every other again (`prec` keeps what it holds and is no longer read)"""
-        self._precedence = None
-        self._desc = None
+        self._off('precedence')
+
+    def _route_list(self) -> list:
+        return [self._route_table[self._route_offs[k]:self._route_offs[k + 1]] for k in range(len(self._route_offs) - 1)]
+
+    def _line_tables(self, who: str, tabs: tuple, default) -> tuple:
+        """the per-path-point tables of signalise / actuate (stop, group) and reserve (stop, group, exit): the caller's, all of them or
+        none -- then default(the batch's routes) --, one word per path point"""
+        names = ('stop and group', 'both stop and group, or neither') if len(tabs) == 2 else ('stop, group and exit', 'stop, group and exit, or none of them')
+        if any(t is None for t in tabs):
+            if any(t is not None for t in tabs):
+                raise ValueError('%s: give %s' % (who, names[1]))
+            tabs = default(self._route_list())
+        tabs = tuple(np.asarray(t) for t in tabs)
+        n_points = int(self.path.shape[0])
+        if any(t.shape != (n_points,) for t in tabs):
+            raise ValueError('%s: %s hold one word per path point (%d)' % (who, names[0], n_points))
+        return tabs
+
+    def _per_instance(self, who: str, name: str, v) -> np.ndarray:
+        """the controller (actuate) or manager (reserve) of every instance: an integer array (B,), default 0"""
+        v = np.zeros(self.B, dtype=np.int64) if v is None else np.asarray(v)
+        if not np.issubdtype(v.dtype, np.integer) or v.shape != (self.B,):
+            raise ValueError('%s: %s is an integer array of shape (B,) = (%d,)' % (who, name, self.B))
+        return v
+
+    def _brake(self, brake: Optional[float]) -> float:
+        return abs(float(self.params.max_decel)) if brake is None else float(brake)
+
+    def _planless_signals(self, tabs: dict, brake: float, n_groups: int):
+        """the signals struct of actuate / reserve: the stop lines and the hold, the lights come from the junction's own stage"""
+        self._signal_tabs = tabs
+        self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), None, None, None, None, None,
+                                      self.held.data_ptr(), brake, int(self.path.shape[0]), 0, n_groups, 0)
 
     def signalise(self, plans, plan_of=None, stop=None, group=None, offset=None, brake: Optional[float] = None):
         """TRAFFIC SIGNALS (mpcx_closed_loop_run_signals).  One more small launch behind the conflict search holds an agent at its stop
@@ -686,15 +720,7 @@ class IntersectionBatch:
         n_groups = int(green[0].shape[0])
         if not 1 <= n_groups <= _lib.SIGNAL_GROUPS_MAX:
             raise ValueError('signalise: %d signal groups, 1 .. %d' % (n_groups, _lib.SIGNAL_GROUPS_MAX))
-        n_points = int(self.path.shape[0])
-        if stop is None or group is None:
-            if stop is not None or group is not None:
-                raise ValueError('signalise: give both stop and group, or neither')
-            routes = [self._route_table[self._route_offs[k]:self._route_offs[k + 1]] for k in range(len(self._route_offs) - 1)]
-            stop, group = stop_lines(routes)
-        stop, group = np.asarray(stop), np.asarray(group)
-        if stop.shape != (n_points,) or group.shape != (n_points,):
-            raise ValueError('signalise: stop and group hold one word per path point (%d)' % n_points)
+        stop, group = self._line_tables('signalise', (stop, group), stop_lines)
 
         def per_agent(v, name, default):
             if v is None:
@@ -704,7 +730,7 @@ class IntersectionBatch:
                 raise ValueError('signalise: %s is an integer array of shape (B,) = (%d,), (B, A) or (P,)' % (name, self.B))
             return (np.repeat(v, self.A) if v.shape == (self.B,) and self.B != self.P else v.reshape(-1)).astype(np.int64)
         plan_of, offset = per_agent(plan_of, 'plan_of', 0), per_agent(offset, 'offset', 0)
-        brake = abs(float(self.params.max_decel)) if brake is None else float(brake)
+        brake = self._brake(brake)
         c = self.ctx
         tabs = dict(path_stop=c.i32(stop), path_group=c.i32(group), plan_cycle=c.i32(np.array([int(pl['cycle']) for pl in plans])),
                     plan_amber=c.i32(np.array([int(pl['amber']) for pl in plans])), plan_green=c.i32(np.stack(green)), plan_of=c.i32(plan_of))
@@ -713,10 +739,8 @@ class IntersectionBatch:
         self._signal_tabs = tabs
         self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), tabs['plan_cycle'].data_ptr(),
                                       tabs['plan_amber'].data_ptr(), tabs['plan_green'].data_ptr(), tabs['plan_of'].data_ptr(),
-                                      self.tick.data_ptr(), self.held.data_ptr(), brake, n_points, len(plans), n_groups, 0)
-        self._actuation = None              # (a fixed plan replaces a controller as the source of the lights)
-        self._reservation = None            # (... and a junction manager)
-        self._desc = None
+                                      self.tick.data_ptr(), self.held.data_ptr(), brake, len(stop), len(plans), n_groups, 0)
+        self._off('actuation', 'reservation')   # (a fixed plan replaces a controller or a junction manager as the source of the lights)
         c.synchronize()
 
     def advise_speed(self, v_min: float = 1.0, lead: int = 1, reach: float = 60.0, v_cruise: Optional[float] = None):
@@ -742,8 +766,7 @@ class IntersectionBatch:
     def stop_advising(self):
         """switch the advice off and nothing else: the batch enqueues exactly the launches of one that never had it (`advised` keeps what
         it holds and is no longer written)"""
-        self._advice = None
-        self._desc = None
+        self._off('advice')
 
     def share_plans(self, share=None):
         """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
@@ -772,8 +795,7 @@ class IntersectionBatch:
     def keep_plans_private(self):
         """switch the shared plans off and nothing else: the batch enqueues exactly the launches of one that never shared (`shared_frames`
         keeps what it holds and is no longer written)"""
-        self._intent = None
-        self._desc = None
+        self._off('intent')
 
     def actuate(self, controllers, ctrl_of=None, stop=None, group=None, brake: Optional[float] = None):
         """VEHICLE-ACTUATED SIGNALS (mpcx_closed_loop_run_actuated).  Every instance is a junction (n_per = A) with a controller on the
@@ -811,23 +833,10 @@ class IntersectionBatch:
                     raise ValueError('actuate: controller %d: %s is an integer or one integer per phase' % (k, name))
                 times[k, :, col] = v
             ctrl[k] = [int(ct['amber']), int(ct['all_red']), int(ct['detect'])]
-        n_points = int(self.path.shape[0])
-        if stop is None or group is None:
-            if stop is not None or group is not None:
-                raise ValueError('actuate: give both stop and group, or neither')
-            routes = [self._route_table[self._route_offs[k]:self._route_offs[k + 1]] for k in range(len(self._route_offs) - 1)]
-            stop, group = stop_lines(routes)
-        stop, group = np.asarray(stop), np.asarray(group)
-        if stop.shape != (n_points,) or group.shape != (n_points,):
-            raise ValueError('actuate: stop and group hold one word per path point (%d)' % n_points)
+        stop, group = self._line_tables('actuate', (stop, group), stop_lines)
         # the signal groups: every group a phase or a path point names (a point with a group beyond the limit is a defective entry: free)
         n_groups = min(max(int(masks.max()).bit_length(), int(group.max()) + 1 if len(group) else 1), _lib.SIGNAL_GROUPS_MAX)
-        if ctrl_of is None:
-            ctrl_of = np.zeros(self.B, dtype=np.int64)
-        ctrl_of = np.asarray(ctrl_of)
-        if not np.issubdtype(ctrl_of.dtype, np.integer) or ctrl_of.shape != (self.B,):
-            raise ValueError('actuate: ctrl_of is an integer array of shape (B,) = (%d,)' % self.B)
-        brake = abs(float(self.params.max_decel)) if brake is None else float(brake)
+        ctrl_of, brake = self._per_instance('actuate', 'ctrl_of', ctrl_of), self._brake(brake)
         c = self.ctx
         tabs = dict(path_stop=c.i32(stop), path_group=c.i32(group), phase_groups=c.i32(masks), phase_time=c.i32(times), ctrl_time=c.i32(ctrl),
                     ctrl_of=c.i32(ctrl_of))
@@ -835,15 +844,11 @@ class IntersectionBatch:
         self.junction_state = torch.zeros((self.B, 4), dtype=torch.int32, device=c.device)
         self.lights = torch.zeros(self.B, dtype=torch.int32, device=c.device)
         self.calls = torch.zeros(self.B, dtype=torch.int32, device=c.device)
-        self._signal_tabs = tabs
-        self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), None, None, None, None, None,
-                                      self.held.data_ptr(), brake, n_points, 0, n_groups, 0)
+        self._planless_signals(tabs, brake, n_groups)
         self._actuation = _lib.ActuationC(tabs['phase_groups'].data_ptr(), tabs['phase_time'].data_ptr(), tabs['ctrl_time'].data_ptr(),
                                           tabs['ctrl_of'].data_ptr(), self.junction_state.data_ptr(), self.lights.data_ptr(),
                                           self.calls.data_ptr(), self.A, self.B, n_phases, len(controllers), 0)
-        self._advice = None                 # (there is no plan left to look ahead into)
-        self._reservation = None            # (a controller replaces a junction manager as the source of the hold)
-        self._desc = None
+        self._off('advice', 'reservation')  # (there is no plan left to look ahead into; a controller replaces a junction manager)
         c.synchronize()
 
     def reserve(self, managers, manager_of=None, stop=None, group=None, exit=None, conflict=None, lane=None, brake: Optional[float] = None):
@@ -873,30 +878,16 @@ class IntersectionBatch:
         times = np.array([[int(m['detect']), big if m.get('patience') is None else int(m['patience'])] for m in managers], dtype=np.int64)
         if (times[:, 0] < 1).any() or (times[:, 1] < 0).any() or (times > big).any():
             raise ValueError('reserve: detect >= 1 path point, patience >= 0 steps or None, both int32')
-        n_points = int(self.path.shape[0])
-        routes = [self._route_table[self._route_offs[k]:self._route_offs[k + 1]] for k in range(len(self._route_offs) - 1)]
-        tabs3 = (stop, group, exit)
-        if any(t is None for t in tabs3):
-            if any(t is not None for t in tabs3):
-                raise ValueError('reserve: give stop, group and exit, or none of them')
-            stop, group, exit = movement_lines(routes)
-        stop, group, exit = np.asarray(stop), np.asarray(group), np.asarray(exit)
-        if stop.shape != (n_points,) or group.shape != (n_points,) or exit.shape != (n_points,):
-            raise ValueError('reserve: stop, group and exit hold one word per path point (%d)' % n_points)
+        stop, group, exit = self._line_tables('reserve', (stop, group, exit), movement_lines)
         if conflict is None or lane is None:
             if conflict is not None or lane is not None:
                 raise ValueError('reserve: give both conflict and lane, or neither')
-            conflict, lane = movement_conflicts(routes, stop, exit, np.asarray(self.ip.circle_centers), float(self.ip.radius))
+            conflict, lane = movement_conflicts(self._route_list(), stop, exit, np.asarray(self.ip.circle_centers), float(self.ip.radius))
         conflict, lane = np.asarray(conflict), np.asarray(lane)
         n_groups = len(conflict)
         if conflict.ndim != 1 or lane.shape != conflict.shape or not 1 <= n_groups <= _lib.SIGNAL_GROUPS_MAX:
             raise ValueError('reserve: conflict and lane hold one word per movement, 1 .. %d movements' % _lib.SIGNAL_GROUPS_MAX)
-        if manager_of is None:
-            manager_of = np.zeros(self.B, dtype=np.int64)
-        manager_of = np.asarray(manager_of)
-        if not np.issubdtype(manager_of.dtype, np.integer) or manager_of.shape != (self.B,):
-            raise ValueError('reserve: manager_of is an integer array of shape (B,) = (%d,)' % self.B)
-        brake = abs(float(self.params.max_decel)) if brake is None else float(brake)
+        manager_of, brake = self._per_instance('reserve', 'manager_of', manager_of), self._brake(brake)
         c = self.ctx
         tabs = dict(path_stop=c.i32(stop), path_group=c.i32(group), path_exit=c.i32(exit), conflict=c.i32(conflict), lane=c.i32(lane),
                     mgr_time=c.i32(times), mgr_of=c.i32(manager_of))
@@ -904,34 +895,24 @@ class IntersectionBatch:
         self.held, self.granted = zeros(self.P), zeros(self.P)
         self.since = torch.full((self.P,), -1, dtype=torch.int32, device=c.device)
         self.junction_clock, self.occupied, self.queued = zeros(self.B), zeros(self.B), zeros(self.B)
-        self._signal_tabs = tabs
-        self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), None, None, None, None, None,
-                                      self.held.data_ptr(), brake, n_points, 0, n_groups, 0)
+        self._planless_signals(tabs, brake, n_groups)
         self._reservation = _lib.ReservationC(tabs['path_exit'].data_ptr(), tabs['conflict'].data_ptr(), tabs['lane'].data_ptr(),
                                               tabs['mgr_time'].data_ptr(), tabs['mgr_of'].data_ptr(), self.granted.data_ptr(),
                                               self.since.data_ptr(), self.junction_clock.data_ptr(), self.occupied.data_ptr(),
                                               self.queued.data_ptr(), self.A, self.B, len(managers), 0)
-        self._actuation = None              # (a junction manager replaces a controller or a plan as the source of the hold)
-        self._advice = None                 # (there is no plan to look ahead into)
-        self._desc = None
+        self._off('actuation', 'advice')    # (a junction manager replaces a controller or a plan; there is no plan to look ahead into)
         c.synchronize()
 
     def unsignalise(self):
         """switch the signals off, fixed or actuated -- and the advice that draws on them -- and nothing else: the batch enqueues exactly the launches of one that never had them
         (`tick`, `held` and the junction words keep what they hold and are no longer read or written)"""
-        self._signals = None
-        self._actuation = None
-        self._reservation = None
-        self._advice = None                 # (advice looks ahead into the signals' plan)
-        self._desc = None
+        self._off('signals')                # (advice looks ahead into the signals' plan)
 
     def stop_respawning(self):
         """switch respawn off and nothing else: the batch enqueues exactly the launches of one with admission alone.  Vehicles in flight
         finish (and stay departed), waiting ones still enter; `served` and the episode table keep what they hold.  Routing goes with it: a
         slot keeps the route its last reset gave it"""
-        self._respawn = None
-        self._routes = None
-        self._desc = None
+        self._off('respawn')
 
     def served_count(self) -> int:
         """episodes finished so far, over all slots (one small reduction and one synchronisation)"""
@@ -1074,10 +1055,7 @@ class IntersectionBatch:
         if self._desc is None:
             self._desc = self._descriptor()
         self._claim_context()
-        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, log=None if self.log is None else self.log.c, opts=self._opts,
-                                 retire=self._retire, scene=self._scene, admit=self._admit, respawn=self._respawn, routes=self._routes,
-                                 precedence=self._precedence, signals=self._signals, actuation=self._actuation, advice=self._advice,
-                                 intent=self._intent, reservation=self._reservation)
+        self.ctx.closed_loop_run(self.ip, self._desc, n_steps, graph, **self._stage_structs())
         self.steps_done += n_steps
 
     def step(self):
@@ -1165,30 +1143,14 @@ class IntersectionBatch:
         if self.traffic is not None:         # the actors' states (x, y, theta, counter / cursor) and the pool as the last step saw it
             out['traffic_state'] = self.traffic_state.cpu().numpy().copy()
             out['obs6'] = self.obs6.cpu().numpy().copy()
-        if self._retire is not None:
-            out['done'], out['steps_driven'] = self.done.cpu().numpy().copy(), self.steps_driven.cpu().numpy().copy()
-        if self._scene is not None:
-            out['absent'] = self.absent.cpu().numpy().copy()
-        if self._admit is not None:
-            out['wait'], out['entered_step'] = self.wait.cpu().numpy().copy(), self.entered_step.cpu().numpy().copy()
-        if self._respawn is not None:
-            out['served'] = self.served.cpu().numpy().copy()
+        for st, words in _SNAPSHOT_WORDS.items():
+            if getattr(self, '_' + st) is not None:
+                out.update({key: getattr(self, attr).cpu().numpy().copy() for key, attr in words})
         if self._routes is not None:         # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
-        if self._precedence is not None:     # the precedence word of every pool row (a smaller word goes first)
-            out['precedence'] = self.prec.cpu().numpy().copy()
-        if self._signals is not None:        # 0 free, 1 held at red, 2 held at amber, as the last step's signal stage left it
-            out['held'] = self.held.cpu().numpy().copy()
-        if self._advice is not None:         # the speed advised to every agent in the last step, 0 = none
-            out['advised'] = self.advised.cpu().numpy().copy()
-        if self._intent is not None:         # frames of every agent's own row taken from its plan in the last step (pred_steps or 0)
-            out['shared_frames'] = self.shared_frames.cpu().numpy().copy()
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
             js = self.junction_state.cpu().numpy()
             out['phase'], out['stage'], out['lights'] = js[:, 0].copy(), js[:, 1].copy(), self.lights.cpu().numpy().copy()
-        if self._reservation is not None:    # per agent: its reservation and first request; per junction: the movements on the crossing
-            out['granted'], out['since'] = self.granted.cpu().numpy().copy(), self.since.cpu().numpy().copy()
-            out['occupied'] = self.occupied.cpu().numpy().copy()
         return out
 
     def stop_index(self) -> np.ndarray:

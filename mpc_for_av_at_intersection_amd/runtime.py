@@ -644,47 +644,15 @@ class Context:
                                                    _ptr(pool_row), int(obs6.shape[0]), _ptr(obs6)))
 
     @_ordered
-    def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False,
-                        log: Optional['_lib.RunLogC'] = None, opts: Optional['_lib.ClosedLoopOptsC'] = None,
-                        retire: Optional['_lib.RetireC'] = None, scene: Optional['_lib.SceneC'] = None,
-                        admit: Optional['_lib.AdmitC'] = None, respawn: Optional['_lib.RespawnC'] = None,
-                        routes: Optional['_lib.RoutesC'] = None, precedence: Optional['_lib.PrecedenceC'] = None,
-                        signals: Optional['_lib.SignalsC'] = None, actuation: Optional['_lib.ActuationC'] = None,
-                        advice: Optional['_lib.AdviceC'] = None, intent: Optional['_lib.IntentC'] = None,
-                        reservation: Optional['_lib.ReservationC'] = None):
+    def closed_loop_run(self, ip: InteractionParams, desc: '_lib.ClosedLoopC', n_steps: int, graph: bool = False, **stages):
         """mpcx_closed_loop_run: n_steps of the scenario loop body on the buffers `desc` names, no host work between.
-        log: a _lib.RunLogC -- every step then ends with the run log's record stage (mpcx_closed_loop_run_logged).
-        opts: a _lib.ClosedLoopOptsC -- the stop mode (mpcx_closed_loop_run_opts); None = the path cut.
-        retire: a _lib.RetireC -- agents are retired at their goal (mpcx_closed_loop_run_retire); None = they are driven on.
-        scene: a _lib.SceneC -- departure: pool rows with absent != 0 are out of the scene and an arrival sets the agent's own word
-        (mpcx_closed_loop_run_scene; refused without retire); None = arrived cars stay in the scene.
-        admit: a _lib.AdmitC -- admission: waiting agents enter on their schedule once their start pose is clear (mpcx_closed_loop_run_admit;
-        refused without scene); None = everybody is in from the start.
-        respawn: a _lib.RespawnC -- respawn: an arrived agent's slot is reset for the next vehicle of its stream and handed back to the
-        admission gate (mpcx_closed_loop_run_respawn; refused without admit); None = a departed slot stays empty.
-        routes: a _lib.RoutesC -- every vehicle of a slot takes its own route from its own start pose (mpcx_closed_loop_run_routes; refused
-        without respawn); None = a slot keeps its route.
-        precedence: a _lib.PrecedenceC -- right of way: an agent sees the present rows whose word is larger than its own as standing cars
-        (mpcx_closed_loop_run_precedence; refused without scene, and in ENTRY mode without admit); None = everybody yields to everybody.
-        signals: a _lib.SignalsC -- traffic signals: one more launch behind the conflict search holds agents at their stop lines
-        (mpcx_closed_loop_run_signals; needs none of the others); None = no signals.
-        actuation: a _lib.ActuationC -- vehicle-actuated signals: a controller per junction takes the place of the signals' fixed plan
-        (mpcx_closed_loop_run_actuated; refused without signals); None = the signals' own plan.
-        advice: a _lib.AdviceC -- signal-aware approach speed: one more launch between the window stage and the QP caps the speed reference
-        of an agent that would reach its stop line on red (mpcx_closed_loop_run_advised; refused without signals under a fixed plan, with
-        actuation and outside speed mode); None = no advice.
-        intent: a _lib.IntentC -- shared plans: one more launch between the prediction and the conflict search predicts a sharing agent from
-        its last MPC solution instead of its last controls (mpcx_closed_loop_run_intent; refused in the agent-sharded layout); None = every
-        agent is predicted from its last controls.
-        reservation: a _lib.ReservationC -- crossing reservations: a manager per junction takes the place of the signals' fixed plan and
-        admits only compatible movements (mpcx_closed_loop_run_reserved; refused without signals, with a plan, actuation or advice); None =
-        no reservations."""
-        ref = lambda s: None if s is None else C.byref(s)
+        **stages: one keyword per optional stage, the stage's struct or None = off.  _lib.STAGES lists them, each with what it does, what
+        it is refused without and what None means; a keyword that is not in that list is a TypeError."""
+        structs = _lib.stage_structs(stages)
         # (the widest entry point: NULL is "none" for every stage, and the narrower ones are that call with NULLs)
-        self._chk(self.lib.mpcx_closed_loop_run_reserved(self._ctx, C.byref(ip.to_c()), C.byref(desc), ref(log), ref(opts), ref(retire),
-                                                         ref(scene), ref(admit), ref(respawn), ref(routes), ref(precedence), ref(signals),
-                                                         ref(actuation), ref(advice), ref(intent), ref(reservation), int(n_steps),
-                                                         1 if graph else 0))
+        run = getattr(self.lib, _lib.LOOP_ENTRY_POINTS[-1])
+        self._chk(run(self._ctx, C.byref(ip.to_c()), C.byref(desc), *(None if s is None else C.byref(s) for s in structs), int(n_steps),
+                      1 if graph else 0))
 
     @_ordered
     def signal_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', done=None):

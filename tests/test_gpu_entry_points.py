@@ -66,7 +66,7 @@ def _batch(c, stock, stages):
 
 
 def _structs(sim):
-    return dict(log=None if sim.log is None else sim.log.c, opts=sim._opts, retire=sim._retire, scene=sim._scene, admit=sim._admit)
+    return sim._stage_structs()         # (every stage of _lib.STAGES: those beyond admission are off in every batch here)
 
 
 def _call(sim, name, graph):
