@@ -1025,6 +1025,56 @@ int32_t mpcx_reserve_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const doubl
                                 const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
                                 const int32_t *done /*P or NULL*/, const mpcx_signals *signals, const mpcx_reservation *reservation);
 
+/* ---- car following: an agent keeps a standstill distance and a time gap to the car ahead of it on its own path.  The conflict search
+ * knows no leader -- it cuts the path where a prediction of the car in front meets the ego's own full-throttle prediction --, so a queue
+ * behind a stop line, a platoon and two streams that merge into one arm have nothing that separates them.  With following on, one launch
+ * (follow_kernel, csrc/mpcx_follow.hip; the rule is csrc/mpcx_follow_core.h) behind the signal / actuated / reserve stage -- behind the
+ * conflict search where there are no signals -- finds every agent's leader and lowers its cut_len, and in MPCX_STOP_SPEED one more
+ * (follow_clamp_kernel) behind every window stage caps row 2 of its xref.  The stage attaches to the CONTEXT (mpcx_set_following), as the
+ * linearisation passes and the tuning rows do: every mpcx_closed_loop_run* entry point runs it while it is set.
+ * For agent q with done[q] == 0 (otherwise only "no leader" is written): THE OTHERS are the rows of its pool window other than obs_skip[q],
+ * in row order, the first MPCX_MAX_OBS of them, rows outside the pool or with absent[r] != 0 left out; agents and scripted actors alike,
+ * obs6 as the head of this step packed it.  (1) k*(r) = the k in [traj_idx[q], min(traj_idx[q] + reach, path_len[q] - 1)] of q's full path
+ * that minimises dx dx + dy dy to (x_r, y_r), the lowest k of equals.  (2) r is a candidate if k*(r) > traj_idx[q], the minimum is <=
+ * lateral^2 and |wrap(yaw_path[k*] - yaw_r)| <= heading (wrap: 2 pi subtracted or added at most 33 times; no sin / cos).  (3) the leader is
+ * the candidate with the smallest k*, the lowest pool row of equals: leader[q] = its row, gap[q] = (k* - traj_idx[q]) dl, v_l =
+ * max(obs6[r][2], 0).  (4) with v = max(state[q][2], 0): s = k* - ceil((standstill + time_gap v) / dl) in MPCX_STOP_CUT, s = k* -
+ * ceil(standstill / dl) in MPCX_STOP_SPEED; s is clamped to >= traj_idx[q] + 1 and cut_len[q] = min(cut_len[q], s).  (5) cap[q] =
+ * max(v_min, -brake time_gap + sqrt(brake^2 time_gap^2 + v_l^2 + 2 brake max(gap - standstill, 0))), Gipps' safe speed.  No leader: leader
+ * -1, gap -1.0, cap 0.0, cut_len untouched.  (6) MPCX_STOP_SPEED: every entry of row 2 of q's xref becomes fmin(entry, cap[q]) where
+ * cap[q] > 0.  Precedence words are not consulted.  Host and device agree bit for bit.
+ * NULL or an all-zero struct: off -- the loop enqueues exactly the launches of a context that never had it, with the same arguments.  The
+ * cached graph's key covers the struct by value, and a run with the stage on does not take step fusion.  MPCX_E_INVALID ("following: ...")
+ * from the run or the stage call before anything is launched, whatever n_steps is: leader, gap or cap NULL; n_rows != P; standstill, brake,
+ * lateral or heading not finite or not positive; time_gap not finite or negative; v_min not finite or not positive; reach outside
+ * 1..MPCX_MAX_REMAINING; a nonzero reserved word; the agent-sharded layout. */
+typedef struct {
+    int32_t *leader;             /* n_rows = P, caller-owned, out: the pool row of agent q's leader in the last step, -1 = none */
+    double *gap;                 /* n_rows, out: the distance to it along q's path (m), -1.0 = none */
+    double *cap;                 /* n_rows, out: the safe speed behind it (m/s), 0.0 = none */
+    double standstill;           /* distance kept to a leader at rest (> 0, m) */
+    double time_gap;             /* ... plus this many seconds of the follower's own speed (>= 0, s) */
+    double brake;                /* the deceleration both cars are taken to brake with (> 0, m/s^2) */
+    double v_min;                /* the cap is never below this (> 0, m/s) */
+    double lateral;              /* a row counts if it is within this distance of the path (> 0, m) */
+    double heading;              /* ... and heads along it within this angle (> 0, rad) */
+    int32_t reach;               /* path points ahead that are scanned (1..MPCX_MAX_REMAINING) */
+    int32_t n_rows, reserved;    /* reserved: 0 */
+} mpcx_following;
+/* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
+int32_t mpcx_set_following(mpcx_ctx *ctx, const mpcx_following *following /*NULL or all-zero = off*/);
+/* one step's search stage alone (what the closed loop enqueues in front of the window stage): steps 1 - 5.  stop_mode: MPCX_STOP_CUT or
+ * MPCX_STOP_SPEED; the struct is the argument's, not the context's, and is checked as above. */
+int32_t mpcx_follow_step_batch(mpcx_ctx *ctx, int32_t P, double dl, int32_t stop_mode, const double *state /*P,4*/, const double *path_xyyaw,
+                               const int32_t *path_off /*P*/, const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/,
+                               int32_t *cut_len /*P*/, const int32_t *done /*P or NULL*/, int32_t n_obs_pool, const double *obs6 /*NOBS,6*/,
+                               const int32_t *obs_off /*P*/, const int32_t *obs_cnt /*P*/, const int32_t *obs_skip /*P or NULL*/,
+                               const int32_t *absent /*NOBS or NULL*/, const mpcx_following *following);
+/* one step's clamp alone (what the closed loop enqueues behind every window stage in MPCX_STOP_SPEED): step 6 on xref (P,4,T+1) from the
+ * struct's cap as the search stage left it. */
+int32_t mpcx_follow_cap_step_batch(mpcx_ctx *ctx, int32_t P, const int32_t *done /*P or NULL*/, const mpcx_following *following,
+                                   double *xref /*P,4,T+1*/);
+
 /* ---- multi-GPU exchange (the reference is single-process and has no counterpart).  One process per
  * GPU, one communicator per context: rank 0 calls mpcx_comm_unique_id, the caller distributes the MPCX_COMM_ID_BYTES bytes
  * to every rank by whatever means it has (torch.distributed broadcast in this package), every rank calls mpcx_comm_init.

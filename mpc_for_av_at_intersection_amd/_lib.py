@@ -136,6 +136,15 @@ class ReservationC(C.Structure):
                 ('n_per', C.c_int32), ('n_junctions', C.c_int32), ('n_mgr', C.c_int32), ('reserved', C.c_int32)]
 
 
+class FollowingC(C.Structure):
+    """mirror of mpcx_following (include/mpcx.h): car following; leader (n_rows = P int32, out), gap and cap (n_rows float64, out) are
+    device addresses.  Not a row of STAGES: the stage attaches to the context (Context.set_following), not to an entry point"""
+    _fields_ = [('leader', C.c_void_p), ('gap', C.c_void_p), ('cap', C.c_void_p), ('standstill', C.c_double), ('time_gap', C.c_double),
+                ('brake', C.c_double), ('v_min', C.c_double), ('lateral', C.c_double), ('heading', C.c_double), ('reach', C.c_int32),
+                ('n_rows', C.c_int32), ('reserved', C.c_int32)]
+
+
+MAX_REMAINING = 1024                            # MPCX_MAX_REMAINING: the largest mpcx_following.reach
 SIGNAL_GROUPS_MAX = 16                          # MPCX_SIGNAL_GROUPS_MAX
 RESERVE_PER_MAX = 64                            # MPCX_RESERVE_PER_MAX: agents per junction under reservations
 ACTUATION_PHASES_MAX = 8                        # MPCX_ACTUATION_PHASES_MAX
@@ -292,7 +301,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_admit_step_batch', 'mpcx_respawn_step_batch', 'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary',
            'mpcx_admit_step_batch_precedence', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
            'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
-           'mpcx_reserve_step_batch'] + LOOP_ENTRY_POINTS
+           'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch'] + LOOP_ENTRY_POINTS
 
 
 def load():
@@ -387,5 +396,10 @@ def load():
                                                   [C.POINTER(IntentC)])
     lib.mpcx_reserve_step_batch.restype = i32
     lib.mpcx_reserve_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(ReservationC)]
+    lib.mpcx_set_following.restype = i32; lib.mpcx_set_following.argtypes = [vp, C.POINTER(FollowingC)]
+    lib.mpcx_follow_step_batch.restype = i32
+    lib.mpcx_follow_step_batch.argtypes = [vp, i32, C.c_double, i32] + [vp] * 7 + [i32] + [vp] * 5 + [C.POINTER(FollowingC)]
+    lib.mpcx_follow_cap_step_batch.restype = i32
+    lib.mpcx_follow_cap_step_batch.argtypes = [vp, i32, vp, C.POINTER(FollowingC), vp]
     _lib = lib
     return lib

@@ -42,6 +42,9 @@ window stage and the QP); the hold stays the safety net behind it.
 `reserve(managers)` runs the crossing UNSIGNALISED BY RESERVATION: every instance is a junction with a manager on the device that admits a
 car only if its movement (movement_lines()) conflicts with no movement that holds the crossing (movement_conflicts()), first come, first
 served; everybody else waits at its stop line.  The launch takes the place of the signals', the hold at the line is the same.
+`follow()` is CAR FOLLOWING, beside every other stage and in both stop modes: every agent finds the nearest vehicle ahead on its own path
+and stops a standstill distance plus a time gap behind it -- the hold at a line that moves --, in speed mode under Gipps' safe speed as a
+cap on its speed reference (one launch in front of the window stage, in speed mode one behind it).
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -378,6 +381,10 @@ class IntersectionBatch:
         self.occupied: Optional[torch.Tensor] = None         # ... int32 (B,), the movements that held the crossing in the last step
         self.queued: Optional[torch.Tensor] = None           # ... int32 (B,), the requesters denied in the last step
         self._reservation = None
+        self.leader: Optional[torch.Tensor] = None           # follow(): int32 (P,), the pool row of the agent's leader in the last step, -1 = none
+        self.gap: Optional[torch.Tensor] = None              # ... float64 (P,), the distance to it along the agent's path, -1 = none
+        self.follow_cap: Optional[torch.Tensor] = None       # ... float64 (P,), the safe speed behind it, 0 = none
+        self._following = None                               # (not a stage of _lib.STAGES: it is set on the context, _claim_context)
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -768,6 +775,38 @@ class IntersectionBatch:
         it holds and is no longer written)"""
         self._off('advice')
 
+    def follow(self, standstill: float = 6.0, time_gap: float = 1.0, brake: float = 3.0, v_min: float = 0.5, lateral: float = 1.5,
+               heading: float = 0.8, reach: Optional[int] = None):
+        """CAR FOLLOWING (mpcx_set_following), in both stop modes and beside every other stage.  The conflict search knows no leader: a
+        queue, a platoon and two streams that merge have nothing that keeps them apart.  With following every agent looks `reach` path
+        points ahead on its OWN path (default: 40 m of it) for the nearest vehicle of its pool window -- agents and scripted cars alike --
+        that is within `lateral` metres of the path and heads along it within `heading` radians, and stops `standstill` metres (reference
+        point to reference point: more than the 4.33 m at which the stock car's discs touch) plus `time_gap` seconds of its own speed
+        behind it: the signals' hold at a line that moves.  In speed mode the stop point keeps `standstill` only and the time gap is in a
+        cap on the speed reference, Gipps' safe speed for a deceleration `brake`, never below `v_min`.  One more launch in front of the
+        window stage, in speed mode one more behind it.  Right of way is not consulted.  The defaults are those of the closed-loop runs of
+        tests/test_follow_cpu.py.  Allocates `leader` (-1), `gap` (-1) and `follow_cap` (0) and drops the cached descriptor;
+        stop_following() switches it off."""
+        if self.exchange == 'rccl' or callable(self.exchange):
+            raise ValueError('follow: not in the agent-sharded layout (shard by instances)')
+        reach = min(int(round(40.0 / self.dl)), _lib.MAX_REMAINING) if reach is None else int(reach)
+        vals = [float(v) for v in (standstill, time_gap, brake, v_min, lateral, heading)]
+        if not (np.isfinite(vals).all() and all(v > 0 for v in vals[:1] + vals[2:]) and vals[1] >= 0 and 1 <= reach <= _lib.MAX_REMAINING):
+            raise ValueError('follow: standstill, brake, v_min, lateral, heading > 0, time_gap >= 0, all finite, reach in 1..%d points' % _lib.MAX_REMAINING)
+        dev = self.ctx.device
+        self.leader = torch.full((self.P,), -1, dtype=torch.int32, device=dev)
+        self.gap = torch.full((self.P,), -1.0, dtype=torch.float64, device=dev)
+        self.follow_cap = torch.zeros(self.P, dtype=torch.float64, device=dev)
+        self._following = _lib.FollowingC(self.leader.data_ptr(), self.gap.data_ptr(), self.follow_cap.data_ptr(), *vals, reach, self.P, 0)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def stop_following(self):
+        """switch following off and nothing else: the batch enqueues exactly the launches of one that never had it (`leader`, `gap` and
+        `follow_cap` keep what they hold and are no longer written)"""
+        self._following = None
+        self._desc = None
+
     def share_plans(self, share=None):
         """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
         it applied in the last step, held for pred_steps frames -- the reference's prediction of a scripted car.  A sharing agent is seen
@@ -1033,6 +1072,7 @@ class IntersectionBatch:
         if getattr(self.ctx, 'lin_passes', 1) != self.lin_passes:
             self.ctx.set_linearisation_passes(self.lin_passes)
         self.ctx.set_instance_tuning(self.tuning)
+        self.ctx.set_following(self._following)
 
     def run(self, n_steps: int, graph: bool = False):
         """n_steps of the closed loop with no host work in between (mpcx_closed_loop_run)."""
@@ -1110,6 +1150,9 @@ class IntersectionBatch:
             c.actuated_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._actuation)
         elif self._signals is not None:     # the signal stage: between the conflict search and the window stage, as in the loop
             c.signal_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals)
+        if self._following is not None:     # the following stage: behind the signal stage, in front of the window stage, as in the loop
+            c.follow_step(self.dl, _lib.STOP_SPEED if speed else _lib.STOP_CUT, self.state, self.path, self.path_off, self.path_len, self.traj_idx,
+                          self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self._following, obs_skip=self.obs_skip)
         # the previous solution (zeros where the last solve failed or on the first step) is the warm start
         for it in range(self.lin_passes):       # lib/mpc.py:226-237: from the second pass on the previous pass's speeds space the window
             if speed:       # the whole path + the stop index (mpcx_mpc_prepare_batch_stop).  len_seen is a side effect the NEXT step
@@ -1120,6 +1163,8 @@ class IntersectionBatch:
                 if self._advice is not None:    # the advice stage: between the window stage and the QP, as in the loop
                     c.advise_step(self.dl, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._advice,
                                   self.pre['xref'])
+                if self._following is not None:     # the following clamp: behind the window stage (and the advice), as in the loop
+                    c.follow_cap_step(self._following, self.pre['xref'])
             else:
                 c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.inter['cut_len'], self.dl, self.target_ind, out=self.pre,
                           path_v=self.path_v, x_prev=self.sol['x'] if it else None)
@@ -1146,6 +1191,8 @@ class IntersectionBatch:
         for st, words in _SNAPSHOT_WORDS.items():
             if getattr(self, '_' + st) is not None:
                 out.update({key: getattr(self, attr).cpu().numpy().copy() for key, attr in words})
+        if self._following is not None:      # the leader's pool row (-1 = none), the distance to it and the safe speed behind it, last step's
+            out.update(leader=self.leader.cpu().numpy().copy(), gap=self.gap.cpu().numpy().copy(), follow_cap=self.follow_cap.cpu().numpy().copy())
         if self._routes is not None:         # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
@@ -1164,6 +1211,8 @@ class IntersectionBatch:
         stops = self.inter['hit_idx'].cpu().numpy() >= 0
         if self._signals is not None:
             stops = stops | (self.held.cpu().numpy() != 0)
+        if self._following is not None:     # (the stop point behind a leader lies on the path whenever there is a leader)
+            stops = stops | (self.leader.cpu().numpy() >= 0)
         return np.where(stops, self.inter['cut_len'].cpu().numpy(), _lib.NO_STOP).astype(np.int32)
 
 

@@ -17,9 +17,11 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1392] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1480] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
+    mpcx_following following = {};        // car following (mpcx_set_following): the struct by value, padding zeroed; all zeros while off
+    bool have_following = false;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
     const int32_t *order_now = nullptr, *order_prev = nullptr;   // optional pair: entries that differ mark a discontinuous change of the reference
     // scratch of mpcx_closed_loop_run for P agents: [P] cut lengths of the previous step | [3 P] what the conflict search's nearest-index
@@ -229,6 +231,16 @@ int32_t mpcx_reservation_validate(mpcx_ctx *ctx, const mpcx_reservation *s, cons
 int32_t mpcx_reserve_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
                              const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals,
                              const mpcx_reservation *reservation);
+// car following (mpcx_follow.hip): "no following" test, check of the struct against the run, the two launches alone (the search behind the
+// signal stage or the conflict search, the clamp behind a window stage in speed mode)
+bool mpcx_following_absent(const mpcx_following *s);
+int32_t mpcx_following_validate(mpcx_ctx *ctx, const mpcx_following *s, int32_t P, int32_t exchange);
+int32_t mpcx_follow_enqueue(mpcx_ctx *ctx, int32_t P, double dl, bool speed, const double *state, const double *path_xyyaw,
+                            const int32_t *path_off, const int32_t *path_len, const int32_t *traj_idx, int32_t *cut_len,
+                            const int32_t *done /*or nullptr*/, int32_t n_obs_pool, const double *obs6, const int32_t *obs_off,
+                            const int32_t *obs_cnt, const int32_t *obs_skip /*or nullptr*/, const int32_t *absent /*or nullptr*/,
+                            const mpcx_following *following);
+int32_t mpcx_follow_cap_enqueue(mpcx_ctx *ctx, int32_t P, const int32_t *done /*or nullptr*/, const mpcx_following *following, double *xref);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -95,10 +95,15 @@ struct LoopStages {
     // crossing reservations: reserve_kernel in signal_kernel's place; needs signals without a plan, and neither actuation nor advice.  A
     // manager per junction admits an agent only if its movement conflicts with none that holds the crossing; the hold is signal_kernel's.
     const mpcx_reservation *reserve = nullptr;
+    // car following (mpcx_set_following: it attaches to the context, not to an entry point): follow_kernel behind the signal / actuated /
+    // reserve stage, or behind the conflict search where there are no signals; needs the local pool.  It lowers c->cut_len to a stop point
+    // behind the agent's leader before the window stage reads it and writes leader, gap and cap; in MPCX_STOP_SPEED follow_clamp_kernel
+    // behind every window stage (and the advice stage) caps row 2 of c->xref.  &ctx->following while on.
+    const mpcx_following *follow = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -109,6 +114,7 @@ struct LoopKey {
     mpcx_closed_loop desc;
     mpcx_run_log log; mpcx_closed_loop_opts opts; mpcx_retire retire; mpcx_scene scene; mpcx_admit admit; mpcx_respawn respawn;
     mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice; mpcx_intent intent; mpcx_reservation reservation;
+    mpcx_following following;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -203,11 +209,16 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         rc = mpcx_intent_validate(ctx, a.intent, c->P, c->exchange, c->obs6 ? rows : 0, c->obs_skip);
         if (rc == MPCX_OK) st->intent = a.intent;
     }
+    if (rc != MPCX_OK) return rc;
+    if (ctx->have_following) {
+        rc = mpcx_following_validate(ctx, &ctx->following, c->P, c->exchange);
+        if (rc == MPCX_OK) st->follow = &ctx->following;
+    }
     return rc;
 }
 
-// The middle of a step, the same on both paths: the conflict search (-> the signal stage) -> lin_passes x (reference window (-> the advice
-// stage) -> solve).
+// The middle of a step, the same on both paths: the conflict search (-> the signal stage) (-> the following stage) -> lin_passes x (reference
+// window (-> the advice stage) (-> the following clamp) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
 static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopStages &st,
@@ -236,6 +247,11 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
                          : mpcx_signal_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals);
         if (rc != MPCX_OK) return rc;
     }
+    if (st.follow) {
+        rc = mpcx_follow_enqueue(ctx, P, c->dl, speed, c->state, c->path_xyyaw, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, pool_rows,
+                                 c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, ix.absent, st.follow);
+        if (rc != MPCX_OK) return rc;
+    }
     // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
     // previous pass's speeds (row 2 of its x) and the rollout uses its inputs.  (Where a pass fails the reference crashes in the next
     // one -- zip over None; here the next pass starts from the untouched warm start, as after a failed step.)
@@ -252,6 +268,10 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
         if (rc != MPCX_OK) return rc;
         if (st.advice) {
             rc = mpcx_advise_enqueue(ctx, P, c->dl, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, st.advice, c->xref);
+            if (rc != MPCX_OK) return rc;
+        }
+        if (st.follow && speed) {
+            rc = mpcx_follow_cap_enqueue(ctx, P, done, st.follow, c->xref);
             if (rc != MPCX_OK) return rc;
         }
         // (further linearisation passes build their order in line, from the iteration counts of the pass before)
@@ -456,6 +476,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.log, st.log); key_put(key.retire, st.retire); key_put(key.scene, st.scene); key_put(key.admit, st.admit);
     key_put(key.respawn, st.respawn); key_put(key.routes, st.routes); key_put(key.precedence, st.precedence); key_put(key.signals, st.signals);
     key_put(key.advice, st.advice); key_put(key.intent, st.intent); key_put(key.reservation, st.reserve);
+    key_put(key.following, st.follow);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;

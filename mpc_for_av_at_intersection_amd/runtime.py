@@ -850,6 +850,44 @@ class Context:
             self._chk(self.lib.mpcx_set_instance_tuning(self._ctx, _ptr(rows), int(rows.shape[0])))
         self._tuning = rows
 
+    def set_following(self, following: Optional['_lib.FollowingC']):
+        """mpcx_set_following: car following for every closed-loop run of this context from now on; None (or an all-zero struct) = off.
+        The context copies the struct; the device buffers it names (leader, gap, cap) stay the caller's and are kept alive here while set."""
+        self._chk(self.lib.mpcx_set_following(self._ctx, None if following is None else C.byref(following)))
+        self._following = following
+
+    @_ordered
+    def follow_step(self, dl: float, stop_mode: int, state, path, path_off, path_len, traj_idx, cut_len, obs6, obs_off, obs_cnt,
+                    following: '_lib.FollowingC', obs_skip=None, done=None, absent=None):
+        """mpcx_follow_step_batch: ONE step's following search as the closed loop enqueues it in front of the window stage.  cut_len (P int32:
+        the cut length, or stop index in speed mode) is lowered in place and the struct's leader, gap and cap are written; stop_mode:
+        _lib.STOP_CUT or _lib.STOP_SPEED; obs6 (pool rows, 6): the pool as the head of the step packed it; obs_skip: the agents' own rows,
+        done: the retirement words (P int32 each), absent: the scene's words (pool rows), or None."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state'); self._want(obs6, torch.float64, (obs6.shape[0], 6), 'obs6')
+        self._want(path, torch.float64, (path.shape[0], 3), 'path')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('cut_len', cut_len), ('obs_off', obs_off),
+                        ('obs_cnt', obs_cnt), ('obs_skip', obs_skip), ('done', done)):
+            if t is not None:
+                self._want(t, torch.int32, (Pn,), name)
+        if absent is not None:
+            self._want(absent, torch.int32, (obs6.shape[0],), 'absent')
+        self._chk(self.lib.mpcx_follow_step_batch(self._ctx, Pn, float(dl), int(stop_mode), _ptr(state), _ptr(path), _ptr(path_off), _ptr(path_len),
+                                                  _ptr(traj_idx), _ptr(cut_len), _ptr(done), int(obs6.shape[0]), _ptr(obs6), _ptr(obs_off),
+                                                  _ptr(obs_cnt), _ptr(obs_skip), _ptr(absent), C.byref(following)))
+
+    @_ordered
+    def follow_cap_step(self, following: '_lib.FollowingC', xref, done=None):
+        """mpcx_follow_cap_step_batch: ONE step's following clamp as the closed loop enqueues it behind a window stage in speed mode: row 2 of
+        xref (P, 4, T + 1 float64) is capped in place at the struct's cap, as follow_step left it, for every agent with a leader."""
+        if self.params is None:
+            raise MpcxError('follow_cap_step: set_mpc_params has not been called (the stage sizes the window from the horizon)')
+        Pn = int(xref.shape[0])
+        self._want(xref, torch.float64, (Pn, 4, self.params.T + 1), 'xref')
+        if done is not None:
+            self._want(done, torch.int32, (Pn,), 'done')
+        self._chk(self.lib.mpcx_follow_cap_step_batch(self._ctx, Pn, _ptr(done), C.byref(following), _ptr(xref)))
+
     @_ordered
     def set_qp_order_hint(self, prev_iters: Optional[torch.Tensor], ref_now: Optional[torch.Tensor] = None,
                           ref_prev: Optional[torch.Tensor] = None):
