@@ -1063,6 +1063,20 @@ typedef struct {
 } mpcx_following;
 /* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
 int32_t mpcx_set_following(mpcx_ctx *ctx, const mpcx_following *following /*NULL or all-zero = off*/);
+/* ---- the stages together.  With several optional stages on, a step is: admission, the entry-order stamp; pool pack and prediction; the
+ * intent stage; the conflict search; the hold (signal, actuated or reserve stage); the following stage; per linearisation pass the window
+ * stage, the advice stage, the following clamp and the QP; the plant; record, retire, respawn.  What that order implies:
+ *   one car, three views   agent q sees a present row r of its window (1) standing at its pose if prec[r] > prec[obs_skip[q]], whatever
+ *                          the intent stage wrote into r's predicted frames; (2) else on its owner's plan of the step before, if the owner
+ *                          shares, drives, is present and its last status is MPCX_QP_OPTIMAL; (3) else through the constant prediction.
+ *                          The following stage reads obs6[r] itself: the leader's true speed, whether it yields or shares.
+ *   the cut is a minimum   conflict search, hold and follower each only lower cut_len; the advice stage reads the result.  A reservation
+ *                          manager reads traj_idx as the conflict search left it and never the follower's stop point.
+ *   a reset slot           the respawn stages reset no word of the signal, reservation, following or intent stages, nor status.  Each of
+ *                          those stages rewrites its words for every agent in every step, retired ones included; a slot that is admitted
+ *                          again in the very next step starts from what its predecessor's last step left (held, granted, since), and its
+ *                          signal clock runs on.
+ * tests/stack_helpers.py composes the host builds of the rules in this order; tests/test_gpu_stack.py replays the device against it. */
 /* one step's search stage alone (what the closed loop enqueues in front of the window stage): steps 1 - 5.  stop_mode: MPCX_STOP_CUT or
  * MPCX_STOP_SPEED; the struct is the argument's, not the context's, and is checked as above. */
 int32_t mpcx_follow_step_batch(mpcx_ctx *ctx, int32_t P, double dl, int32_t stop_mode, const double *state /*P,4*/, const double *path_xyyaw,

@@ -228,6 +228,17 @@ def intent_agent_step(p, full, dl, st, trajs, traj_idx, prev, target, u, centers
     body of oracle_py.agent_step (speedref_helpers.agent_step in speed mode) from the conflict check on, then the hold of
     signal_helpers.signal_agent_step where decide(traj_idx, v) -> (held, s) is given.  prev: the previous cut length (speed mode: path
     length; 0 / None before the first step).  Returns agent_step's dict with `cut` (speed mode: the stop index, 999 = none), `held`, `line`."""
+    traj_idx, hit, cut, n_res = intent_search(p, full, st, trajs, traj_idx, prev, centers, radius, margin, speed, frame_window, max_accel)
+    held, line = (0, -1) if decide is None else decide(int(traj_idx), st[2])
+    if held and line < cut:
+        cut = line
+    r = intent_solve(p, full, dl, st, target, u, cut, speed, v_ref=v_ref)
+    return dict(r, traj_idx=traj_idx, hit=hit, cut=int(cut), held=int(held), line=int(line), n_res=n_res)
+
+
+def intent_search(p, full, st, trajs, traj_idx, prev, centers, radius, margin, speed, frame_window=20, max_accel=2.0):
+    """The first half of intent_agent_step, up to the cut the conflict leaves: (traj_idx, hit, cut, number of resampled ego poses); cut is
+    the path length (speed mode: NO_STOP) where there is no conflict."""
     full = np.ascontiguousarray(full, np.float64)
     x, y, v, yaw = st
     advance = True
@@ -248,22 +259,43 @@ def intent_agent_step(p, full, dl, st, trajs, traj_idx, prev, target, u, centers
     cut = S.NO_STOP if speed else len(full)
     if hit is not None:
         cut = max(traj_idx + 1, orc.cutoff_idx(full, hit[0], hit[1]) - margin)
-    held, line = (0, -1) if decide is None else decide(int(traj_idx), v)
-    if held and line < cut:
-        cut = line
-    if speed:
-        cv = S.speed_profile(len(full), cut, v_ref=v_ref)
-        xref, target_ind, re = orc.calc_ref_trajectory(p, st, full[:, 0], full[:, 1], full[:, 2], dl, target, cv=cv)
-    else:
-        tmp = full[:cut]
-        xref, target_ind, re = orc.calc_ref_trajectory(p, st, tmp[:, 0], tmp[:, 1], tmp[:, 2], dl, target)
-    if target_ind < 0:
-        raise Exception("something wrong")
+    return traj_idx, hit, cut, len(tres)
+
+
+def intent_solve(p, full, dl, st, target, u, cut, speed, v_ref=S.V_REF, caps=(), passes=1):
+    """The second half of intent_agent_step: the window on full[:cut] (speed mode: on the whole path with the speed profile zeroed from
+    cut on and lowered to every positive speed in `caps`), the rollout of the warm start and the QP.  passes > 1: the successive
+    linearisation of lib/mpc.py:226-237 -- every further pass takes its window from the target index of the pass before, spaced by that
+    pass's speeds (row 2 of its x), and its rollout and warm start from that pass's controls.  Returns dict(target_ind, xref, xbar, re,
+    sol) of the last pass and `xref_free`, the last pass's window before the caps."""
+    full = np.ascontiguousarray(full, np.float64)
+    x, y, v, yaw = st
     uw = np.zeros((2, p.T)) if u is None else np.asarray(u, float)
-    xbar = orc.predict_motion(p, [x, y, v, yaw], uw[0], uw[1])
-    sol = orc.qp_solve(p, [x, y, v, yaw], xref, xbar, re, uw)
-    return dict(traj_idx=traj_idx, hit=hit, cut=int(cut), held=int(held), line=int(line), target_ind=target_ind, xref=xref, xbar=xbar, re=re,
-                sol=sol, n_res=len(tres))
+    ov, target_ind, xref_free = None, target, None
+    for _ in range(passes):
+        kw = {} if ov is None else dict(ov=ov)
+        if speed:
+            cv = S.speed_profile(len(full), cut, v_ref=v_ref)
+            free = cv
+            for c in caps:
+                if c > 0.0:
+                    cv = np.minimum(cv, c)
+            xref, target_new, re = orc.calc_ref_trajectory(p, st, full[:, 0], full[:, 1], full[:, 2], dl, target_ind, cv=cv, **kw)
+            if cv is not free:
+                xref_free = orc.calc_ref_trajectory(p, st, full[:, 0], full[:, 1], full[:, 2], dl, target_ind, cv=free, **kw)[0]
+            else:
+                xref_free = xref
+        else:
+            tmp = full[:cut]
+            xref, target_new, re = orc.calc_ref_trajectory(p, st, tmp[:, 0], tmp[:, 1], tmp[:, 2], dl, target_ind, **kw)
+            xref_free = xref
+        target_ind = target_new
+        if target_ind < 0:
+            raise Exception("something wrong")
+        xbar = orc.predict_motion(p, [x, y, v, yaw], uw[0], uw[1])
+        sol = orc.qp_solve(p, [x, y, v, yaw], xref, xbar, re, uw)
+        ov, uw = sol.x[2].copy(), sol.u.copy()
+    return dict(target_ind=target_ind, xref=xref, xbar=xbar, re=re, sol=sol, xref_free=xref_free)
 
 
 def seen_trajectory(p, six, plan, cc, pred_steps):

@@ -41,9 +41,10 @@ def classify(w, q):
     return 'approach', g, s - ti
 
 
-def rule_numpy(w, backwards=False, log=None):
+def rule_numpy(w, backwards=False, log=None, refused=None):
     """the rule restated on a dict of numpy arrays (words()), in place on grant, since, clock, occupied, queued, held and cut_len; returns
-    the agents held.  log: a list that receives (junction, agent, movement, occ before the grant) for every grant given"""
+    the agents held.  log: a list that receives (junction, agent, movement, occ before the grant) for every grant given; refused: a list
+    that receives (junction, agent, movement, occ, blocked, ahead) as they stood for every request denied"""
     n_per, J = int(w['n_per']), len(w['mgr_of'])
     n_mgr = len(w['mgr_time'])
     got = 0
@@ -82,6 +83,8 @@ def rule_numpy(w, backwards=False, log=None):
                 w['grant'][q] = 1
                 occ |= 1 << g
             else:
+                if refused is not None:
+                    refused.append((j, q, g, occ, blocked, ahead))
                 ahead |= 1 << g
                 denied += 1
                 if t - since >= patience:
