@@ -1063,9 +1063,73 @@ typedef struct {
 } mpcx_following;
 /* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
 int32_t mpcx_set_following(mpcx_ctx *ctx, const mpcx_following *following /*NULL or all-zero = off*/);
+
+/* ---- the near-miss log: who came close to whom, how close, and how many frames from a predicted contact.  The run log keeps one clearance
+ * per agent and step and says nothing of the other vehicle; a looming contact is invisible until the discs overlap.  With the safety stage
+ * on, one launch (safety_kernel, csrc/mpcx_safety.hip; the rule is csrc/mpcx_safety_core.h) directly behind the conflict search -- before
+ * the hold stage -- finds for every driving agent the vehicle nearest to it and the first predicted contact, keeps a per-agent table of
+ * ENCOUNTERS in device memory, and mpcx_safety_summary reduces the tables to a CONFLICT MATRIX per pair of movements.  The stage changes no
+ * decision of the loop and no existing buffer: it reads obs6, the prediction of every pool row as the conflict search read it (after the
+ * intent stage), traj_idx as the conflict search left it, path_off, state, done and absent, and writes only its own words, every one a word
+ * of agent q.  It attaches to the CONTEXT (mpcx_set_safety), as following does: every mpcx_closed_loop_run* entry point runs it while set.
+ * For agent q with own row o = obs_skip[q]: THE OTHERS are following's -- the rows of its pool window other than o, in row order, the first
+ * MPCX_MAX_OBS of them, rows outside the pool or with absent[r] != 0 left out; precedence words are not consulted.  NOT MEASURED: done[q]
+ * != 0, o outside the pool, absent[o] != 0, no others -- every per-step word is "none", the open encounter is closed, tick[q] advances.
+ * (1) c_now = the minimum over the others and the 2 x 2 pairs of discs of hypot(..) - 2 radius at the poses of obs6 -- the run log's
+ * clearance of the step, bit for bit --, r_now its row, the lowest slot of equals; nobody: +inf, -1.  (2) d2(r, k) = the minimum over the
+ * 2 x 2 pairs of discs of dx dx + dy dy between frames k of rows o and r of the prediction; k(r) = the lowest k in [0, pred_steps) with
+ * d2(r, k) < (2 radius)^2; (k_ttc, r_ttc) = the smallest k(r), the lowest slot of equals; none: -1, -1.  Frame k is the pose (k + 1) dt
+ * ahead.  (3) partner[q] = r_now, clearance[q] = c_now, ttc_row[q] = r_ttc, ttc_frame[q] = k_ttc.  (4) critical = c_now < near or 0 <=
+ * k_ttc < ttc_frames, the encounter's partner p = r_now if c_now < near, else r_ttc; enc_row[q] is the partner of the open encounter.  Not
+ * critical: enc_row[q] = -1.  Critical and enc_row[q] != p: event e = n_events[q]++ opens, enc_row[q] = p, and if e < capacity its record is
+ * written (an event beyond capacity is counted and tracked, not stored): ev_i32[q][e] = tick[q] (open), tick[q] (last), p, row_agent[p]
+ * (-1 for a scripted actor), path_off[q], path_off[row_agent[p]] (or -1), traj_idx[q], k_ttc; ev_f64[q][e] = c_now, state[q].v.  Critical
+ * and enc_row[q] == p with a stored record: word 1 = tick[q], word 7 = the smaller non-negative of itself and k_ttc, ev_f64[0] =
+ * fmin(itself, c_now).  Last, always: tick[q]++.  Host and device agree bit for bit on the integer words.
+ * NULL or an all-zero struct: off -- the loop enqueues exactly the launches of a context that never had it, with the same arguments.  The
+ * cached graph's key covers the struct by value, and a run with the stage on does not take step fusion.  MPCX_E_INVALID ("safety: ...")
+ * from the run or the stage call before anything is launched, whatever n_steps is: a required pointer NULL (the event arrays only with
+ * capacity > 0); n_rows != P; n_pool not the run's pool rows; near not finite or negative; ttc_frames outside 0..pred_steps; capacity < 0;
+ * a radius that is not finite; a nonzero reserved word; no obs_skip; the agent-sharded layout. */
+typedef struct {
+    int32_t *partner;            /* n_rows = P, caller-owned, out: the pool row nearest to agent q in the last step, -1 = none */
+    double *clearance;           /* n_rows, out: its clearance (m), +inf = none */
+    int32_t *ttc_row;            /* n_rows, out: the pool row of the first predicted contact, -1 = none */
+    int32_t *ttc_frame;          /* n_rows, out: its frame; the contact is (frame + 1) dt ahead; -1 = none */
+    int32_t *tick;               /* n_rows, in-out (zero-initialised): steps the stage has run for the agent */
+    int32_t *enc_row;            /* n_rows, in-out (initialised to -1): the partner row of the open encounter */
+    int32_t *n_events;           /* n_rows, in-out (zero-initialised): encounters opened so far, stored or not */
+    int32_t *ev_i32;             /* n_rows x capacity x 8, out: the event records' integer words */
+    double *ev_f64;              /* n_rows x capacity x 2, out: minimum clearance of the event, the agent's speed when it opened */
+    const int32_t *row_agent;    /* n_pool: the agent that owns pool row r, -1 (or anything outside [0, P)) for a scripted actor */
+    double near;                 /* an encounter is open while the clearance is below this (finite, >= 0, m) */
+    int32_t ttc_frames;          /* ... or a contact is predicted in fewer frames than this (0..pred_steps) */
+    int32_t capacity;            /* event records per agent (>= 0; 0: ev_i32 and ev_f64 may be NULL) */
+    int32_t n_rows, n_pool, reserved;    /* reserved: 0 */
+} mpcx_safety;
+/* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
+int32_t mpcx_set_safety(mpcx_ctx *ctx, const mpcx_safety *safety /*NULL or all-zero = off*/);
+/* one step's safety stage alone (what the closed loop enqueues behind the conflict search).  pred: n_obs_pool x ip->pred_steps x 4 doubles
+ * ([row][frame][2 discs][2]), DEVICE, or NULL = the context's own prediction as its last conflict search left it; ip gives radius,
+ * circle_centers, pred_steps and dt.  The struct is the argument's, not the context's, and is checked as above. */
+int32_t mpcx_safety_step_batch(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state /*P,4*/,
+                               const int32_t *path_off /*P*/, const int32_t *traj_idx /*P*/, const int32_t *done /*P or NULL*/,
+                               int32_t n_obs_pool, const double *obs6 /*NOBS,6*/, const double *pred /*NOBS,pred_steps,4 or NULL*/,
+                               const int32_t *obs_off /*P*/, const int32_t *obs_cnt /*P*/, const int32_t *obs_skip /*P*/,
+                               const int32_t *absent /*NOBS or NULL*/, const mpcx_safety *safety);
+/* the conflict matrix, reduced on the device (one wavefront per instance of A consecutive agents): over the stored events (e <
+ * min(n_events[q], capacity)) per pair (class of q, class of the partner).  The class of an event side is the route r with route_off[r] ==
+ * its path_off word (words 4 and 5), the lowest r of equals; class R = no route (an actor, or an unknown offset).  out_i64[b][R+1][R+1][3]:
+ * events, events with minimum clearance < 0, events whose word 7 >= 0.  out_f64[b][R+1][R+1][2]: the minimum of the minimum clearance (a NaN
+ * is skipped; +inf: no events), the minimum over the events with word 7 >= 0 of (word 7 + 1) dt (+inf: none).  Integer sums and minima
+ * only: exact whatever the lane mapping.  Every pointer is a DEVICE pointer. */
+int32_t mpcx_safety_summary(mpcx_ctx *ctx, int32_t P, int32_t A, int32_t capacity, int32_t R, const int32_t *route_off /*R*/, double dt,
+                            const int32_t *n_events /*P*/, const int32_t *ev_i32 /*P,capacity,8*/, const double *ev_f64 /*P,capacity,2*/,
+                            int64_t *out_i64 /*P/A,R+1,R+1,3*/, double *out_f64 /*P/A,R+1,R+1,2*/);
+
 /* ---- the stages together.  With several optional stages on, a step is: admission, the entry-order stamp; pool pack and prediction; the
- * intent stage; the conflict search; the hold (signal, actuated or reserve stage); the following stage; per linearisation pass the window
- * stage, the advice stage, the following clamp and the QP; the plant; record, retire, respawn.  What that order implies:
+ * intent stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the following stage; per linearisation
+ * pass the window stage, the advice stage, the following clamp and the QP; the plant; record, retire, respawn.  What that order implies:
  *   one car, three views   agent q sees a present row r of its window (1) standing at its pose if prec[r] > prec[obs_skip[q]], whatever
  *                          the intent stage wrote into r's predicted frames; (2) else on its owner's plan of the step before, if the owner
  *                          shares, drives, is present and its last status is MPCX_QP_OPTIMAL; (3) else through the constant prediction.
@@ -1075,7 +1139,11 @@ int32_t mpcx_set_following(mpcx_ctx *ctx, const mpcx_following *following /*NULL
  *   a reset slot           the respawn stages reset no word of the signal, reservation, following or intent stages, nor status.  Each of
  *                          those stages rewrites its words for every agent in every step, retired ones included; a slot that is admitted
  *                          again in the very next step starts from what its predecessor's last step left (held, granted, since), and its
- *                          signal clock runs on.
+ *                          signal clock runs on.  Nor do they reset a word of the safety stage: tick, enc_row and n_events run on and
+ *                          a slot's event table holds the events of every vehicle it carried; an event carries its ticks and path_off,
+ *                          which is enough to join it with the episode table on the host.
+ *   the safety stage       reads the prediction exactly as the conflict search read it and traj_idx as it left it; it writes no word any
+ *                          other stage reads.
  * tests/stack_helpers.py composes the host builds of the rules in this order; tests/test_gpu_stack.py replays the device against it. */
 /* one step's search stage alone (what the closed loop enqueues in front of the window stage): steps 1 - 5.  stop_mode: MPCX_STOP_CUT or
  * MPCX_STOP_SPEED; the struct is the argument's, not the context's, and is checked as above. */

@@ -144,6 +144,22 @@ class FollowingC(C.Structure):
                 ('n_rows', C.c_int32), ('reserved', C.c_int32)]
 
 
+class SafetyC(C.Structure):
+    """mirror of mpcx_safety (include/mpcx.h): the near-miss log; every pointer is a device address -- partner, ttc_row, ttc_frame, tick,
+    enc_row, n_events (n_rows = P int32), clearance (n_rows float64), ev_i32 (n_rows x capacity x 8 int32), ev_f64 (n_rows x capacity x 2
+    float64), row_agent (n_pool int32, in).  Not a row of STAGES: the stage attaches to the context (Context.set_safety)"""
+    _fields_ = [('partner', C.c_void_p), ('clearance', C.c_void_p), ('ttc_row', C.c_void_p), ('ttc_frame', C.c_void_p), ('tick', C.c_void_p),
+                ('enc_row', C.c_void_p), ('n_events', C.c_void_p), ('ev_i32', C.c_void_p), ('ev_f64', C.c_void_p), ('row_agent', C.c_void_p),
+                ('near', C.c_double), ('ttc_frames', C.c_int32), ('capacity', C.c_int32), ('n_rows', C.c_int32), ('n_pool', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+# the words of an event record of the near-miss log (ev_i32[q][e][0..7]; ev_f64[q][e] = the minimum clearance, the agent's speed at opening)
+SAFETY_I32 = ('open', 'last', 'row', 'row_agent', 'path_off', 'partner_path_off', 'traj_idx', 'ttc_frame')
+SAFETY_F64 = ('min_clearance', 'v')
+# the columns of mpcx_safety_summary's tables (out_i64[b][i][j][0..2], out_f64[b][i][j][0..1])
+SAFETY_SUMMARY_I64 = ('events', 'contacts', 'predicted')
+SAFETY_SUMMARY_F64 = ('min_clearance', 'min_ttc')
 MAX_REMAINING = 1024                            # MPCX_MAX_REMAINING: the largest mpcx_following.reach
 SIGNAL_GROUPS_MAX = 16                          # MPCX_SIGNAL_GROUPS_MAX
 RESERVE_PER_MAX = 64                            # MPCX_RESERVE_PER_MAX: agents per junction under reservations
@@ -301,7 +317,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_admit_step_batch', 'mpcx_respawn_step_batch', 'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary',
            'mpcx_admit_step_batch_precedence', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
            'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
-           'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch'] + LOOP_ENTRY_POINTS
+           'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch',
+           'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary'] + LOOP_ENTRY_POINTS
 
 
 def load():
@@ -401,5 +418,10 @@ def load():
     lib.mpcx_follow_step_batch.argtypes = [vp, i32, C.c_double, i32] + [vp] * 7 + [i32] + [vp] * 5 + [C.POINTER(FollowingC)]
     lib.mpcx_follow_cap_step_batch.restype = i32
     lib.mpcx_follow_cap_step_batch.argtypes = [vp, i32, vp, C.POINTER(FollowingC), vp]
+    lib.mpcx_set_safety.restype = i32; lib.mpcx_set_safety.argtypes = [vp, C.POINTER(SafetyC)]
+    lib.mpcx_safety_step_batch.restype = i32
+    lib.mpcx_safety_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 4 + [i32] + [vp] * 6 + [C.POINTER(SafetyC)]
+    lib.mpcx_safety_summary.restype = i32
+    lib.mpcx_safety_summary.argtypes = [vp, i32, i32, i32, i32, vp, C.c_double] + [vp] * 5
     _lib = lib
     return lib

@@ -45,6 +45,9 @@ served; everybody else waits at its stop line.  The launch takes the place of th
 `follow()` is CAR FOLLOWING, beside every other stage and in both stop modes: every agent finds the nearest vehicle ahead on its own path
 and stops a standstill distance plus a time gap behind it -- the hold at a line that moves --, in speed mode under Gipps' safe speed as a
 cap on its speed reference (one launch in front of the window stage, in speed mode one behind it).
+`watch_safety()` is THE NEAR-MISS LOG, beside every other stage: one launch behind the conflict search names every agent's nearest vehicle
+and its first predicted contact and keeps a table of encounters on the device; near_misses() reads it, conflict_matrix() reduces it per
+pair of movements.  It decides nothing.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -62,6 +65,9 @@ RUN_LOG_MAX_BYTES = 1 << 30     # attach_log refuses a larger log unless told ot
 EPISODE_DTYPE = np.dtype([(n, '<i4') for n in ('slot', 'generation', 'due', 'entered', 'arrived', 'steps_driven', 'delay')] + [('contact', '?'),
                          ('min_clearance', '<f8'), ('row_begin', '<i4'), ('row_end', '<i4')])
 MOVEMENT_DTYPE = np.dtype([(n, '<i8') for n in _lib.SUMMARY_I64] + [('min_clearance', '<f8')])
+# IntersectionBatch.near_misses() and conflict_matrix(): an event of the near-miss log, a cell of the conflict matrix
+NEAR_MISS_DTYPE = np.dtype([('agent', '<i4')] + [(n, '<i4') for n in _lib.SAFETY_I32] + [('min_clearance', '<f8'), ('v', '<f8'), ('ttc', '<f8')])
+CONFLICT_DTYPE = np.dtype([(n, '<i8') for n in _lib.SAFETY_SUMMARY_I64] + [(n, '<f8') for n in _lib.SAFETY_SUMMARY_F64])
 # IntersectionBatch.snapshot(): stage -> (key, attribute) of the device words it adds while the stage is on.  precedence: the word of every
 # pool row; held: 0 free, 1 at red, 2 at amber; advised: the speed advised in the last step, 0 = none; shared_frames: frames of the agent's
 # own row taken from its plan in the last step; granted, since: per agent; occupied: per junction, the movements on the crossing
@@ -385,6 +391,12 @@ class IntersectionBatch:
         self.gap: Optional[torch.Tensor] = None              # ... float64 (P,), the distance to it along the agent's path, -1 = none
         self.follow_cap: Optional[torch.Tensor] = None       # ... float64 (P,), the safe speed behind it, 0 = none
         self._following = None                               # (not a stage of _lib.STAGES: it is set on the context, _claim_context)
+        self.partner: Optional[torch.Tensor] = None          # watch_safety(): int32 (P,), the pool row nearest to the agent in the last step, -1 = none
+        self.near_clearance: Optional[torch.Tensor] = None   # ... float64 (P,), its clearance, +inf = none
+        self.ttc_row: Optional[torch.Tensor] = None          # ... int32 (P,), the pool row of the first predicted contact, -1 = none
+        self.ttc_frame: Optional[torch.Tensor] = None        # ... int32 (P,), its frame: (frame + 1) ip.dt seconds ahead, -1 = none
+        self.n_events: Optional[torch.Tensor] = None         # ... int32 (P,), encounters opened so far, stored or not
+        self._safety = None                                  # (set on the context too)
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -807,6 +819,86 @@ class IntersectionBatch:
         self._following = None
         self._desc = None
 
+    def watch_safety(self, near: float = 0.5, ttc: float = 2.0, capacity: int = 8):
+        """THE NEAR-MISS LOG (mpcx_set_safety), beside every other stage and in both stop modes: one more launch directly behind the conflict
+        search finds, for every driving agent, the vehicle of its pool window nearest to it (`partner`, `near_clearance`: the run log's
+        clearance with a name to it) and the first frame of the prediction in which its discs touch another's (`ttc_row`, `ttc_frame`), and
+        keeps a table of ENCOUNTERS per agent in device memory: an event opens when the clearance falls below `near` metres or a contact is
+        predicted within `ttc` seconds (floor(ttc / ip.dt) frames), follows the same partner, and closes when neither holds; `capacity`
+        events are stored per agent, further ones are counted.  The stage changes no decision and no other buffer.  near_misses() reads
+        the events back, conflict_matrix() reduces them per pair of movements on the device.  Allocates the words (partner, ttc_row,
+        ttc_frame, the open encounter = -1; near_clearance = +inf; the rest = 0) and drops the cached descriptor; stop_watching() switches
+        it off.  Slots that respawn keep counting: an event carries its ticks and path_off."""
+        if self.exchange == 'rccl' or callable(self.exchange):
+            raise ValueError('watch_safety: not in the agent-sharded layout (shard by instances)')
+        if self.obs_skip is None:
+            raise ValueError('watch_safety: the batch has no obs_skip (the agents\' own pool rows)')
+        near, ttc, capacity = float(near), float(ttc), int(capacity)
+        if not (np.isfinite(near) and near >= 0 and np.isfinite(ttc) and ttc >= 0 and capacity >= 0):
+            raise ValueError('watch_safety: near >= 0, ttc >= 0, both finite, capacity >= 0')
+        frames = min(int(np.floor(ttc / float(self.ip.dt))), int(self.ip.pred_steps))
+        dev, P, rows = self.ctx.device, self.P, int(self.obs6.shape[0])
+        owner = np.full(rows, -1, np.int32)
+        own = self.obs_skip.cpu().numpy()
+        ok = (own >= 0) & (own < rows)
+        owner[own[ok]] = np.arange(P, dtype=np.int32)[ok]
+        self._row_agent = self.ctx.i32(owner)
+        full = lambda v, dt: torch.full((P,), v, dtype=dt, device=dev)
+        self.partner, self.ttc_row, self.ttc_frame, self._enc_row = (full(-1, torch.int32) for _ in range(4))
+        self.near_clearance = full(float('inf'), torch.float64)
+        self._safety_tick, self.n_events = full(0, torch.int32), full(0, torch.int32)
+        self._ev_i32 = torch.zeros((P, capacity, 8), dtype=torch.int32, device=dev)
+        self._ev_f64 = torch.zeros((P, capacity, 2), dtype=torch.float64, device=dev)
+        self._safety = _lib.SafetyC(self.partner.data_ptr(), self.near_clearance.data_ptr(), self.ttc_row.data_ptr(), self.ttc_frame.data_ptr(),
+                                    self._safety_tick.data_ptr(), self._enc_row.data_ptr(), self.n_events.data_ptr(),
+                                    self._ev_i32.data_ptr() if capacity else None, self._ev_f64.data_ptr() if capacity else None,
+                                    self._row_agent.data_ptr(), near, frames, capacity, P, rows, 0)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def stop_watching(self):
+        """switch the near-miss log off and nothing else: the batch enqueues exactly the launches of one that never had it (the words and
+        the events keep what they hold and are no longer written)"""
+        self._safety = None
+        self._desc = None
+
+    def near_misses(self) -> np.ndarray:
+        """the stored events of the near-miss log, in agent order and, per agent, in the order they opened (synchronises): a structured
+        array of NEAR_MISS_DTYPE -- agent, the words of _lib.SAFETY_I32 (open and last tick, the partner's pool row, row_agent: the agent that owns it
+        or -1 for a scripted car, the two path offsets, traj_idx at opening, the smallest frame of a predicted contact or -1), min_clearance,
+        v (the agent's speed at opening) and ttc = (ttc_frame + 1) ip.dt seconds, +inf without a predicted contact"""
+        if self.n_events is None:
+            raise MpcxError('near_misses(): watch_safety() has not been called')
+        self.ctx.synchronize()
+        wi, wf, n = self._ev_i32.cpu().numpy(), self._ev_f64.cpu().numpy(), self.n_events.cpu().numpy()
+        q, e = np.nonzero(np.arange(wi.shape[1])[None, :] < n[:, None])
+        out = np.zeros(len(q), NEAR_MISS_DTYPE)
+        out['agent'] = q
+        for k, name in enumerate(_lib.SAFETY_I32):
+            out[name] = wi[q, e, k]
+        out['min_clearance'], out['v'] = wf[q, e, 0], wf[q, e, 1]
+        out['ttc'] = np.where(out['ttc_frame'] >= 0, (out['ttc_frame'] + 1.0) * float(self.ip.dt), np.inf)
+        return out
+
+    def conflict_matrix(self, routes=None) -> np.ndarray:
+        """the conflict matrix of the near-miss log, reduced on the device (mpcx_safety_summary; one small launch; synchronises): a
+        structured array (B, R + 1, R + 1) of CONFLICT_DTYPE -- per instance and pair (movement of the agent, movement of its partner),
+        over the stored events: events, contacts (events whose minimum clearance is negative), predicted (events with a predicted
+        contact), min_clearance and min_ttc in seconds (+inf: none).  routes: the route indices that are the classes, None = every
+        route of the batch in order; class R -- the last row and column -- is "no route": a scripted car, or a route not listed."""
+        if self.n_events is None:
+            raise MpcxError('conflict_matrix(): watch_safety() has not been called')
+        offs = self._route_offs[:-1] if routes is None else self._route_offs[:-1][np.asarray(routes, dtype=np.int64)]
+        out_i, out_f = self.ctx.safety_summary(self.A, self.ctx.i32(offs.astype(np.int32)), float(self.ip.dt), self.n_events, self._ev_i32, self._ev_f64)
+        self.ctx.synchronize()
+        wi, wf = out_i.cpu().numpy(), out_f.cpu().numpy()
+        out = np.zeros(wi.shape[:3], CONFLICT_DTYPE)
+        for k, name in enumerate(_lib.SAFETY_SUMMARY_I64):
+            out[name] = wi[..., k]
+        for k, name in enumerate(_lib.SAFETY_SUMMARY_F64):
+            out[name] = wf[..., k]
+        return out
+
     def share_plans(self, share=None):
         """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
         it applied in the last step, held for pred_steps frames -- the reference's prediction of a scripted car.  A sharing agent is seen
@@ -1073,6 +1165,7 @@ class IntersectionBatch:
             self.ctx.set_linearisation_passes(self.lin_passes)
         self.ctx.set_instance_tuning(self.tuning)
         self.ctx.set_following(self._following)
+        self.ctx.set_safety(self._safety)
 
     def run(self, n_steps: int, graph: bool = False):
         """n_steps of the closed loop with no host work in between (mpcx_closed_loop_run)."""
@@ -1144,6 +1237,8 @@ class IntersectionBatch:
         c.interaction(self.ip, self.state, self.path, self.path_cs, self.path_off, self.path_len,
                       self.prev_len if speed else self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self.obs_skip,
                       self.traj_idx, out=self.inter, intent=self._intent, u_sol=self.sol['u'], status=self.sol['status'])
+        if self._safety is not None:        # the safety stage: directly behind the conflict search, on the prediction it read, as in the loop
+            c.safety_step(self.ip, self.state, self.path_off, self.traj_idx, self.obs6, self.obs_off, self.obs_cnt, self.obs_skip, self._safety)
         if self._reservation is not None:   # the reservation stage, in the place of the signal stage
             c.reserve_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._reservation)
         elif self._actuation is not None:   # the actuated signal stage, in the place of the signal stage
@@ -1193,6 +1288,10 @@ class IntersectionBatch:
                 out.update({key: getattr(self, attr).cpu().numpy().copy() for key, attr in words})
         if self._following is not None:      # the leader's pool row (-1 = none), the distance to it and the safe speed behind it, last step's
             out.update(leader=self.leader.cpu().numpy().copy(), gap=self.gap.cpu().numpy().copy(), follow_cap=self.follow_cap.cpu().numpy().copy())
+        if self._safety is not None:         # the nearest vehicle and the first predicted contact of the last step, the encounters so far
+            out.update(partner=self.partner.cpu().numpy().copy(), near_clearance=self.near_clearance.cpu().numpy().copy(),
+                       ttc_row=self.ttc_row.cpu().numpy().copy(), ttc_frame=self.ttc_frame.cpu().numpy().copy(),
+                       n_events=self.n_events.cpu().numpy().copy())
         if self._routes is not None:         # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed

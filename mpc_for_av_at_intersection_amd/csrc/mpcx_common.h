@@ -17,11 +17,13 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1480] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1600] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     mpcx_following following = {};        // car following (mpcx_set_following): the struct by value, padding zeroed; all zeros while off
     bool have_following = false;
+    mpcx_safety safety = {};              // the near-miss log (mpcx_set_safety): the struct by value, padding zeroed; all zeros while off
+    bool have_safety = false;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
     const int32_t *order_now = nullptr, *order_prev = nullptr;   // optional pair: entries that differ mark a discontinuous change of the reference
     // scratch of mpcx_closed_loop_run for P agents: [P] cut lengths of the previous step | [3 P] what the conflict search's nearest-index
@@ -241,6 +243,14 @@ int32_t mpcx_follow_enqueue(mpcx_ctx *ctx, int32_t P, double dl, bool speed, con
                             const int32_t *obs_cnt, const int32_t *obs_skip /*or nullptr*/, const int32_t *absent /*or nullptr*/,
                             const mpcx_following *following);
 int32_t mpcx_follow_cap_enqueue(mpcx_ctx *ctx, int32_t P, const int32_t *done /*or nullptr*/, const mpcx_following *following, double *xref);
+// the near-miss log (mpcx_safety.hip): "no safety stage" test, check of the struct against the run (n_pool: its pool rows), the launch alone
+// (directly behind the conflict search; pred: n_obs_pool x pred_steps x 4 doubles)
+bool mpcx_safety_absent(const mpcx_safety *s);
+int32_t mpcx_safety_validate(mpcx_ctx *ctx, const mpcx_safety *s, const mpcx_interaction_params *ip, int32_t P, int32_t n_pool, int32_t exchange);
+int32_t mpcx_safety_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, int32_t P, const double *state, const int32_t *path_off,
+                            const int32_t *traj_idx, const int32_t *done /*or nullptr*/, int32_t n_obs_pool, const double *obs6,
+                            const double *pred, const int32_t *obs_off, const int32_t *obs_cnt, const int32_t *obs_skip,
+                            const int32_t *absent /*or nullptr*/, const mpcx_safety *safety);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -100,10 +100,14 @@ struct LoopStages {
     // behind the agent's leader before the window stage reads it and writes leader, gap and cap; in MPCX_STOP_SPEED follow_clamp_kernel
     // behind every window stage (and the advice stage) caps row 2 of c->xref.  &ctx->following while on.
     const mpcx_following *follow = nullptr;
+    // the near-miss log (mpcx_set_safety: it attaches to the context too): safety_kernel directly behind the conflict search, before the
+    // hold; needs the local pool and obs_skip.  It reads obs6, ctx->pred and traj_idx as the conflict search left them and writes only the
+    // struct's own words: no other launch of the step sees it.  &ctx->safety while on.
+    const mpcx_safety *safety = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -115,6 +119,7 @@ struct LoopKey {
     mpcx_run_log log; mpcx_closed_loop_opts opts; mpcx_retire retire; mpcx_scene scene; mpcx_admit admit; mpcx_respawn respawn;
     mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice; mpcx_intent intent; mpcx_reservation reservation;
     mpcx_following following;
+    mpcx_safety safety;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -214,10 +219,16 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         rc = mpcx_following_validate(ctx, &ctx->following, c->P, c->exchange);
         if (rc == MPCX_OK) st->follow = &ctx->following;
     }
+    if (rc != MPCX_OK) return rc;
+    if (ctx->have_safety) {
+        if (!c->obs_skip) return mpcx_fail(ctx, MPCX_E_INVALID, "safety: the descriptor has no obs_skip (the agents' own pool rows)");
+        rc = mpcx_safety_validate(ctx, &ctx->safety, ip, c->P, c->n_actors > 0 ? c->pool_rows : c->P, c->exchange);
+        if (rc == MPCX_OK) st->safety = &ctx->safety;
+    }
     return rc;
 }
 
-// The middle of a step, the same on both paths: the conflict search (-> the signal stage) (-> the following stage) -> lin_passes x (reference
+// The middle of a step, the same on both paths: the conflict search (-> the safety stage) (-> the signal stage) (-> the following stage) -> lin_passes x (reference
 // window (-> the advice stage) (-> the following clamp) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
@@ -241,6 +252,11 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
                                           speed ? st.opts.prev_len : c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows,
                                           c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, c->traj_idx, c->hit_idx, c->hit_xy, c->cut_len, ix);
     if (rc != MPCX_OK) return rc;
+    if (st.safety) {
+        rc = mpcx_safety_enqueue(ctx, ip, P, c->state, c->path_off, c->traj_idx, done, pool_rows, c->obs6, ctx->pred, c->obs_off, c->obs_cnt,
+                                 c->obs_skip, ix.absent, st.safety);
+        if (rc != MPCX_OK) return rc;
+    }
     if (st.signals) {
         rc = st.reserve  ? mpcx_reserve_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, st.reserve)
            : st.actuated ? mpcx_actuated_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, &st.actuation)
@@ -477,6 +493,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.respawn, st.respawn); key_put(key.routes, st.routes); key_put(key.precedence, st.precedence); key_put(key.signals, st.signals);
     key_put(key.advice, st.advice); key_put(key.intent, st.intent); key_put(key.reservation, st.reserve);
     key_put(key.following, st.follow);
+    key_put(key.safety, st.safety);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;

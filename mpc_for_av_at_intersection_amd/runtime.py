@@ -856,6 +856,57 @@ class Context:
         self._chk(self.lib.mpcx_set_following(self._ctx, None if following is None else C.byref(following)))
         self._following = following
 
+    def set_safety(self, safety: Optional['_lib.SafetyC']):
+        """mpcx_set_safety: the near-miss log for every closed-loop run of this context from now on; None (or an all-zero struct) = off.
+        The context copies the struct; the device buffers it names stay the caller's and are kept alive here while set."""
+        self._chk(self.lib.mpcx_set_safety(self._ctx, None if safety is None else C.byref(safety)))
+        self._safety = safety
+
+    @_ordered
+    def safety_step(self, ip: InteractionParams, state, path_off, traj_idx, obs6, obs_off, obs_cnt, obs_skip, safety: '_lib.SafetyC', pred=None,
+                    done=None, absent=None):
+        """mpcx_safety_step_batch: ONE step's safety stage as the closed loop enqueues it behind the conflict search: the struct's per-step
+        words, encounter words and event records are written.  obs6 (pool rows, 6): the pool as the head of the step packed it; pred
+        (pool rows, ip.pred_steps, 2, 2) float64: the predicted disc centres, None = the context's own prediction as its last conflict
+        search (interaction() or a closed-loop step) left it; done: the retirement words (P int32), absent: the scene's words (pool rows),
+        or None."""
+        Pn, rows = int(state.shape[0]), int(obs6.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state'); self._want(obs6, torch.float64, (rows, 6), 'obs6')
+        for name, t in (('path_off', path_off), ('traj_idx', traj_idx), ('obs_off', obs_off), ('obs_cnt', obs_cnt), ('obs_skip', obs_skip),
+                        ('done', done)):
+            if t is not None:
+                self._want(t, torch.int32, (Pn,), name)
+        if absent is not None:
+            self._want(absent, torch.int32, (rows,), 'absent')
+        if pred is not None:
+            self._want(pred, torch.float64, (rows, int(ip.pred_steps), 2, 2), 'pred')
+        cip = ip.to_c()
+        self._chk(self.lib.mpcx_safety_step_batch(self._ctx, C.byref(cip), Pn, _ptr(state), _ptr(path_off), _ptr(traj_idx), _ptr(done), rows,
+                                                  _ptr(obs6), _ptr(pred), _ptr(obs_off), _ptr(obs_cnt), _ptr(obs_skip), _ptr(absent),
+                                                  C.byref(safety)))
+
+    @_ordered
+    def safety_summary(self, A: int, route_off, dt: float, n_events, ev_i32, ev_f64):
+        """mpcx_safety_summary: the conflict matrix of the near-miss log per instance of A consecutive agents and pair of movements, reduced
+        on the device.  route_off (R,) int32: the routes' offsets into the path tables (an event side whose path_off word is none of them
+        is class R: an actor, or an unknown offset); n_events (P,), ev_i32 (P, capacity, 8) int32, ev_f64 (P, capacity, 2) float64, P = B A.
+        Returns device tensors (B, R + 1, R + 1, 3) int64 -- _lib.SAFETY_SUMMARY_I64: events, events with a contact, events with a predicted
+        contact -- and (B, R + 1, R + 1, 2) float64 -- the minimum clearance and the shortest time to a predicted contact (s); +inf: none."""
+        Pn, cap = int(ev_i32.shape[0]), int(ev_i32.shape[1])
+        R = 0 if route_off is None else int(route_off.shape[0])
+        self._want(n_events, torch.int32, (Pn,), 'n_events'); self._want(ev_i32, torch.int32, (Pn, cap, 8), 'ev_i32')
+        self._want(ev_f64, torch.float64, (Pn, cap, 2), 'ev_f64')
+        if route_off is not None:
+            self._want(route_off, torch.int32, (R,), 'route_off')
+        if A < 1 or Pn % int(A):
+            raise MpcxError('safety_summary: %d agents do not divide into instances of %d (MPCX_E_INVALID)' % (Pn, A))
+        B = Pn // int(A)
+        out_i = torch.zeros((B, R + 1, R + 1, 3), dtype=torch.int64, device=self.device)
+        out_f = torch.full((B, R + 1, R + 1, 2), float('inf'), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.mpcx_safety_summary(self._ctx, Pn, int(A), cap, R, _ptr(route_off), float(dt), _ptr(n_events), _ptr(ev_i32),
+                                               _ptr(ev_f64), _ptr(out_i), _ptr(out_f)))
+        return out_i, out_f
+
     @_ordered
     def follow_step(self, dl: float, stop_mode: int, state, path, path_off, path_len, traj_idx, cut_len, obs6, obs_off, obs_cnt,
                     following: '_lib.FollowingC', obs_skip=None, done=None, absent=None):
