@@ -1127,8 +1127,61 @@ int32_t mpcx_safety_summary(mpcx_ctx *ctx, int32_t P, int32_t A, int32_t capacit
                             const int32_t *n_events /*P*/, const int32_t *ev_i32 /*P,capacity,8*/, const double *ev_f64 /*P,capacity,2*/,
                             int64_t *out_i64 /*P/A,R+1,R+1,3*/, double *out_f64 /*P/A,R+1,R+1,2*/);
 
+/* ---- line of sight: buildings hide cars from each other.  Without it the conflict search of agent q reads the prediction of every present
+ * row of its window, wherever that car is.  With the sight stage on, one launch (sight_kernel, csrc/mpcx_sight.hip; the rule is
+ * csrc/mpcx_sight_core.h) behind the pack of the pool and the intent stage and in front of the conflict search decides, per agent, which rows
+ * of its window it sees, and the conflict search takes its SIGHT instantiation (csrc/mpcx_interaction_sight.hip), which ANDs the agent's word
+ * onto its ballot of present rows: a row agent q cannot see is, for q and only for q, an absent row.  It attaches to the CONTEXT
+ * (mpcx_set_sight), as following and the near-miss log do: every mpcx_closed_loop_run* entry point runs it while set, and it needs
+ * retirement and a scene (the conflict search's list of present rows is the scene's).  The per-stage entry points mpcx_interaction_batch and
+ * mpcx_interaction_batch_intent carry no scene and therefore never take the SIGHT instantiation.
+ * For agent q with own row o = obs_skip[q], eye E = (state[q].x, state[q].y) and window offset j < min(obs_cnt[q], 64), r = obs_off[q] + j:
+ * NOT A CANDIDATE if r is outside the pool, r == o or absent[r] != 0 -- bit j = 0, not counted.  OUT OF RANGE if dx dx + dy dy > range range
+ * with (dx, dy) = T - E, T = the (x, y) of obs6[r]: hidden (no trig, no car extent: the reference point stands for the car).  In range and
+ * heard[r] != 0: seen, the occluders are not consulted (a connected vehicle announces its pose).  Otherwise seen iff no occluder of the
+ * agent's set blocks the segment E -> T.  OCCLUDERS are convex polygons as half-plane rows (a, b, c), inside <=> a x + b y + c <= 0, CSR:
+ * occluder i has the rows hp[3 hp_off[i] .. 3 hp_off[i + 1]) and the host-computed box box[4 i ..] = (x0, y0, x1, y1); set s is the occluders
+ * set_off[s] .. set_off[s + 1), agent q's set is set_of[q]; an empty set is an open junction, so a sweep of worlds is one batch.  An occluder
+ * is skipped if the segment's own box misses its box (four comparisons, part of the rule); else Cyrus-Beck: t_in = 0, t_out = 1, per row den =
+ * a dx + b dy, num = -((a Ex + b Ey) + c); den == 0 and num < 0: outside, the polygon is finished; den > 0: t_out = min(t_out, num / den); den
+ * < 0: t_in = max(t_in, num / den); it blocks iff it was not left early and t_in < t_out (strict: a grazing segment is not blocked; an eye
+ * or a target inside is blocked; T == E is blocked iff E is inside).  A shrink of the occluders (a car whose centre is just behind a corner
+ * is seen by its body) is applied by the host when it builds the table.  OUTPUTS, every one a word of agent q, no atomics: sight[q] bit j =
+ * the row at window offset j is seen, n_seen[q] its population count, n_hidden[q] the candidates that are not seen; a retired agent
+ * (done[q] != 0) writes 0, 0, 0.  Host and device agree bit for bit.
+ * NULL or an all-zero struct: off -- the loop enqueues exactly the launches of a context that never had it, with the same arguments.  The
+ * cached graph's key covers the struct by value, and a run with the stage on does not take step fusion.  MPCX_E_INVALID ("sight: ...") from
+ * the run or the stage call before anything is launched, whatever n_steps is: a required pointer NULL (heard may be NULL; hp and box only
+ * with n_occ > 0); n_rows != P; n_pool not the run's pool rows; range NaN or not positive (+inf is allowed); n_sets < 1; n_occ < 0; set_off
+ * not non-decreasing from 0 within 0..n_occ; hp_off not non-decreasing from 0; a run without retirement and a scene; a nonzero reserved
+ * word; no obs_skip (from the stage call; in a run the scene it lives on refuses that first, as it refuses the agent-sharded layout).  The
+ * two offset tables are read back from the device for their check (two blocking copies) ONCE per struct: the context remembers the
+ * pointers and counts that passed and forgets them when mpcx_set_sight is given a struct that differs from the one it holds, so run(1) in
+ * a loop reads nothing back.  Do not change the tables in place while set; after mpcx_set_sight(NULL) a new mpcx_set_sight has them
+ * checked again.  set_of is NOT read back: the Python layer checks it on the host, and the rule takes a word outside [0, n_sets) as the
+ * empty set, so a bad word never reads outside the tables. */
+typedef struct {
+    uint64_t *sight;             /* n_rows = P, caller-owned, out: bit j = the row at window offset j of agent q is seen */
+    int32_t *n_seen, *n_hidden;  /* n_rows each, out: rows seen; candidates not seen */
+    const double *hp;            /* hp_off[n_occ] x 3: the half-plane rows (a, b, c) of every occluder */
+    const int32_t *hp_off;       /* n_occ + 1: occluder i has the rows hp_off[i] .. hp_off[i + 1] */
+    const double *box;           /* n_occ x 4: (x0, y0, x1, y1) of every occluder */
+    const int32_t *set_off;      /* n_sets + 1: set s is the occluders set_off[s] .. set_off[s + 1] */
+    const int32_t *set_of;       /* n_rows: the set of agent q */
+    const int32_t *heard;        /* n_pool or NULL: != 0 = the row is seen wherever it is in range */
+    double range;                /* the sensor range (m); > 0, +inf allowed */
+    int32_t n_occ, n_sets, n_rows, n_pool, reserved;    /* reserved: 0 */
+} mpcx_sight;
+/* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
+int32_t mpcx_set_sight(mpcx_ctx *ctx, const mpcx_sight *sight /*NULL or all-zero = off*/);
+/* one step's sight stage alone (what the closed loop enqueues in front of the conflict search), on the pool as packed in obs6.  The struct
+ * is the argument's, not the context's, and is checked as above. */
+int32_t mpcx_sight_step_batch(mpcx_ctx *ctx, int32_t P, const double *state /*P,4*/, const int32_t *done /*P or NULL*/, int32_t n_obs_pool,
+                              const double *obs6 /*NOBS,6*/, const int32_t *obs_off /*P*/, const int32_t *obs_cnt /*P*/,
+                              const int32_t *obs_skip /*P*/, const int32_t *absent /*NOBS or NULL*/, const mpcx_sight *sight);
+
 /* ---- the stages together.  With several optional stages on, a step is: admission, the entry-order stamp; pool pack and prediction; the
- * intent stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the following stage; per linearisation
+ * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the following stage; per linearisation
  * pass the window stage, the advice stage, the following clamp and the QP; the plant; record, retire, respawn.  What that order implies:
  *   one car, three views   agent q sees a present row r of its window (1) standing at its pose if prec[r] > prec[obs_skip[q]], whatever
  *                          the intent stage wrote into r's predicted frames; (2) else on its owner's plan of the step before, if the owner
@@ -1144,6 +1197,11 @@ int32_t mpcx_safety_summary(mpcx_ctx *ctx, int32_t P, int32_t A, int32_t capacit
  *                          which is enough to join it with the episode table on the host.
  *   the safety stage       reads the prediction exactly as the conflict search read it and traj_idx as it left it; it writes no word any
  *                          other stage reads.
+ *   the sight stage        only the conflict search reads its word.  The following stage and the near-miss log keep reading the physical
+ *                          scene: a leader on one's own path is in view, and the log must see the contacts that occlusion causes (its
+ *                          clearance is unchanged by construction).  Nor do the admission gate, the reservation manager or the run log's
+ *                          clearance consult it.  A yielding row (precedence) or a sharing row (intent) that is not seen is simply not in
+ *                          the agent's list.
  * tests/stack_helpers.py composes the host builds of the rules in this order; tests/test_gpu_stack.py replays the device against it. */
 /* one step's search stage alone (what the closed loop enqueues in front of the window stage): steps 1 - 5.  stop_mode: MPCX_STOP_CUT or
  * MPCX_STOP_SPEED; the struct is the argument's, not the context's, and is checked as above. */

@@ -154,6 +154,16 @@ class SafetyC(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class SightC(C.Structure):
+    """mirror of mpcx_sight (include/mpcx.h): line of sight; every pointer is a device address -- sight (n_rows = P uint64, out), n_seen,
+    n_hidden (n_rows int32, out), hp (rows x 3 float64), hp_off (n_occ + 1 int32), box (n_occ x 4 float64), set_off (n_sets + 1 int32),
+    set_of (n_rows int32), heard (n_pool int32 or None).  Not a row of STAGES: the stage attaches to the context (Context.set_sight)"""
+    _fields_ = [('sight', C.c_void_p), ('n_seen', C.c_void_p), ('n_hidden', C.c_void_p), ('hp', C.c_void_p), ('hp_off', C.c_void_p),
+                ('box', C.c_void_p), ('set_off', C.c_void_p), ('set_of', C.c_void_p), ('heard', C.c_void_p), ('range', C.c_double),
+                ('n_occ', C.c_int32), ('n_sets', C.c_int32), ('n_rows', C.c_int32), ('n_pool', C.c_int32), ('reserved', C.c_int32)]
+
+
+SIGHT_WINDOW = 64                               # window offsets a word of mpcx_sight.sight holds
 # the words of an event record of the near-miss log (ev_i32[q][e][0..7]; ev_f64[q][e] = the minimum clearance, the agent's speed at opening)
 SAFETY_I32 = ('open', 'last', 'row', 'row_agent', 'path_off', 'partner_path_off', 'traj_idx', 'ttc_frame')
 SAFETY_F64 = ('min_clearance', 'v')
@@ -318,7 +328,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_admit_step_batch_precedence', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
            'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
            'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch',
-           'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary'] + LOOP_ENTRY_POINTS
+           'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary', 'mpcx_set_sight', 'mpcx_sight_step_batch'] + LOOP_ENTRY_POINTS
 
 
 def load():
@@ -423,5 +433,8 @@ def load():
     lib.mpcx_safety_step_batch.argtypes = [vp, C.POINTER(InteractionParamsC), i32] + [vp] * 4 + [i32] + [vp] * 6 + [C.POINTER(SafetyC)]
     lib.mpcx_safety_summary.restype = i32
     lib.mpcx_safety_summary.argtypes = [vp, i32, i32, i32, i32, vp, C.c_double] + [vp] * 5
+    lib.mpcx_set_sight.restype = i32; lib.mpcx_set_sight.argtypes = [vp, C.POINTER(SightC)]
+    lib.mpcx_sight_step_batch.restype = i32
+    lib.mpcx_sight_step_batch.argtypes = [vp, i32, vp, vp, i32] + [vp] * 5 + [C.POINTER(SightC)]
     _lib = lib
     return lib

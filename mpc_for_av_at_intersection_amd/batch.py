@@ -48,6 +48,9 @@ cap on its speed reference (one launch in front of the window stage, in speed mo
 `watch_safety()` is THE NEAR-MISS LOG, beside every other stage: one launch behind the conflict search names every agent's nearest vehicle
 and its first predicted contact and keeps a table of encounters on the device; near_misses() reads it, conflict_matrix() reduces it per
 pair of movements.  It decides nothing.
+`occlude()` is LINE OF SIGHT, beside every other stage on a scene: one launch in front of the conflict search decides which rows of its
+window every agent sees (sensor range, convex occluders, connected vehicles that are heard), and the conflict search leaves the others out of
+that agent's obstacle list.  corner_blocks() gives the buildings of the stock four-way world.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -397,6 +400,11 @@ class IntersectionBatch:
         self.ttc_frame: Optional[torch.Tensor] = None        # ... int32 (P,), its frame: (frame + 1) ip.dt seconds ahead, -1 = none
         self.n_events: Optional[torch.Tensor] = None         # ... int32 (P,), encounters opened so far, stored or not
         self._safety = None                                  # (set on the context too)
+        self.sight: Optional[torch.Tensor] = None            # occlude(): int64 (P,), the bits of the uint64 word: bit j = the row at window offset j is seen
+        self.n_seen: Optional[torch.Tensor] = None           # ... int32 (P,), rows seen in the last step
+        self.n_hidden: Optional[torch.Tensor] = None         # ... int32 (P,), candidates not seen in the last step
+        self._sight = None                                   # (set on the context too)
+        self._sight_tabs = None                              # ... the device tables the struct names: hp, hp_off, box, set_off, set_of, heard or None
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -435,7 +443,13 @@ class IntersectionBatch:
         """switch the named stages off, and with each the stages that live on it (_lib.stage_dependents); drops the cached descriptor"""
         entry = self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY
         for k in stages:
-            for d in {k} | _lib.stage_dependents(k, entry):
+            if k == 'sight':                # (attached to the context, no row of _lib.STAGES: nothing lives on it)
+                self._sight = None
+                continue
+            off = {k} | _lib.stage_dependents(k, entry)
+            if off & {'retire', 'scene'}:   # line of sight lives on the scene
+                self._sight = None
+            for d in off:
                 setattr(self, '_' + d, None)
         self._desc = None
 
@@ -899,6 +913,70 @@ class IntersectionBatch:
             out[name] = wf[..., k]
         return out
 
+    def occlude(self, occluders, sensor_range: float = 60.0, shrink: float = 0.0, set_of=None, hear='shared'):
+        """LINE OF SIGHT (mpcx_set_sight), beside every other stage: buildings hide cars from each other.  One more launch in front of the
+        conflict search decides, per agent, which rows of its pool window it sees -- in range of `sensor_range` metres of its reference
+        point and with no occluder across the segment from its reference point to the other's -- and the conflict search leaves the rows
+        it does not see out of the agent's obstacle list, as it leaves out the departed ones.  Nothing else consults the word: the
+        following stage, the near-miss log, the run log's clearance, the admission gate and a reservation manager read the physical scene.
+        occluders: a list of `Obstacle`s (lib/obstacles.py: anything with to_convex()), or a list of such lists for a table of sets;
+        set_of: the set of every instance, shape (B,), default 0 -- an empty list is an open junction, so a sweep of worlds is one batch.
+        shrink >= 0 takes that much off every side of every occluder (to_convex(-shrink)): a car whose centre is just behind a corner is
+        seen by its body.  hear: 'shared' -- the rows of the agents that share their plans (share_plans() first; taken as it stands now;
+        nobody if the batch shares no plans) are seen wherever they are in range, a connected vehicle announces its pose --, None, or an
+        int array over the pool rows.
+        A world's own obstacle list (lib/scenario.py) is not a good occluder set as it stands: it contains the medians and the
+        hidden=True wrong-way lanes, which are no buildings; corner_blocks() gives the four corner buildings of the stock four-way world.
+        Needs retire_at_goal(leave_scene=True) first (the list of present rows is the scene's) and therefore run(): step_staged() has no
+        retired mask.  Allocates `sight`, `n_seen`, `n_hidden` (zero) and the tables and drops the cached descriptor; see_everything()
+        switches it off, keep_driving() and retire_at_goal() drop it with the scene."""
+        if self._scene is None:
+            raise MpcxError('occlude: line of sight needs a scene (MPCX_E_INVALID): retire_at_goal(leave_scene=True) first')
+        if self.exchange == 'rccl' or callable(self.exchange):
+            raise ValueError('occlude: not in the agent-sharded layout (shard by instances)')
+        sensor_range, shrink = float(sensor_range), float(shrink)
+        if not (sensor_range > 0) or not (np.isfinite(shrink) and shrink >= 0):
+            raise ValueError('occlude: sensor_range > 0 (inf allowed), shrink >= 0 and finite')
+        occluders = list(occluders)
+        sets = [list(s) for s in occluders] if occluders and all(isinstance(s, (list, tuple)) for s in occluders) else [occluders]
+        hp, hp_off, box, set_off = occluder_table(sets, shrink)
+        which = np.zeros(self.B, np.int64) if set_of is None else np.asarray(set_of)
+        if which.shape != (self.B,) or which.dtype.kind not in 'iu' or (which < 0).any() or (which >= len(sets)).any():
+            raise ValueError('occlude: set_of must be an integer array of shape (B,) = (%d,) with values in [0, %d)' % (self.B, len(sets)))
+        dev, P, rows = self.ctx.device, self.P, int(self.obs6.shape[0])
+        heard = None
+        if isinstance(hear, str):
+            if hear != 'shared':
+                raise ValueError('occlude: hear is \'shared\', None or an int array over the %d pool rows' % rows)
+            if self._intent is not None:
+                self.ctx.synchronize()
+                heard = np.zeros(rows, np.int32)
+                own, flags = self.obs_skip.cpu().numpy().astype(np.int64), self.share.cpu().numpy()
+                ok = (own >= 0) & (own < rows) & (flags != 0)
+                heard[own[ok]] = 1
+        elif hear is not None:
+            heard = np.asarray(hear)
+            if heard.shape != (rows,) or heard.dtype.kind not in 'biu':
+                raise ValueError('occlude: hear must be an int array over the %d pool rows' % rows)
+            heard = (heard != 0).astype(np.int32)
+        f64 = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev)
+        self._sight_tabs = (f64(hp.reshape(-1)), self.ctx.i32(hp_off), f64(box.reshape(-1)), self.ctx.i32(set_off),
+                            self.ctx.i32(np.repeat(which.astype(np.int32), self.A)), None if heard is None else self.ctx.i32(heard))
+        t = self._sight_tabs
+        self.sight = torch.zeros(P, dtype=torch.int64, device=dev)
+        self.n_seen, self.n_hidden = torch.zeros(P, dtype=torch.int32, device=dev), torch.zeros(P, dtype=torch.int32, device=dev)
+        n_occ = len(hp_off) - 1
+        self._sight = _lib.SightC(self.sight.data_ptr(), self.n_seen.data_ptr(), self.n_hidden.data_ptr(), t[0].data_ptr() if len(hp) else None,
+                                  t[1].data_ptr(), t[2].data_ptr() if n_occ else None, t[3].data_ptr(), t[4].data_ptr(),
+                                  None if t[5] is None else t[5].data_ptr(), sensor_range, n_occ, len(sets), P, rows, 0)
+        self._desc = None
+        self.ctx.synchronize()
+
+    def see_everything(self):
+        """switch line of sight off and nothing else: the batch enqueues exactly the launches of one that never had it (`sight`, `n_seen`
+        and `n_hidden` keep what they hold and are no longer written)"""
+        self._off('sight')
+
     def share_plans(self, share=None):
         """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
         it applied in the last step, held for pred_steps frames -- the reference's prediction of a scripted car.  A sharing agent is seen
@@ -1166,6 +1244,7 @@ class IntersectionBatch:
         self.ctx.set_instance_tuning(self.tuning)
         self.ctx.set_following(self._following)
         self.ctx.set_safety(self._safety)
+        self.ctx.set_sight(self._sight)
 
     def run(self, n_steps: int, graph: bool = False):
         """n_steps of the closed loop with no host work in between (mpcx_closed_loop_run)."""
@@ -1292,7 +1371,10 @@ class IntersectionBatch:
             out.update(partner=self.partner.cpu().numpy().copy(), near_clearance=self.near_clearance.cpu().numpy().copy(),
                        ttc_row=self.ttc_row.cpu().numpy().copy(), ttc_frame=self.ttc_frame.cpu().numpy().copy(),
                        n_events=self.n_events.cpu().numpy().copy())
-        if self._routes is not None:         # the route every slot is on now: the run of the path tables its path_off names
+        if self._sight is not None:          # who saw whom in the last step: the uint64 word per agent and its two counts
+            out.update(sight=self.sight.cpu().numpy().view(np.uint64).copy(), n_seen=self.n_seen.cpu().numpy().copy(),
+                       n_hidden=self.n_hidden.cpu().numpy().copy())
+        if self._routes is not None:        # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
             js = self.junction_state.cpu().numpy()
@@ -1313,6 +1395,53 @@ class IntersectionBatch:
         if self._following is not None:     # (the stop point behind a leader lies on the path whenever there is a leader)
             stops = stops | (self.leader.cpu().numpy() >= 0)
         return np.where(stops, self.inter['cut_len'].cpu().numpy(), _lib.NO_STOP).astype(np.int32)
+
+
+def corner_blocks(setback: float = 5.0, extent: float = 42.0):
+    """the four corner buildings of the stock four-way world as BoxObstacles: squares of side `extent` whose inner corners stand at
+    (+-setback, +-setback) -- the occluders of IntersectionBatch.occlude() for a blind junction.  The world's own obstacle list is not a good
+    occluder set as it stands: it also holds the medians and the hidden=True wrong-way lanes."""
+    from .lib.obstacles import BoxObstacle
+    c = float(setback) + float(extent) / 2.0
+    return [BoxObstacle(xy_width=(float(extent), float(extent)), height=0.5, xy_center=(sx * c, sy * c)) for sx, sy in ((1, 1), (-1, 1), (-1, -1), (1, -1))]
+
+
+def _convex_box(rows: np.ndarray):
+    """the bounding box (x0, y0, x1, y1) of the convex polygon {a x + b y + c <= 0 for all rows}: over the pairwise intersections of its
+    lines that satisfy every row (to 1e-9 of the rows' scale); None for an empty or unbounded one"""
+    pts = []
+    n = len(rows)
+    for i in range(n):
+        for j in range(i + 1, n):
+            m = np.array([rows[i, :2], rows[j, :2]])
+            det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+            if det == 0.0:
+                continue
+            p = np.array([(-rows[i, 2] * m[1, 1] + rows[j, 2] * m[0, 1]) / det, (-rows[j, 2] * m[0, 0] + rows[i, 2] * m[1, 0]) / det])
+            if (rows[:, :2] @ p + rows[:, 2] <= 1e-9 * (1.0 + np.abs(rows).max())).all():
+                pts.append(p)
+    if len(pts) < 2:
+        return None
+    pts = np.array(pts)
+    return np.array([pts[:, 0].min(), pts[:, 1].min(), pts[:, 0].max(), pts[:, 1].max()])
+
+
+def occluder_table(obstacle_lists, shrink: float = 0.0):
+    """the occluder tables of mpcx_sight for a list of obstacle lists (one list = one set): (hp, hp_off, box, set_off) -- hp (rows, 3)
+    float64, the half-plane rows to_convex(-shrink) of every occluder, inside <=> a x + b y + c <= 0; hp_off (n_occ + 1,) int32; box
+    (n_occ, 4) float64, (x0, y0, x1, y1) of every occluder; set_off (n_sets + 1,) int32.  An occluder that the shrink leaves empty is
+    dropped."""
+    hp, hp_off, box, set_off = [], [0], [], [0]
+    for obstacles in obstacle_lists:
+        for o in obstacles:
+            rows = np.asarray(o.to_convex(-float(shrink)), dtype=np.float64).reshape(-1, 3)
+            bb = _convex_box(rows)
+            if bb is None:
+                continue
+            hp.append(rows); box.append(bb); hp_off.append(hp_off[-1] + len(rows))
+        set_off.append(len(box))
+    return (np.concatenate(hp) if hp else np.zeros((0, 3)), np.asarray(hp_off, np.int32), np.array(box, dtype=np.float64).reshape(-1, 4),
+            np.asarray(set_off, np.int32))
 
 
 def stop_lines(routes, half_width: float = 12.0, setback: float = 6.0):

@@ -17,13 +17,21 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1600] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1712] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     mpcx_following following = {};        // car following (mpcx_set_following): the struct by value, padding zeroed; all zeros while off
     bool have_following = false;
     mpcx_safety safety = {};              // the near-miss log (mpcx_set_safety): the struct by value, padding zeroed; all zeros while off
     bool have_safety = false;
+    mpcx_sight sight = {};                // line of sight (mpcx_set_sight): the struct by value, padding zeroed; all zeros while off
+    bool have_sight = false;
+    struct SightTables {                  // the offset tables of a mpcx_sight that were read back and passed their check (mpcx_sight_validate)
+        const int32_t *set_off = nullptr, *hp_off = nullptr;
+        const double *hp = nullptr;
+        int32_t n_sets = 0, n_occ = 0;
+        bool ok = false;
+    } sight_tables;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
     const int32_t *order_now = nullptr, *order_prev = nullptr;   // optional pair: entries that differ mark a discontinuous change of the reference
     // scratch of mpcx_closed_loop_run for P agents: [P] cut lengths of the previous step | [3 P] what the conflict search's nearest-index
@@ -98,6 +106,9 @@ struct mpcx_interaction_extras {
     // shared plans (mpcx_intent.hip; nullptr: off): one more launch between the prediction and the conflict search re-rolls the plans of the
     // sharing agents into their own pool rows
     const mpcx_intent_launch *intent = nullptr;
+    // line of sight (mpcx_sight.hip; nullptr: off; needs absent): one more launch behind the prediction and the intent stage writes every
+    // agent's word of seen rows, and the conflict search takes its SIGHT instantiation (mpcx_interaction_sight.hip)
+    const mpcx_sight *sight = nullptr;
 };
 struct mpcx_window_extras {
     bool scatter = false;               // turn the conflict search's (key, slot) in ctx->bins into the queue order in ctx->order
@@ -251,6 +262,13 @@ int32_t mpcx_safety_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *ip, in
                             const int32_t *traj_idx, const int32_t *done /*or nullptr*/, int32_t n_obs_pool, const double *obs6,
                             const double *pred, const int32_t *obs_off, const int32_t *obs_cnt, const int32_t *obs_skip,
                             const int32_t *absent /*or nullptr*/, const mpcx_safety *safety);
+// line of sight (mpcx_sight.hip): "no sight stage" test, check of the struct against the run (n_pool: its pool rows; reads the two offset
+// tables back), the launch alone (in front of the conflict search, on the pool as packed)
+bool mpcx_sight_absent(const mpcx_sight *s);
+int32_t mpcx_sight_validate(mpcx_ctx *ctx, const mpcx_sight *s, int32_t P, int32_t n_pool);
+int32_t mpcx_sight_enqueue(mpcx_ctx *ctx, int32_t P, const double *state, const int32_t *done /*or nullptr*/, int32_t n_obs_pool,
+                           const double *obs6, const int32_t *obs_off, const int32_t *obs_cnt, const int32_t *obs_skip,
+                           const int32_t *absent /*or nullptr*/, const mpcx_sight *sight);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(64) void moving_collision_kernel(MovArgs a) {
 }
 
 // One launcher per kernel: the instantiation follows from what the call carries -- right of way (x.prec; compiled in mpcx_interaction_prec.hip),
-// a scene (x.absent), retirement (x.done) or none of them.
+// line of sight (x.sight; compiled in mpcx_interaction_sight.hip), a scene (x.absent), retirement (x.done) or none of them.
 static void launch_predict(bool mapped, int lanes, hipStream_t st, const PredArgs &pa, const mpcx_interaction_extras &x) {
     const dim3 grid((lanes + 63) / 64), block(64);
     if (x.prec) launch_predict_stand(mapped, lanes, st, pa);
@@ -77,7 +77,8 @@ static void launch_predict(bool mapped, int lanes, hipStream_t st, const PredArg
 }
 
 static void launch_interaction(int P, size_t lds, hipStream_t st, const InterArgs &ia, const mpcx_interaction_extras &x) {
-    if (x.prec) launch_interaction_prec(P, lds, st, ia);
+    if (x.sight) launch_interaction_sight(P, lds, st, ia, (const unsigned long long *)x.sight->sight, x.prec != nullptr);
+    else if (x.prec) launch_interaction_prec(P, lds, st, ia);
     else if (x.absent) hipLaunchKernelGGL((interaction_kernel<true, true>), dim3(P), dim3(64), lds, st, ia);
     else if (x.done) hipLaunchKernelGGL(interaction_kernel<true>, dim3(P), dim3(64), lds, st, ia);
     else hipLaunchKernelGGL(interaction_kernel<false>, dim3(P), dim3(64), lds, st, ia);
@@ -115,6 +116,7 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
         return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: pred_steps outside 1..%d or bad dt/L/frame_window", MPCX_PRED_STEPS_MAX);
     if (x.absent && (!x.done || n_obs_pool < 1)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: a scene without retirement or without a pool");
     if ((x.prec || x.stand) && (!x.absent || !x.prec || !x.stand)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: precedence without a scene, or without one of prec and stand");
+    if (x.sight && (!x.absent || !obs_skip)) return mpcx_fail(ctx, MPCX_E_INVALID, "interaction_batch: line of sight without a scene or without obs_skip");
     { int32_t rc = mpcx_ensure_pred(ctx, (size_t)(n_obs_pool > 0 ? n_obs_pool : 1) * ip->pred_steps * 4); if (rc != MPCX_OK) return rc; }
     if (x.predicted) {
         // (the head of the closed loop's step has packed and predicted the pool already)
@@ -131,6 +133,10 @@ int32_t mpcx_interaction_enqueue(mpcx_ctx *ctx, const mpcx_interaction_params *i
     }
     if (x.intent) {     // shared plans: the sharing agents' own rows are re-rolled from their plans before anybody searches them
         const int32_t rc = mpcx_intent_enqueue(ctx, ip, P, state, obs_skip, n_obs_pool, *x.intent);
+        if (rc != MPCX_OK) return rc;
+    }
+    if (x.sight) {      // line of sight: every agent's word of seen rows, on the pool as packed, before anybody searches it
+        const int32_t rc = mpcx_sight_enqueue(ctx, P, state, x.done, n_obs_pool, obs6, obs_off, obs_cnt, obs_skip, x.absent, x.sight);
         if (rc != MPCX_OK) return rc;
     }
     // capacity (mpcx_interaction_capacity): the LDS that holds the cumulative lengths of max_rem path points later holds the ego discs of

@@ -104,10 +104,14 @@ struct LoopStages {
     // hold; needs the local pool and obs_skip.  It reads obs6, ctx->pred and traj_idx as the conflict search left them and writes only the
     // struct's own words: no other launch of the step sees it.  &ctx->safety while on.
     const mpcx_safety *safety = nullptr;
+    // line of sight (mpcx_set_sight: it attaches to the context too): sight_kernel inside the conflict search's stage, behind the pack of
+    // the pool and the intent stage, and the SIGHT instantiation of the conflict search; needs retirement, a scene and obs_skip.
+    // &ctx->sight while on.
+    const mpcx_sight *sight = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -120,6 +124,7 @@ struct LoopKey {
     mpcx_routes routes; mpcx_precedence precedence; mpcx_signals signals; mpcx_actuation actuation; mpcx_advice advice; mpcx_intent intent; mpcx_reservation reservation;
     mpcx_following following;
     mpcx_safety safety;
+    mpcx_sight sight;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -225,10 +230,18 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         rc = mpcx_safety_validate(ctx, &ctx->safety, ip, c->P, c->n_actors > 0 ? c->pool_rows : c->P, c->exchange);
         if (rc == MPCX_OK) st->safety = &ctx->safety;
     }
+    if (rc != MPCX_OK) return rc;
+    if (ctx->have_sight) {
+        if (!st->retire || !st->scene)
+            return mpcx_fail(ctx, MPCX_E_INVALID, "sight: the run has no retirement and scene (the conflict search's list of present rows is the scene's)");
+        // (the scene has been checked: the layout is not agent-sharded and the descriptor has obs_skip)
+        rc = mpcx_sight_validate(ctx, &ctx->sight, c->P, c->n_actors > 0 ? c->pool_rows : c->P);
+        if (rc == MPCX_OK) st->sight = &ctx->sight;
+    }
     return rc;
 }
 
-// The middle of a step, the same on both paths: the conflict search (-> the safety stage) (-> the signal stage) (-> the following stage) -> lin_passes x (reference
+// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the following stage) -> lin_passes x (reference
 // window (-> the advice stage) (-> the following clamp) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
@@ -247,6 +260,7 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
     ix.done = done;
     ix.absent = st.scene ? st.scene->absent : nullptr;
     if (st.precedence) { ix.prec = st.precedence->prec; ix.stand = st.precedence->stand; }
+    ix.sight = st.sight;
     if (speed) ix.key_prev = c->cut_len;        // "the cut moved" = the stop index moved
     int32_t rc = mpcx_interaction_enqueue(ctx, ip, P, c->state, c->path_xyyaw, c->path_cs, c->path_off, c->path_len,
                                           speed ? st.opts.prev_len : c->cut_len /* previous step's cut; read before it is rewritten */, pool_rows,
@@ -494,6 +508,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.advice, st.advice); key_put(key.intent, st.intent); key_put(key.reservation, st.reserve);
     key_put(key.following, st.follow);
     key_put(key.safety, st.safety);
+    key_put(key.sight, st.sight);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;

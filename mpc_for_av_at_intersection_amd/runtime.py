@@ -862,6 +862,27 @@ class Context:
         self._chk(self.lib.mpcx_set_safety(self._ctx, None if safety is None else C.byref(safety)))
         self._safety = safety
 
+    def set_sight(self, sight: Optional['_lib.SightC']):
+        """mpcx_set_sight: line of sight for every closed-loop run of this context from now on; None (or an all-zero struct) = off.  The
+        context copies the struct; the device buffers it names stay the caller's and are kept alive here while set."""
+        self._chk(self.lib.mpcx_set_sight(self._ctx, None if sight is None else C.byref(sight)))
+        self._sight = sight
+
+    @_ordered
+    def sight_step(self, state, obs6, obs_off, obs_cnt, obs_skip, sight: '_lib.SightC', done=None, absent=None):
+        """mpcx_sight_step_batch: ONE step's sight stage as the closed loop enqueues it in front of the conflict search: the struct's sight,
+        n_seen and n_hidden words are written.  state (P, 4); obs6 (pool rows, 6): the pool as the head of the step packed it; done: the
+        retirement words (P int32), absent: the scene's words (pool rows), or None."""
+        Pn, rows = int(state.shape[0]), int(obs6.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state'); self._want(obs6, torch.float64, (rows, 6), 'obs6')
+        for name, t in (('obs_off', obs_off), ('obs_cnt', obs_cnt), ('obs_skip', obs_skip), ('done', done)):
+            if t is not None:
+                self._want(t, torch.int32, (Pn,), name)
+        if absent is not None:
+            self._want(absent, torch.int32, (rows,), 'absent')
+        self._chk(self.lib.mpcx_sight_step_batch(self._ctx, Pn, _ptr(state), _ptr(done), rows, _ptr(obs6), _ptr(obs_off), _ptr(obs_cnt),
+                                                 _ptr(obs_skip), _ptr(absent), C.byref(sight)))
+
     @_ordered
     def safety_step(self, ip: InteractionParams, state, path_off, traj_idx, obs6, obs_off, obs_cnt, obs_skip, safety: '_lib.SafetyC', pred=None,
                     done=None, absent=None):
