@@ -219,7 +219,11 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         for (int r = 0; r < ROWS; r++) { sv[r] = cx.ld_s(ls * ROWS + r); lv[r] = cx.ld_l(ls * ROWS + r); }
     };
     // gradient of the cost (no multipliers) wrt x_{t+1} and u_t at the current iterate; recomputed where needed rather than
-    // kept across the Riccati sweep (30 doubles per lane that the sweep needs for the cost-to-go)
+    // kept across the Riccati sweep (30 doubles per lane that the sweep needs for the cost-to-go).
+    // Its sums of two products are spelt as the fused multiply-adds the compiler has always made of them in the kernels without tuning
+    // rows (which product of a pair is fused is a free choice of the back end, and with per-lane weights -- the TUNED kernels -- it chose
+    // the other one: uniform rows then differed from the same set as launch-wide parameters by rounding, u up to 3e-11).  Written out,
+    // every instantiation computes the same thing; tests/test_gpu_tuning.py holds uniform rows and launch-wide parameters to the same bits.
     auto cost_grad = [&](double (&G0)[SPL], double (&G1)[SPL], double (&G2)[SPL], double (&G3)[SPL], double (&H0)[SPL], double (&H1)[SPL]) {
         double Un0[SPL], Un1[SPL], Up0[SPL], Up1[SPL];
         prev_of(U1, Up1); prev_of(U0, Up0); next_of(U0, Un0); next_of(U1, Un1);
@@ -227,11 +231,11 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         for (int ls = 0; ls < SPL; ls++) {
             const int t = q * SPL + ls;
             const double e0 = X0[ls], e1 = X1[ls], e2 = X2[ls] - XRV[ls], e3 = X3[ls];
-            G0[ls] = WXX(ls) * e0 + Wxy[ls] * e1; G1[ls] = Wxy[ls] * e0 + WYY(ls) * e1; G2[ls] = WV(ls) * e2; G3[ls] = WP(ls) * e3;
+            G0[ls] = fma(Wxy[ls], e1, WXX(ls) * e0); G1[ls] = fma(Wxy[ls], e0, WYY(ls) * e1); G2[ls] = WV(ls) * e2; G3[ls] = WP(ls) * e3;
             const bool has_next = act[ls] && (t + 1 < T);
             double g0 = (RA_(ls) + JW_(ls)) * U0[ls], g1 = RS_(ls) * U1[ls];
-            if (rate[ls]) { g0 += Rda * (U0[ls] - Up0[ls]); g1 += Rds * (U1[ls] - Up1[ls]); }
-            if (has_next) { g0 -= Rda * (Un0[ls] - U0[ls]); g1 -= Rds * (Un1[ls] - U1[ls]); }
+            if (rate[ls]) { g0 = fma(Rda, U0[ls] - Up0[ls], g0); g1 = fma(Rds, U1[ls] - Up1[ls], g1); }
+            if (has_next) { g0 = fma(-Rda, Un0[ls] - U0[ls], g0); g1 = fma(-Rds, Un1[ls] - U1[ls], g1); }
             H0[ls] = g0; H1[ls] = g1;               // zero on slots beyond the horizon (u = 0 there, no rate terms)
         }
     };
