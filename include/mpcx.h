@@ -387,6 +387,10 @@ int32_t mpcx_closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip, c
  * (head_kernel); the run ends with the last step's plant update in a launch of its own.  Every buffer holds the same bits when the call
  * returns.  on = 0: the launch sequence without fusion (the rollout on the side stream beside the conflict search), for every run. */
 int32_t mpcx_set_step_fusion(mpcx_ctx *ctx, int32_t on);
+/* Plain rounds of the stage-structured QP solver (on by default).  In a round in which no problem of a wavefront is in its trial or a polish
+ * round the solver runs second copies of its row passes, compiled without the selects that tell those rounds apart.  on = 0: the generic
+ * text in every round.  The results are the same bits either way (tests/test_gpu_qp_plain_passes.py); the switch is there to show it. */
+int32_t mpcx_qp_set_plain_rounds(mpcx_ctx *ctx, int32_t on);
 /* run statistics accumulated on the device by every step of mpcx_closed_loop_run since the last reset (what the reference's scripts
  * print per run: solver failures; plus iteration counts): out4 = (agent-steps, interior-point iterations, failed solves, max iterations).
  * Synchronises the context's stream. */

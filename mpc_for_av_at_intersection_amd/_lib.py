@@ -322,7 +322,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_cutoff_index_batch', 'mpcx_predict_obstacles_batch', 'mpcx_selftest_wave_ops', 'mpcx_selftest_mfma', 'mpcx_profile_qp',
            'mpcx_profile_qp_read', 'mpcx_set_instance_tuning', 'mpcx_set_qp_solver', 'mpcx_qp_set_order_hint', 'mpcx_expand_multi_batch',
            'mpcx_comm_unique_id', 'mpcx_comm_init', 'mpcx_comm_destroy', 'mpcx_allgather_states', 'mpcx_closed_loop_stats',
-           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_set_step_fusion', 'mpcx_astar_batch',
+           'mpcx_mpc_prepare_batch_ov', 'mpcx_set_linearisation_passes', 'mpcx_set_step_fusion', 'mpcx_qp_set_plain_rounds', 'mpcx_astar_batch',
            'mpcx_traffic_step_batch', 'mpcx_record_step_batch', 'mpcx_mpc_prepare_batch_stop', 'mpcx_record_step_batch_goal',
            'mpcx_admit_step_batch', 'mpcx_respawn_step_batch', 'mpcx_respawn_step_batch_routes', 'mpcx_episode_summary',
            'mpcx_admit_step_batch_precedence', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
@@ -355,6 +355,7 @@ def load():
     lib.mpcx_mpc_prepare_batch_ov.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, C.c_double, vp, vp, C.c_int64, vp, vp, vp]
     lib.mpcx_set_linearisation_passes.restype = i32; lib.mpcx_set_linearisation_passes.argtypes = [vp, i32]
     lib.mpcx_set_step_fusion.restype = i32; lib.mpcx_set_step_fusion.argtypes = [vp, i32]
+    lib.mpcx_qp_set_plain_rounds.restype = i32; lib.mpcx_qp_set_plain_rounds.argtypes = [vp, i32]
     lib.mpcx_astar_batch.restype = i32
     lib.mpcx_astar_batch.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp]
     lib.mpcx_search_model_create.restype = vp

@@ -126,6 +126,12 @@ int32_t mpcx_set_step_fusion(mpcx_ctx *ctx, int32_t on) {
     return MPCX_OK;
 }
 
+int32_t mpcx_qp_set_plain_rounds(mpcx_ctx *ctx, int32_t on) {
+    if (!ctx) return MPCX_E_INVALID;
+    ctx->qp_plain_rounds = on != 0;
+    return MPCX_OK;
+}
+
 int32_t mpcx_profile_qp(mpcx_ctx *ctx, int32_t enable) {
     if (!ctx) return MPCX_E_INVALID;
     ctx->prof_qp = enable != 0;

@@ -54,6 +54,7 @@ struct mpcx_ctx {
     size_t multi_cap = 0;
     int qp_solver = 0;          // 0 = automatic, 1 = condensed (one wavefront per QP), 2 = stage-structured (mpcx_set_qp_solver)
     bool step_fusion = true;    // mpcx_closed_loop_run takes plant, prediction and rollout in one launch where it can (mpcx_set_step_fusion)
+    bool qp_plain_rounds = true;        // the stage solver runs the plain copies of its row passes where a round allows it (mpcx_qp_set_plain_rounds)
     int lin_passes = 1;         // linearisation passes per step of mpcx_closed_loop_run (lib/mpc.py MAX_ITER; mpcx_set_linearisation_passes)
     bool prof_qp = false;       // bracket qp_kernel launches with events (mpcx_profile_qp)
     std::vector<hipEvent_t> prof_ev;   // start/stop pairs recorded so far
@@ -314,6 +315,7 @@ struct QpArgs {
     int32_t *fail_list, *fail_count;
     const int32_t *queue_len;
     int has_queue_len;
+    int plain_rounds;             // stage solver: rounds without a trial or polishing problem run the plain copies of the row passes (mpcx_qp_set_plain_rounds)
 };
 
 void launch_qp_stage(const QpArgs &a, hipStream_t st, int n_cu);   // mpcx_qp_quad.hip

@@ -128,7 +128,7 @@ struct LoopKey {
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
-    int qp_solver, lin_passes;          // the captured launch is the solver chosen at capture time
+    int qp_solver, lin_passes, qp_plain_rounds;          // the captured launch is the solver chosen at capture time
 };
 static_assert(sizeof(LoopKey) <= sizeof(mpcx_ctx::loop_key), "loop_key too small");
 
@@ -512,7 +512,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;
-    key.qp_solver = ctx->qp_solver; key.lin_passes = ctx->lin_passes;
+    key.qp_solver = ctx->qp_solver; key.lin_passes = ctx->lin_passes; key.qp_plain_rounds = ctx->qp_plain_rounds ? 1 : 0;
     if (!ctx->loop_exec || memcmp(&key, ctx->loop_key, sizeof key) != 0) {
         if (ctx->loop_exec) {
             (void)hipStreamSynchronize(ctx->stream);

@@ -765,7 +765,7 @@ int32_t mpcx_qp_enqueue(mpcx_ctx *ctx, int32_t B, const double *x0, const double
     } else if (hipMemsetAsync(ctx->ticket, 0, MPCX_TICKET_WORDS * sizeof(int32_t), ctx->stream) != hipSuccess)
         return mpcx_fail(ctx, MPCX_E_LAUNCH, "qp_solve_batch: hipMemsetAsync failed");
     mpcx::QpArgs a{ctx->mpc, B, ctx->ticket, u_warm != nullptr, x0, xref, xbar, u_warm, reaches_end, x_out, u_out, kkt, status, iters,
-                   ctx->tune, ctx->tune != nullptr, order, order != nullptr, 0, nullptr, nullptr, nullptr, 0};
+                   ctx->tune, ctx->tune != nullptr, order, order != nullptr, 0, nullptr, nullptr, nullptr, 0, ctx->qp_plain_rounds ? 1 : 0};
     if (ord.ready && ord.queue_len) { a.queue_len = ord.queue_len; a.has_queue_len = 1; }     // retirement: tickets up to the device-side count
     if (!use_stage) {
         // The condensed solver's 64-row LDL' loses a few more digits than the Riccati recursion on the worst-conditioned problems

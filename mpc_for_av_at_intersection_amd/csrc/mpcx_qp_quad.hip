@@ -17,8 +17,11 @@ struct GroupCx {
     static constexpr int LQ = LQ_, SPL = SPL_;
     static constexpr bool JERK = JERK_;       // the five-state problem of lib/mpc_jerk.py (mpcx_mpc_params.model)
     static_assert(LQ == 8, "groups of 8 lanes");
-    // a plain copy of the predictor's row pass (mpcx_qp_stage.h; DESIGN 4.1 has the counts and timings)
-    static constexpr int PLAIN_PASSES = mpcx_stage::PLAIN_C;
+    // plain copies of the predictor's and of the corrector's row pass (mpcx_qp_stage.h).  Every instantiation takes the same two: each has
+    // less scratch with them than without (DESIGN 4.1 has the list, the counts and the timings).  The residual pass gets none: with all
+    // three copies the five-state kernel at SPL = 4 gave wrong solutions (cause not found; each pair of copies is right).  The multiplier
+    // step and the update get none: with theirs the scratch of every SPL = 3 and 4 instantiation goes up and the launch gets slower.
+    static constexpr int PLAIN_PASSES = mpcx_stage::PLAIN_C | mpcx_stage::PLAIN_D;
     int q, lane;
     lds_double *sh;                       // s [SPL*8][64], lam [SPL*8][64], gains [SPL*8][64], spare [2*SPL][64]
     // row_shl:1 / row_shr:1 = value of lane q+1 / q-1.
@@ -73,6 +76,7 @@ template <int LQ, int SPL, bool TUNED>
 struct QueueSrc {
     const QpArgs &a;
     __device__ __forceinline__ mpcx_mpc_params params() const { return a.p; }
+    __device__ __forceinline__ bool plain_rounds() const { return a.plain_rounds != 0; }     // mpcx_qp_set_plain_rounds
     __device__ __forceinline__ mpcx_stage::Problem at(int b) const {
         const int T = a.p.T, W = T + 1;
         return mpcx_stage::Problem{a.x0 + (size_t)b * 4, a.xref + (size_t)b * 4 * W, a.xbar + (size_t)b * 4 * W,

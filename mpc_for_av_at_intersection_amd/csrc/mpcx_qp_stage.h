@@ -32,6 +32,14 @@
 #define MPCX_HD inline
 #endif
 #define MPCX_UNROLL _Pragma("unroll")
+// Head of a compound statement whose floating-point grouping is spelt out: no multiply and add of it is contracted behind the source's back
+// (hipcc's default is -ffp-contract=fast-honor-pragmas), every fused multiply-add in it is written as fma().  Other compilers (the host
+// build of tests/stage_ref) take the text as it stands.
+#if defined(__clang__)
+#define MPCX_FP_PINNED _Pragma("clang fp contract(off)")
+#else
+#define MPCX_FP_PINNED
+#endif
 #define MPCX_NOUNROLL _Pragma("nounroll")
 
 namespace mpcx_stage {
@@ -44,14 +52,24 @@ enum { ROWS = 8 };
 
 // Plain rounds.  The row passes serve three kinds of round with one text: an ordinary iteration, the trial round and the polish
 // round; the flags that tell them apart cost selects on every row visit.  In a round in which NO lane of the wavefront is in a
-// trial or polish round those flags are constants (pa = false, ipm = true), and a policy may ask for a second copy of a row pass
-// compiled with them folded: Cx::PLAIN_PASSES is a mask of the passes that get one.  Both copies are the same text on the same
-// operands in the same order, and a copy is kept only if the compiler also groups its FMAs as in the generic text (checked on the
-// GPU, bit for bit), so a problem's numbers do not depend on the path its rounds took.  Only the predictor's row pass (C) has one:
-// the plain copies of pass A and of the corrector's pass (D) came out with other FMA groupings -- last bits moved -- and that of
-// the multiplier step raised the kernel's scratch (DESIGN 4.1 has every pass's numbers).  A policy without the member (the host
+// trial or polish round those flags are constants (pa = false, ipm = true, full = on), and a policy may ask for a second copy of a row
+// pass compiled with them folded: Cx::PLAIN_PASSES is a mask of the passes that get one.  Both copies are the same text on the same
+// operands in the same order.  That alone does not make them the same numbers: left to itself the back end decides which multiply of
+// a sum of products is fused into the add, and it decided differently from copy to copy (and from row to row, by what happened to
+// sit in one basic block).  So the passes A, D, the multiplier step, the safeguard and the update are written under MPCX_FP_PINNED
+// with their fused multiply-adds spelt out, in the grouping the single generic text had compiled to before: a problem's
+// numbers then depend neither on the path its rounds took nor on the instantiation.  Pass C, the first to get a copy, is NOT pinned:
+// its two copies have come out with one grouping in every build so far, and what holds them to it is tests/test_gpu_qp_plain_passes.py
+// (switch on against off) and the benchmark's dumped outputs against the parent's, nothing in the text.  A launch can be told to run
+// the generic text only (src.plain_rounds(), for the tests that compare the two).  A policy without the member PLAIN_PASSES (the host
 // build) runs the generic text only.
-enum { PLAIN_C = 1 };
+enum { PLAIN_C = 1,     // the predictor's row pass
+       PLAIN_D = 2,     // the corrector's row pass
+       PLAIN_A = 4,     // the residual pass at the head of a round (its own ballot: it sits before the refill and the exit tests).
+                        // FORBIDDEN for now (static_assert in solve_queue): with C, D and A together the five-state kernel at SPL = 4
+                        // returned wrong solutions, cause not found
+       PLAIN_E = 8 };   // the multiplier step and the update (no policy asks for it: it costs scratch and time)
+  // the multiplier step and the update (no policy asks for it today: it costs scratch)
 template <class Cx, class = void> struct plain_passes : std::integral_constant<int, 0> {};
 template <class Cx> struct plain_passes<Cx, std::void_t<decltype(Cx::PLAIN_PASSES)>> : std::integral_constant<int, Cx::PLAIN_PASSES> {};
 
@@ -67,6 +85,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
     constexpr int LQ = Cx::LQ, SPL = Cx::SPL;
     constexpr bool JERK = Cx::JERK;
     constexpr int PASSES = plain_passes<Cx>::value;
+    static_assert((PASSES & PLAIN_A) == 0, "PLAIN_A gave wrong solutions beside PLAIN_C | PLAIN_D in the five-state SPL = 4 kernel; find the cause first (DESIGN 7)");
     // a row pass is a generic lambda over std::bool_constant<PLAIN>: this runs its plain copy if the policy asked for one and the
     // round is plain (the same for every lane of the wavefront), the generic text otherwise
     auto by_round = [](auto has_plain, bool plain_round, auto &&pass) {
@@ -74,6 +93,8 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         else pass(std::false_type{});
     };
     const int q = cx.q;
+    bool plain_on = false;                  // the launch allows plain rounds (a policy with plain copies says so: src.plain_rounds())
+    if constexpr (PASSES != 0) plain_on = src.plain_rounds();
     mpcx_mpc_params P = src.params();       // weights / limits may be replaced per problem by fetch(); T, dt, L never change
     int pbi = 0;                            // index of the group's problem: its pointers are rebuilt where they are needed (set-up, hand-in)
     double PH[SPL] = {};                                      // yaw of the linearisation point (for C_t)
@@ -417,15 +438,20 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 cx.fence();
             }
             // ---- local pass A: rows, complementarity, gradient pieces
-            const bool ipm = !(trial || polish);
+            // plain for this pass: no lane is in a trial or polish round as the flags stand HERE (the refill and the exit tests may set them below)
+            const bool plain_a = plain_on && !cx.any(trial || polish);
             prev_of(U1, Dprev);
             double L45[SPL], N45[SPL];                    // (lam4 - lam5), (nu4 - nu5) of the predictor
             double QL2[SPL], QA2[SPL], RL0[SPL], RL1[SPL], RA0[SPL], RA1[SPL];
             double mu_s = 0.0, rp_m = 0.0;
             cost_grad(PG0, PG1, PG2, PG3, PH0, PH1);
+            by_round(std::bool_constant<(PASSES & PLAIN_A) != 0>{}, plain_a, [&](auto plain) {
+            MPCX_FP_PINNED
+            constexpr bool PLAIN = decltype(plain)::value;
+            const bool polish_r = !PLAIN && polish, ipm = PLAIN || !(trial || polish);
             MPCX_UNROLL
             for (int ls = 0; ls < SPL; ls++) {
-                double lam[ROWS], nu[ROWS], dd[ROWS], sv[ROWS], lv[ROWS];
+                double lam[ROWS], rpv[ROWS], isv[ROWS], dd[ROWS], sv[ROWS], lv[ROWS];
                 rows_of(ls, sv, lv);
                 MPCX_UNROLL
                 for (int r = 0; r < ROWS; r++) {
@@ -435,22 +461,26 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                     // iteration's own formulas d = lam / s, nu = d (s + gap) give for a row with the slack lam / rho -- so an active
                     // row is an ordinary row with that slack, an inactive one a row with a zero multiplier, and no pass below has polish
                     // arithmetic of its own.
-                    const bool pa = polish & (sv[r] < 0.0);  // the row is in a polishing group's active set (bitwise: a lane-varying && / || compiles to a branch per row)
+                    const bool pa = polish_r & (sv[r] < 0.0);  // the row is in a polishing group's active set (bitwise: a lane-varying && / || compiles to a branch per row)
                     const double s = pa ? lv[r] * (1.0 / MPCX_POLISH_RHO) : fabs(sv[r]);
                     const double l = (pa | (on & ipm)) ? lv[r] : 0.0;
                     const double is = cx.rcp(s);
                     const double rp = on ? s + row_gap(ls, r, Dprev[ls]) : 0.0;
-                    const double d = l * is;
-                    dd[r] = d;
-                    lam[r] = l;
-                    nu[r] = d * rp;
-                    mu_s += s * l;
+                    dd[r] = l * is;                          // d = lam / s, rounded: nu = d * rp below
+                    lam[r] = l; isv[r] = is; rpv[r] = rp;
+                    mu_s = fma(s, l, mu_s);
                     rp_m = fmax(rp_m, fabs(rp));
                 }
-                DSa[ls] = dd[0] + dd[1]; DSd[ls] = dd[2] + dd[3]; DSr[ls] = dd[4] + dd[5]; DSv[ls] = dd[6] + dd[7];
+                // a pair's sum d + d' takes the first product fused, its difference nu - nu' = d rp - d' rp' the first one as well; the
+                // rate pair of the lane's first slot adds its two rounded weights.  That is the grouping this pass has had since it was
+                // written (the compiler's own choice then), spelt out so that every copy and every instantiation computes it.
+                auto dsum = [&](int r) { return fma(lam[r], isv[r], dd[r + 1]); };
+                auto ndif = [&](int r) { return fma(dd[r], rpv[r], -(dd[r + 1] * rpv[r + 1])); };
+                DSa[ls] = dsum(0); DSd[ls] = dsum(2); DSr[ls] = ls == 0 ? dd[4] + dd[5] : dsum(4); DSv[ls] = dsum(6);
                 RL0[ls] = lam[0] - lam[1]; RL1[ls] = lam[2] - lam[3]; L45[ls] = lam[4] - lam[5]; QL2[ls] = lam[6] - lam[7];
-                RA0[ls] = nu[0] - nu[1]; RA1[ls] = nu[2] - nu[3]; N45[ls] = nu[4] - nu[5]; QA2[ls] = nu[6] - nu[7];
+                RA0[ls] = ndif(0); RA1[ls] = ndif(2); N45[ls] = ndif(4); QA2[ls] = ndif(6);
             }
+            });
             double L45n[SPL], N45n[SPL];
             next_of(L45, L45n); next_of(N45, N45n);
             cx.stamp(1);                    // [local pass A]
@@ -458,6 +488,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             double O0[SPL] = {}, O1[SPL] = {};
             double rd_z = 0.0;
             {
+                MPCX_FP_PINNED              // PG2 is a product (cost_grad): it enters rounded
                 double Q2t[SPL], R0t[SPL], R1t[SPL];
                 MPCX_UNROLL
                 for (int ls = 0; ls < SPL; ls++) {
@@ -468,11 +499,14 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 rd_z = costate(PG0, PG1, Q2t, PG3, R0t, R1t, O0, O1);
             }
             // from here on PG / PH hold the predictor's linear terms (cost gradient + G' nu with nu = d * rp)
-            MPCX_UNROLL
-            for (int ls = 0; ls < SPL; ls++) {
-                PG2[ls] += QA2[ls];
-                PH0[ls] += RA0[ls];
-                PH1[ls] += RA1[ls] + N45[ls] - N45n[ls];
+            {
+                MPCX_FP_PINNED              // PG2 is a product (cost_grad): it enters rounded here as well
+                MPCX_UNROLL
+                for (int ls = 0; ls < SPL; ls++) {
+                    PG2[ls] += QA2[ls];
+                    PH0[ls] += RA0[ls];
+                    PH1[ls] += RA1[ls] + N45[ls] - N45n[ls];
+                }
             }
             double rd_m = fabs(rd_z);
             MPCX_UNROLL
@@ -635,16 +669,22 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                         const double g4 = pv[4], g5 = pv[5];
                         const double a0 = A0[ls], a1 = A1[ls], a2 = A2[ls], a3 = A3[ls], b3 = B3[ls];
                         // 2. G = P * F  (columns v, psi, a, delta of F = d z_{t+1} / d (x, y, v, psi, a, delta))
-                        const double Gv0 = a0 * p00 + a2 * p01 + p02, Gv1 = a0 * p01 + a2 * p11 + p12, Gv2 = a0 * p02 + a2 * p12 + p22;
-                        const double Gp0 = a1 * p00 + a3 * p01 + p03, Gp1 = a1 * p01 + a3 * p11 + p13, Gp2 = a1 * p02 + a3 * p12 + p23;
-                        const double Gp3 = a1 * p03 + a3 * p13 + p33;
+                        // A sum of two products and a term.  Which product is fused into the other, rounded one is the back end's free choice, and it
+                        // moved in this sweep when unrelated code elsewhere in the kernel changed.  So the choice is written out, as the
+                        // compiler had made it when these lines were plain sums: the first product is the fused one (pp), except
+                        // in the two sums over (p00, p01) of every slot but the lane's first, where it is the second (pq).
+                        auto pp = [](double a, double x, double b, double y, double c) { return fma(a, x, b * y) + c; };
+                        auto pq = [](double a, double x, double b, double y, double c) { return fma(b, y, a * x) + c; };
+                        const double Gv0 = ls == 0 ? pp(a0, p00, a2, p01, p02) : pq(a0, p00, a2, p01, p02), Gv1 = pp(a0, p01, a2, p11, p12), Gv2 = pp(a0, p02, a2, p12, p22);
+                        const double Gp0 = ls == 0 ? pp(a1, p00, a3, p01, p03) : pq(a1, p00, a3, p01, p03), Gp1 = pp(a1, p01, a3, p11, p13), Gp2 = pp(a1, p02, a3, p12, p23);
+                        const double Gp3 = pp(a1, p03, a3, p13, p33);
                         const double Ga0 = dt * p02 + p04, Ga1 = dt * p12 + p14, Ga2 = dt * p22 + p24, Ga3 = dt * p23 + p34, Ga4 = dt * p24 + p44;
                         const double Gd0 = b3 * p03 + p05, Gd1 = b3 * p13 + p15, Gd2 = b3 * p23 + p25, Gd3 = b3 * p33 + p35;
                         const double Gd4 = b3 * p34 + p45, Gd5 = b3 * p35 + p55;
                         // 3. Phi = F' G
-                        const double Fvv = a0 * Gv0 + a2 * Gv1 + Gv2, Fvp = a0 * Gp0 + a2 * Gp1 + Gp2;
-                        const double Fva = a0 * Ga0 + a2 * Ga1 + Ga2, Fvd = a0 * Gd0 + a2 * Gd1 + Gd2;
-                        const double Fpp = a1 * Gp0 + a3 * Gp1 + Gp3, Fpa = a1 * Ga0 + a3 * Ga1 + Ga3, Fpd = a1 * Gd0 + a3 * Gd1 + Gd3;
+                        const double Fvv = pp(a0, Gv0, a2, Gv1, Gv2), Fvp = pp(a0, Gp0, a2, Gp1, Gp2);
+                        const double Fva = pp(a0, Ga0, a2, Ga1, Ga2), Fvd = pp(a0, Gd0, a2, Gd1, Gd2);
+                        const double Fpp = pp(a1, Gp0, a3, Gp1, Gp3), Fpa = pp(a1, Ga0, a3, Ga1, Ga3), Fpd = pp(a1, Gd0, a3, Gd1, Gd3);
                         // 4. input, rate and barrier terms
                         const double rho_a = rate[ls] ? Rda : 0.0;
                         const double rho_d = rate[ls] ? Rds + DSr[ls] : 0.0;
@@ -676,7 +716,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                         const double wd = hu1 - l * hu0;
                         const double k1 = -wd * i2, k0 = -hu0 * i1 - l * k1;
                         KA0[ls] = k0; KA1[ls] = k1;
-                        const double hz[6] = {g0, g1, a0 * g0 + a2 * g1 + g2, a1 * g0 + a3 * g1 + g3, 0.0, 0.0};
+                        const double hz[6] = {g0, g1, pp(a0, g0, a2, g1, g2), pp(a1, g0, a3, g1, g3), 0.0, 0.0};
                         // 6. new cost-to-go at z_t (without x_t's own cost): Hzz + Huz' K,  hz + K' hu
                         const double zz[21] = {p00, p01, Gv0, Gp0, 0.0, 0.0,
                                                p11, Gv1, Gp1, 0.0, 0.0,
@@ -777,7 +817,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         bool viol = false;              // trial / polish: the predictor's end point is no KKT point (a row violated, a multiplier negative)
         // The round is plain from here to its end if no lane is in a trial or polish round now: the refill (trial) and the exit tests
         // (polish, pinit) are behind us, and what the step sets (polish for the next round) is read by no pass of this round.
-        const bool plain_round = !cx.any(trial || polish || pinit);
+        const bool plain_round = plain_on && !cx.any(trial || polish || pinit);
         // per row, recomputed from (s, lam, u, x) wherever needed instead of being kept: rp = s + gap, d = lam / s
         by_round(std::bool_constant<(PASSES & PLAIN_C) != 0>{}, plain_round, [&](auto plain) {
         constexpr bool PLAIN = decltype(plain)::value;
@@ -878,6 +918,11 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         double DZC = 0.0;               // JERK: the corrector's step of x4_0
         double RC[SPL][ROWS];           // rc / s of the corrector (kept in registers across the two corrector sweeps)
         {
+            double CG0[SPL], CG1[SPL], CG2[SPL], CG3[SPL], CH0[SPL], CH1[SPL];
+            by_round(std::bool_constant<(PASSES & PLAIN_D) != 0>{}, plain_round, [&](auto plain) {
+            MPCX_FP_PINNED
+            constexpr bool PLAIN = decltype(plain)::value;
+            const bool trial_r = !PLAIN && was_trial, polish_r = !PLAIN && was_polish;
             double C01[SPL], C23[SPL], C45[SPL], C67[SPL], C45n[SPL];
             MPCX_UNROLL
             for (int ls = 0; ls < SPL; ls++) {
@@ -886,28 +931,35 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 MPCX_UNROLL
                 for (int r = 0; r < ROWS; r++) {
                     const bool on = row_on(ls, r);
-                    const bool pa = was_polish & (sv[r] < 0.0);
-                    const bool full = on & !was_trial & !was_polish;             // a row of an ordinary iteration
+                    const bool pa = polish_r & (sv[r] < 0.0);
+                    const bool full = on & !trial_r & !polish_r;                 // a row of an ordinary iteration
                     const double s = pa ? lv[r] * (1.0 / MPCX_POLISH_RHO) : fabs(sv[r]);
                     const double l = (pa | full) ? lv[r] : 0.0;
                     const double is = cx.rcp(s);
                     const double rp = on ? s + row_gap(ls, r, Dprev[ls]) : 0.0;
                     const double dsa = on ? -rp - row_dir(r, DA0[ls], DA1[ls], DAp[ls], EA2[ls]) : 0.0;
-                    const double dla = -l - (l * is) * dsa;
+                    const double dla = fma(-(l * is), dsa, -l);
                     // a trial / polish round has no corrector (no second-order term, no centring): its right-hand side is the predictor's
                     // again, the second forward sweep repeats the first, and the step below -- at full length, if the round was accepted --
                     // IS the move to the end point that was checked
-                    const double rc = s * l + (full ? alpha_aff * (dsa * dla) - smu : 0.0);
+                    const double rc = fma(s, l, full ? fma(alpha_aff, dsa * dla, -smu) : 0.0);
                     RC[ls][r] = rc * is;                                         // rc / s
-                    nu[r] = l + (l * rp) * is - rc * is;
+                    // nu = lam + lam rp / s - rc / s.  The last term is the rounded rc / s kept above -- except in the rate pair of the lane's
+                    // first slot, where it is fused: the grouping this pass has had since it was written (the compiler's own choice then,
+                    // DESIGN 4.1), spelt out so that every copy and every instantiation computes it
+                    const double a1 = fma(l * rp, is, l);
+                    nu[r] = (ls == 0 && (r == 4 || r == 5)) ? fma(-is, rc, a1) : a1 - RC[ls][r];
                 }
                 C01[ls] = nu[0] - nu[1]; C23[ls] = nu[2] - nu[3]; C45[ls] = nu[4] - nu[5]; C67[ls] = nu[6] - nu[7];
             }
             next_of(C45, C45n);
-            double CG0[SPL], CG1[SPL], CG2[SPL], CG3[SPL], CH0[SPL], CH1[SPL];
             cost_grad(CG0, CG1, CG2, CG3, CH0, CH1);
             MPCX_UNROLL
-            for (int ls = 0; ls < SPL; ls++) { CG2[ls] += C67[ls]; CH0[ls] += C01[ls]; CH1[ls] += C23[ls] + C45[ls] - C45n[ls]; }
+            for (int ls = 0; ls < SPL; ls++) {
+                CG2[ls] = fma(WV(ls), X2[ls] - XRV[ls], C67[ls]);           // cost_grad's product, fused with the rows' term
+                CH0[ls] += C01[ls]; CH1[ls] += C23[ls] + C45[ls] - C45n[ls];
+            }
+            });
             double pv[JERK ? 7 : 6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             for (int turn = NTURN - 1; turn >= 0; turn--) {
                 if (q == turn) {
@@ -957,6 +1009,10 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             const double rp = on ? s + row_gap(ls, r, Dprev[ls]) : 0.0;
             return on ? -rp - row_dir(r, D0[ls], D1[ls], Dp[ls], E2[ls]) : 0.0;
         };
+        by_round(std::bool_constant<(PASSES & PLAIN_E) != 0>{}, plain_round, [&](auto plain) {
+        MPCX_FP_PINNED
+        constexpr bool PLAIN = decltype(plain)::value;
+        const bool trial_r = !PLAIN && was_trial, polish_r = !PLAIN && was_polish;
         MPCX_UNROLL
         for (int ls = 0; ls < SPL; ls++) {
             double sv[ROWS], lv[ROWS];
@@ -964,19 +1020,20 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             MPCX_UNROLL
             for (int r = 0; r < ROWS; r++) {
                 const bool on = row_on(ls, r);
-                const bool pa = was_polish & (sv[r] < 0.0);
-                const bool full = on & !was_trial & !was_polish;
+                const bool pa = polish_r & (sv[r] < 0.0);
+                const bool full = on & !trial_r & !polish_r;
                 const double s = pa ? lv[r] * (1.0 / MPCX_POLISH_RHO) : fabs(sv[r]);
                 const double l = (pa | full) ? lv[r] : 0.0;
                 const double ds = slack_step(ls, r, s);
                 // the multiplier step; in a trial / polish round the rows outside the active set end with a zero multiplier (written as a
                 // step from the stored one, so that the update below has no special case), the rows inside it with lam + rho gap'
-                const double dl = (pa | full) ? -RC[ls][r] - (l * cx.rcp(s)) * ds : -lv[r];
+                const double dl = (pa | full) ? fma(-(l * cx.rcp(s)), ds, -RC[ls][r]) : -lv[r];
                 cx.st_k(ls * ROWS + r, dl);
                 am_p = fmin(am_p, (on && ds < 0.0) ? -s * cx.rcp_fast(ds) : 1e300);
                 am_d = fmin(am_d, (on && dl < 0.0) ? -l * cx.rcp_fast(dl) : 1e300);
             }
         }
+        });
         cx.fence();
         // separate step lengths for (u, x, s) and for lam: the creeping instances are blocked by a slack in one iteration and by a
         // multiplier in the next; a common step length pays for both every time (maximum 20 -> 16 iterations on the closed-loop
@@ -987,6 +1044,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         // centrality safeguard: shorten until min s*lam >= 1e-3 * mean at the new point (at most 6 times)
         double mu_next = 0.0;           // mu at the point the step leads to (of the last evaluation: exact unless the step was shortened after it)
         for (int tr = 0; tr < 6; tr++) {
+            MPCX_FP_PINNED
             double pmin = 1e300, psum = 0.0;
             MPCX_UNROLL
             for (int ls = 0; ls < SPL; ls++) {
@@ -998,8 +1056,13 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 for (int r = 0; r < ROWS; r++) {
                     const bool on = row_on(ls, r);
                     const double s = fabs(sv[r]), l = lv[r];
-                    const double pr = (s + alpha * slack_step(ls, r, s)) * (l + alpha_d * dv[r]);
-                    pmin = fmin(pmin, on ? pr : 1e300); psum += on ? pr : 0.0;
+                    const double sn = fma(alpha, slack_step(ls, r, s), s), ln = fma(alpha_d, dv[r], l);
+                    const double pr = sn * ln;
+                    pmin = fmin(pmin, on ? pr : 1e300);
+                    // the sum takes the rounded product -- except for the leading run of rows that share one switch (rows 0..3 of the lane's
+                    // first slot), whose products are fused into it: the grouping this loop has had since it was written
+                    if (ls == 0 && r < 4) psum = on ? fma(sn, ln, psum) : psum;
+                    else psum += on ? pr : 0.0;
                 }
             }
             const double gmn = cx.gmin(pmin), gsm = cx.gsum(psum);
@@ -1009,7 +1072,12 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             if (!ok && !was_trial && !was_polish) { alpha *= 0.7; alpha_d *= 0.7; }      // (a trial / polish group takes the full step or none)
         }
         cx.stamp(8);                    // [local pass E + safeguard]
+        const bool trial_was = was_trial, polish_was = was_polish;
         // ---- step
+        by_round(std::bool_constant<(PASSES & PLAIN_E) != 0>{}, plain_round, [&](auto plain) {
+        MPCX_FP_PINNED
+        constexpr bool PLAIN = decltype(plain)::value;
+        const bool was_trial = !PLAIN && trial_was, was_polish = !PLAIN && polish_was;
         if (running && (!(was_trial || was_polish) || accepted)) {
             // is the new iterate close enough to polish?  (same rule in the condensed solver: mu of the new point, the primal residual shrinks by
             // 1 - alpha, the dual one by about the smaller of the two step lengths.)  If so the group polishes from the next round on,
@@ -1026,7 +1094,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                     MPCX_UNROLL
                     for (int r = 0; r < ROWS; r++) {          // rows that are off have ds = dl = 0
                         const double s = fabs(sv[ls * ROWS + r]);
-                        const double sn = s + alpha * slack_step(ls, r, s), ln = lv[ls * ROWS + r] + alpha_d * dv[ls * ROWS + r];
+                        const double sn = fma(alpha, slack_step(ls, r, s), s), ln = fma(alpha_d, dv[ls * ROWS + r], lv[ls * ROWS + r]);
                         // an accepted trial / polish point: the true slack (>= 0 up to rounding; floored so that lam / s stays finite)
                         const double sw = ((was_trial | was_polish) & row_on(ls, r)) ? fmax(sn, 1e-30) : sn;
                         cx.st_s(ls * ROWS + r, (pnext & (sn < ln)) ? -sw : sw);
@@ -1035,13 +1103,15 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             }
             MPCX_UNROLL
             for (int ls = 0; ls < SPL; ls++) {
-                U0[ls] += alpha * D0[ls]; U1[ls] += alpha * D1[ls];
-                X0[ls] += alpha * E0[ls]; X1[ls] += alpha * E1[ls]; X2[ls] += alpha * E2[ls]; X3[ls] += alpha * E3[ls];
+                U0[ls] = fma(alpha, D0[ls], U0[ls]); U1[ls] = fma(alpha, D1[ls], U1[ls]);
+                X0[ls] = fma(alpha, E0[ls], X0[ls]); X1[ls] = fma(alpha, E1[ls], X1[ls]);
+                X2[ls] = fma(alpha, E2[ls], X2[ls]); X3[ls] = fma(alpha, E3[ls], X3[ls]);
             }
-            if constexpr (JERK) Z0 += alpha * DZC;
+            if constexpr (JERK) Z0 = fma(alpha, DZC, Z0);
             if (!was_trial && !was_polish) it++;
             if (pnext) { polish = true; ptries = 0; pend = 0; }
         }
+        });
         cx.stamp(9);                    // [update]
     }
 #undef PX

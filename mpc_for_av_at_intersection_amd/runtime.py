@@ -986,6 +986,11 @@ class Context:
         side stream.  The results are the same bits either way."""
         self._chk(self.lib.mpcx_set_step_fusion(self._ctx, 1 if on else 0))
 
+    def set_qp_plain_rounds(self, on: bool):
+        """stage-structured QP solver: True (the default) = rounds without a trial or polishing problem run the plain copies of the row
+        passes; False = the generic text in every round.  The results are the same bits either way."""
+        self._chk(self.lib.mpcx_qp_set_plain_rounds(self._ctx, 1 if on else 0))
+
     def profile_qp(self, enable: bool):
         """bracket every qp_kernel launch with HIP events on the context's stream (mpcx_profile_qp)"""
         self._chk(self.lib.mpcx_profile_qp(self._ctx, 1 if enable else 0))
