@@ -1184,8 +1184,67 @@ int32_t mpcx_sight_step_batch(mpcx_ctx *ctx, int32_t P, const double *state /*P,
                               const double *obs6 /*NOBS,6*/, const int32_t *obs_off /*P*/, const int32_t *obs_cnt /*P*/,
                               const int32_t *obs_skip /*P*/, const int32_t *absent /*NOBS or NULL*/, const mpcx_sight *sight);
 
+/* ---- keep clear: a car whose light lets it go waits at its line while the crossing is occupied by a movement that conflicts with its own.
+ * The signal hold looks at the light and nothing else, and the conflict search sees a late car of the phase before only as a prediction and
+ * only once the released car is moving: under a two-phase plan the first car of a phase drives into a car that is still crossing.  With the
+ * keep-clear stage on, one launch (keepclear_kernel, csrc/mpcx_keepclear.hip; the rule is csrc/mpcx_keepclear_core.h) directly behind the
+ * hold (signal_kernel or actuated_signal_kernel) and in front of the following stage works out, per junction, which movements are inside
+ * the crossing and holds such a car at its stop line by the cut the signal hold makes.  It costs nothing when the box is empty, where a
+ * longer all-red costs capacity in every cycle.  It attaches to the CONTEXT (mpcx_set_keepclear), as following, the near-miss log and line
+ * of sight do: every mpcx_closed_loop_run* entry point runs it while set; it needs signals (fixed plan or actuated) and is refused beside
+ * a reservation, whose manager already keeps the crossing clear.
+ * The signal groups stay what they are.  A junction is n_per consecutive agents, n_per <= 64: junction j owns agents [j n_per, (j + 1)
+ * n_per), n_per n_junctions = P.  Tables: path_move[n_points] the movement of the route on that path point, at most
+ * MPCX_SIGNAL_GROUPS_MAX movements; path_exit[n_points] the route-local index e at which a vehicle on this point has left the crossing, -1
+ * if no crossing lies ahead or under the point; conflict[n_moves], bit h of word g set when movements g and h may not be in the crossing
+ * together (symmetric, no diagonal).  The stop line (path_stop), held and brake are the run's mpcx_signals'.  State, caller-owned device
+ * memory: waited[P] in-out, zero-initialised; boxed[P] out (0 / 1); occupied[n_junctions] out (the movements inside the crossing);
+ * n_boxed[n_junctions] out.
+ * Per junction and step: (1) every agent q, with ti = traj_idx[q] as this step's conflict search left it, i = path_off[q] + ti, s =
+ * path_stop[i], m = path_move[i], e = path_exit[i]: OUT if done[q] != 0 (retired, or waiting for admission), i outside [0, n_points), e <
+ * 0, e > path_len[q], ti >= e, m outside [0, n_moves), or ti < s with s >= path_len[q]; INSIDE if not OUT and (s < 0 or ti >= s); otherwise
+ * APPROACH.  (2) occ = OR of 1 << m over the INSIDE agents.  (3) an APPROACH agent is a candidate if held[q] == 0 as this step's hold left
+ * it, s - ti <= detect and (conflict[m] & occ) != 0; a candidate is BOXED if waited[q] != 0 -- a car that stood at its line in the step
+ * before does not start into an occupied box, the amber rule's stickiness -- or if it can stop, (double)(s - ti) dl >= v v / (2.0 brake)
+ * with v = state[q][2], the signal hold's own expression; otherwise it is free: a car that arrives at speed on green and cannot stop any
+ * more is left to the conflict search, as on amber.  Boxed: boxed[q] = 1, cut_len[q] = min(cut_len[q], s); everybody else: boxed[q] = 0,
+ * cut_len untouched.  (4) waited[q] = 1 for an APPROACH agent with held[q] != 0 or boxed[q] != 0, 0 for everybody else.  (5) occupied[j] =
+ * occ, n_boxed[j] = the number boxed.  The comparison of (3) is the only floating point.  Host and device agree bit for bit.
+ * The stage writes no word of another stage: held stays the signal stage's, so the actuated controller's calls and the advice stage read
+ * what they read without it.  NULL or an all-zero struct: off -- the loop enqueues exactly the launches of a context that never had it,
+ * with the same arguments.  The cached graph's key covers the struct by value (it has no padding: six int32 close its 80 bytes), and a run
+ * with the stage on does not take step fusion.  MPCX_E_INVALID ("keepclear: ...") from the run or the stage call before anything is
+ * launched, whatever n_steps is: no signals; a reservation in the run; one of the seven pointers (or the signals' path_stop or held) NULL;
+ * n_per outside 1..64 or n_per n_junctions != P; n_moves outside 1..MPCX_SIGNAL_GROUPS_MAX; n_points not the signals'; detect < 1; a
+ * conflict word with bits at or above n_moves, with its own bit, or not symmetric; more than one linearisation pass; the agent-sharded
+ * layout; a nonzero reserved word.  The conflict table is read back from the device for its check (one blocking copy) ONCE per struct: the
+ * context remembers the pointer and count that passed and forgets them when mpcx_set_keepclear is given a struct that differs from the
+ * one it holds, so run(1) in a loop reads nothing back.  Do not change the table in place while set; after mpcx_set_keepclear(NULL) a new
+ * mpcx_set_keepclear has it checked again.  The per-agent, per-junction and per-point words are not read back -- a bad word is data (OUT),
+ * never a GPU fault. */
+#define MPCX_KEEPCLEAR_PER_MAX 64
+typedef struct {
+    const int32_t *path_move;    /* n_points: the movement of the route on this path point */
+    const int32_t *path_exit;    /* n_points: route-local index at which a vehicle on this point has left the crossing, -1 = none */
+    const int32_t *conflict;     /* n_moves: bit h of word g = movements g and h may not be in the crossing together */
+    int32_t *boxed;              /* P, caller-owned, out: 1 = the agent was held at its line by this stage in the last step */
+    int32_t *waited;             /* P, caller-owned, in-out, zero-initialised: 1 = the agent stood at its line (held or boxed) in the last step */
+    int32_t *occupied;           /* n_junctions, out: the mask of movements inside the crossing */
+    int32_t *n_boxed;            /* n_junctions, out: the number of agents boxed this step */
+    int32_t detect;              /* an agent is looked at from this many path points before its line on (>= 1) */
+    int32_t n_per, n_junctions, n_moves, n_points, reserved;     /* reserved: 0 */
+} mpcx_keepclear;
+/* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
+int32_t mpcx_set_keepclear(mpcx_ctx *ctx, const mpcx_keepclear *keepclear /*NULL or all-zero = off*/);
+/* one step's keep-clear stage alone (what the closed loop enqueues behind the hold); the arguments of mpcx_signal_step_batch plus the
+ * struct, called behind mpcx_signal_step_batch or mpcx_actuated_step_batch on the same signals: it reads their held as that call left it.
+ * The struct is the argument's, not the context's, and is checked as above (its conflict table in every call). */
+int32_t mpcx_keepclear_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
+                                  const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
+                                  const int32_t *done /*P or NULL*/, const mpcx_signals *signals, const mpcx_keepclear *keepclear);
+
 /* ---- the stages together.  With several optional stages on, a step is: admission, the entry-order stamp; pool pack and prediction; the
- * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the following stage; per linearisation
+ * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the keep-clear stage; the following stage; per linearisation
  * pass the window stage, the advice stage, the following clamp and the QP; the plant; record, retire, respawn.  What that order implies:
  *   one car, three views   agent q sees a present row r of its window (1) standing at its pose if prec[r] > prec[obs_skip[q]], whatever
  *                          the intent stage wrote into r's predicted frames; (2) else on its owner's plan of the step before, if the owner
@@ -1206,6 +1265,12 @@ int32_t mpcx_sight_step_batch(mpcx_ctx *ctx, int32_t P, const double *state /*P,
  *                          clearance is unchanged by construction).  Nor do the admission gate, the reservation manager or the run log's
  *                          clearance consult it.  A yielding row (precedence) or a sharing row (intent) that is not seen is simply not in
  *                          the agent's list.
+ *   the keep-clear stage   reads held as this step's hold left it and never writes it: snapshot()'s held, the actuated controller's calls
+ *                          and the advice stage see the lights alone.  It is one more minimum on cut_len, in front of the follower's.  It
+ *                          reads traj_idx as the conflict search left it, like the reservation manager.  The respawn stages reset neither
+ *                          boxed nor waited: a vehicle that arrives has been OUT since its exit point, and a reset slot waits at the
+ *                          gate with done != 0, which is OUT too, so the stage itself has cleared waited before the slot's next
+ *                          vehicle drives -- the word heals itself.
  * tests/stack_helpers.py composes the host builds of the rules in this order; tests/test_gpu_stack.py replays the device against it. */
 /* one step's search stage alone (what the closed loop enqueues in front of the window stage): steps 1 - 5.  stop_mode: MPCX_STOP_CUT or
  * MPCX_STOP_SPEED; the struct is the argument's, not the context's, and is checked as above. */

@@ -163,6 +163,16 @@ class SightC(C.Structure):
                 ('n_occ', C.c_int32), ('n_sets', C.c_int32), ('n_rows', C.c_int32), ('n_pool', C.c_int32), ('reserved', C.c_int32)]
 
 
+class KeepClearC(C.Structure):
+    """mirror of mpcx_keepclear (include/mpcx.h): keep clear; every pointer is a device address -- path_move / path_exit (n_points int32),
+    conflict (n_moves int32), boxed / waited (P int32), occupied / n_boxed (n_junctions int32).  Not a row of STAGES: the stage attaches to
+    the context (Context.set_keepclear)"""
+    _fields_ = [('path_move', C.c_void_p), ('path_exit', C.c_void_p), ('conflict', C.c_void_p), ('boxed', C.c_void_p), ('waited', C.c_void_p),
+                ('occupied', C.c_void_p), ('n_boxed', C.c_void_p), ('detect', C.c_int32), ('n_per', C.c_int32), ('n_junctions', C.c_int32),
+                ('n_moves', C.c_int32), ('n_points', C.c_int32), ('reserved', C.c_int32)]
+
+
+KEEPCLEAR_PER_MAX = 64                          # MPCX_KEEPCLEAR_PER_MAX: agents per junction under keep clear
 SIGHT_WINDOW = 64                               # window offsets a word of mpcx_sight.sight holds
 # the words of an event record of the near-miss log (ev_i32[q][e][0..7]; ev_f64[q][e] = the minimum clearance, the agent's speed at opening)
 SAFETY_I32 = ('open', 'last', 'row', 'row_agent', 'path_off', 'partner_path_off', 'traj_idx', 'ttc_frame')
@@ -328,7 +338,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_admit_step_batch_precedence', 'mpcx_signal_step_batch', 'mpcx_closed_loop_queue', 'mpcx_interaction_prediction',
            'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
            'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch',
-           'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary', 'mpcx_set_sight', 'mpcx_sight_step_batch'] + LOOP_ENTRY_POINTS
+           'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary', 'mpcx_set_sight', 'mpcx_sight_step_batch',
+           'mpcx_set_keepclear', 'mpcx_keepclear_step_batch'] + LOOP_ENTRY_POINTS
 
 
 def load():
@@ -437,5 +448,8 @@ def load():
     lib.mpcx_set_sight.restype = i32; lib.mpcx_set_sight.argtypes = [vp, C.POINTER(SightC)]
     lib.mpcx_sight_step_batch.restype = i32
     lib.mpcx_sight_step_batch.argtypes = [vp, i32, vp, vp, i32] + [vp] * 5 + [C.POINTER(SightC)]
+    lib.mpcx_set_keepclear.restype = i32; lib.mpcx_set_keepclear.argtypes = [vp, C.POINTER(KeepClearC)]
+    lib.mpcx_keepclear_step_batch.restype = i32
+    lib.mpcx_keepclear_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(KeepClearC)]
     _lib = lib
     return lib

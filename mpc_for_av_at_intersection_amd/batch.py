@@ -51,6 +51,8 @@ pair of movements.  It decides nothing.
 `occlude()` is LINE OF SIGHT, beside every other stage on a scene: one launch in front of the conflict search decides which rows of its
 window every agent sees (sensor range, convex occluders, connected vehicles that are heard), and the conflict search leaves the others out of
 that agent's obstacle list.  corner_blocks() gives the buildings of the stock four-way world.
+`keep_clear()` is KEEP CLEAR for a batch under signalise() or actuate(): one launch behind the hold keeps a car whose light lets it go at its
+stop line while a movement that conflicts with its own (cross_phase_conflicts()) is inside the crossing; enter_on_green() switches it off.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -405,6 +407,12 @@ class IntersectionBatch:
         self.n_hidden: Optional[torch.Tensor] = None         # ... int32 (P,), candidates not seen in the last step
         self._sight = None                                   # (set on the context too)
         self._sight_tabs = None                              # ... the device tables the struct names: hp, hp_off, box, set_off, set_of, heard or None
+        self.boxed: Optional[torch.Tensor] = None            # keep_clear(): int32 (P,), 1 = the agent was kept at its line in the last step
+        self.box_waited: Optional[torch.Tensor] = None       # ... int32 (P,), 1 = the agent stood at its line (held or boxed) in the last step
+        self.box_occupied: Optional[torch.Tensor] = None     # ... int32 (B,), the movements inside the crossing in the last step
+        self.n_boxed: Optional[torch.Tensor] = None          # ... int32 (B,), the agents boxed in the last step
+        self._keepclear = None                               # (set on the context too)
+        self._keepclear_tabs = None                          # ... the device tables the struct names: path_move, path_exit, conflict
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -443,12 +451,14 @@ class IntersectionBatch:
         """switch the named stages off, and with each the stages that live on it (_lib.stage_dependents); drops the cached descriptor"""
         entry = self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY
         for k in stages:
-            if k == 'sight':                # (attached to the context, no row of _lib.STAGES: nothing lives on it)
-                self._sight = None
+            if k in ('sight', 'keepclear'):     # (attached to the context, no row of _lib.STAGES: nothing lives on it)
+                setattr(self, '_' + k, None)
                 continue
             off = {k} | _lib.stage_dependents(k, entry)
             if off & {'retire', 'scene'}:   # line of sight lives on the scene
                 self._sight = None
+            if 'signals' in off:            # keep clear lives on the signals
+                self._keepclear = None
             for d in off:
                 setattr(self, '_' + d, None)
         self._desc = None
@@ -977,6 +987,63 @@ class IntersectionBatch:
         and `n_hidden` keep what they hold and are no longer written)"""
         self._off('sight')
 
+    def keep_clear(self, conflict=None, move=None, exit=None, detect: Optional[int] = None, phases=((0, 2), (1, 3))):
+        """KEEP CLEAR (mpcx_set_keepclear), for a batch under signalise() or actuate(), in both stop modes.  The hold looks at the light
+        and nothing else: under a two-phase plan the first car of a phase starts into a car of the phase before that is still crossing.
+        With keep clear one more small launch behind the hold works out, per instance (a junction of A <= 64 agents), which movements are
+        inside the crossing -- from the stop line to the exit point --, and an agent within `detect` path points of its line whose light
+        lets it go, but whose movement conflicts with one that is inside, is held at its line by the cut the signal hold makes.  A car that
+        stood at its line in the step before (held by the light or boxed) stays; a car that arrives at speed on green stays only if it can
+        still stop with the signals' `brake`, else it is left to the conflict search, as on amber.  `held` stays the light's word.
+        move, exit: the per-path-point tables, both or neither (default: movement_lines() of the batch's routes); conflict: one bit mask
+        per movement, symmetric, without a diagonal (default: cross_phase_conflicts(movement_conflicts(...), phases) with the batch's disc
+        model: only movements of arms that share no phase keep each other out, so a permissive turn is not blocked by the opposed arm);
+        detect: default the whole approach (the largest stop-line index).
+        Allocates `boxed`, `box_waited`, `box_occupied`, `n_boxed` (zero) and the tables and drops the cached descriptor;
+        enter_on_green() switches it off, as does unsignalise() or reserve()."""
+        if self._signals is None:
+            raise ValueError('keep_clear: needs signalise() or actuate() -- the stage holds a car whose light lets it go')
+        if self._reservation is not None:
+            raise ValueError('keep_clear: the batch runs under reserve(), whose manager already keeps the crossing clear')
+        if self.exchange == 'rccl' or callable(self.exchange):
+            raise ValueError('keep_clear: not in the agent-sharded layout (shard by instances)')
+        if not 1 <= self.A <= _lib.KEEPCLEAR_PER_MAX:
+            raise ValueError('keep_clear: a junction holds 1 .. %d agents, the batch has A = %d' % (_lib.KEEPCLEAR_PER_MAX, self.A))
+        stop = self._signal_tabs['path_stop'].cpu().numpy()
+        if move is None or exit is None:
+            if move is not None or exit is not None:
+                raise ValueError('keep_clear: give both move and exit, or neither')
+            _, move, exit = movement_lines(self._route_list())
+        move, exit = np.asarray(move), np.asarray(exit)
+        n_points = int(self.path.shape[0])
+        if move.shape != (n_points,) or exit.shape != (n_points,):
+            raise ValueError('keep_clear: move and exit hold one word per path point (%d)' % n_points)
+        if conflict is None:
+            full, _ = movement_conflicts(self._route_list(), stop, exit, np.asarray(self.ip.circle_centers), float(self.ip.radius))
+            conflict = cross_phase_conflicts(full, phases)
+        conflict = np.asarray(conflict)
+        if conflict.ndim != 1 or not 1 <= len(conflict) <= _lib.SIGNAL_GROUPS_MAX or not np.issubdtype(conflict.dtype, np.integer):
+            raise ValueError('keep_clear: conflict holds one integer word per movement, 1 .. %d movements' % _lib.SIGNAL_GROUPS_MAX)
+        detect = max(int(stop.max()) if len(stop) else 1, 1) if detect is None else int(detect)
+        if not 1 <= detect <= int(np.iinfo(np.int32).max):
+            raise ValueError('keep_clear: detect >= 1 path point, int32')
+        c = self.ctx
+        tabs = dict(path_move=c.i32(move), path_exit=c.i32(exit), conflict=c.i32(conflict))
+        zeros = lambda n: torch.zeros(n, dtype=torch.int32, device=c.device)
+        self.boxed, self.box_waited, self.box_occupied, self.n_boxed = zeros(self.P), zeros(self.P), zeros(self.B), zeros(self.B)
+        self._keepclear_tabs = tabs
+        self._keepclear = _lib.KeepClearC(tabs['path_move'].data_ptr(), tabs['path_exit'].data_ptr(), tabs['conflict'].data_ptr(),
+                                          self.boxed.data_ptr(), self.box_waited.data_ptr(), self.box_occupied.data_ptr(),
+                                          self.n_boxed.data_ptr(), detect, self.A, self.B, len(conflict), n_points, 0)
+        c.set_keepclear(None)       # (a new table may sit where an old one sat: the context checks the next struct it is given afresh)
+        self._desc = None
+        c.synchronize()
+
+    def enter_on_green(self):
+        """switch keep clear off and nothing else: the batch enqueues exactly the launches of one that never had it (`boxed`, `box_waited`,
+        `box_occupied` and `n_boxed` keep what they hold and are no longer written)"""
+        self._off('keepclear')
+
     def share_plans(self, share=None):
         """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
         it applied in the last step, held for pred_steps frames -- the reference's prediction of a scripted car.  A sharing agent is seen
@@ -1109,7 +1176,7 @@ class IntersectionBatch:
                                               tabs['mgr_time'].data_ptr(), tabs['mgr_of'].data_ptr(), self.granted.data_ptr(),
                                               self.since.data_ptr(), self.junction_clock.data_ptr(), self.occupied.data_ptr(),
                                               self.queued.data_ptr(), self.A, self.B, len(managers), 0)
-        self._off('actuation', 'advice')    # (a junction manager replaces a controller or a plan; there is no plan to look ahead into)
+        self._off('actuation', 'advice', 'keepclear')   # (a junction manager replaces a controller or a plan; there is no plan to look ahead into; the manager itself keeps the crossing clear)
         c.synchronize()
 
     def unsignalise(self):
@@ -1245,6 +1312,7 @@ class IntersectionBatch:
         self.ctx.set_following(self._following)
         self.ctx.set_safety(self._safety)
         self.ctx.set_sight(self._sight)
+        self.ctx.set_keepclear(self._keepclear)
 
     def run(self, n_steps: int, graph: bool = False):
         """n_steps of the closed loop with no host work in between (mpcx_closed_loop_run)."""
@@ -1324,6 +1392,8 @@ class IntersectionBatch:
             c.actuated_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._actuation)
         elif self._signals is not None:     # the signal stage: between the conflict search and the window stage, as in the loop
             c.signal_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals)
+        if self._keepclear is not None:     # the keep-clear stage: behind the signal / actuated stage, on the held it left, as in the loop
+            c.keepclear_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._keepclear)
         if self._following is not None:     # the following stage: behind the signal stage, in front of the window stage, as in the loop
             c.follow_step(self.dl, _lib.STOP_SPEED if speed else _lib.STOP_CUT, self.state, self.path, self.path_off, self.path_len, self.traj_idx,
                           self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self._following, obs_skip=self.obs_skip)
@@ -1374,6 +1444,9 @@ class IntersectionBatch:
         if self._sight is not None:          # who saw whom in the last step: the uint64 word per agent and its two counts
             out.update(sight=self.sight.cpu().numpy().view(np.uint64).copy(), n_seen=self.n_seen.cpu().numpy().copy(),
                        n_hidden=self.n_hidden.cpu().numpy().copy())
+        if self._keepclear is not None:      # who was kept at its line in the last step, who stood there, and the movements inside per junction
+            out.update(boxed=self.boxed.cpu().numpy().copy(), box_waited=self.box_waited.cpu().numpy().copy(),
+                       box_occupied=self.box_occupied.cpu().numpy().copy(), n_boxed=self.n_boxed.cpu().numpy().copy())
         if self._routes is not None:        # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
@@ -1551,6 +1624,22 @@ def movement_conflicts(routes, stop, exit, circle_centers, radius: float, margin
                 conflict[g] |= 1 << h
                 conflict[h] |= 1 << g
     return conflict.astype(np.int32), lane.astype(np.int32)
+
+
+def cross_phase_conflicts(conflict, phases=((0, 2), (1, 3))):
+    """The conflict table of IntersectionBatch.keep_clear from movement_conflicts()' (one word per movement 3 (arm - 1) + (turn - 1)): bit h
+    of word g is kept only if the arms g // 3 and h // 3 share no phase of `phases` (a sequence of sequences of arms = signal groups; the
+    default is two_phase_plan()'s and two_phase_controller()'s).  Movements that are green together sort themselves out as ever -- a
+    permissive turn against the opposed arm must not be blocked by it --; the contacts a two-phase plan leaves are between arms of
+    different phases.  Symmetric if `conflict` is.  Pure numpy: no GPU, no state."""
+    conflict = np.asarray(conflict, dtype=np.int64)
+    together = {(a, b) for ph in phases for a in ph for b in ph}
+    out = np.zeros_like(conflict)
+    for g in range(len(conflict)):
+        for h in range(len(conflict)):
+            if (int(conflict[g]) >> h) & 1 and (g // 3, h // 3) not in together:
+                out[g] |= 1 << h
+    return out.astype(np.int32)
 
 
 def two_phase_plan(cycle: int, green: int, amber: int) -> dict:

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1712] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1792] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     mpcx_following following = {};        // car following (mpcx_set_following): the struct by value, padding zeroed; all zeros while off
@@ -32,6 +32,13 @@ struct mpcx_ctx {
         int32_t n_sets = 0, n_occ = 0;
         bool ok = false;
     } sight_tables;
+    mpcx_keepclear keepclear = {};        // keep clear (mpcx_set_keepclear): the struct by value, padding zeroed; all zeros while off
+    bool have_keepclear = false;
+    struct KeepClearTable {               // the conflict table of a mpcx_keepclear that was read back and passed its check (mpcx_keepclear_validate)
+        const int32_t *conflict = nullptr;
+        int32_t n_moves = 0;
+        bool ok = false;
+    } keepclear_table;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
     const int32_t *order_now = nullptr, *order_prev = nullptr;   // optional pair: entries that differ mark a discontinuous change of the reference
     // scratch of mpcx_closed_loop_run for P agents: [P] cut lengths of the previous step | [3 P] what the conflict search's nearest-index
@@ -270,6 +277,14 @@ int32_t mpcx_sight_validate(mpcx_ctx *ctx, const mpcx_sight *s, int32_t P, int32
 int32_t mpcx_sight_enqueue(mpcx_ctx *ctx, int32_t P, const double *state, const int32_t *done /*or nullptr*/, int32_t n_obs_pool,
                            const double *obs6, const int32_t *obs_off, const int32_t *obs_cnt, const int32_t *obs_skip,
                            const int32_t *absent /*or nullptr*/, const mpcx_sight *sight);
+// keep clear (mpcx_keepclear.hip): "no keep-clear stage" test, check of the struct against the run (sg: the run's signals or nullptr;
+// reserved_run: the run also carries a reservation; reads the conflict table back once per struct), the launch alone (behind the hold, in
+// front of the following stage)
+bool mpcx_keepclear_absent(const mpcx_keepclear *s);
+int32_t mpcx_keepclear_validate(mpcx_ctx *ctx, const mpcx_keepclear *s, const mpcx_signals *sg, int32_t P, int32_t exchange, bool reserved_run);
+int32_t mpcx_keepclear_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
+                               const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals,
+                               const mpcx_keepclear *keepclear);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

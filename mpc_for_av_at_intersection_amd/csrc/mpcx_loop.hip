@@ -108,10 +108,15 @@ struct LoopStages {
     // the pool and the intent stage, and the SIGHT instantiation of the conflict search; needs retirement, a scene and obs_skip.
     // &ctx->sight while on.
     const mpcx_sight *sight = nullptr;
+    // keep clear (mpcx_set_keepclear: it attaches to the context too): keepclear_kernel directly behind signal_kernel /
+    // actuated_signal_kernel and in front of the following stage; needs signals and no reservation.  It reads held as the hold left it and,
+    // for an agent whose light lets it go while a conflicting movement is inside the crossing, lowers c->cut_len to the agent's stop line.
+    // &ctx->keepclear while on.
+    const mpcx_keepclear *keepclear = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight && !keepclear; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -125,6 +130,7 @@ struct LoopKey {
     mpcx_following following;
     mpcx_safety safety;
     mpcx_sight sight;
+    mpcx_keepclear keepclear;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -191,6 +197,12 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (!mpcx_precedence_absent(a.precedence)) st->precedence = a.precedence;
     if (st->precedence && (rc = mpcx_precedence_validate(ctx, st->precedence, st->scene, st->admit)) != MPCX_OK) return rc;
     if (!mpcx_signals_absent(a.signals)) st->signals = a.signals;
+    if (ctx->have_keepclear) {      // in front of the hold's own checks, so that what the stage cannot run with is refused in its name; it
+                                    // reads the signals' pointers and counts only, which the hold's check below then goes through
+        rc = mpcx_keepclear_validate(ctx, &ctx->keepclear, st->signals, c->P, c->exchange, !mpcx_reservation_absent(a.reservation));
+        if (rc != MPCX_OK) return rc;
+        st->keepclear = &ctx->keepclear;
+    }
     if (!mpcx_reservation_absent(a.reservation)) {  // checks the signals it draws on too, and refuses a controller or advice beside it
         rc = mpcx_reservation_validate(ctx, a.reservation, st->signals, c->P, c->exchange, !mpcx_actuation_absent(a.actuation),
                                        !mpcx_advice_absent(a.advice));
@@ -241,7 +253,7 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     return rc;
 }
 
-// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the following stage) -> lin_passes x (reference
+// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the keep-clear stage) (-> the following stage) -> lin_passes x (reference
 // window (-> the advice stage) (-> the following clamp) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
@@ -275,6 +287,10 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
         rc = st.reserve  ? mpcx_reserve_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, st.reserve)
            : st.actuated ? mpcx_actuated_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, &st.actuation)
                          : mpcx_signal_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals);
+        if (rc != MPCX_OK) return rc;
+    }
+    if (st.keepclear) {
+        rc = mpcx_keepclear_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, st.keepclear);
         if (rc != MPCX_OK) return rc;
     }
     if (st.follow) {
@@ -509,6 +525,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.following, st.follow);
     key_put(key.safety, st.safety);
     key_put(key.sight, st.sight);
+    key_put(key.keepclear, st.keepclear);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;

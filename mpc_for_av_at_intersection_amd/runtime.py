@@ -868,6 +868,28 @@ class Context:
         self._chk(self.lib.mpcx_set_sight(self._ctx, None if sight is None else C.byref(sight)))
         self._sight = sight
 
+    def set_keepclear(self, keepclear: Optional['_lib.KeepClearC']):
+        """mpcx_set_keepclear: keep clear for every closed-loop run of this context from now on; None (or an all-zero struct) = off.  The
+        context copies the struct; the device buffers it names stay the caller's and are kept alive here while set."""
+        self._chk(self.lib.mpcx_set_keepclear(self._ctx, None if keepclear is None else C.byref(keepclear)))
+        self._keepclear = keepclear
+
+    @_ordered
+    def keepclear_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, signals: '_lib.SignalsC', keepclear: '_lib.KeepClearC',
+                       done=None):
+        """mpcx_keepclear_step_batch: ONE step's keep-clear stage as the closed loop enqueues it behind the signal / actuated stage, on the
+        signals' held as that stage left it.  cut_len (P int32) is lowered in place for a boxed agent, and the struct's boxed, waited,
+        occupied and n_boxed are written; done: the retirement words (P int32) or None."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('cut_len', cut_len)):
+            self._want(t, torch.int32, (Pn,), name)
+        if done is not None:
+            self._want(done, torch.int32, (Pn,), 'done')
+        self._chk(self.lib.mpcx_keepclear_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
+                                                     _ptr(cut_len), _ptr(done), None if signals is None else C.byref(signals),
+                                                     C.byref(keepclear)))
+
     @_ordered
     def sight_step(self, state, obs6, obs_off, obs_cnt, obs_skip, sight: '_lib.SightC', done=None, absent=None):
         """mpcx_sight_step_batch: ONE step's sight stage as the closed loop enqueues it in front of the conflict search: the struct's sight,
