@@ -1243,8 +1243,73 @@ int32_t mpcx_keepclear_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const dou
                                   const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
                                   const int32_t *done /*P or NULL*/, const mpcx_signals *signals, const mpcx_keepclear *keepclear);
 
+/* ---- priority road: a car of a minor movement waits at its stop line until the conflicting movements of smaller rank leave it a gap.
+ * give_way('entry') ranks by order of entry and give_way(order=) by slot, and the conflict search cuts a path only where two predictions
+ * meet: a minor-road car pulls out in front of a major-road car, which then yields to it.  With the priority stage on, one launch
+ * (priority_kernel, csrc/mpcx_priority.hip; the rule is csrc/mpcx_priority_core.h) in the hold's place -- behind the conflict search and
+ * the safety stage, in front of the following stage -- holds such a car at its line by the cut the signal hold makes, in both stop modes.
+ * It attaches to the CONTEXT (mpcx_set_priority), as following, the near-miss log, line of sight and keep clear do: every
+ * mpcx_closed_loop_run* entry point runs it while set.  A junction is run by lights, by a manager, or by priority: the stage is refused
+ * beside signals, actuation or a reservation, so the stop lines are its own table.
+ * A junction is n_per consecutive agents, n_per <= 64: junction j owns agents [j n_per, (j + 1) n_per), n_per n_junctions = P.  Tables:
+ * path_stop[n_points], path_move[n_points], path_exit[n_points] as mpcx_signals' and mpcx_keepclear's (the route-local index of the next
+ * stop line at or after the point, -1 = none; the movement of the route, at most MPCX_SIGNAL_GROUPS_MAX movements; the route-local index at
+ * which a vehicle on the point has left the crossing, -1 = none); conflict[n_moves], bit h of word g set when movements g and h cross
+ * (symmetric, no diagonal); rank[n_moves] >= 0, a smaller rank goes first; gap[n_moves], finite and >= 0, the critical gap in seconds of
+ * movement m when it gives way.  Scalars: v_floor (> 0, the least speed an approaching car is taken to have), brake (> 0), detect (>= 1
+ * path point).  State, caller-owned device memory: waited[P] in-out, zero-initialised; yielding[P] out (0 / 1); blocker[P] out, an agent
+ * index, -1 = none; lag[P] out, seconds, +inf = none; occupied[n_junctions] out (the movements inside the crossing); n_yielding[n_junctions]
+ * out.
+ * Per junction and step, everything is read before anything is written: (1) every agent q is OUT, INSIDE or APPROACH with (m, s, ti)
+ * exactly as the keep-clear stage classifies it (above), done[q] != 0 being OUT.  (2) an agent r that is not OUT has eta_r = 0.0 if INSIDE,
+ * else (double)(s_r - ti_r) dl / fmax(state[r][2], v_floor); occ = OR of 1 << m over the INSIDE agents.  (3) an APPROACH agent q with
+ * s_q - ti_q <= detect: lag[q] = the minimum of eta_r over the agents r != q of the junction that are not OUT, have rank[m_r] < rank[m_q]
+ * and bit m_r of conflict[m_q] set; blocker[q] = the agent that attains it, the lowest index among equals; none: +inf and -1.  q is
+ * THREATENED iff lag[q] < gap[m_q].  Everybody else: lag = +inf, blocker = -1, yielding = 0, waited = 0.  (4) a threatened q YIELDS if
+ * waited[q] != 0 or if it can still stop, (double)(s - ti) dl >= v v / (2.0 brake), the signal hold's own expression; otherwise it is free
+ * and left to the conflict search, as on amber.  Yields: yielding[q] = 1, cut_len[q] = min(cut_len[q], s).  (5) waited[q] = yielding[q].
+ * (6) occupied[j] = occ, n_yielding[j] = the number yielding.  eta is one multiply and one IEEE division, the rest comparisons: host and
+ * device agree bit for bit, lag included.  Equal ranks stay with the conflict search.
+ * The stage writes no word of another stage and only lowers cut_len.  NULL or an all-zero struct: off -- the loop enqueues exactly the
+ * launches of a context that never had it, with the same arguments.  The cached graph's key covers the struct by value (it has no padding:
+ * twelve pointers, two doubles and six int32 are its 136 bytes), and a run with the stage on does not take step fusion.  MPCX_E_INVALID
+ * ("priority: ...") from the run or the stage call before anything is launched, whatever n_steps is: one of the twelve pointers NULL;
+ * n_per outside 1..64 or n_per n_junctions != P; n_moves outside 1..MPCX_SIGNAL_GROUPS_MAX; n_points < 1; detect < 1; v_floor or brake not
+ * finite or not positive; a nonzero reserved word; signals, actuation or a reservation in the run; the agent-sharded layout; more than one
+ * linearisation pass; a conflict word with bits at or above n_moves, with its own bit, or not symmetric; a negative rank; a gap that is
+ * not finite or is negative.  The three per-movement tables are read back from the device for their check (blocking copies) ONCE per
+ * struct: the context remembers the pointers and count that passed and forgets them when mpcx_set_priority is given a struct that differs
+ * from the one it holds, so run(1) in a loop reads nothing back.  Do not change the tables in place while set.  The per-agent,
+ * per-junction and per-point words are not read back -- a bad word is data (OUT), never a GPU fault. */
+#define MPCX_PRIORITY_PER_MAX 64
+typedef struct {
+    const int32_t *path_stop;    /* n_points: route-local index of the next stop line at or after this path point, -1 = none */
+    const int32_t *path_move;    /* n_points: the movement of the route on this path point */
+    const int32_t *path_exit;    /* n_points: route-local index at which a vehicle on this point has left the crossing, -1 = none */
+    const int32_t *conflict;     /* n_moves: bit h of word g = movements g and h cross */
+    const int32_t *rank;         /* n_moves: >= 0, a smaller rank goes first */
+    const double *gap;           /* n_moves: the critical gap in seconds of the movement when it gives way (finite, >= 0) */
+    int32_t *waited;             /* P, caller-owned, in-out, zero-initialised: 1 = the agent yielded in the last step */
+    int32_t *yielding;           /* P, caller-owned, out: 1 = the agent was held at its line by this stage in the last step */
+    int32_t *blocker;            /* P, out: the agent whose arrival is the lag, -1 = none */
+    double *lag;                 /* P, out: seconds until the first conflicting agent of smaller rank is at its line, +inf = none */
+    int32_t *occupied;           /* n_junctions, out: the mask of movements inside the crossing */
+    int32_t *n_yielding;         /* n_junctions, out: the number of agents yielding this step */
+    double v_floor;              /* m/s, > 0: an approaching agent is taken to drive at least this fast */
+    double brake;                /* m/s^2, > 0: the deceleration of the can-stop test */
+    int32_t detect;              /* an agent is looked at from this many path points before its line on (>= 1) */
+    int32_t n_per, n_junctions, n_moves, n_points, reserved;     /* reserved: 0 */
+} mpcx_priority;
+/* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
+int32_t mpcx_set_priority(mpcx_ctx *ctx, const mpcx_priority *priority /*NULL or all-zero = off*/);
+/* one step's priority stage alone (what the closed loop enqueues in the hold's place).  The struct is the argument's, not the context's,
+ * and is checked as above (its per-movement tables in every call). */
+int32_t mpcx_priority_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
+                                 const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
+                                 const int32_t *done /*P or NULL*/, const mpcx_priority *priority);
+
 /* ---- the stages together.  With several optional stages on, a step is: admission, the entry-order stamp; pool pack and prediction; the
- * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the keep-clear stage; the following stage; per linearisation
+ * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the keep-clear stage; the priority stage (in the hold's place: never beside one); the following stage; per linearisation
  * pass the window stage, the advice stage, the following clamp and the QP; the plant; record, retire, respawn.  What that order implies:
  *   one car, three views   agent q sees a present row r of its window (1) standing at its pose if prec[r] > prec[obs_skip[q]], whatever
  *                          the intent stage wrote into r's predicted frames; (2) else on its owner's plan of the step before, if the owner
@@ -1271,6 +1336,12 @@ int32_t mpcx_keepclear_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const dou
  *                          boxed nor waited: a vehicle that arrives has been OUT since its exit point, and a reset slot waits at the
  *                          gate with done != 0, which is OUT too, so the stage itself has cleared waited before the slot's next
  *                          vehicle drives -- the word heals itself.
+ *   the priority stage     reads traj_idx as the conflict search left it and the physical scene -- not the sight word, not prec: scripted
+ *                          actors are members of no junction, and conflicts between equal ranks stay with the conflict search.  It is one
+ *                          more minimum on cut_len, in front of the follower's.  A major-road car still reads an approaching minor car's
+ *                          constant-velocity prediction and may brake for a car that is about to stop (give_way(order=) with the ranks
+ *                          as words, or shared plans, are the remedies).  waited heals itself as keep clear's does: a reset slot is OUT
+ *                          while it waits at the gate.  In MPCX_STOP_SPEED the hold is soft, as the signals' is.
  * tests/stack_helpers.py composes the host builds of the rules in this order; tests/test_gpu_stack.py replays the device against it. */
 /* one step's search stage alone (what the closed loop enqueues in front of the window stage): steps 1 - 5.  stop_mode: MPCX_STOP_CUT or
  * MPCX_STOP_SPEED; the struct is the argument's, not the context's, and is checked as above. */

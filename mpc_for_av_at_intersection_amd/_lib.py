@@ -172,6 +172,17 @@ class KeepClearC(C.Structure):
                 ('n_moves', C.c_int32), ('n_points', C.c_int32), ('reserved', C.c_int32)]
 
 
+class PriorityC(C.Structure):
+    """mirror of mpcx_priority (include/mpcx.h): priority road; every pointer is a device address -- path_stop / path_move / path_exit
+    (n_points int32), conflict / rank (n_moves int32), gap (n_moves float64), waited / yielding / blocker (P int32), lag (P float64),
+    occupied / n_yielding (n_junctions int32).  Not a row of STAGES: the stage attaches to the context (Context.set_priority)"""
+    _fields_ = [('path_stop', C.c_void_p), ('path_move', C.c_void_p), ('path_exit', C.c_void_p), ('conflict', C.c_void_p), ('rank', C.c_void_p),
+                ('gap', C.c_void_p), ('waited', C.c_void_p), ('yielding', C.c_void_p), ('blocker', C.c_void_p), ('lag', C.c_void_p),
+                ('occupied', C.c_void_p), ('n_yielding', C.c_void_p), ('v_floor', C.c_double), ('brake', C.c_double), ('detect', C.c_int32),
+                ('n_per', C.c_int32), ('n_junctions', C.c_int32), ('n_moves', C.c_int32), ('n_points', C.c_int32), ('reserved', C.c_int32)]
+
+
+PRIORITY_PER_MAX = 64                           # MPCX_PRIORITY_PER_MAX: agents per junction under the priority rule
 KEEPCLEAR_PER_MAX = 64                          # MPCX_KEEPCLEAR_PER_MAX: agents per junction under keep clear
 SIGHT_WINDOW = 64                               # window offsets a word of mpcx_sight.sight holds
 # the words of an event record of the near-miss log (ev_i32[q][e][0..7]; ev_f64[q][e] = the minimum clearance, the agent's speed at opening)
@@ -339,7 +350,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
            'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch',
            'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary', 'mpcx_set_sight', 'mpcx_sight_step_batch',
-           'mpcx_set_keepclear', 'mpcx_keepclear_step_batch'] + LOOP_ENTRY_POINTS
+           'mpcx_set_keepclear', 'mpcx_keepclear_step_batch', 'mpcx_set_priority', 'mpcx_priority_step_batch'] + LOOP_ENTRY_POINTS
 
 
 def load():
@@ -451,5 +462,8 @@ def load():
     lib.mpcx_set_keepclear.restype = i32; lib.mpcx_set_keepclear.argtypes = [vp, C.POINTER(KeepClearC)]
     lib.mpcx_keepclear_step_batch.restype = i32
     lib.mpcx_keepclear_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(SignalsC), C.POINTER(KeepClearC)]
+    lib.mpcx_set_priority.restype = i32; lib.mpcx_set_priority.argtypes = [vp, C.POINTER(PriorityC)]
+    lib.mpcx_priority_step_batch.restype = i32
+    lib.mpcx_priority_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(PriorityC)]
     _lib = lib
     return lib

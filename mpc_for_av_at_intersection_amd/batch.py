@@ -53,6 +53,9 @@ window every agent sees (sensor range, convex occluders, connected vehicles that
 that agent's obstacle list.  corner_blocks() gives the buildings of the stock four-way world.
 `keep_clear()` is KEEP CLEAR for a batch under signalise() or actuate(): one launch behind the hold keeps a car whose light lets it go at its
 stop line while a movement that conflicts with its own (cross_phase_conflicts()) is inside the crossing; enter_on_green() switches it off.
+`priority_road()` is the PRIORITY-CONTROLLED JUNCTION, for a batch without signals: one launch in the hold's place keeps a car of a minor
+movement at its stop line until the conflicting movements of smaller rank (priority_ranks()) leave it its critical gap; all_roads_equal()
+switches it off.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -413,6 +416,14 @@ class IntersectionBatch:
         self.n_boxed: Optional[torch.Tensor] = None          # ... int32 (B,), the agents boxed in the last step
         self._keepclear = None                               # (set on the context too)
         self._keepclear_tabs = None                          # ... the device tables the struct names: path_move, path_exit, conflict
+        self.yielding: Optional[torch.Tensor] = None         # priority_road(): int32 (P,), 1 = the agent was kept at its line in the last step
+        self.yield_waited: Optional[torch.Tensor] = None     # ... int32 (P,), the same word as the stage's memory (in-out)
+        self.blocker: Optional[torch.Tensor] = None          # ... int32 (P,), the agent whose arrival is the lag, -1 = none
+        self.lag: Optional[torch.Tensor] = None              # ... float64 (P,), seconds to the first conflicting car of smaller rank, +inf = none
+        self.crossing: Optional[torch.Tensor] = None         # ... int32 (B,), the movements inside the crossing in the last step
+        self.n_yielding: Optional[torch.Tensor] = None       # ... int32 (B,), the agents yielding in the last step
+        self._priority = None                                # (set on the context too)
+        self._priority_tabs = None                           # ... the device tables the struct names: path_stop, path_move, path_exit, conflict, rank, gap
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -451,7 +462,7 @@ class IntersectionBatch:
         """switch the named stages off, and with each the stages that live on it (_lib.stage_dependents); drops the cached descriptor"""
         entry = self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY
         for k in stages:
-            if k in ('sight', 'keepclear'):     # (attached to the context, no row of _lib.STAGES: nothing lives on it)
+            if k in ('sight', 'keepclear', 'priority'):     # (attached to the context, no row of _lib.STAGES: nothing lives on it)
                 setattr(self, '_' + k, None)
                 continue
             off = {k} | _lib.stage_dependents(k, entry)
@@ -783,7 +794,7 @@ class IntersectionBatch:
         self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), tabs['plan_cycle'].data_ptr(),
                                       tabs['plan_amber'].data_ptr(), tabs['plan_green'].data_ptr(), tabs['plan_of'].data_ptr(),
                                       self.tick.data_ptr(), self.held.data_ptr(), brake, len(stop), len(plans), n_groups, 0)
-        self._off('actuation', 'reservation')   # (a fixed plan replaces a controller or a junction manager as the source of the lights)
+        self._off('actuation', 'reservation', 'priority')   # (a junction is run by lights, by a manager, or by priority; a fixed plan replaces a controller or a junction manager as the source of the lights)
         c.synchronize()
 
     def advise_speed(self, v_min: float = 1.0, lead: int = 1, reach: float = 60.0, v_cruise: Optional[float] = None):
@@ -1044,6 +1055,73 @@ class IntersectionBatch:
         `box_occupied` and `n_boxed` keep what they hold and are no longer written)"""
         self._off('keepclear')
 
+    def priority_road(self, major=(0, 2), rank=None, gap=4.0, v_floor: float = 1.0, brake: Optional[float] = None, detect: Optional[int] = None,
+                      stop=None, move=None, exit=None, conflict=None):
+        """PRIORITY ROAD (mpcx_set_priority), for a batch without signals, in both stop modes: the junction most roads have, a major road
+        crossed by a minor road under give-way signs.  One more small launch in the hold's place -- behind the conflict search, in front
+        of the following stage -- works out, per instance (a junction of A <= 64 agents), for every agent within `detect` path points of
+        its stop line the LAG: the least time `(s - traj_idx) dl / max(v, v_floor)` (0 inside the crossing) of a car of the junction whose
+        movement conflicts with its own and has a smaller rank.  An agent whose lag is below its movement's critical `gap` (seconds) is
+        held at its line by the cut the signal hold makes -- if it stood there in the step before, or if it can still stop with `brake`;
+        else it is left to the conflict search, as on amber.  Equal ranks stay with the conflict search.
+        major: the arms (0 .. 3) of the major road; rank: one non-negative integer per movement, a smaller rank goes first (default:
+        priority_ranks(major)); gap: a scalar or one value per movement; stop, move, exit: the per-path-point tables, all of them or none
+        (default: movement_lines() of the batch's routes); conflict: one bit mask per movement, symmetric, without a diagonal (default:
+        the full movement_conflicts() table with the batch's disc model); detect: default the whole approach (the largest stop-line
+        index); brake: default abs(MAX_DECEL) of the batch's parameters.
+        Refused under signalise() / actuate() / reserve() -- a junction is run by lights, by a manager, or by priority; calling one of
+        them later switches this stage off.  Allocates `yielding`, `yield_waited`, `blocker`, `lag`, `crossing`, `n_yielding` and the
+        tables and drops the cached descriptor; all_roads_equal() switches it off."""
+        if self._signals is not None or self._actuation is not None or self._reservation is not None:
+            raise ValueError('priority_road: the batch runs under signalise(), actuate() or reserve() -- a junction is run by lights, by a '
+                             'manager, or by priority')
+        if self.exchange == 'rccl' or callable(self.exchange):
+            raise ValueError('priority_road: not in the agent-sharded layout (shard by instances)')
+        if not 1 <= self.A <= _lib.PRIORITY_PER_MAX:
+            raise ValueError('priority_road: a junction holds 1 .. %d agents, the batch has A = %d' % (_lib.PRIORITY_PER_MAX, self.A))
+        if len({t is None for t in (stop, move, exit)}) > 1:
+            raise ValueError('priority_road: give stop, move and exit, or none of them')
+        stop, move, exit = self._line_tables('priority_road', (stop, move, exit), movement_lines)
+        if conflict is None:
+            conflict, _ = movement_conflicts(self._route_list(), stop, exit, np.asarray(self.ip.circle_centers), float(self.ip.radius))
+        conflict = np.asarray(conflict)
+        if conflict.ndim != 1 or not 1 <= len(conflict) <= _lib.SIGNAL_GROUPS_MAX or not np.issubdtype(conflict.dtype, np.integer):
+            raise ValueError('priority_road: conflict holds one integer word per movement, 1 .. %d movements' % _lib.SIGNAL_GROUPS_MAX)
+        n_moves = len(conflict)
+        rank = np.asarray(priority_ranks(major) if rank is None else rank)
+        if rank.shape != (n_moves,) or not np.issubdtype(rank.dtype, np.integer) or (rank < 0).any():
+            raise ValueError('priority_road: rank holds one non-negative integer per movement (%d)' % n_moves)
+        gap = np.broadcast_to(np.asarray(gap, dtype=np.float64), (n_moves,)) if np.ndim(gap) == 0 else np.asarray(gap, dtype=np.float64)
+        if gap.shape != (n_moves,) or not np.isfinite(gap).all() or (gap < 0).any():
+            raise ValueError('priority_road: gap is a finite, non-negative number of seconds, or one per movement (%d)' % n_moves)
+        v_floor, brake = float(v_floor), self._brake(brake)
+        if not (np.isfinite(v_floor) and v_floor > 0 and np.isfinite(brake) and brake > 0):
+            raise ValueError('priority_road: v_floor and brake are finite and positive')
+        detect = max(int(stop.max()) if len(stop) else 1, 1) if detect is None else int(detect)
+        if not 1 <= detect <= int(np.iinfo(np.int32).max):
+            raise ValueError('priority_road: detect >= 1 path point, int32')
+        c = self.ctx
+        tabs = dict(path_stop=c.i32(stop), path_move=c.i32(move), path_exit=c.i32(exit), conflict=c.i32(conflict), rank=c.i32(rank),
+                    gap=torch.as_tensor(np.ascontiguousarray(gap), dtype=torch.float64, device=c.device))
+        zeros = lambda n: torch.zeros(n, dtype=torch.int32, device=c.device)
+        self.yielding, self.yield_waited, self.crossing, self.n_yielding = zeros(self.P), zeros(self.P), zeros(self.B), zeros(self.B)
+        self.blocker = torch.full((self.P,), -1, dtype=torch.int32, device=c.device)
+        self.lag = torch.full((self.P,), float('inf'), dtype=torch.float64, device=c.device)
+        self._priority_tabs = tabs
+        self._priority = _lib.PriorityC(tabs['path_stop'].data_ptr(), tabs['path_move'].data_ptr(), tabs['path_exit'].data_ptr(),
+                                        tabs['conflict'].data_ptr(), tabs['rank'].data_ptr(), tabs['gap'].data_ptr(),
+                                        self.yield_waited.data_ptr(), self.yielding.data_ptr(), self.blocker.data_ptr(), self.lag.data_ptr(),
+                                        self.crossing.data_ptr(), self.n_yielding.data_ptr(), v_floor, brake, detect, self.A, self.B, n_moves,
+                                        int(self.path.shape[0]), 0)
+        c.set_priority(None)        # (a new table may sit where an old one sat: the context checks the next struct it is given afresh)
+        self._desc = None
+        c.synchronize()
+
+    def all_roads_equal(self):
+        """switch the priority rule off and nothing else: the batch enqueues exactly the launches of one that never had it (`yielding`,
+        `yield_waited`, `blocker`, `lag`, `crossing` and `n_yielding` keep what they hold and are no longer written)"""
+        self._off('priority')
+
     def share_plans(self, share=None):
         """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
         it applied in the last step, held for pred_steps frames -- the reference's prediction of a scripted car.  A sharing agent is seen
@@ -1124,7 +1202,7 @@ class IntersectionBatch:
         self._actuation = _lib.ActuationC(tabs['phase_groups'].data_ptr(), tabs['phase_time'].data_ptr(), tabs['ctrl_time'].data_ptr(),
                                           tabs['ctrl_of'].data_ptr(), self.junction_state.data_ptr(), self.lights.data_ptr(),
                                           self.calls.data_ptr(), self.A, self.B, n_phases, len(controllers), 0)
-        self._off('advice', 'reservation')  # (there is no plan left to look ahead into; a controller replaces a junction manager)
+        self._off('advice', 'reservation', 'priority')  # (a junction is run by lights, by a manager, or by priority; there is no plan left to look ahead into; a controller replaces a junction manager)
         c.synchronize()
 
     def reserve(self, managers, manager_of=None, stop=None, group=None, exit=None, conflict=None, lane=None, brake: Optional[float] = None):
@@ -1176,7 +1254,7 @@ class IntersectionBatch:
                                               tabs['mgr_time'].data_ptr(), tabs['mgr_of'].data_ptr(), self.granted.data_ptr(),
                                               self.since.data_ptr(), self.junction_clock.data_ptr(), self.occupied.data_ptr(),
                                               self.queued.data_ptr(), self.A, self.B, len(managers), 0)
-        self._off('actuation', 'advice', 'keepclear')   # (a junction manager replaces a controller or a plan; there is no plan to look ahead into; the manager itself keeps the crossing clear)
+        self._off('actuation', 'advice', 'keepclear', 'priority')   # (a junction is run by lights, by a manager, or by priority; a junction manager replaces a controller or a plan; there is no plan to look ahead into; the manager itself keeps the crossing clear)
         c.synchronize()
 
     def unsignalise(self):
@@ -1313,6 +1391,7 @@ class IntersectionBatch:
         self.ctx.set_safety(self._safety)
         self.ctx.set_sight(self._sight)
         self.ctx.set_keepclear(self._keepclear)
+        self.ctx.set_priority(self._priority)
 
     def run(self, n_steps: int, graph: bool = False):
         """n_steps of the closed loop with no host work in between (mpcx_closed_loop_run)."""
@@ -1394,6 +1473,8 @@ class IntersectionBatch:
             c.signal_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals)
         if self._keepclear is not None:     # the keep-clear stage: behind the signal / actuated stage, on the held it left, as in the loop
             c.keepclear_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._keepclear)
+        if self._priority is not None:      # the priority stage: in the hold's place, as in the loop
+            c.priority_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._priority)
         if self._following is not None:     # the following stage: behind the signal stage, in front of the window stage, as in the loop
             c.follow_step(self.dl, _lib.STOP_SPEED if speed else _lib.STOP_CUT, self.state, self.path, self.path_off, self.path_len, self.traj_idx,
                           self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self._following, obs_skip=self.obs_skip)
@@ -1447,6 +1528,10 @@ class IntersectionBatch:
         if self._keepclear is not None:      # who was kept at its line in the last step, who stood there, and the movements inside per junction
             out.update(boxed=self.boxed.cpu().numpy().copy(), box_waited=self.box_waited.cpu().numpy().copy(),
                        box_occupied=self.box_occupied.cpu().numpy().copy(), n_boxed=self.n_boxed.cpu().numpy().copy())
+        if self._priority is not None:       # who was kept at its line in the last step, for whom and by what lag, and the movements inside per junction
+            out.update(yielding=self.yielding.cpu().numpy().copy(), yield_waited=self.yield_waited.cpu().numpy().copy(),
+                       blocker=self.blocker.cpu().numpy().copy(), lag=self.lag.cpu().numpy().copy(),
+                       crossing=self.crossing.cpu().numpy().copy(), n_yielding=self.n_yielding.cpu().numpy().copy())
         if self._routes is not None:        # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
@@ -1640,6 +1725,18 @@ def cross_phase_conflicts(conflict, phases=((0, 2), (1, 3))):
             if (int(conflict[g]) >> h) & 1 and (g // 3, h // 3) not in together:
                 out[g] |= 1 << h
     return out.astype(np.int32)
+
+
+def priority_ranks(major=(0, 2), left_turn: int = 1):
+    """The rank table of IntersectionBatch.priority_road for the twelve movements 3 arm + (turn - 1) of a four-arm crossing, int32 (12,): on
+    an arm of `major` (arms 0 .. 3 = stop_lines()' signal groups) 1 for the turn `left_turn` and 0 otherwise, on the other arms 3 for that
+    turn and 2 otherwise.  A smaller rank goes first: the major road's through and near-side traffic, its turn across the opposed stream, the
+    minor road, the minor road's turn across.  With the stock routes turn 1 is the turn that crosses the opposed straight
+    (movement_conflicts() has movement (arm 3, turn 1) against (arm 1, turn 2)).  Pure numpy: no GPU, no state."""
+    major = {int(a) for a in major}
+    if not major <= {0, 1, 2, 3} or left_turn not in (1, 2, 3):
+        raise ValueError('priority_ranks: major holds arms 0 .. 3, left_turn is 1, 2 or 3')
+    return np.array([(0 if g // 3 in major else 2) + (1 if g % 3 == left_turn - 1 else 0) for g in range(12)], dtype=np.int32)
 
 
 def two_phase_plan(cycle: int, green: int, amber: int) -> dict:

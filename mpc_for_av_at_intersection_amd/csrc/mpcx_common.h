@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1792] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1928] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     mpcx_following following = {};        // car following (mpcx_set_following): the struct by value, padding zeroed; all zeros while off
@@ -39,6 +39,14 @@ struct mpcx_ctx {
         int32_t n_moves = 0;
         bool ok = false;
     } keepclear_table;
+    mpcx_priority priority = {};          // priority road (mpcx_set_priority): the struct by value (it has no padding); all zeros while off
+    bool have_priority = false;
+    struct PriorityTables {               // the per-movement tables of a mpcx_priority that were read back and passed their check (mpcx_priority_validate)
+        const int32_t *conflict = nullptr, *rank = nullptr;
+        const double *gap = nullptr;
+        int32_t n_moves = 0;
+        bool ok = false;
+    } priority_tables;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
     const int32_t *order_now = nullptr, *order_prev = nullptr;   // optional pair: entries that differ mark a discontinuous change of the reference
     // scratch of mpcx_closed_loop_run for P agents: [P] cut lengths of the previous step | [3 P] what the conflict search's nearest-index
@@ -285,6 +293,12 @@ int32_t mpcx_keepclear_validate(mpcx_ctx *ctx, const mpcx_keepclear *s, const mp
 int32_t mpcx_keepclear_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
                                const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_signals *signals,
                                const mpcx_keepclear *keepclear);
+// priority road (mpcx_priority.hip): "no priority stage" test, check of the struct against the run (held_run: the run carries signals,
+// actuation or a reservation; reads the three per-movement tables back once per struct), the launch alone (in the hold's place)
+bool mpcx_priority_absent(const mpcx_priority *s);
+int32_t mpcx_priority_validate(mpcx_ctx *ctx, const mpcx_priority *s, int32_t P, int32_t exchange, bool held_run);
+int32_t mpcx_priority_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
+                              const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_priority *priority);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -113,10 +113,15 @@ struct LoopStages {
     // for an agent whose light lets it go while a conflicting movement is inside the crossing, lowers c->cut_len to the agent's stop line.
     // &ctx->keepclear while on.
     const mpcx_keepclear *keepclear = nullptr;
+    // priority road (mpcx_set_priority: it attaches to the context too): priority_kernel in the hold's place -- behind the conflict search
+    // and the safety stage, in front of the following stage; refused beside signals, actuation or a reservation.  For an agent of a minor
+    // movement that meets a conflicting car of smaller rank within its critical gap it lowers c->cut_len to the agent's stop line.
+    // &ctx->priority while on.
+    const mpcx_priority *priority = nullptr;
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight && !keepclear; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight && !keepclear && !priority; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -131,6 +136,7 @@ struct LoopKey {
     mpcx_safety safety;
     mpcx_sight sight;
     mpcx_keepclear keepclear;
+    mpcx_priority priority;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
     const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
@@ -203,6 +209,12 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         if (rc != MPCX_OK) return rc;
         st->keepclear = &ctx->keepclear;
     }
+    if (ctx->have_priority) {       // in front of the holds' own checks too: a junction is run by lights, by a manager, or by priority
+        rc = mpcx_priority_validate(ctx, &ctx->priority, c->P, c->exchange,
+                                    st->signals || !mpcx_actuation_absent(a.actuation) || !mpcx_reservation_absent(a.reservation));
+        if (rc != MPCX_OK) return rc;
+        st->priority = &ctx->priority;
+    }
     if (!mpcx_reservation_absent(a.reservation)) {  // checks the signals it draws on too, and refuses a controller or advice beside it
         rc = mpcx_reservation_validate(ctx, a.reservation, st->signals, c->P, c->exchange, !mpcx_actuation_absent(a.actuation),
                                        !mpcx_advice_absent(a.advice));
@@ -253,7 +265,7 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     return rc;
 }
 
-// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the keep-clear stage) (-> the following stage) -> lin_passes x (reference
+// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the keep-clear stage) (-> the priority stage) (-> the following stage) -> lin_passes x (reference
 // window (-> the advice stage) (-> the following clamp) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
@@ -291,6 +303,10 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
     }
     if (st.keepclear) {
         rc = mpcx_keepclear_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.signals, st.keepclear);
+        if (rc != MPCX_OK) return rc;
+    }
+    if (st.priority) {
+        rc = mpcx_priority_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.priority);
         if (rc != MPCX_OK) return rc;
     }
     if (st.follow) {
@@ -526,6 +542,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.safety, st.safety);
     key_put(key.sight, st.sight);
     key_put(key.keepclear, st.keepclear);
+    key_put(key.priority, st.priority);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
     key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;

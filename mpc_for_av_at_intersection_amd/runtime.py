@@ -890,6 +890,26 @@ class Context:
                                                      _ptr(cut_len), _ptr(done), None if signals is None else C.byref(signals),
                                                      C.byref(keepclear)))
 
+    def set_priority(self, priority: Optional['_lib.PriorityC']):
+        """mpcx_set_priority: the priority rule for every closed-loop run of this context from now on; None (or an all-zero struct) = off.
+        The context copies the struct; the device buffers it names stay the caller's and are kept alive here while set."""
+        self._chk(self.lib.mpcx_set_priority(self._ctx, None if priority is None else C.byref(priority)))
+        self._priority = priority
+
+    @_ordered
+    def priority_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, priority: '_lib.PriorityC', done=None):
+        """mpcx_priority_step_batch: ONE step's priority stage as the closed loop enqueues it in the hold's place.  cut_len (P int32) is
+        lowered in place for a yielding agent, and the struct's waited, yielding, blocker, lag, occupied and n_yielding are written; done:
+        the retirement words (P int32) or None."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('cut_len', cut_len)):
+            self._want(t, torch.int32, (Pn,), name)
+        if done is not None:
+            self._want(done, torch.int32, (Pn,), 'done')
+        self._chk(self.lib.mpcx_priority_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
+                                                    _ptr(cut_len), _ptr(done), C.byref(priority)))
+
     @_ordered
     def sight_step(self, state, obs6, obs_off, obs_cnt, obs_skip, sight: '_lib.SightC', done=None, absent=None):
         """mpcx_sight_step_batch: ONE step's sight stage as the closed loop enqueues it in front of the conflict search: the struct's sight,
