@@ -1308,9 +1308,64 @@ int32_t mpcx_priority_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const doub
                                  const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
                                  const int32_t *done /*P or NULL*/, const mpcx_priority *priority);
 
+/* ---- firm hold: in MPCX_STOP_SPEED a car that a hold keeps at its stop line stops in front of it.  Every rule that stops a car at a line
+ * (signals, actuation, a reservation, keep clear, the priority road) lowers cut_len to the line's index s.  In MPCX_STOP_CUT the path ends
+ * there; in MPCX_STOP_SPEED only the speed reference is zeroed from s on, and that does not hold a car: the window's position reference
+ * advances by max(v, 10 / 3.6) dt whatever the car does and runs over the line, and the nearest-index search answers start + 1 for a car
+ * that stands on start, so traj_idx climbs to s and the hold's "on or past the line" frees a car that stands 2 m before its line.  With the
+ * stage on, two small launches (brake_mark_kernel behind the last hold stage and the following stage, in front of the window stage;
+ * brake_clamp_kernel behind every window stage, beside the advice and following clamps; csrc/mpcx_brake.hip, the rule is
+ * csrc/mpcx_brake_core.h) end a line-held agent's position reference on a stop point in front of its line, put a braking profile on its
+ * speed reference and pin its index while it is physically behind the line.  It attaches to the CONTEXT (mpcx_set_braking), as
+ * following, keep clear and the priority road do: every mpcx_closed_loop_run* entry point runs it while set.
+ * Agent q is LINE-HELD in a step if done[q] == 0, one of the hold words that are on in THAT run is nonzero for it -- mpcx_signals.held
+ * (signals, actuation, a reservation), mpcx_keepclear.boxed, mpcx_priority.yielding; which of them are read follows the stages of the run
+ * that is enqueued, not those at the time of mpcx_set_braking --, and s = path_stop[path_off[q] + traj_idx[q]] is a valid line ahead by
+ * the hold's own test: path_off[q] + traj_idx[q] in [0, n_points), 0 <= traj_idx[q] < s < path_len[q] (path_stop and n_points: the
+ * signals', else the priority road's).  Then m = ceil(setback / dl), e = max(s - m, 2), E = path point e - 1.
+ *   (a) the window stage builds q's window on full[:e], searching from min(target_ind[q], e - 1): the loop hands it a per-agent length
+ *       array the mark launch wrote (e for a line-held agent, path_len[q] for everybody else) in place of path_len.  The goal test, the
+ *       run log and prev_len (the next conflict search's prev_cut_len, restored by the clamp launch) stay the whole path's.
+ *   (b) every entry t of row 2 of q's xref becomes fmin(entry, sqrt(2 brake d_t)), d_t the Euclidean distance of window point t (rows 0, 1)
+ *       to E.  With advice and the following clamp on, all clamps apply; a minimum of minima does not depend on their order.
+ *   (c) q is behind its line iff (x - p_s.x)(p_s.x - p_{s-1}.x) + (y - p_s.y)(p_s.y - p_{s-1}.y) < 0.  Behind: traj_idx[q] =
+ *       min(traj_idx[q], e - 1), written after the holds have read traj_idx.  Not behind (a physical overrun): nothing is pinned, the hold
+ *       frees the agent as it does without the stage, overran[q] += 1.
+ *   (d) firm[q] = e, brake_cap[q] = the profile at window point 0.  An agent that is not line-held: firm = 0, brake_cap = 0.0, and nothing
+ *       else of it is touched -- the window stage computes for it what it computes without the stage.
+ * In MPCX_STOP_CUT the mark launch alone runs and writes firm and brake_cap = 0.0; nothing else changes, the cut is hard already.
+ * NULL or an all-zero struct: off -- the loop enqueues exactly the launches of a context that never had it, with the same arguments.  The
+ * cached graph's key covers the struct by value (two doubles and three pointers: 40 bytes, no padding), and a run with the stage on does
+ * not take step fusion.  MPCX_E_INVALID ("braking: ...") from the run or a stage call before anything is launched, whatever n_steps is:
+ * firm, overran or brake_cap NULL; brake not finite or not positive; setback not finite or below 2 dl (the pin needs two points between
+ * e and s); the agent-sharded layout; more than one linearisation pass; a run with no source of stop lines (no signals, actuation,
+ * reservation or priority road). */
+typedef struct {
+    double brake;                /* m/s^2, > 0: the deceleration of the braking profile */
+    double setback;              /* m, >= 2 dl: the stop point lies ceil(setback / dl) path points in front of the line */
+    int32_t *firm;               /* P, caller-owned, out: 0, or the stop index e of a line-held agent */
+    int32_t *overran;            /* P, caller-owned, in-out, zero-initialised: steps in which the agent was line-held beyond its line */
+    double *brake_cap;           /* P, caller-owned, out: the braking profile at window point 0, 0.0 = not line-held (or MPCX_STOP_CUT) */
+} mpcx_braking;
+/* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
+int32_t mpcx_set_braking(mpcx_ctx *ctx, const mpcx_braking *braking /*NULL or all-zero = off*/);
+/* one step's mark launch alone (what the closed loop enqueues in front of the window stage).  held, boxed, yielding: the hold words that
+ * are on (at least one).  MPCX_STOP_SPEED: target_ind is clamped and win_len written (both required); MPCX_STOP_CUT: both may be NULL. */
+int32_t mpcx_brake_mark_step_batch(mpcx_ctx *ctx, int32_t P, double dl, int32_t stop_mode, const int32_t *path_off /*P*/,
+                                   const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *target_ind /*P*/,
+                                   int32_t *win_len /*P, out*/, const int32_t *done /*P or NULL*/, const int32_t *path_stop /*n_points*/,
+                                   int32_t n_points, const int32_t *held /*P or NULL*/, const int32_t *boxed /*P or NULL*/,
+                                   const int32_t *yielding /*P or NULL*/, const mpcx_braking *braking);
+/* one step's clamp launch alone (what the closed loop enqueues behind every window stage in MPCX_STOP_SPEED): (b) - (d) on xref (P,4,T+1)
+ * from firm as the mark launch left it.  prev_len: the words the window stage left at the window's length, or NULL. */
+int32_t mpcx_brake_clamp_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const double *path_xyyaw,
+                                    const int32_t *path_off /*P*/, const int32_t *path_len /*P*/, int32_t *traj_idx /*P*/,
+                                    int32_t *prev_len /*P or NULL*/, const int32_t *done /*P or NULL*/, const int32_t *path_stop /*n_points*/,
+                                    int32_t n_points, const mpcx_braking *braking, double *xref /*P,4,T+1*/);
+
 /* ---- the stages together.  With several optional stages on, a step is: admission, the entry-order stamp; pool pack and prediction; the
- * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the keep-clear stage; the priority stage (in the hold's place: never beside one); the following stage; per linearisation
- * pass the window stage, the advice stage, the following clamp and the QP; the plant; record, retire, respawn.  What that order implies:
+ * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the keep-clear stage; the priority stage (in the hold's place: never beside one); the following stage; the firm hold's mark; per linearisation
+ * pass the window stage, the advice stage, the following clamp, the firm hold's clamp and the QP; the plant; record, retire, respawn.  What that order implies:
  *   one car, three views   agent q sees a present row r of its window (1) standing at its pose if prec[r] > prec[obs_skip[q]], whatever
  *                          the intent stage wrote into r's predicted frames; (2) else on its owner's plan of the step before, if the owner
  *                          shares, drives, is present and its last status is MPCX_QP_OPTIMAL; (3) else through the constant prediction.
@@ -1342,6 +1397,10 @@ int32_t mpcx_priority_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const doub
  *                          constant-velocity prediction and may brake for a car that is about to stop (give_way(order=) with the ranks
  *                          as words, or shared plans, are the remedies).  waited heals itself as keep clear's does: a reset slot is OUT
  *                          while it waits at the gate.  In MPCX_STOP_SPEED the hold is soft, as the signals' is.
+ *   the firm hold          reads the hold words and traj_idx as this step's holds left them, and pins traj_idx only behind the last
+ *                          launch that reads it.  It never touches cut_len: a conflict cut or a follower's stop point below the line keeps
+ *                          zeroing the speed reference where it did.  Conflict-search stops are a moving stop index, not a line, and stay
+ *                          soft; a boxed or yielding car has no patience.
  * tests/stack_helpers.py composes the host builds of the rules in this order; tests/test_gpu_stack.py replays the device against it. */
 /* one step's search stage alone (what the closed loop enqueues in front of the window stage): steps 1 - 5.  stop_mode: MPCX_STOP_CUT or
  * MPCX_STOP_SPEED; the struct is the argument's, not the context's, and is checked as above. */

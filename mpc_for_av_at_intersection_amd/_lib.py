@@ -182,6 +182,12 @@ class PriorityC(C.Structure):
                 ('n_per', C.c_int32), ('n_junctions', C.c_int32), ('n_moves', C.c_int32), ('n_points', C.c_int32), ('reserved', C.c_int32)]
 
 
+class BrakingC(C.Structure):
+    """mirror of mpcx_braking (include/mpcx.h): firm hold; firm / overran (P int32) and brake_cap (P float64) are device addresses.  Not a
+    row of STAGES: the stage attaches to the context (Context.set_braking)"""
+    _fields_ = [('brake', C.c_double), ('setback', C.c_double), ('firm', C.c_void_p), ('overran', C.c_void_p), ('brake_cap', C.c_void_p)]
+
+
 PRIORITY_PER_MAX = 64                           # MPCX_PRIORITY_PER_MAX: agents per junction under the priority rule
 KEEPCLEAR_PER_MAX = 64                          # MPCX_KEEPCLEAR_PER_MAX: agents per junction under keep clear
 SIGHT_WINDOW = 64                               # window offsets a word of mpcx_sight.sight holds
@@ -350,7 +356,8 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
            'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch',
            'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary', 'mpcx_set_sight', 'mpcx_sight_step_batch',
-           'mpcx_set_keepclear', 'mpcx_keepclear_step_batch', 'mpcx_set_priority', 'mpcx_priority_step_batch'] + LOOP_ENTRY_POINTS
+           'mpcx_set_keepclear', 'mpcx_keepclear_step_batch', 'mpcx_set_priority', 'mpcx_priority_step_batch',
+           'mpcx_set_braking', 'mpcx_brake_mark_step_batch', 'mpcx_brake_clamp_step_batch'] + LOOP_ENTRY_POINTS
 
 
 def load():
@@ -465,5 +472,10 @@ def load():
     lib.mpcx_set_priority.restype = i32; lib.mpcx_set_priority.argtypes = [vp, C.POINTER(PriorityC)]
     lib.mpcx_priority_step_batch.restype = i32
     lib.mpcx_priority_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(PriorityC)]
+    lib.mpcx_set_braking.restype = i32; lib.mpcx_set_braking.argtypes = [vp, C.POINTER(BrakingC)]
+    lib.mpcx_brake_mark_step_batch.restype = i32
+    lib.mpcx_brake_mark_step_batch.argtypes = [vp, i32, C.c_double, i32] + [vp] * 7 + [i32] + [vp] * 3 + [C.POINTER(BrakingC)]
+    lib.mpcx_brake_clamp_step_batch.restype = i32
+    lib.mpcx_brake_clamp_step_batch.argtypes = [vp, i32, C.c_double] + [vp] * 8 + [i32, C.POINTER(BrakingC), vp]
     _lib = lib
     return lib

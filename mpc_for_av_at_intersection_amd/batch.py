@@ -56,6 +56,9 @@ stop line while a movement that conflicts with its own (cross_phase_conflicts())
 `priority_road()` is the PRIORITY-CONTROLLED JUNCTION, for a batch without signals: one launch in the hold's place keeps a car of a minor
 movement at its stop line until the conflicting movements of smaller rank (priority_ranks()) leave it its critical gap; all_roads_equal()
 switches it off.
+`hold_firmly()` is the FIRM HOLD for speed mode: two small launches around the window stage make a car that signals, a reservation, keep
+clear or the priority road keep at its line really stop in front of it (the position reference ends on a stop point, a braking profile
+caps the speed reference, the path index is pinned while the car is behind the line); hold_softly() switches it off.
 """
 import dataclasses
 from typing import List, Optional, Sequence
@@ -424,6 +427,11 @@ class IntersectionBatch:
         self.n_yielding: Optional[torch.Tensor] = None       # ... int32 (B,), the agents yielding in the last step
         self._priority = None                                # (set on the context too)
         self._priority_tabs = None                           # ... the device tables the struct names: path_stop, path_move, path_exit, conflict, rank, gap
+        self.firm: Optional[torch.Tensor] = None             # hold_firmly(): int32 (P,), 0 or the stop index e of an agent held at its line in the last step
+        self.overran: Optional[torch.Tensor] = None          # ... int32 (P,), the steps in which the agent was held while physically beyond its line
+        self.brake_cap: Optional[torch.Tensor] = None        # ... float64 (P,), the braking profile at the head of the window, 0.0 = not held at a line
+        self._braking = None                                 # (set on the context too)
+        self._win_len = None                                 # ... step_staged(): int32 (P,), the lengths the window stage is handed in place of path_len
 
     def attach_log(self, capacity: int, goal_dis: Optional[float] = None, stop_speed: Optional[float] = None,
                    max_bytes: Optional[int] = RUN_LOG_MAX_BYTES) -> RunLog:
@@ -853,6 +861,52 @@ class IntersectionBatch:
         `follow_cap` keep what they hold and are no longer written)"""
         self._following = None
         self._desc = None
+
+    def hold_firmly(self, brake: float = 3.0, setback: float = 2.0):
+        """FIRM HOLD (mpcx_set_braking), for stop_mode='speed'; in cut mode it only writes its words, the cut is hard already.  Every rule
+        that stops a car at a line -- signalise(), actuate(), reserve(), keep_clear(), priority_road() -- lowers the stop index to the line,
+        and in speed mode that is soft: the window's position reference runs ahead at 10 km/h whatever the car does, and the path index of
+        a standing car climbs a point a step until the hold sees it "on the line" and lets it go.  With the firm hold an agent whose hold
+        word (`held`, `boxed`, `yielding` -- those of the stages that are on when a run is enqueued) is nonzero has its window built on
+        the path up to a stop point ceil(setback / dl) points in front of its line, every entry of its speed reference capped at
+        sqrt(2 brake d) with d the distance of that window point to the stop point, and its path index pinned to the stop point while it is
+        physically behind the line (a half-plane test; a car that is beyond it is left to the hold, and counted in `overran`).  One small
+        launch in front of the window stage and one behind it.  Needs a source of stop lines at run time; switching signals, keep clear or
+        the priority road on or off afterwards leaves the firm hold on.  brake > 0; setback >= 2 dl.  Allocates `firm`, `overran` and
+        `brake_cap` and drops the cached descriptor; hold_softly() switches it off."""
+        if self.exchange == 'rccl' or callable(self.exchange):
+            raise ValueError('hold_firmly: not in the agent-sharded layout (shard by instances)')
+        brake, setback = float(brake), float(setback)
+        if not (np.isfinite(brake) and brake > 0 and np.isfinite(setback) and setback >= 2.0 * self.dl):
+            raise ValueError('hold_firmly: brake > 0 and setback >= 2 dl = %g, both finite' % (2.0 * self.dl))
+        dev = self.ctx.device
+        self.firm = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        self.overran = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        self.brake_cap = torch.zeros(self.P, dtype=torch.float64, device=dev)
+        self._win_len = torch.zeros(self.P, dtype=torch.int32, device=dev)
+        self._braking = _lib.BrakingC(brake, setback, self.firm.data_ptr(), self.overran.data_ptr(), self.brake_cap.data_ptr())
+        self._desc = None
+        self.ctx.synchronize()
+
+    def hold_softly(self):
+        """switch the firm hold off and nothing else: the batch enqueues exactly the launches of one that never had it (`firm`, `overran`
+        and `brake_cap` keep what they hold and are no longer written)"""
+        self._braking = None
+        self._desc = None
+
+    @property
+    def n_firm(self) -> int:
+        """the number of agents the firm hold kept at a stop point in the last step (synchronises); 0 while off"""
+        if self._braking is None:
+            return 0
+        self.ctx.synchronize()
+        return int((self.firm != 0).sum().item())
+
+    def _line_words(self):
+        """the firm hold's view of the stages that are on now: (path_stop, held, boxed, yielding), None where there is none"""
+        sig, pri = self._signals is not None, self._priority is not None
+        stop = self._signal_tabs['path_stop'] if sig else self._priority_tabs['path_stop'] if pri else None
+        return (stop, self.held if sig else None, self.boxed if self._keepclear is not None else None, self.yielding if pri else None)
 
     def watch_safety(self, near: float = 0.5, ttc: float = 2.0, capacity: int = 8):
         """THE NEAR-MISS LOG (mpcx_set_safety), beside every other stage and in both stop modes: one more launch directly behind the conflict
@@ -1392,6 +1446,7 @@ class IntersectionBatch:
         self.ctx.set_sight(self._sight)
         self.ctx.set_keepclear(self._keepclear)
         self.ctx.set_priority(self._priority)
+        self.ctx.set_braking(self._braking)
 
     def run(self, n_steps: int, graph: bool = False):
         """n_steps of the closed loop with no host work in between (mpcx_closed_loop_run)."""
@@ -1478,18 +1533,30 @@ class IntersectionBatch:
         if self._following is not None:     # the following stage: behind the signal stage, in front of the window stage, as in the loop
             c.follow_step(self.dl, _lib.STOP_SPEED if speed else _lib.STOP_CUT, self.state, self.path, self.path_off, self.path_len, self.traj_idx,
                           self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self._following, obs_skip=self.obs_skip)
+        firm = self._braking is not None
+        if firm:        # the firm hold's mark: behind the last hold and the following stage, in front of the window stage, as in the loop
+            if self.lin_passes != 1:
+                raise MpcxError('braking: not supported with more than one linearisation pass (%d)' % self.lin_passes)
+            stop, held, boxed, yielding = self._line_words()
+            if stop is None:
+                raise MpcxError('braking: the run has no source of stop lines (signals, actuation, a reservation or the priority road)')
+            c.brake_mark_step(self.dl, _lib.STOP_SPEED if speed else _lib.STOP_CUT, self.path_off, self.path_len, self.traj_idx, self.target_ind,
+                              self._win_len, stop, self._braking, held=held, boxed=boxed, yielding=yielding)
         # the previous solution (zeros where the last solve failed or on the first step) is the warm start
         for it in range(self.lin_passes):       # lib/mpc.py:226-237: from the second pass on the previous pass's speeds space the window
             if speed:       # the whole path + the stop index (mpcx_mpc_prepare_batch_stop).  len_seen is a side effect the NEXT step
                             # relies on: the window kernel leaves the path length in prev_len, which the next interaction() reads
-                c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.path_len, self.dl, self.target_ind, out=self.pre,
-                          path_v=self.path_v, x_prev=self.sol['x'] if it else None, stop_idx=self.inter['cut_len'], v_ref=self.v_ref,
+                c.prepare(self.state, self.sol['u'], self.path, self.path_off, self._win_len if firm else self.path_len, self.dl, self.target_ind,
+                          out=self.pre, path_v=self.path_v, x_prev=self.sol['x'] if it else None, stop_idx=self.inter['cut_len'], v_ref=self.v_ref,
                           len_seen=self.prev_len)
                 if self._advice is not None:    # the advice stage: between the window stage and the QP, as in the loop
                     c.advise_step(self.dl, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._advice,
                                   self.pre['xref'])
                 if self._following is not None:     # the following clamp: behind the window stage (and the advice), as in the loop
                     c.follow_cap_step(self._following, self.pre['xref'])
+                if firm:        # the firm hold's clamp: behind the window stage, beside the other clamps, as in the loop
+                    c.brake_clamp_step(self.dl, self.state, self.path, self.path_off, self.path_len, self.traj_idx, stop, self._braking,
+                                       self.pre['xref'], prev_len=self.prev_len)
             else:
                 c.prepare(self.state, self.sol['u'], self.path, self.path_off, self.inter['cut_len'], self.dl, self.target_ind, out=self.pre,
                           path_v=self.path_v, x_prev=self.sol['x'] if it else None)
@@ -1518,6 +1585,8 @@ class IntersectionBatch:
                 out.update({key: getattr(self, attr).cpu().numpy().copy() for key, attr in words})
         if self._following is not None:      # the leader's pool row (-1 = none), the distance to it and the safe speed behind it, last step's
             out.update(leader=self.leader.cpu().numpy().copy(), gap=self.gap.cpu().numpy().copy(), follow_cap=self.follow_cap.cpu().numpy().copy())
+        if self._braking is not None:        # the stop index of an agent held firmly at its line, its overruns so far, the profile at the window's head
+            out.update(firm=self.firm.cpu().numpy().copy(), overran=self.overran.cpu().numpy().copy(), brake_cap=self.brake_cap.cpu().numpy().copy())
         if self._safety is not None:         # the nearest vehicle and the first predicted contact of the last step, the encounters so far
             out.update(partner=self.partner.cpu().numpy().copy(), near_clearance=self.near_clearance.cpu().numpy().copy(),
                        ttc_row=self.ttc_row.cpu().numpy().copy(), ttc_frame=self.ttc_frame.cpu().numpy().copy(),

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1928] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[1976] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     mpcx_following following = {};        // car following (mpcx_set_following): the struct by value, padding zeroed; all zeros while off
@@ -47,6 +47,10 @@ struct mpcx_ctx {
         int32_t n_moves = 0;
         bool ok = false;
     } priority_tables;
+    mpcx_braking braking = {};            // firm hold (mpcx_set_braking): the struct by value (it has no padding); all zeros while off
+    bool have_braking = false;
+    int32_t *win_len = nullptr;           // scratch of mpcx_closed_loop_run with the firm hold on: [P] the lengths the window stage is handed in place of path_len
+    size_t win_len_cap = 0;
     const int32_t *order_hint = nullptr;  // iteration counts of a previous solve (device) or nullptr (mpcx_qp_set_order_hint)
     const int32_t *order_now = nullptr, *order_prev = nullptr;   // optional pair: entries that differ mark a discontinuous change of the reference
     // scratch of mpcx_closed_loop_run for P agents: [P] cut lengths of the previous step | [3 P] what the conflict search's nearest-index
@@ -299,6 +303,17 @@ bool mpcx_priority_absent(const mpcx_priority *s);
 int32_t mpcx_priority_validate(mpcx_ctx *ctx, const mpcx_priority *s, int32_t P, int32_t exchange, bool held_run);
 int32_t mpcx_priority_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
                               const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_priority *priority);
+// firm hold (mpcx_brake.hip): "no firm hold" test, check of the struct against the run (lines: the run has a source of stop lines), the two
+// launches alone (the mark in front of the window stage, the clamp behind it in speed mode)
+bool mpcx_braking_absent(const mpcx_braking *s);
+int32_t mpcx_braking_validate(mpcx_ctx *ctx, const mpcx_braking *s, double dl, int32_t exchange, int32_t lin_passes, bool lines);
+int32_t mpcx_brake_mark_enqueue(mpcx_ctx *ctx, int32_t P, double dl, bool speed, const int32_t *path_off, const int32_t *path_len,
+                                const int32_t *traj_idx, int32_t *target_ind, int32_t *win_len, const int32_t *done /*or nullptr*/,
+                                const int32_t *path_stop, int32_t n_points, const int32_t *held, const int32_t *boxed, const int32_t *yielding,
+                                const mpcx_braking *braking);
+int32_t mpcx_brake_clamp_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const double *path_xyyaw, const int32_t *path_off,
+                                 const int32_t *path_len, int32_t *traj_idx, int32_t *len_seen /*or nullptr*/, const int32_t *done /*or nullptr*/,
+                                 const int32_t *path_stop, int32_t n_points, const mpcx_braking *braking, double *xref);
 int32_t mpcx_ensure_ticket(mpcx_ctx *ctx);                    // work-queue word (mpcx_qp.hip)
 // Work-queue key: expected length of a solve.  hint = the previous step's iteration count; a problem whose path cut moved since
 // the previous step starts far from its warm start and is counted as MPCX_JUMP_BONUS iterations (mpcx_qp.hip has the measurements).

@@ -118,10 +118,17 @@ struct LoopStages {
     // movement that meets a conflicting car of smaller rank within its critical gap it lowers c->cut_len to the agent's stop line.
     // &ctx->priority while on.
     const mpcx_priority *priority = nullptr;
+    // firm hold (mpcx_set_braking: it attaches to the context too): brake_mark_kernel behind the last hold stage and the following stage, in
+    // front of the window stage; in MPCX_STOP_SPEED brake_clamp_kernel behind every window stage, beside the advice and following clamps.
+    // Needs a source of stop lines (signals, actuation, a reservation or the priority road), the local pool and one linearisation pass.  The
+    // mark writes ctx->win_len, which the window stage is handed in place of path_len: a line-held agent's window ends on its stop point,
+    // everybody else's length is path_len's.  `lines`: the table and the hold words of THIS run's stages.  &ctx->braking while on.
+    const mpcx_braking *brake = nullptr;
+    struct { const int32_t *path_stop, *held, *boxed, *yielding; int32_t n_points; } lines = {nullptr, nullptr, nullptr, nullptr, 0};
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight && !keepclear && !priority; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight && !keepclear && !priority && !brake; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -137,9 +144,10 @@ struct LoopKey {
     mpcx_sight sight;
     mpcx_keepclear keepclear;
     mpcx_priority priority;
+    mpcx_braking braking;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
-    const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats;      // the context's scratch the launches were given
+    const void *admit_tab, *pred, *tune, *order, *prev_cut, *bins, *stats, *win_len;      // the context's scratch the launches were given
     int qp_solver, lin_passes, qp_plain_rounds;          // the captured launch is the solver chosen at capture time
 };
 static_assert(sizeof(LoopKey) <= sizeof(mpcx_ctx::loop_key), "loop_key too small");
@@ -203,6 +211,12 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (!mpcx_precedence_absent(a.precedence)) st->precedence = a.precedence;
     if (st->precedence && (rc = mpcx_precedence_validate(ctx, st->precedence, st->scene, st->admit)) != MPCX_OK) return rc;
     if (!mpcx_signals_absent(a.signals)) st->signals = a.signals;
+    if (ctx->have_braking) {        // in front of the holds' own checks: what the stage cannot run with is refused in its name
+        rc = mpcx_braking_validate(ctx, &ctx->braking, c->dl, c->exchange, ctx->lin_passes,
+                                   st->signals || !mpcx_actuation_absent(a.actuation) || !mpcx_reservation_absent(a.reservation) || ctx->have_priority);
+        if (rc != MPCX_OK) return rc;
+        st->brake = &ctx->braking;
+    }
     if (ctx->have_keepclear) {      // in front of the hold's own checks, so that what the stage cannot run with is refused in its name; it
                                     // reads the signals' pointers and counts only, which the hold's check below then goes through
         rc = mpcx_keepclear_validate(ctx, &ctx->keepclear, st->signals, c->P, c->exchange, !mpcx_reservation_absent(a.reservation));
@@ -262,11 +276,18 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         rc = mpcx_sight_validate(ctx, &ctx->sight, c->P, c->n_actors > 0 ? c->pool_rows : c->P);
         if (rc == MPCX_OK) st->sight = &ctx->sight;
     }
+    if (rc == MPCX_OK && st->brake) {       // the stop lines and the hold words of the stages that are on in this run
+        st->lines.path_stop = st->signals ? st->signals->path_stop : st->priority->path_stop;
+        st->lines.n_points = st->signals ? st->signals->n_points : st->priority->n_points;
+        st->lines.held = st->signals ? st->signals->held : nullptr;
+        st->lines.boxed = st->keepclear ? st->keepclear->boxed : nullptr;
+        st->lines.yielding = st->priority ? st->priority->yielding : nullptr;
+    }
     return rc;
 }
 
-// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the keep-clear stage) (-> the priority stage) (-> the following stage) -> lin_passes x (reference
-// window (-> the advice stage) (-> the following clamp) -> solve).
+// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the keep-clear stage) (-> the priority stage) (-> the following stage) (-> the firm hold's mark) -> lin_passes x (reference
+// window (-> the advice stage) (-> the following clamp) (-> the firm hold's clamp) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
 static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_params *ip, const mpcx_closed_loop *c, const LoopStages &st,
@@ -314,6 +335,12 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
                                  c->obs6, c->obs_off, c->obs_cnt, c->obs_skip, ix.absent, st.follow);
         if (rc != MPCX_OK) return rc;
     }
+    if (st.brake) {
+        rc = mpcx_brake_mark_enqueue(ctx, P, c->dl, speed, c->path_off, c->path_len, c->traj_idx, c->target_ind, ctx->win_len, done, st.lines.path_stop,
+                                     st.lines.n_points, st.lines.held, st.lines.boxed, st.lines.yielding, st.brake);
+        if (rc != MPCX_OK) return rc;
+    }
+    const bool firm = st.brake && speed;        // the window stage reads the mark's lengths
     // lib/mpc.py:226-237: MAX_ITER passes of (reference window, rollout, QP); from the second pass on the window is spaced by the
     // previous pass's speeds (row 2 of its x) and the rollout uses its inputs.  (Where a pass fails the reference crashes in the next
     // one -- zip over None; here the next pass starts from the untouched warm start, as after a failed step.)
@@ -325,7 +352,7 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
         wx.rollout_done = rollout_done;
         if (speed) { wx.stop_idx = c->cut_len; wx.v_ref = st.opts.v_ref; wx.len_seen = st.opts.prev_len; }
         wx.done = done; wx.queue_len = queue_len;
-        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, speed ? c->path_len : c->cut_len, c->dl,
+        rc = mpcx_window_enqueue(ctx, P, c->state, c->u_sol, c->path_xyyaw, c->path_v, c->path_off, firm ? ctx->win_len : speed ? c->path_len : c->cut_len, c->dl,
                                  c->target_ind, pass ? c->x_sol + 2 * Wd : nullptr, 4 * (int64_t)Wd, c->xref, c->reaches_end, c->xbar, wx);
         if (rc != MPCX_OK) return rc;
         if (st.advice) {
@@ -334,6 +361,11 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
         }
         if (st.follow && speed) {
             rc = mpcx_follow_cap_enqueue(ctx, P, done, st.follow, c->xref);
+            if (rc != MPCX_OK) return rc;
+        }
+        if (firm) {
+            rc = mpcx_brake_clamp_enqueue(ctx, P, c->dl, c->state, c->path_xyyaw, c->path_off, c->path_len, c->traj_idx, st.opts.prev_len, done,
+                                          st.lines.path_stop, st.lines.n_points, st.brake, c->xref);
             if (rc != MPCX_OK) return rc;
         }
         // (further linearisation passes build their order in line, from the iteration counts of the pass before)
@@ -517,6 +549,10 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     }
     rc = mpcx_grow(ctx, (void **)&ctx->prev_cut, &ctx->prev_cut_cap, 4 * (size_t)c->P * sizeof(int32_t), "the previous cut lengths");   // P cut lengths | near_hints
     if (rc != MPCX_OK) return rc;
+    if (st.brake) {
+        rc = mpcx_grow(ctx, (void **)&ctx->win_len, &ctx->win_len_cap, (size_t)c->P * sizeof(int32_t), "the window lengths");
+        if (rc != MPCX_OK) return rc;
+    }
 
     if (!use_graph) {
         if (ctx->step_fusion && c->exchange == 0 && c->n_actors == 0 && ctx->lin_passes == 1 && st.none())
@@ -543,9 +579,10 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.sight, st.sight);
     key_put(key.keepclear, st.keepclear);
     key_put(key.priority, st.priority);
+    key_put(key.braking, st.brake);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;
-    key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats;
+    key.prev_cut = ctx->prev_cut; key.bins = ctx->bins; key.stats = ctx->stats; key.win_len = st.brake ? ctx->win_len : nullptr;
     key.qp_solver = ctx->qp_solver; key.lin_passes = ctx->lin_passes; key.qp_plain_rounds = ctx->qp_plain_rounds ? 1 : 0;
     if (!ctx->loop_exec || memcmp(&key, ctx->loop_key, sizeof key) != 0) {
         if (ctx->loop_exec) {

@@ -910,6 +910,54 @@ class Context:
         self._chk(self.lib.mpcx_priority_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
                                                     _ptr(cut_len), _ptr(done), C.byref(priority)))
 
+    def set_braking(self, braking: Optional['_lib.BrakingC']):
+        """mpcx_set_braking: the firm hold for every closed-loop run of this context from now on; None (or an all-zero struct) = off.  The
+        context copies the struct; the device buffers it names stay the caller's and are kept alive here while set."""
+        self._chk(self.lib.mpcx_set_braking(self._ctx, None if braking is None else C.byref(braking)))
+        self._braking = braking
+
+    @_ordered
+    def brake_mark_step(self, dl: float, stop_mode: int, path_off, path_len, traj_idx, target_ind, win_len, path_stop, braking: '_lib.BrakingC',
+                        held=None, boxed=None, yielding=None, done=None):
+        """mpcx_brake_mark_step_batch: ONE step's firm-hold mark as the closed loop enqueues it in front of the window stage.  The struct's
+        firm and brake_cap are written; in speed mode target_ind (P int32) is clamped in place and win_len (P int32) receives the lengths the
+        window stage is to be handed in place of path_len.  path_stop: the stop-line table (n_points int32); held, boxed, yielding: the hold
+        words that are on (P int32 each or None); done: the retirement words or None."""
+        Pn = int(path_off.shape[0])
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('target_ind', target_ind), ('win_len', win_len),
+                        ('held', held), ('boxed', boxed), ('yielding', yielding), ('done', done)):
+            if t is not None:
+                self._want(t, torch.int32, (Pn,), name)
+        n_points = 0 if path_stop is None else int(path_stop.shape[0])
+        if path_stop is not None:
+            self._want(path_stop, torch.int32, (n_points,), 'path_stop')
+        self._chk(self.lib.mpcx_brake_mark_step_batch(self._ctx, Pn, float(dl), int(stop_mode), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
+                                                      _ptr(target_ind), _ptr(win_len), _ptr(done), _ptr(path_stop), n_points, _ptr(held), _ptr(boxed),
+                                                      _ptr(yielding), C.byref(braking)))
+
+    @_ordered
+    def brake_clamp_step(self, dl: float, state, path, path_off, path_len, traj_idx, path_stop, braking: '_lib.BrakingC', xref, prev_len=None,
+                         done=None):
+        """mpcx_brake_clamp_step_batch: ONE step's firm-hold clamp as the closed loop enqueues it behind a window stage in speed mode: for
+        every agent the mark left a stop index for, row 2 of xref (P, 4, T + 1 float64) is capped in place by the braking profile, traj_idx is
+        pinned while the agent is behind its line, the struct's overran and brake_cap are written and prev_len (P int32 or None) is restored
+        to the whole path's length."""
+        if self.params is None:
+            raise MpcxError('brake_clamp_step: set_mpc_params has not been called (the stage sizes the window from the horizon)')
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state')
+        self._want(xref, torch.float64, (Pn, 4, self.params.T + 1), 'xref')
+        self._want(path, torch.float64, (int(path.shape[0]), 3), 'path')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('prev_len', prev_len), ('done', done)):
+            if t is not None:
+                self._want(t, torch.int32, (Pn,), name)
+        n_points = 0 if path_stop is None else int(path_stop.shape[0])
+        if path_stop is not None:
+            self._want(path_stop, torch.int32, (n_points,), 'path_stop')
+        self._chk(self.lib.mpcx_brake_clamp_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path), _ptr(path_off), _ptr(path_len),
+                                                       _ptr(traj_idx), _ptr(prev_len), _ptr(done), _ptr(path_stop), n_points, C.byref(braking),
+                                                       _ptr(xref)))
+
     @_ordered
     def sight_step(self, state, obs6, obs_off, obs_cnt, obs_skip, sight: '_lib.SightC', done=None, absent=None):
         """mpcx_sight_step_batch: ONE step's sight stage as the closed loop enqueues it in front of the conflict search: the struct's sight,
