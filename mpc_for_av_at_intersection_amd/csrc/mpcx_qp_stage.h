@@ -561,8 +561,24 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         double I66 = 1.0, DZA = 0.0;               // and the predictor's step of x4_0
         auto prev_block = [&](int ls, double &ka4, double &ka5, double &kd4, double &kd5) {
             const double ra = RHon[ls] ? Rda : 0.0, rd = RHd[ls];
-            kd4 = -LL[ls] * ra * I2[ls]; ka4 = ra * I1[ls] - LL[ls] * kd4;
+            kd4 = -LL[ls] * ra * I2[ls]; ka4 = fma(ra, I1[ls], -(LL[ls] * kd4));
             kd5 = rd * I2[ls];           ka5 = -LL[ls] * kd5;
+        };
+        // a x + b y of the vector sweeps below (the previous-input block times the carry): one product is rounded, the other fused onto it.
+        // Which one is the back end's free choice, and it moved when the gains' loads left the turn bodies (same counts of every FP
+        // instruction, other bits).  So the choice is written out as the compiler had made it while the loads sat in the turns.
+        auto two = [](bool second, double a, double x, double b, double y) { return second ? fma(b, y, a * x) : fma(a, x, b * y); };
+        // The state block of a lane's gains (8 per slot) for a vector sweep.  Every lane reads only its own column of the storage, so where
+        // GAINS_ONCE holds all lanes load theirs together in front of the sweep's turn loop: loaded inside a turn, the first use waits for
+        // the loads with nothing to hide them behind (one wavefront per SIMD), once per turn.  The Riccati sweep's stores are in front of
+        // the fence behind it, and the storage is re-used (multiplier step) only behind the last forward sweep.  At four slots per lane
+        // the 64 registers held across the turn loop cost scratch in every instantiation: there a turn loads its own.
+        constexpr bool GAINS_ONCE = SPL <= 3;
+        auto load_gains = [&](double (&kk)[SPL][8]) {
+            MPCX_UNROLL
+            for (int ls = 0; ls < SPL; ls++)
+                MPCX_UNROLL
+                for (int c = 0; c < 8; c++) kk[ls][c] = cx.ld_k(ls * 8 + c);
         };
         bool bad = false;
         {
@@ -753,17 +769,16 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         if (running && !trial && !polish && any_bad) { status = loose ? MPCX_QP_OPTIMAL : MPCX_QP_NUMERIC; running = false; }
 
         // forward sweep with gains (K, kk): fills the direction (du, dx_{t+1})
-        auto forward = [&](const double (&k0)[SPL], const double (&k1)[SPL], double dz0, double (&D0)[SPL], double (&D1)[SPL],
-                           double (&E0)[SPL], double (&E1)[SPL], double (&E2)[SPL], double (&E3)[SPL]) {
+        // (kh: the lane's gains where GAINS_ONCE holds, not read otherwise)
+        auto forward = [&](const double (&kh)[SPL][8], const double (&k0)[SPL], const double (&k1)[SPL], double dz0, double (&D0)[SPL],
+                           double (&D1)[SPL], double (&E0)[SPL], double (&E1)[SPL], double (&E2)[SPL], double (&E3)[SPL]) {
             double z[JERK ? 7 : 6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             if constexpr (JERK) z[6] = dz0;
             for (int turn = 0; turn < NTURN; turn++) {
                 if (q == turn) {
-                    double kk[SPL][8];           // this lane's gains, all in flight before the first is used
-                    MPCX_UNROLL
-                    for (int ls = 0; ls < SPL; ls++)
-                        MPCX_UNROLL
-                        for (int c = 0; c < 8; c++) kk[ls][c] = cx.ld_k(ls * 8 + c);
+                    double kt[SPL][8];           // this lane's gains, all in flight before the first is used
+                    if constexpr (!GAINS_ONCE) load_gains(kt);
+                    const double (&kk)[SPL][8] = GAINS_ONCE ? kh : kt;
                     MPCX_UNROLL
                     for (int ls = 0; ls < SPL; ls++) {
                         {
@@ -773,7 +788,8 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                             {
                                 double ka4, ka5, kd4, kd5;
                                 prev_block(ls, ka4, ka5, kd4, kd5);
-                                da += ka4 * z[4] + ka5 * z[5]; dd += kd4 * z[4] + kd5 * z[5];
+                                // the first product is the fused one, except in the lane's first slot
+                                da += two(ls == 0, ka4, z[4], ka5, z[5]); dd += two(ls == 0, kd4, z[4], kd5, z[5]);
                             }
                             if constexpr (JERK) { da += KZa[ls] * z[6]; dd += KZd[ls] * z[6]; }
                             const double n0 = z[0] + A0[ls] * z[2] + A1[ls] * z[3], n1 = z[1] + A2[ls] * z[2] + A3[ls] * z[3];
@@ -810,7 +826,9 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         cx.stamp(3);                    // [Riccati sweep]
         // ---- predictor direction, affine step length, centring parameter
         double DA0[SPL] = {}, DA1[SPL] = {}, EA0[SPL] = {}, EA1[SPL] = {}, EA2[SPL] = {}, EA3[SPL] = {}, DAp[SPL];
-        forward(KA0, KA1, DZA, DA0, DA1, EA0, EA1, EA2, EA3);
+        double kg[SPL][8];              // the lane's gains across a vector sweep (GAINS_ONCE)
+        if constexpr (GAINS_ONCE) load_gains(kg);
+        forward(kg, KA0, KA1, DZA, DA0, DA1, EA0, EA1, EA2, EA3);
         cx.stamp(4);                    // [forward sweep 1]
         prev_of(DA1, DAp);
         double al = 1.0, c1 = 0.0, c2 = 0.0;
@@ -961,13 +979,12 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             }
             });
             double pv[JERK ? 7 : 6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if constexpr (GAINS_ONCE) load_gains(kg);      // one load for this sweep and the forward sweep behind it
             for (int turn = NTURN - 1; turn >= 0; turn--) {
                 if (q == turn) {
-                    double kk[SPL][8];           // this lane's gains, all in flight before the first is used
-                    MPCX_UNROLL
-                    for (int ls = 0; ls < SPL; ls++)
-                        MPCX_UNROLL
-                        for (int c = 0; c < 8; c++) kk[ls][c] = cx.ld_k(ls * 8 + c);
+                    double kt[SPL][8];           // this lane's gains, all in flight before the first is used
+                    if constexpr (!GAINS_ONCE) load_gains(kt);
+                    const double (&kk)[SPL][8] = GAINS_ONCE ? kg : kt;
                     MPCX_UNROLL
                     for (int ls = SPL - 1; ls >= 0; ls--) {
                         const double g0 = pv[0] + CG0[ls], g1 = pv[1] + CG1[ls], g2 = pv[2] + CG2[ls], g3 = pv[3] + CG3[ls];
@@ -984,7 +1001,10 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                         {
                             double ka4, ka5, kd4, kd5;
                             prev_block(ls, ka4, ka5, kd4, kd5);
-                            pv[4] = ka4 * hu0 + kd4 * hu1; pv[5] = ka5 * hu0 + kd5 * hu1;
+                            // the first product is the fused one in the lane's last two slots, the second in the slots before them;
+                            // with seven states it is the second in every slot
+                            const bool second = JERK || ls + 2 < SPL;
+                            pv[4] = two(second, ka4, hu0, kd4, hu1); pv[5] = two(second, ka5, hu0, kd5, hu1);
                         }
                         if constexpr (JERK) pv[6] = (dt * g2 + pv[6]) + KZa[ls] * hu0 + KZd[ls] * hu1;
                     }
@@ -998,7 +1018,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         }
         double D0[SPL] = {}, D1[SPL] = {}, E0[SPL] = {}, E1[SPL] = {}, E2[SPL] = {}, E3[SPL] = {}, Dp[SPL];
         cx.stamp(6);                    // [local pass D + corrector vector sweep]
-        forward(KC0, KC1, DZC, D0, D1, E0, E1, E2, E3);
+        forward(kg, KC0, KC1, DZC, D0, D1, E0, E1, E2, E3);
         cx.stamp(7);                    // [forward sweep 2]
         prev_of(D1, Dp);
         // the gains are dead from here on: their storage takes the multiplier step dl (the slack step ds is recomputed)
