@@ -1308,8 +1308,92 @@ int32_t mpcx_priority_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const doub
                                  const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
                                  const int32_t *done /*P or NULL*/, const mpcx_priority *priority);
 
+/* ---- stop signs: a car of a signed movement comes to a standstill at its stop line, and the cars that have stopped leave in the order in
+ * which they stopped; in the two-way case a stopped car also waits for a gap in the unsigned road.  The priority road holds a minor-road
+ * car only while a conflicting car is within its gap -- on an empty road it drives through its line, under a saturated major stream it
+ * starves --, and a reservation orders cars by their first request without making them stop.  With the stop-sign stage on, one launch
+ * (stopsign_kernel, csrc/mpcx_stopsign.hip; the rule is csrc/mpcx_stopsign_core.h) in the hold's place -- behind the conflict search and
+ * the safety stage, in front of the following stage, where priority_kernel runs -- holds a signed car at its line by the cut the signal
+ * hold makes until it has stood there and its turn has come, in both stop modes.  It attaches to the CONTEXT (mpcx_set_stopsign), as the
+ * priority road does: every mpcx_closed_loop_run* entry point runs it while set.  A junction is run by lights, by a manager, by priority,
+ * or by signs: the stage is refused beside signals, actuation, a reservation or the priority road, so the stop lines are its own table.
+ * A junction is n_per consecutive agents, n_per <= 64: junction j owns agents [j n_per, (j + 1) n_per), n_per n_junctions = P.  Tables:
+ * path_stop[n_points], path_move[n_points], path_exit[n_points] as mpcx_priority's; conflict[n_moves], bit h of word g set when movements
+ * g and h cross (symmetric, no diagonal); lane[n_moves], bit h of word g set when they queue in the same approach lane (bit g of word g
+ * is set), as mpcx_reservation's; sign[n_moves], 0 = uncontrolled, 1 = stop sign; gap[n_moves], finite and >= 0, the critical gap in
+ * seconds of a signed movement against unsigned traffic.  Scalars: v_stop (> 0: a car at or below this speed stands), zone (>= 1: path
+ * points before the line within which a standstill counts as the stop), detect (>= zone), brake (> 0), v_floor (> 0), patience (>= 0,
+ * steps).  State, caller-owned device memory, in-out: stopped_at[P], the junction clock at which the agent completed its stop, -1 = not
+ * yet, -1-initialised; go[P] (0 / 1), stopping[P] (0 / 1: the hold word and last step's stickiness), clock[n_junctions],
+ * ran[n_junctions] (a running count of the cars that entered a signed movement without a release), all zero-initialised.  Out: lag[P]
+ * (seconds, +inf = none), blocker[P] (an agent index, -1 = none), occupied[n_junctions], n_waiting[n_junctions].
+ * Per junction and step, everything is read before anything is written: (1) t = clock[j], a negative word counting as 0; clock[j] = t + 1,
+ * wrapping as the reservation's clock does.  (2) every agent q is OUT, INSIDE or APPROACH with (m, s, ti) exactly as the keep-clear stage
+ * classifies it on the stage's tables, done[q] != 0 being OUT; d = s - ti.  OUT: go = 0, stopped_at = -1, stopping = 0.  INSIDE: it
+ * occupies m; with sign[m] != 0 and go == 0 it ran the sign and ran[j] counts it, once; then go = 1, stopped_at is left alone, stopping =
+ * 0.  APPROACH on an unsigned movement: never held, go = 0, stopped_at = -1, stopping = 0; eta = (double)d dl / fmax(v, v_floor) is what
+ * signed cars see of it.  APPROACH, signed, go != 0: it occupies m -- a release is never revoked --, stopping = 0.  APPROACH, signed, go ==
+ * 0, d > detect: stopped_at = -1, stopping = 0.  APPROACH, signed, go == 0, d <= detect: SUBJECT; if stopped_at < 0, d <= zone and v <=
+ * v_stop then stopped_at = t; a subject agent with stopped_at >= 0 REQUESTS.  (3) occ = OR of 1 << m over the occupying agents.  (4) a
+ * requester q: lag[q] = the lexicographic minimum of (eta_r, r) over the unsigned APPROACH agents r of the junction with bit m_r of
+ * conflict[m_q] set, blocker[q] the agent that attains it, none: +inf and -1; everybody else: +inf and -1.  (5) the requesters in ascending
+ * order of (stopped_at, index within the junction), from ahead = blocked = 0: released (go = 1, occ |= 1 << m) if (conflict[m] & (occ |
+ * blocked)) == 0, (lane[m] & ahead) == 0 and lag >= gap[m]; otherwise denied, ahead |= 1 << m, and if aged, (int64)t - stopped_at >=
+ * patience, also blocked |= 1 << m.  (6) a subject agent with go == 0 after (5) is held if stopping[q] != 0 from the step before or if it
+ * can still stop, (double)d dl >= v v / (2.0 brake), the signal hold's own expression: stopping = 1, cut_len[q] = min(cut_len[q], s);
+ * otherwise stopping = 0, the car is left to the conflict search and ran will count it.  (7) occupied[j] = occ, n_waiting[j] = the number
+ * of agents with stopping != 0.  eta is one multiply and one IEEE division, the rest comparisons: host and device agree bit for bit, lag
+ * included.
+ * The stage writes no word of another stage and only lowers cut_len.  A slot reset by the respawn stages is OUT while it waits at the
+ * gate, so the four agent words heal themselves.  NULL or an all-zero struct: off -- the loop enqueues exactly the launches of a context
+ * that never had it, with the same arguments.  The cached graph's key covers the struct by value (it has no padding: sixteen pointers,
+ * three doubles and eight int32 are its 184 bytes), and a run with the stage on does not take step fusion.  With the firm hold on, the
+ * stop lines are this stage's and stopping is the hold word the mark launch reads.  MPCX_E_INVALID ("stopsign: ...") from the run or the
+ * stage call before anything is launched, whatever n_steps is: one of the sixteen pointers NULL; a nonzero reserved word; n_per outside
+ * 1..64 or n_per n_junctions != P; n_moves outside 1..MPCX_SIGNAL_GROUPS_MAX; n_points < 1; zone < 1 or zone > detect; patience < 0;
+ * v_stop, brake or v_floor not finite or not positive; signals, actuation, a reservation or the priority road in the run; the
+ * agent-sharded layout; more than one linearisation pass; a conflict or lane word with bits at or above n_moves; a conflict word with its
+ * own bit or not symmetric; a lane word without its own bit; a sign that is neither 0 nor 1; a gap that is not finite or is negative.
+ * The four per-movement tables are read back from the device for their check (blocking copies) ONCE per struct: the context remembers the
+ * pointers and count that passed and forgets them when mpcx_set_stopsign is given a struct that differs from the one it holds, so run(1)
+ * in a loop reads nothing back.  Do not change the tables in place while set.  The per-agent, per-junction and per-point words are not
+ * read back -- a bad word is data (OUT), never a GPU fault. */
+#define MPCX_STOPSIGN_PER_MAX 64
+typedef struct {
+    const int32_t *path_stop;    /* n_points: route-local index of the next stop line at or after this path point, -1 = none */
+    const int32_t *path_move;    /* n_points: the movement of the route on this path point */
+    const int32_t *path_exit;    /* n_points: route-local index at which a vehicle on this point has left the crossing, -1 = none */
+    const int32_t *conflict;     /* n_moves: bit h of word g = movements g and h cross */
+    const int32_t *lane;         /* n_moves: bit h of word g = movements g and h queue in the same approach lane (bit g of word g set) */
+    const int32_t *sign;         /* n_moves: 0 = uncontrolled, 1 = stop sign */
+    const double *gap;           /* n_moves: the critical gap in seconds of a signed movement against unsigned traffic (finite, >= 0) */
+    int32_t *stopped_at;         /* P, caller-owned, in-out, -1-initialised: the junction clock at which the agent completed its stop */
+    int32_t *go;                 /* P, caller-owned, in-out, zero-initialised: 1 = released (or inside) */
+    int32_t *stopping;           /* P, caller-owned, in-out, zero-initialised: 1 = the agent was held at its line by this stage in the last step */
+    int32_t *clock;              /* n_junctions, caller-owned, in-out, zero-initialised: the junction's step count */
+    int32_t *ran;                /* n_junctions, caller-owned, in-out, zero-initialised: cars that entered a signed movement unreleased */
+    double *lag;                 /* P, out: seconds until the first conflicting unsigned car is at its line, +inf = none */
+    int32_t *blocker;            /* P, out: the agent whose arrival is the lag, -1 = none */
+    int32_t *occupied;           /* n_junctions, out: the mask of movements inside the crossing or released into it */
+    int32_t *n_waiting;          /* n_junctions, out: the number of agents held this step */
+    double v_stop;               /* m/s, > 0: a car at or below this speed stands */
+    double brake;                /* m/s^2, > 0: the deceleration of the can-stop test */
+    double v_floor;              /* m/s, > 0: an approaching unsigned car is taken to drive at least this fast */
+    int32_t zone;                /* path points before the line within which a standstill counts as the stop (>= 1) */
+    int32_t detect;              /* an agent is looked at from this many path points before its line on (>= zone) */
+    int32_t patience;            /* steps after which a denied requester blocks the movements that cross its own (>= 0) */
+    int32_t n_per, n_junctions, n_moves, n_points, reserved;     /* reserved: 0 */
+} mpcx_stopsign;
+/* copies the struct into the context (the buffers it names stay the caller's and must stay valid while set); NULL or all-zero = off */
+int32_t mpcx_set_stopsign(mpcx_ctx *ctx, const mpcx_stopsign *stopsign /*NULL or all-zero = off*/);
+/* one step's stop-sign stage alone (what the closed loop enqueues in the hold's place): steps 1 - 7 above.  The struct is the argument's,
+ * not the context's, and is checked as above (its per-movement tables in every call). */
+int32_t mpcx_stopsign_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const double *state /*P,4*/, const int32_t *path_off /*P*/,
+                                 const int32_t *path_len /*P*/, const int32_t *traj_idx /*P*/, int32_t *cut_len /*P*/,
+                                 const int32_t *done /*P or NULL*/, const mpcx_stopsign *stopsign);
+
 /* ---- firm hold: in MPCX_STOP_SPEED a car that a hold keeps at its stop line stops in front of it.  Every rule that stops a car at a line
- * (signals, actuation, a reservation, keep clear, the priority road) lowers cut_len to the line's index s.  In MPCX_STOP_CUT the path ends
+ * (signals, actuation, a reservation, keep clear, the priority road, stop signs) lowers cut_len to the line's index s.  In MPCX_STOP_CUT the path ends
  * there; in MPCX_STOP_SPEED only the speed reference is zeroed from s on, and that does not hold a car: the window's position reference
  * advances by max(v, 10 / 3.6) dt whatever the car does and runs over the line, and the nearest-index search answers start + 1 for a car
  * that stands on start, so traj_idx climbs to s and the hold's "on or past the line" frees a car that stands 2 m before its line.  With the
@@ -1319,10 +1403,11 @@ int32_t mpcx_priority_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const doub
  * speed reference and pin its index while it is physically behind the line.  It attaches to the CONTEXT (mpcx_set_braking), as
  * following, keep clear and the priority road do: every mpcx_closed_loop_run* entry point runs it while set.
  * Agent q is LINE-HELD in a step if done[q] == 0, one of the hold words that are on in THAT run is nonzero for it -- mpcx_signals.held
- * (signals, actuation, a reservation), mpcx_keepclear.boxed, mpcx_priority.yielding; which of them are read follows the stages of the run
+ * (signals, actuation, a reservation), mpcx_keepclear.boxed, mpcx_priority.yielding or, under stop signs, mpcx_stopsign.stopping in its
+ * place (the two never run together); which of them are read follows the stages of the run
  * that is enqueued, not those at the time of mpcx_set_braking --, and s = path_stop[path_off[q] + traj_idx[q]] is a valid line ahead by
  * the hold's own test: path_off[q] + traj_idx[q] in [0, n_points), 0 <= traj_idx[q] < s < path_len[q] (path_stop and n_points: the
- * signals', else the priority road's).  Then m = ceil(setback / dl), e = max(s - m, 2), E = path point e - 1.
+ * signals', else the priority road's, else the stop signs').  Then m = ceil(setback / dl), e = max(s - m, 2), E = path point e - 1.
  *   (a) the window stage builds q's window on full[:e], searching from min(target_ind[q], e - 1): the loop hands it a per-agent length
  *       array the mark launch wrote (e for a line-held agent, path_len[q] for everybody else) in place of path_len.  The goal test, the
  *       run log and prev_len (the next conflict search's prev_cut_len, restored by the clamp launch) stay the whole path's.
@@ -1339,7 +1424,7 @@ int32_t mpcx_priority_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const doub
  * not take step fusion.  MPCX_E_INVALID ("braking: ...") from the run or a stage call before anything is launched, whatever n_steps is:
  * firm, overran or brake_cap NULL; brake not finite or not positive; setback not finite or below 2 dl (the pin needs two points between
  * e and s); the agent-sharded layout; more than one linearisation pass; a run with no source of stop lines (no signals, actuation,
- * reservation or priority road). */
+ * reservation, priority road or stop signs). */
 typedef struct {
     double brake;                /* m/s^2, > 0: the deceleration of the braking profile */
     double setback;              /* m, >= 2 dl: the stop point lies ceil(setback / dl) path points in front of the line */
@@ -1364,7 +1449,7 @@ int32_t mpcx_brake_clamp_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const d
                                     int32_t n_points, const mpcx_braking *braking, double *xref /*P,4,T+1*/);
 
 /* ---- the stages together.  With several optional stages on, a step is: admission, the entry-order stamp; pool pack and prediction; the
- * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the keep-clear stage; the priority stage (in the hold's place: never beside one); the following stage; the firm hold's mark; per linearisation
+ * intent stage; the sight stage; the conflict search; the safety stage; the hold (signal, actuated or reserve stage); the keep-clear stage; the priority stage or the stop-sign stage (in the hold's place: never beside one, nor beside each other); the following stage; the firm hold's mark; per linearisation
  * pass the window stage, the advice stage, the following clamp, the firm hold's clamp and the QP; the plant; record, retire, respawn.  What that order implies:
  *   one car, three views   agent q sees a present row r of its window (1) standing at its pose if prec[r] > prec[obs_skip[q]], whatever
  *                          the intent stage wrote into r's predicted frames; (2) else on its owner's plan of the step before, if the owner
@@ -1397,6 +1482,12 @@ int32_t mpcx_brake_clamp_step_batch(mpcx_ctx *ctx, int32_t P, double dl, const d
  *                          constant-velocity prediction and may brake for a car that is about to stop (give_way(order=) with the ranks
  *                          as words, or shared plans, are the remedies).  waited heals itself as keep clear's does: a reset slot is OUT
  *                          while it waits at the gate.  In MPCX_STOP_SPEED the hold is soft, as the signals' is.
+ *   the stop-sign stage    reads traj_idx as the conflict search left it and the physical scene, like the priority stage, and is one more
+ *                          minimum on cut_len in front of the follower's.  An unsigned car still reads a signed car's constant-velocity
+ *                          prediction and may brake for a car that is about to stop.  go, stopped_at, stopping, lag and blocker heal
+ *                          themselves: a reset slot is OUT while it waits at the gate; clock and ran run on.  In MPCX_STOP_SPEED the hold
+ *                          is soft unless the firm hold is on: the path index of a standing car climbs to its line, the stage then sees
+ *                          it INSIDE, and ran counts it.
  *   the firm hold          reads the hold words and traj_idx as this step's holds left them, and pins traj_idx only behind the last
  *                          launch that reads it.  It never touches cut_len: a conflict cut or a follower's stop point below the line keeps
  *                          zeroing the speed reference where it did.  Conflict-search stops are a moving stop index, not a line, and stay

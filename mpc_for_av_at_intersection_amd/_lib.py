@@ -182,6 +182,19 @@ class PriorityC(C.Structure):
                 ('n_per', C.c_int32), ('n_junctions', C.c_int32), ('n_moves', C.c_int32), ('n_points', C.c_int32), ('reserved', C.c_int32)]
 
 
+class StopSignC(C.Structure):
+    """mirror of mpcx_stopsign (include/mpcx.h): stop signs; every pointer is a device address -- path_stop / path_move / path_exit
+    (n_points int32), conflict / lane / sign (n_moves int32), gap (n_moves float64), stopped_at / go / stopping / blocker (P int32), lag
+    (P float64), clock / ran / occupied / n_waiting (n_junctions int32).  Not a row of STAGES: the stage attaches to the context
+    (Context.set_stopsign)"""
+    _fields_ = [('path_stop', C.c_void_p), ('path_move', C.c_void_p), ('path_exit', C.c_void_p), ('conflict', C.c_void_p), ('lane', C.c_void_p),
+                ('sign', C.c_void_p), ('gap', C.c_void_p), ('stopped_at', C.c_void_p), ('go', C.c_void_p), ('stopping', C.c_void_p),
+                ('clock', C.c_void_p), ('ran', C.c_void_p), ('lag', C.c_void_p), ('blocker', C.c_void_p), ('occupied', C.c_void_p),
+                ('n_waiting', C.c_void_p), ('v_stop', C.c_double), ('brake', C.c_double), ('v_floor', C.c_double), ('zone', C.c_int32),
+                ('detect', C.c_int32), ('patience', C.c_int32), ('n_per', C.c_int32), ('n_junctions', C.c_int32), ('n_moves', C.c_int32),
+                ('n_points', C.c_int32), ('reserved', C.c_int32)]
+
+
 class BrakingC(C.Structure):
     """mirror of mpcx_braking (include/mpcx.h): firm hold; firm / overran (P int32) and brake_cap (P float64) are device addresses.  Not a
     row of STAGES: the stage attaches to the context (Context.set_braking)"""
@@ -189,6 +202,7 @@ class BrakingC(C.Structure):
 
 
 PRIORITY_PER_MAX = 64                           # MPCX_PRIORITY_PER_MAX: agents per junction under the priority rule
+STOPSIGN_PER_MAX = 64                           # MPCX_STOPSIGN_PER_MAX: agents per junction under stop signs
 KEEPCLEAR_PER_MAX = 64                          # MPCX_KEEPCLEAR_PER_MAX: agents per junction under keep clear
 SIGHT_WINDOW = 64                               # window offsets a word of mpcx_sight.sight holds
 # the words of an event record of the near-miss log (ev_i32[q][e][0..7]; ev_f64[q][e] = the minimum clearance, the agent's speed at opening)
@@ -356,7 +370,7 @@ EXPORTS = ['mpcx_create', 'mpcx_destroy', 'mpcx_last_error', 'mpcx_version', 'mp
            'mpcx_actuated_step_batch', 'mpcx_advise_step_batch', 'mpcx_interaction_batch_intent',
            'mpcx_reserve_step_batch', 'mpcx_set_following', 'mpcx_follow_step_batch', 'mpcx_follow_cap_step_batch',
            'mpcx_set_safety', 'mpcx_safety_step_batch', 'mpcx_safety_summary', 'mpcx_set_sight', 'mpcx_sight_step_batch',
-           'mpcx_set_keepclear', 'mpcx_keepclear_step_batch', 'mpcx_set_priority', 'mpcx_priority_step_batch',
+           'mpcx_set_keepclear', 'mpcx_keepclear_step_batch', 'mpcx_set_priority', 'mpcx_priority_step_batch', 'mpcx_set_stopsign', 'mpcx_stopsign_step_batch',
            'mpcx_set_braking', 'mpcx_brake_mark_step_batch', 'mpcx_brake_clamp_step_batch'] + LOOP_ENTRY_POINTS
 
 
@@ -472,6 +486,9 @@ def load():
     lib.mpcx_set_priority.restype = i32; lib.mpcx_set_priority.argtypes = [vp, C.POINTER(PriorityC)]
     lib.mpcx_priority_step_batch.restype = i32
     lib.mpcx_priority_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(PriorityC)]
+    lib.mpcx_set_stopsign.restype = i32; lib.mpcx_set_stopsign.argtypes = [vp, C.POINTER(StopSignC)]
+    lib.mpcx_stopsign_step_batch.restype = i32
+    lib.mpcx_stopsign_step_batch.argtypes = [vp, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(StopSignC)]
     lib.mpcx_set_braking.restype = i32; lib.mpcx_set_braking.argtypes = [vp, C.POINTER(BrakingC)]
     lib.mpcx_brake_mark_step_batch.restype = i32
     lib.mpcx_brake_mark_step_batch.argtypes = [vp, i32, C.c_double, i32] + [vp] * 7 + [i32] + [vp] * 3 + [C.POINTER(BrakingC)]

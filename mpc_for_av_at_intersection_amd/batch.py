@@ -56,8 +56,11 @@ stop line while a movement that conflicts with its own (cross_phase_conflicts())
 `priority_road()` is the PRIORITY-CONTROLLED JUNCTION, for a batch without signals: one launch in the hold's place keeps a car of a minor
 movement at its stop line until the conflicting movements of smaller rank (priority_ranks()) leave it its critical gap; all_roads_equal()
 switches it off.
+`stop_signs()` is the STOP-CONTROLLED JUNCTION, all-way or two-way (sign_table()), for a batch without signals: one launch in the same
+place keeps a car of a signed movement at its stop line until it has stood there and the cars that stopped before it, and the unsigned
+traffic within its critical gap, let it go; no_signs() switches it off.
 `hold_firmly()` is the FIRM HOLD for speed mode: two small launches around the window stage make a car that signals, a reservation, keep
-clear or the priority road keep at its line really stop in front of it (the position reference ends on a stop point, a braking profile
+clear, the priority road or stop signs keep at its line really stop in front of it (the position reference ends on a stop point, a braking profile
 caps the speed reference, the path index is pinned while the car is behind the line); hold_softly() switches it off.
 """
 import dataclasses
@@ -427,6 +430,17 @@ class IntersectionBatch:
         self.n_yielding: Optional[torch.Tensor] = None       # ... int32 (B,), the agents yielding in the last step
         self._priority = None                                # (set on the context too)
         self._priority_tabs = None                           # ... the device tables the struct names: path_stop, path_move, path_exit, conflict, rank, gap
+        self.stopping: Optional[torch.Tensor] = None         # stop_signs(): int32 (P,), 1 = the agent was held at its line in the last step
+        self.stopped_at: Optional[torch.Tensor] = None       # ... int32 (P,), the junction clock at which the agent completed its stop, -1 = not yet
+        self.released: Optional[torch.Tensor] = None         # ... int32 (P,), 1 = the agent has been released into the crossing (or is inside)
+        self.sign_lag: Optional[torch.Tensor] = None         # ... float64 (P,), seconds to the first conflicting unsigned car, +inf = none
+        self.sign_blocker: Optional[torch.Tensor] = None     # ... int32 (P,), the agent whose arrival is the lag, -1 = none
+        self.sign_clock: Optional[torch.Tensor] = None       # ... int32 (B,), every junction's clock
+        self.ran_sign: Optional[torch.Tensor] = None         # ... int32 (B,), the cars that entered a signed movement unreleased, so far
+        self.sign_occupied: Optional[torch.Tensor] = None    # ... int32 (B,), the movements inside the crossing or released into it in the last step
+        self.n_waiting: Optional[torch.Tensor] = None        # ... int32 (B,), the agents held in the last step
+        self._stopsign = None                                # (set on the context too)
+        self._stopsign_tabs = None                           # ... the device tables the struct names
         self.firm: Optional[torch.Tensor] = None             # hold_firmly(): int32 (P,), 0 or the stop index e of an agent held at its line in the last step
         self.overran: Optional[torch.Tensor] = None          # ... int32 (P,), the steps in which the agent was held while physically beyond its line
         self.brake_cap: Optional[torch.Tensor] = None        # ... float64 (P,), the braking profile at the head of the window, 0.0 = not held at a line
@@ -470,7 +484,7 @@ class IntersectionBatch:
         """switch the named stages off, and with each the stages that live on it (_lib.stage_dependents); drops the cached descriptor"""
         entry = self._precedence is not None and self._precedence.mode == _lib.PRECEDENCE_ENTRY
         for k in stages:
-            if k in ('sight', 'keepclear', 'priority'):     # (attached to the context, no row of _lib.STAGES: nothing lives on it)
+            if k in ('sight', 'keepclear', 'priority', 'stopsign'):     # (attached to the context, no row of _lib.STAGES: nothing lives on it)
                 setattr(self, '_' + k, None)
                 continue
             off = {k} | _lib.stage_dependents(k, entry)
@@ -802,7 +816,7 @@ class IntersectionBatch:
         self._signals = _lib.SignalsC(tabs['path_stop'].data_ptr(), tabs['path_group'].data_ptr(), tabs['plan_cycle'].data_ptr(),
                                       tabs['plan_amber'].data_ptr(), tabs['plan_green'].data_ptr(), tabs['plan_of'].data_ptr(),
                                       self.tick.data_ptr(), self.held.data_ptr(), brake, len(stop), len(plans), n_groups, 0)
-        self._off('actuation', 'reservation', 'priority')   # (a junction is run by lights, by a manager, or by priority; a fixed plan replaces a controller or a junction manager as the source of the lights)
+        self._off('actuation', 'reservation', 'priority', 'stopsign')   # (a junction is run by lights, by a manager, or by priority; a fixed plan replaces a controller or a junction manager as the source of the lights)
         c.synchronize()
 
     def advise_speed(self, v_min: float = 1.0, lead: int = 1, reach: float = 60.0, v_cruise: Optional[float] = None):
@@ -864,10 +878,10 @@ class IntersectionBatch:
 
     def hold_firmly(self, brake: float = 3.0, setback: float = 2.0):
         """FIRM HOLD (mpcx_set_braking), for stop_mode='speed'; in cut mode it only writes its words, the cut is hard already.  Every rule
-        that stops a car at a line -- signalise(), actuate(), reserve(), keep_clear(), priority_road() -- lowers the stop index to the line,
+        that stops a car at a line -- signalise(), actuate(), reserve(), keep_clear(), priority_road(), stop_signs() -- lowers the stop index to the line,
         and in speed mode that is soft: the window's position reference runs ahead at 10 km/h whatever the car does, and the path index of
         a standing car climbs a point a step until the hold sees it "on the line" and lets it go.  With the firm hold an agent whose hold
-        word (`held`, `boxed`, `yielding` -- those of the stages that are on when a run is enqueued) is nonzero has its window built on
+        word (`held`, `boxed`, `yielding`, `stopping` -- those of the stages that are on when a run is enqueued) is nonzero has its window built on
         the path up to a stop point ceil(setback / dl) points in front of its line, every entry of its speed reference capped at
         sqrt(2 brake d) with d the distance of that window point to the stop point, and its path index pinned to the stop point while it is
         physically behind the line (a half-plane test; a car that is beyond it is left to the hold, and counted in `overran`).  One small
@@ -879,6 +893,9 @@ class IntersectionBatch:
         brake, setback = float(brake), float(setback)
         if not (np.isfinite(brake) and brake > 0 and np.isfinite(setback) and setback >= 2.0 * self.dl):
             raise ValueError('hold_firmly: brake > 0 and setback >= 2 dl = %g, both finite' % (2.0 * self.dl))
+        if self._stopsign is not None and not self._stopsign.zone * self.dl > setback:
+            raise ValueError('hold_firmly: setback = %g m is not inside the stop signs\' zone of %d points = %g m: a car standing on its firm stop '
+                             'point could never stamp its stop' % (setback, self._stopsign.zone, self._stopsign.zone * self.dl))
         dev = self.ctx.device
         self.firm = torch.zeros(self.P, dtype=torch.int32, device=dev)
         self.overran = torch.zeros(self.P, dtype=torch.int32, device=dev)
@@ -904,9 +921,11 @@ class IntersectionBatch:
 
     def _line_words(self):
         """the firm hold's view of the stages that are on now: (path_stop, held, boxed, yielding), None where there is none"""
-        sig, pri = self._signals is not None, self._priority is not None
-        stop = self._signal_tabs['path_stop'] if sig else self._priority_tabs['path_stop'] if pri else None
-        return (stop, self.held if sig else None, self.boxed if self._keepclear is not None else None, self.yielding if pri else None)
+        sig, pri, sgn = self._signals is not None, self._priority is not None, self._stopsign is not None
+        stop = self._signal_tabs['path_stop'] if sig else self._priority_tabs['path_stop'] if pri else self._stopsign_tabs['path_stop'] if sgn else None
+        # (the priority road and stop signs never run together: `stopping` travels where `yielding` does)
+        return (stop, self.held if sig else None, self.boxed if self._keepclear is not None else None,
+                self.yielding if pri else self.stopping if sgn else None)
 
     def watch_safety(self, near: float = 0.5, ttc: float = 2.0, capacity: int = 8):
         """THE NEAR-MISS LOG (mpcx_set_safety), beside every other stage and in both stop modes: one more launch directly behind the conflict
@@ -1154,6 +1173,7 @@ class IntersectionBatch:
         detect = max(int(stop.max()) if len(stop) else 1, 1) if detect is None else int(detect)
         if not 1 <= detect <= int(np.iinfo(np.int32).max):
             raise ValueError('priority_road: detect >= 1 path point, int32')
+        self._off('stopsign')       # (a junction is run by priority or by signs; behind the checks: a refused call changes nothing)
         c = self.ctx
         tabs = dict(path_stop=c.i32(stop), path_move=c.i32(move), path_exit=c.i32(exit), conflict=c.i32(conflict), rank=c.i32(rank),
                     gap=torch.as_tensor(np.ascontiguousarray(gap), dtype=torch.float64, device=c.device))
@@ -1175,6 +1195,98 @@ class IntersectionBatch:
         """switch the priority rule off and nothing else: the batch enqueues exactly the launches of one that never had it (`yielding`,
         `yield_waited`, `blocker`, `lag`, `crossing` and `n_yielding` keep what they hold and are no longer written)"""
         self._off('priority')
+
+    def stop_signs(self, signed=None, gap=5.0, v_stop: float = 0.5, zone: Optional[int] = None, detect: Optional[int] = None,
+                   brake: Optional[float] = None, v_floor: float = 1.0, patience: int = 0, stop=None, move=None, exit=None, conflict=None,
+                   lane=None):
+        """STOP SIGNS (mpcx_set_stopsign), for a batch without signals, in both stop modes: the all-way or two-way stop junction.  One more
+        small launch in the hold's place -- behind the conflict search, in front of the following stage -- holds every car of a SIGNED
+        movement at its stop line by the cut the signal hold makes until it has STOPPED there -- it stood at `v_stop` m/s or less within
+        `zone` path points of its line; the junction clock of that step is its stamp, `stopped_at` -- and its turn has come: the stopped
+        cars of a junction (an instance of A <= 64 agents) are released in the order of their stamps, the lower slot first among equals,
+        each if its movement crosses none that is inside the crossing or released into it, no car of its own approach lane has just been
+        denied in front of it, and no car of an unsigned movement that crosses its own reaches its line within the movement's critical
+        `gap` (seconds; the lag is `(s - traj_idx) dl / max(v, v_floor)`).  A denied car that has waited `patience` steps since its stamp
+        also blocks every later car that crosses it; a later car that crosses no earlier one may go.  A release is never revoked.  A car
+        that can no longer stop with `brake` when it comes within `detect` points is left to the conflict search; `ran_sign` counts the
+        cars that entered a signed movement without a release.
+        signed: None = all-way, every movement carries a sign; else the arms (0 .. 3) that carry signs, the others being the through road
+        (sign_table()), or one 0 / 1 word per movement.  gap: a scalar or one value per movement.  stop, move, exit: the per-path-point
+        tables, all of them or none (default: movement_lines() of the batch's routes); conflict, lane: one bit mask per movement each,
+        both or neither (default: movement_conflicts() with the batch's disc model).  zone: default ceil(4 / dl) points; detect: default
+        the whole approach (the largest stop-line index, at least zone); brake: default abs(MAX_DECEL) of the batch's parameters.
+        Refused under signalise() / actuate() / reserve() -- a junction is run by lights, by a manager, by priority, or by signs; calling
+        one of them later switches this stage off, and it and priority_road() switch each other off.  With hold_firmly() on, zone dl must
+        exceed the firm hold's setback: a car standing on its firm stop point could never stamp otherwise.  Allocates `stopping`,
+        `stopped_at`, `released`, `sign_lag`, `sign_blocker`, `sign_clock`, `ran_sign`, `sign_occupied`, `n_waiting` and the tables and
+        drops the cached descriptor; no_signs() switches it off."""
+        if self._signals is not None or self._actuation is not None or self._reservation is not None:
+            raise ValueError('stop_signs: the batch runs under signalise(), actuate() or reserve() -- a junction is run by lights, by a '
+                             'manager, by priority, or by signs')
+        if self.exchange == 'rccl' or callable(self.exchange):
+            raise ValueError('stop_signs: not in the agent-sharded layout (shard by instances)')
+        if not 1 <= self.A <= _lib.STOPSIGN_PER_MAX:
+            raise ValueError('stop_signs: a junction holds 1 .. %d agents, the batch has A = %d' % (_lib.STOPSIGN_PER_MAX, self.A))
+        if len({t is None for t in (stop, move, exit)}) > 1:
+            raise ValueError('stop_signs: give stop, move and exit, or none of them')
+        stop, move, exit = self._line_tables('stop_signs', (stop, move, exit), movement_lines)
+        if conflict is None or lane is None:
+            if conflict is not None or lane is not None:
+                raise ValueError('stop_signs: give both conflict and lane, or neither')
+            conflict, lane = movement_conflicts(self._route_list(), stop, exit, np.asarray(self.ip.circle_centers), float(self.ip.radius))
+        conflict, lane = np.asarray(conflict), np.asarray(lane)
+        n_moves = len(conflict)
+        if (conflict.ndim != 1 or lane.shape != conflict.shape or not 1 <= n_moves <= _lib.SIGNAL_GROUPS_MAX or
+                not np.issubdtype(conflict.dtype, np.integer) or not np.issubdtype(lane.dtype, np.integer)):
+            raise ValueError('stop_signs: conflict and lane hold one integer word per movement, 1 .. %d movements' % _lib.SIGNAL_GROUPS_MAX)
+        if signed is None:
+            sign = np.ones(n_moves, np.int32)
+        else:
+            sign = np.asarray(signed)
+            if sign.shape != (n_moves,):    # (arms, not one word per movement)
+                if n_moves % 3:
+                    raise ValueError('stop_signs: signed names arms, and %d movements are not three per arm' % n_moves)
+                sign = sign_table(signed, n_moves // 3)
+        if sign.shape != (n_moves,) or not np.issubdtype(sign.dtype, np.integer) or not np.isin(sign, (0, 1)).all():
+            raise ValueError('stop_signs: signed is None, the arms that carry signs, or one 0 / 1 word per movement (%d)' % n_moves)
+        gap = np.broadcast_to(np.asarray(gap, dtype=np.float64), (n_moves,)) if np.ndim(gap) == 0 else np.asarray(gap, dtype=np.float64)
+        if gap.shape != (n_moves,) or not np.isfinite(gap).all() or (gap < 0).any():
+            raise ValueError('stop_signs: gap is a finite, non-negative number of seconds, or one per movement (%d)' % n_moves)
+        v_stop, v_floor, brake, patience = float(v_stop), float(v_floor), self._brake(brake), int(patience)
+        if not (np.isfinite(v_stop) and v_stop > 0 and np.isfinite(v_floor) and v_floor > 0 and np.isfinite(brake) and brake > 0):
+            raise ValueError('stop_signs: v_stop, v_floor and brake are finite and positive')
+        zone = int(np.ceil(4.0 / self.dl)) if zone is None else int(zone)
+        detect = max(int(stop.max()) if len(stop) else 1, zone) if detect is None else int(detect)
+        if not 1 <= zone <= detect <= int(np.iinfo(np.int32).max) or not 0 <= patience <= int(np.iinfo(np.int32).max):
+            raise ValueError('stop_signs: 1 <= zone <= detect path points and patience >= 0 steps, int32')
+        if self._braking is not None and not zone * self.dl > self._braking.setback:
+            raise ValueError('stop_signs: zone = %d points = %g m does not exceed the firm hold\'s setback of %g m: a car standing on its firm '
+                             'stop point could never stamp its stop' % (zone, zone * self.dl, self._braking.setback))
+        self._off('priority')       # (a junction is run by priority or by signs)
+        c = self.ctx
+        tabs = dict(path_stop=c.i32(stop), path_move=c.i32(move), path_exit=c.i32(exit), conflict=c.i32(conflict), lane=c.i32(lane),
+                    sign=c.i32(sign), gap=torch.as_tensor(np.ascontiguousarray(gap), dtype=torch.float64, device=c.device))
+        zeros = lambda n: torch.zeros(n, dtype=torch.int32, device=c.device)
+        self.stopping, self.released, self.sign_clock, self.ran_sign = zeros(self.P), zeros(self.P), zeros(self.B), zeros(self.B)
+        self.sign_occupied, self.n_waiting = zeros(self.B), zeros(self.B)
+        self.stopped_at = torch.full((self.P,), -1, dtype=torch.int32, device=c.device)
+        self.sign_blocker = torch.full((self.P,), -1, dtype=torch.int32, device=c.device)
+        self.sign_lag = torch.full((self.P,), float('inf'), dtype=torch.float64, device=c.device)
+        self._stopsign_tabs = tabs
+        self._stopsign = _lib.StopSignC(tabs['path_stop'].data_ptr(), tabs['path_move'].data_ptr(), tabs['path_exit'].data_ptr(),
+                                        tabs['conflict'].data_ptr(), tabs['lane'].data_ptr(), tabs['sign'].data_ptr(), tabs['gap'].data_ptr(),
+                                        self.stopped_at.data_ptr(), self.released.data_ptr(), self.stopping.data_ptr(),
+                                        self.sign_clock.data_ptr(), self.ran_sign.data_ptr(), self.sign_lag.data_ptr(),
+                                        self.sign_blocker.data_ptr(), self.sign_occupied.data_ptr(), self.n_waiting.data_ptr(), v_stop, brake,
+                                        v_floor, zone, detect, patience, self.A, self.B, n_moves, int(self.path.shape[0]), 0)
+        c.set_stopsign(None)        # (a new table may sit where an old one sat: the context checks the next struct it is given afresh)
+        self._desc = None
+        c.synchronize()
+
+    def no_signs(self):
+        """switch the stop signs off and nothing else: the batch enqueues exactly the launches of one that never had them (the stage's
+        words keep what they hold and are no longer written)"""
+        self._off('stopsign')
 
     def share_plans(self, share=None):
         """SHARED PLANS (mpcx_closed_loop_run_intent).  Every agent is seen by the others through a prediction of its pool row: the controls
@@ -1256,7 +1368,7 @@ class IntersectionBatch:
         self._actuation = _lib.ActuationC(tabs['phase_groups'].data_ptr(), tabs['phase_time'].data_ptr(), tabs['ctrl_time'].data_ptr(),
                                           tabs['ctrl_of'].data_ptr(), self.junction_state.data_ptr(), self.lights.data_ptr(),
                                           self.calls.data_ptr(), self.A, self.B, n_phases, len(controllers), 0)
-        self._off('advice', 'reservation', 'priority')  # (a junction is run by lights, by a manager, or by priority; there is no plan left to look ahead into; a controller replaces a junction manager)
+        self._off('advice', 'reservation', 'priority', 'stopsign')  # (a junction is run by lights, by a manager, or by priority; there is no plan left to look ahead into; a controller replaces a junction manager)
         c.synchronize()
 
     def reserve(self, managers, manager_of=None, stop=None, group=None, exit=None, conflict=None, lane=None, brake: Optional[float] = None):
@@ -1308,7 +1420,7 @@ class IntersectionBatch:
                                               tabs['mgr_time'].data_ptr(), tabs['mgr_of'].data_ptr(), self.granted.data_ptr(),
                                               self.since.data_ptr(), self.junction_clock.data_ptr(), self.occupied.data_ptr(),
                                               self.queued.data_ptr(), self.A, self.B, len(managers), 0)
-        self._off('actuation', 'advice', 'keepclear', 'priority')   # (a junction is run by lights, by a manager, or by priority; a junction manager replaces a controller or a plan; there is no plan to look ahead into; the manager itself keeps the crossing clear)
+        self._off('actuation', 'advice', 'keepclear', 'priority', 'stopsign')   # (a junction is run by lights, by a manager, or by priority; a junction manager replaces a controller or a plan; there is no plan to look ahead into; the manager itself keeps the crossing clear)
         c.synchronize()
 
     def unsignalise(self):
@@ -1446,6 +1558,7 @@ class IntersectionBatch:
         self.ctx.set_sight(self._sight)
         self.ctx.set_keepclear(self._keepclear)
         self.ctx.set_priority(self._priority)
+        self.ctx.set_stopsign(self._stopsign)
         self.ctx.set_braking(self._braking)
 
     def run(self, n_steps: int, graph: bool = False):
@@ -1530,6 +1643,8 @@ class IntersectionBatch:
             c.keepclear_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._signals, self._keepclear)
         if self._priority is not None:      # the priority stage: in the hold's place, as in the loop
             c.priority_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._priority)
+        if self._stopsign is not None:      # the stop-sign stage: in the priority stage's place, as in the loop
+            c.stopsign_step(self.dl, self.state, self.path_off, self.path_len, self.traj_idx, self.inter['cut_len'], self._stopsign)
         if self._following is not None:     # the following stage: behind the signal stage, in front of the window stage, as in the loop
             c.follow_step(self.dl, _lib.STOP_SPEED if speed else _lib.STOP_CUT, self.state, self.path, self.path_off, self.path_len, self.traj_idx,
                           self.inter['cut_len'], self.obs6, self.obs_off, self.obs_cnt, self._following, obs_skip=self.obs_skip)
@@ -1539,7 +1654,7 @@ class IntersectionBatch:
                 raise MpcxError('braking: not supported with more than one linearisation pass (%d)' % self.lin_passes)
             stop, held, boxed, yielding = self._line_words()
             if stop is None:
-                raise MpcxError('braking: the run has no source of stop lines (signals, actuation, a reservation or the priority road)')
+                raise MpcxError('braking: the run has no source of stop lines (signals, actuation, a reservation, the priority road or stop signs)')
             c.brake_mark_step(self.dl, _lib.STOP_SPEED if speed else _lib.STOP_CUT, self.path_off, self.path_len, self.traj_idx, self.target_ind,
                               self._win_len, stop, self._braking, held=held, boxed=boxed, yielding=yielding)
         # the previous solution (zeros where the last solve failed or on the first step) is the warm start
@@ -1601,6 +1716,9 @@ class IntersectionBatch:
             out.update(yielding=self.yielding.cpu().numpy().copy(), yield_waited=self.yield_waited.cpu().numpy().copy(),
                        blocker=self.blocker.cpu().numpy().copy(), lag=self.lag.cpu().numpy().copy(),
                        crossing=self.crossing.cpu().numpy().copy(), n_yielding=self.n_yielding.cpu().numpy().copy())
+        if self._stopsign is not None:       # who was held at its line in the last step, who has stopped and when, who has been released, the cars that ran a sign
+            out.update(stopping=self.stopping.cpu().numpy().copy(), stopped_at=self.stopped_at.cpu().numpy().copy(),
+                       released=self.released.cpu().numpy().copy(), ran_sign=self.ran_sign.cpu().numpy().copy())
         if self._routes is not None:        # the route every slot is on now: the run of the path tables its path_off names
             out['route'] = (np.searchsorted(self._route_offs, self.path_off.cpu().numpy().astype(np.int64), side='right') - 1).astype(np.int32)
         if self._actuation is not None:      # per junction: the state the NEXT step starts from, and the lights the last step showed
@@ -1806,6 +1924,19 @@ def priority_ranks(major=(0, 2), left_turn: int = 1):
     if not major <= {0, 1, 2, 3} or left_turn not in (1, 2, 3):
         raise ValueError('priority_ranks: major holds arms 0 .. 3, left_turn is 1, 2 or 3')
     return np.array([(0 if g // 3 in major else 2) + (1 if g % 3 == left_turn - 1 else 0) for g in range(12)], dtype=np.int32)
+
+
+def sign_table(signed=None, n_arms: int = 4):
+    """The sign table of IntersectionBatch.stop_signs for the 3 n_arms movements 3 arm + (turn - 1) of a crossing, int32: 1 for every
+    movement of an arm in `signed` (arms 0 .. n_arms - 1 = stop_lines()' signal groups), 0 for the others -- the through road.  signed =
+    None: all-way, every movement carries a sign.  Pure numpy: no GPU, no state."""
+    n_arms = int(n_arms)
+    if not 1 <= n_arms or 3 * n_arms > _lib.SIGNAL_GROUPS_MAX:
+        raise ValueError('sign_table: 1 .. %d arms of three movements each' % (_lib.SIGNAL_GROUPS_MAX // 3))
+    arms = set(range(n_arms)) if signed is None else {int(a) for a in signed}
+    if not arms <= set(range(n_arms)):
+        raise ValueError('sign_table: signed holds arms 0 .. %d' % (n_arms - 1))
+    return np.array([1 if g // 3 in arms else 0 for g in range(3 * n_arms)], dtype=np.int32)
 
 
 def two_phase_plan(cycle: int, green: int, amber: int) -> dict:

@@ -72,7 +72,7 @@ int32_t mpcx_braking_validate(mpcx_ctx *ctx, const mpcx_braking *s, double dl, i
         return mpcx_fail(ctx, MPCX_E_INVALID, "braking: not supported in the agent-sharded layout (shard by instances)");
     if (lin_passes != 1) return mpcx_fail(ctx, MPCX_E_INVALID, "braking: not supported with more than one linearisation pass (%d)", lin_passes);
     if (!lines)
-        return mpcx_fail(ctx, MPCX_E_INVALID, "braking: the run has no source of stop lines (signals, actuation, a reservation or the priority road)");
+        return mpcx_fail(ctx, MPCX_E_INVALID, "braking: the run has no source of stop lines (signals, actuation, a reservation, the priority road or stop signs)");
     return MPCX_OK;
 }
 

@@ -3,7 +3,7 @@
 // stage of a closed-loop step, in front of the window stage; brake_clamp_kernel behind every window stage, beside the advice and following
 // clamps; tests/brake_ref/brake_ref.cpp builds it for the host.
 //
-// Every rule that stops a car at a line -- signals, actuated signals, reservations, keep clear, the priority road -- lowers cut_len to the
+// Every rule that stops a car at a line -- signals, actuated signals, reservations, keep clear, the priority road, stop signs -- lowers cut_len to the
 // line's index s.  In cut mode the path ends there.  In speed mode the path stays whole and only the speed reference is zeroed from s on,
 // and that does not hold a car, for two reasons: (1) the window advances by cumsum(max(v, 10 / 3.6) dt), so the POSITION reference of a
 // standing car runs ahead at 2.78 m/s, over the line; (2) calc_nearest_index_in_direction(forward) answers start + 1 for a car that stands
@@ -11,8 +11,8 @@
 // s - traj_idx steps.  The rule ends the position reference on a stop point in front of the line, puts a braking profile on the speed
 // reference and pins the index while the car is physically behind the line.
 //
-// Agent q is LINE-HELD in a step if done[q] == 0, one of the hold words that are on in that step is nonzero for it (held, boxed, yielding:
-// a null pointer is a word that is off), and s = path_stop[path_off[q] + traj_idx[q]] is a valid line ahead by the hold's own test
+// Agent q is LINE-HELD in a step if done[q] == 0, one of the hold words that are on in that step is nonzero for it (held, boxed, yielding --
+// under stop signs the loop hands the stage's stopping in yielding's place --: a null pointer is a word that is off), and s = path_stop[path_off[q] + traj_idx[q]] is a valid line ahead by the hold's own test
 // (signal_hold): i = path_off[q] + traj_idx[q] in [0, n_points), 0 <= traj_idx[q] < s < path_len[q]; and path_off[q] + s lies in the table
 // too.  Then m = ceil(setback / dl), e = max(s - m, 2) -- the length of the path as the window is to see it --, E = path point e - 1.
 //   MARK (one lane per agent, in front of the window stage): firm[q] = e for a line-held agent, else 0; brake_cap[q] = 0.0.  In speed mode

@@ -17,7 +17,7 @@ struct mpcx_ctx {
     double *pred = nullptr;     // predicted obstacle disc centres [NOBS][steps][2 discs][2]
     size_t pred_cap = 0;
     hipGraphExec_t loop_exec = nullptr;   // cached one-step graph of mpcx_closed_loop_run (nullptr = none)
-    unsigned char loop_key[1976] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
+    unsigned char loop_key[2160] = {};    // what the cached graph was captured for: an mpcx::LoopKey (mpcx_loop.hip, which checks that it fits)
     const mpcx_qp_tuning *tune = nullptr; // per-instance tuning rows (device) or nullptr
     int32_t tune_rows = 0;
     mpcx_following following = {};        // car following (mpcx_set_following): the struct by value, padding zeroed; all zeros while off
@@ -47,6 +47,14 @@ struct mpcx_ctx {
         int32_t n_moves = 0;
         bool ok = false;
     } priority_tables;
+    mpcx_stopsign stopsign = {};          // stop signs (mpcx_set_stopsign): the struct by value (it has no padding); all zeros while off
+    bool have_stopsign = false;
+    struct StopSignTables {               // the per-movement tables of a mpcx_stopsign that were read back and passed their check (mpcx_stopsign_validate)
+        const int32_t *conflict = nullptr, *lane = nullptr, *sign = nullptr;
+        const double *gap = nullptr;
+        int32_t n_moves = 0;
+        bool ok = false;
+    } stopsign_tables;
     mpcx_braking braking = {};            // firm hold (mpcx_set_braking): the struct by value (it has no padding); all zeros while off
     bool have_braking = false;
     int32_t *win_len = nullptr;           // scratch of mpcx_closed_loop_run with the firm hold on: [P] the lengths the window stage is handed in place of path_len
@@ -303,6 +311,12 @@ bool mpcx_priority_absent(const mpcx_priority *s);
 int32_t mpcx_priority_validate(mpcx_ctx *ctx, const mpcx_priority *s, int32_t P, int32_t exchange, bool held_run);
 int32_t mpcx_priority_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
                               const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_priority *priority);
+// stop signs (mpcx_stopsign.hip): "no stop-sign stage" test, check of the struct against the run (other: what else runs the junction in
+// this run, nullptr = nothing), and the launch alone
+bool mpcx_stopsign_absent(const mpcx_stopsign *s);
+int32_t mpcx_stopsign_validate(mpcx_ctx *ctx, const mpcx_stopsign *s, int32_t P, int32_t exchange, const char *other);
+int32_t mpcx_stopsign_enqueue(mpcx_ctx *ctx, int32_t P, double dl, const double *state, const int32_t *path_off, const int32_t *path_len,
+                              const int32_t *traj_idx, int32_t *cut_len, const int32_t *done /*or nullptr*/, const mpcx_stopsign *stopsign);
 // firm hold (mpcx_brake.hip): "no firm hold" test, check of the struct against the run (lines: the run has a source of stop lines), the two
 // launches alone (the mark in front of the window stage, the clamp behind it in speed mode)
 bool mpcx_braking_absent(const mpcx_braking *s);

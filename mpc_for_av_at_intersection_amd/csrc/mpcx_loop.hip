@@ -118,9 +118,13 @@ struct LoopStages {
     // movement that meets a conflicting car of smaller rank within its critical gap it lowers c->cut_len to the agent's stop line.
     // &ctx->priority while on.
     const mpcx_priority *priority = nullptr;
+    // stop signs (mpcx_set_stopsign: it attaches to the context too): stopsign_kernel in the priority stage's place; refused beside signals,
+    // actuation, a reservation or the priority road.  It holds an agent of a signed movement at its stop line until it has stood there and
+    // its turn has come, by lowering c->cut_len to the line.  &ctx->stopsign while on.
+    const mpcx_stopsign *stopsign = nullptr;
     // firm hold (mpcx_set_braking: it attaches to the context too): brake_mark_kernel behind the last hold stage and the following stage, in
     // front of the window stage; in MPCX_STOP_SPEED brake_clamp_kernel behind every window stage, beside the advice and following clamps.
-    // Needs a source of stop lines (signals, actuation, a reservation or the priority road), the local pool and one linearisation pass.  The
+    // Needs a source of stop lines (signals, actuation, a reservation, the priority road or stop signs), the local pool and one linearisation pass.  The
     // mark writes ctx->win_len, which the window stage is handed in place of path_len: a line-held agent's window ends on its stop point,
     // everybody else's length is path_len's.  `lines`: the table and the hold words of THIS run's stages.  &ctx->braking while on.
     const mpcx_braking *brake = nullptr;
@@ -128,7 +132,7 @@ struct LoopStages {
 
     LoopStages() { memset(&actuation, 0, sizeof actuation); }
     // no optional stage at all (the stop mode is none: it adds no launch): what step fusion asks for
-    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight && !keepclear && !priority && !brake; }
+    bool none() const { return !log && !retire && !scene && !admit && !respawn && !routes && !precedence && !signals && !actuated && !advice && !intent && !reserve && !follow && !safety && !sight && !keepclear && !priority && !stopsign && !brake; }
     bool speed() const { return opts.stop_mode == MPCX_STOP_SPEED; }
     const int32_t *done() const { return retire ? retire->done : nullptr; }
 };
@@ -144,6 +148,7 @@ struct LoopKey {
     mpcx_sight sight;
     mpcx_keepclear keepclear;
     mpcx_priority priority;
+    mpcx_stopsign stopsign;
     mpcx_braking braking;
     mpcx_interaction_params ip;
     mpcx_mpc_params mpc;
@@ -213,7 +218,7 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
     if (!mpcx_signals_absent(a.signals)) st->signals = a.signals;
     if (ctx->have_braking) {        // in front of the holds' own checks: what the stage cannot run with is refused in its name
         rc = mpcx_braking_validate(ctx, &ctx->braking, c->dl, c->exchange, ctx->lin_passes,
-                                   st->signals || !mpcx_actuation_absent(a.actuation) || !mpcx_reservation_absent(a.reservation) || ctx->have_priority);
+                                   st->signals || !mpcx_actuation_absent(a.actuation) || !mpcx_reservation_absent(a.reservation) || ctx->have_priority || ctx->have_stopsign);
         if (rc != MPCX_OK) return rc;
         st->brake = &ctx->braking;
     }
@@ -228,6 +233,15 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
                                     st->signals || !mpcx_actuation_absent(a.actuation) || !mpcx_reservation_absent(a.reservation));
         if (rc != MPCX_OK) return rc;
         st->priority = &ctx->priority;
+    }
+    if (ctx->have_stopsign) {       // in front of the holds' own checks too: ... or by signs
+        rc = mpcx_stopsign_validate(ctx, &ctx->stopsign, c->P, c->exchange,
+                                    st->signals                               ? "signals" :
+                                    !mpcx_actuation_absent(a.actuation)       ? "actuation" :
+                                    !mpcx_reservation_absent(a.reservation)   ? "a reservation" :
+                                    ctx->have_priority                        ? "the priority road" : nullptr);
+        if (rc != MPCX_OK) return rc;
+        st->stopsign = &ctx->stopsign;
     }
     if (!mpcx_reservation_absent(a.reservation)) {  // checks the signals it draws on too, and refuses a controller or advice beside it
         rc = mpcx_reservation_validate(ctx, a.reservation, st->signals, c->P, c->exchange, !mpcx_actuation_absent(a.actuation),
@@ -277,16 +291,17 @@ static int32_t check_stages(mpcx_ctx *ctx, const mpcx_interaction_params *ip, co
         if (rc == MPCX_OK) st->sight = &ctx->sight;
     }
     if (rc == MPCX_OK && st->brake) {       // the stop lines and the hold words of the stages that are on in this run
-        st->lines.path_stop = st->signals ? st->signals->path_stop : st->priority->path_stop;
-        st->lines.n_points = st->signals ? st->signals->n_points : st->priority->n_points;
+        st->lines.path_stop = st->signals ? st->signals->path_stop : st->priority ? st->priority->path_stop : st->stopsign->path_stop;
+        st->lines.n_points = st->signals ? st->signals->n_points : st->priority ? st->priority->n_points : st->stopsign->n_points;
         st->lines.held = st->signals ? st->signals->held : nullptr;
         st->lines.boxed = st->keepclear ? st->keepclear->boxed : nullptr;
-        st->lines.yielding = st->priority ? st->priority->yielding : nullptr;
+        // (the priority road and stop signs never run together: the mark launch reads the one's yielding or the other's stopping in the same slot)
+        st->lines.yielding = st->priority ? st->priority->yielding : st->stopsign ? st->stopsign->stopping : nullptr;
     }
     return rc;
 }
 
-// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the keep-clear stage) (-> the priority stage) (-> the following stage) (-> the firm hold's mark) -> lin_passes x (reference
+// The middle of a step, the same on both paths: (the sight stage ->) the conflict search (-> the safety stage) (-> the signal stage) (-> the keep-clear stage) (-> the priority or stop-sign stage) (-> the following stage) (-> the firm hold's mark) -> lin_passes x (reference
 // window (-> the advice stage) (-> the following clamp) (-> the firm hold's clamp) -> solve).
 // ix: what the caller knows about the pool (who packs and predicts its rows, where the agents and the scripted cars sit); the rest is filled
 // in here.  rollout_done: xbar is written already, in stream order (head_kernel); else the first pass joins the rollout the caller forked.
@@ -328,6 +343,10 @@ static int32_t enqueue_search_and_solve(mpcx_ctx *ctx, const mpcx_interaction_pa
     }
     if (st.priority) {
         rc = mpcx_priority_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.priority);
+        if (rc != MPCX_OK) return rc;
+    }
+    if (st.stopsign) {
+        rc = mpcx_stopsign_enqueue(ctx, P, c->dl, c->state, c->path_off, c->path_len, c->traj_idx, c->cut_len, done, st.stopsign);
         if (rc != MPCX_OK) return rc;
     }
     if (st.follow) {
@@ -579,6 +598,7 @@ static int32_t closed_loop_run(mpcx_ctx *ctx, const mpcx_interaction_params *ip,
     key_put(key.sight, st.sight);
     key_put(key.keepclear, st.keepclear);
     key_put(key.priority, st.priority);
+    key_put(key.stopsign, st.stopsign);
     key_put(key.braking, st.brake);
     key.opts = st.opts; key.actuation = st.actuation;
     key.admit_tab = ctx->admit_tab; key.pred = ctx->pred; key.tune = ctx->tune; key.order = ctx->order;

@@ -52,6 +52,9 @@ struct PriorityAgent {
     double eta;             // seconds to the line at the present speed, 0.0 inside
 };
 
+// step 2: seconds to the line of an APPROACH agent d path points before it at speed v (also what a stop-sign junction sees of an unsigned car)
+MPCX_REC_FN double priority_eta(int64_t d, double dl, double v, double v_floor) { return (double)d * dl / fmax(v, v_floor); }
+
 // steps 1 and 2 for agent q: keepclear_classify on the stage's own tables, then the movement's rank and conflict word and the agent's eta
 MPCX_REC_FN PriorityAgent priority_classify(const PriorityArgs &a, int q) {
     const mpcx_priority &k = a.pr;
@@ -63,7 +66,7 @@ MPCX_REC_FN PriorityAgent priority_classify(const PriorityArgs &a, int q) {
     p.cf = (uint32_t)k.conflict[c.m];
     if (c.kind == MPCX_KEEPCLEAR_APPROACH) {
         p.d = (int64_t)c.s - (int64_t)c.ti;
-        p.eta = (double)p.d * a.s.dl / fmax(a.s.state[4 * (size_t)q + 2], k.v_floor);
+        p.eta = priority_eta(p.d, a.s.dl, a.s.state[4 * (size_t)q + 2], k.v_floor);
     }
     return p;
 }

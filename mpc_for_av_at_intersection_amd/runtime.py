@@ -910,6 +910,26 @@ class Context:
         self._chk(self.lib.mpcx_priority_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
                                                     _ptr(cut_len), _ptr(done), C.byref(priority)))
 
+    def set_stopsign(self, stopsign: Optional['_lib.StopSignC']):
+        """mpcx_set_stopsign: the stop-sign rule for every closed-loop run of this context from now on; None (or an all-zero struct) = off.
+        The context copies the struct; the device buffers it names stay the caller's and are kept alive here while set."""
+        self._chk(self.lib.mpcx_set_stopsign(self._ctx, None if stopsign is None else C.byref(stopsign)))
+        self._stopsign = stopsign
+
+    @_ordered
+    def stopsign_step(self, dl: float, state, path_off, path_len, traj_idx, cut_len, stopsign: '_lib.StopSignC', done=None):
+        """mpcx_stopsign_step_batch: ONE step's stop-sign stage as the closed loop enqueues it in the hold's place.  cut_len (P int32) is
+        lowered in place for an agent held at its line, and the struct's stopped_at, go, stopping, clock, ran, lag, blocker, occupied and
+        n_waiting are written; done: the retirement words (P int32) or None."""
+        Pn = int(state.shape[0])
+        self._want(state, torch.float64, (Pn, 4), 'state')
+        for name, t in (('path_off', path_off), ('path_len', path_len), ('traj_idx', traj_idx), ('cut_len', cut_len)):
+            self._want(t, torch.int32, (Pn,), name)
+        if done is not None:
+            self._want(done, torch.int32, (Pn,), 'done')
+        self._chk(self.lib.mpcx_stopsign_step_batch(self._ctx, Pn, float(dl), _ptr(state), _ptr(path_off), _ptr(path_len), _ptr(traj_idx),
+                                                    _ptr(cut_len), _ptr(done), C.byref(stopsign)))
+
     def set_braking(self, braking: Optional['_lib.BrakingC']):
         """mpcx_set_braking: the firm hold for every closed-loop run of this context from now on; None (or an all-zero struct) = off.  The
         context copies the struct; the device buffers it names stay the caller's and are kept alive here while set."""
