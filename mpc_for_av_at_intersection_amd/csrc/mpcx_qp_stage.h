@@ -56,11 +56,10 @@ enum { ROWS = 8 };
 // pass compiled with them folded: Cx::PLAIN_PASSES is a mask of the passes that get one.  Both copies are the same text on the same
 // operands in the same order.  That alone does not make them the same numbers: left to itself the back end decides which multiply of
 // a sum of products is fused into the add, and it decided differently from copy to copy (and from row to row, by what happened to
-// sit in one basic block).  So the passes A, D, the multiplier step, the safeguard and the update are written under MPCX_FP_PINNED
+// sit in one basic block).  So the passes A, C, D, the multiplier step, the safeguard and the update are written under MPCX_FP_PINNED
 // with their fused multiply-adds spelt out, in the grouping the single generic text had compiled to before: a problem's
-// numbers then depend neither on the path its rounds took nor on the instantiation.  Pass C, the first to get a copy, is NOT pinned:
-// its two copies have come out with one grouping in every build so far, and what holds them to it is tests/test_gpu_qp_plain_passes.py
-// (switch on against off) and the benchmark's dumped outputs against the parent's, nothing in the text.  A launch can be told to run
+// numbers then depend neither on the path its rounds took nor on the instantiation.  (Pass C, the first to get a copy, was the last to
+// be pinned: its two copies had come out with one grouping in every build, and that one is what is written out.)  A launch can be told to run
 // the generic text only (src.plain_rounds(), for the tests that compare the two).  A policy without the member PLAIN_PASSES (the host
 // build) runs the generic text only.
 enum { PLAIN_C = 1,     // the predictor's row pass
@@ -233,12 +232,29 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         }
     };
     auto row_on = [&](int ls, int r) -> bool { return (r == 4 || r == 5) ? rate[ls] : act[ls]; };
+    // The slot predicate.  act[ls] is one bit per lane and slot, and rate[ls] = act[ls] && t >= 1 differs from it only in the lane's first
+    // slot (t = q SPL + ls >= 1 wherever ls >= 1).  So the six row loops of a round (passes A, C, D, the multiplier step, the safeguard, the
+    // update) run the rows of slot ls under `if (act[ls])`, and inside it a row is on -- row_in -- unless it is one of the rate pair of the
+    // lane's first slot: ls and r are constants of the unrolled loops, so every other `on ? ... : 0.0` folds away.  A slot that is off
+    // (beyond the horizon, or of a group without a problem) is left as the selects left it:
+    //   its per-slot outputs are +0.0 (set in front of the predicate).  With s = 1, lam = 0 and every `on` false each of them was a
+    //     difference or an fma of zeros that ends in (+0) + (-0) or (+0) - (+0): +0.0, never -0.0;
+    //   the accumulators are untouched.  They took x + (+-0.0), fma(1, 0, x), fma(0, -0, x), fmin(x, bound), fmax(x, 0) with x that starts
+    //     at +0.0 (or at the bound) and can never be -0.0 (a sum that has +0.0 in it is not -0.0), so the value was x again;
+    //   its stored rows stay s = 1, lam = 0: the update wrote fma(alpha, 0, 1) = 1 and fma(alpha_d, -0, 0) = +0 over them.  The multiplier
+    //     step no longer writes its dl = -0.0 for them into the gains' storage: only the safeguard and the update read it, under the same
+    //     predicate, and the next Riccati sweep overwrites it.
+    // No cross-lane operation sits under the predicate (prev_of / next_of / cost_grad and the group reductions stay outside), and the rows'
+    // loads are issued in front of it, from addresses that are valid for every lane.
+    auto row_in = [&](int ls, int r) -> bool { return (ls == 0 && (r == 4 || r == 5)) ? rate[0] : true; };
     // slacks and multipliers of one slot, all 16 loads in flight before the first is used (left to itself the compiler loads each
     // row right before its use and waits for it: 24 exposed LDS round trips per pass at one wavefront per SIMD)
     auto rows_of = [&](int ls, double (&sv)[ROWS], double (&lv)[ROWS]) {
         MPCX_UNROLL
         for (int r = 0; r < ROWS; r++) { sv[r] = cx.ld_s(ls * ROWS + r); lv[r] = cx.ld_l(ls * ROWS + r); }
     };
+    // (Loading slot ls + 1's rows before slot ls's arithmetic, and the first slot's ahead of whatever precedes a row loop, was built and
+    // measured: it does not separate from a slot loading its own rows -- DESIGN 4.1.)
     // gradient of the cost (no multipliers) wrt x_{t+1} and u_t at the current iterate; recomputed where needed rather than
     // kept across the Riccati sweep (30 doubles per lane that the sweep needs for the cost-to-go).
     // Its sums of two products are spelt as the fused multiply-adds the compiler has always made of them in the kernels without tuning
@@ -453,9 +469,13 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
             for (int ls = 0; ls < SPL; ls++) {
                 double lam[ROWS], rpv[ROWS], isv[ROWS], dd[ROWS], sv[ROWS], lv[ROWS];
                 rows_of(ls, sv, lv);
+                DSa[ls] = 0.0; DSd[ls] = 0.0; DSr[ls] = 0.0; DSv[ls] = 0.0;
+                RL0[ls] = 0.0; RL1[ls] = 0.0; L45[ls] = 0.0; QL2[ls] = 0.0;
+                RA0[ls] = 0.0; RA1[ls] = 0.0; N45[ls] = 0.0; QA2[ls] = 0.0;
+                if (act[ls]) {
                 MPCX_UNROLL
                 for (int r = 0; r < ROWS; r++) {
-                    const bool on = row_on(ls, r);
+                    const bool on = row_in(ls, r);
                     // A polish round puts weight rho on the rows of the active set, with lam + rho gap as their linear term (lam = the
                     // iterate's multiplier), and nothing on the other rows (a trial round has no active row at all).  That is what the
                     // iteration's own formulas d = lam / s, nu = d (s + gap) give for a row with the slack lam / rho -- so an active
@@ -479,6 +499,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 DSa[ls] = dsum(0); DSd[ls] = dsum(2); DSr[ls] = ls == 0 ? dd[4] + dd[5] : dsum(4); DSv[ls] = dsum(6);
                 RL0[ls] = lam[0] - lam[1]; RL1[ls] = lam[2] - lam[3]; L45[ls] = lam[4] - lam[5]; QL2[ls] = lam[6] - lam[7];
                 RA0[ls] = ndif(0); RA1[ls] = ndif(2); N45[ls] = ndif(4); QA2[ls] = ndif(6);
+                }
             }
             });
             double L45n[SPL], N45n[SPL];
@@ -838,6 +859,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         const bool plain_round = plain_on && !cx.any(trial || polish || pinit);
         // per row, recomputed from (s, lam, u, x) wherever needed instead of being kept: rp = s + gap, d = lam / s
         by_round(std::bool_constant<(PASSES & PLAIN_C) != 0>{}, plain_round, [&](auto plain) {
+        MPCX_FP_PINNED
         constexpr bool PLAIN = decltype(plain)::value;
         const bool polish_r = !PLAIN && polish, ipm_r = PLAIN || !(trial || polish);
         const double veps = trial ? 0.0 : MPCX_POLISH_EPS_G;
@@ -845,9 +867,10 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         for (int ls = 0; ls < SPL; ls++) {
             double sv[ROWS], lv[ROWS];
             rows_of(ls, sv, lv);
+            if (act[ls]) {       // the slot predicate (row_in): al, c1, c2 and viol of a slot that is off stay as they are
             MPCX_UNROLL
             for (int r = 0; r < ROWS; r++) {
-                const bool on = row_on(ls, r);
+                const bool on = row_in(ls, r);
                 const bool pa = polish_r & (sv[r] < 0.0);
                 const double sa = fabs(sv[r]);
                 const double s = pa ? lv[r] * (1.0 / MPCX_POLISH_RHO) : sa;
@@ -856,7 +879,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 const double rp = on ? s + gap : 0.0;
                 const double d = l * cx.rcp(s);
                 const double dsa = on ? -rp - dir : 0.0;
-                const double dla = -l - d * dsa;
+                const double dla = fma(-d, dsa, -l);
                 // the end point of a trial / polish round: rows outside the active set must hold, the new multipliers of the rows inside it
                 // (lam + dla = lam + rho gap') must not be negative.  A plain round has no such end point to check.
                 if constexpr (!PLAIN) {
@@ -867,8 +890,11 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 // ratio tests: any value <= the exact ratio is a valid step bound, the 0.001 margin of MPCX_STEP_FRACTION is 12 orders above rcp_fast's error
                 al = fmin(al, (on && dsa < 0.0) ? -s * cx.rcp_fast(dsa) : 1.0);
                 al = fmin(al, (on && dla < 0.0) ? -l * cx.rcp_fast(dla) : 1.0);
-                c1 += on ? s * dla + l * dsa : 0.0;
-                c2 += dsa * dla;
+                // s dla + l dsa takes the SECOND product fused, and the sum takes it rounded; dsa dla is fused into its sum.  That is the grouping
+                // both copies of this pass have compiled to in every instantiation so far, spelt out like the other passes'
+                c1 += on ? fma(l, dsa, s * dla) : 0.0;
+                c2 = fma(dsa, dla, c2);
+            }
             }
         }
         });
@@ -947,8 +973,12 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 double nu[ROWS], sv[ROWS], lv[ROWS];
                 rows_of(ls, sv, lv);
                 MPCX_UNROLL
+                for (int r = 0; r < ROWS; r++) RC[ls][r] = 0.0;
+                C01[ls] = 0.0; C23[ls] = 0.0; C45[ls] = 0.0; C67[ls] = 0.0;
+                if (act[ls]) {
+                MPCX_UNROLL
                 for (int r = 0; r < ROWS; r++) {
-                    const bool on = row_on(ls, r);
+                    const bool on = row_in(ls, r);
                     const bool pa = polish_r & (sv[r] < 0.0);
                     const bool full = on & !trial_r & !polish_r;                 // a row of an ordinary iteration
                     const double s = pa ? lv[r] * (1.0 / MPCX_POLISH_RHO) : fabs(sv[r]);
@@ -969,6 +999,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                     nu[r] = (ls == 0 && (r == 4 || r == 5)) ? fma(-is, rc, a1) : a1 - RC[ls][r];
                 }
                 C01[ls] = nu[0] - nu[1]; C23[ls] = nu[2] - nu[3]; C45[ls] = nu[4] - nu[5]; C67[ls] = nu[6] - nu[7];
+                }
             }
             next_of(C45, C45n);
             cost_grad(CG0, CG1, CG2, CG3, CH0, CH1);
@@ -1024,8 +1055,8 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         // the gains are dead from here on: their storage takes the multiplier step dl (the slack step ds is recomputed)
         cx.fence();
         double am_p = 1e300, am_d = 1e300;      // step bounds of the primal side (slacks) and of the multipliers, taken separately
-        auto slack_step = [&](int ls, int r, double s) -> double {
-            const bool on = row_on(ls, r);
+        auto slack_step = [&](int ls, int r, double s) -> double {       // (called under the slot predicate only)
+            const bool on = row_in(ls, r);
             const double rp = on ? s + row_gap(ls, r, Dprev[ls]) : 0.0;
             return on ? -rp - row_dir(r, D0[ls], D1[ls], Dp[ls], E2[ls]) : 0.0;
         };
@@ -1037,9 +1068,10 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         for (int ls = 0; ls < SPL; ls++) {
             double sv[ROWS], lv[ROWS];
             rows_of(ls, sv, lv);
+            if (act[ls]) {       // the slot predicate (row_in): a slot that is off bounds no step and stores no dl
             MPCX_UNROLL
             for (int r = 0; r < ROWS; r++) {
-                const bool on = row_on(ls, r);
+                const bool on = row_in(ls, r);
                 const bool pa = polish_r & (sv[r] < 0.0);
                 const bool full = on & !trial_r & !polish_r;
                 const double s = pa ? lv[r] * (1.0 / MPCX_POLISH_RHO) : fabs(sv[r]);
@@ -1052,6 +1084,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 am_p = fmin(am_p, (on && ds < 0.0) ? -s * cx.rcp_fast(ds) : 1e300);
                 am_d = fmin(am_d, (on && dl < 0.0) ? -l * cx.rcp_fast(dl) : 1e300);
             }
+            }
         }
         });
         cx.fence();
@@ -1063,6 +1096,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
         if (alpha_d > 1.0 || was_trial || was_polish) alpha_d = 1.0;
         // centrality safeguard: shorten until min s*lam >= 1e-3 * mean at the new point (at most 6 times)
         double mu_next = 0.0;           // mu at the point the step leads to (of the last evaluation: exact unless the step was shortened after it)
+        MPCX_NOUNROLL                   // (a loop, as it has always compiled: with the slot predicate in its body the compiler would peel all six rounds)
         for (int tr = 0; tr < 6; tr++) {
             MPCX_FP_PINNED
             double pmin = 1e300, psum = 0.0;
@@ -1072,9 +1106,10 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 rows_of(ls, sv, lv);
                 MPCX_UNROLL
                 for (int r = 0; r < ROWS; r++) dv[r] = cx.ld_k(ls * ROWS + r);
+                if (act[ls]) {   // the slot predicate (row_in): pmin and psum of a slot that is off stay as they are
                 MPCX_UNROLL
                 for (int r = 0; r < ROWS; r++) {
-                    const bool on = row_on(ls, r);
+                    const bool on = row_in(ls, r);
                     const double s = fabs(sv[r]), l = lv[r];
                     const double sn = fma(alpha, slack_step(ls, r, s), s), ln = fma(alpha_d, dv[r], l);
                     const double pr = sn * ln;
@@ -1083,6 +1118,7 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                     // first slot), whose products are fused into it: the grouping this loop has had since it was written
                     if (ls == 0 && r < 4) psum = on ? fma(sn, ln, psum) : psum;
                     else psum += on ? pr : 0.0;
+                }
                 }
             }
             const double gmn = cx.gmin(pmin), gsm = cx.gsum(psum);
@@ -1110,16 +1146,19 @@ MPCX_HD void solve_queue(Cx &cx, Src &src) {
                 MPCX_UNROLL
                 for (int k = 0; k < SPL * ROWS; k++) { sv[k] = cx.ld_s(k); lv[k] = cx.ld_l(k); dv[k] = cx.ld_k(k); }
                 MPCX_UNROLL
-                for (int ls = 0; ls < SPL; ls++)
+                for (int ls = 0; ls < SPL; ls++) {
+                    if (act[ls]) {           // the slot predicate (row_in): the rows of a slot that is off stay s = 1, lam = 0
                     MPCX_UNROLL
                     for (int r = 0; r < ROWS; r++) {          // rows that are off have ds = dl = 0
                         const double s = fabs(sv[ls * ROWS + r]);
                         const double sn = fma(alpha, slack_step(ls, r, s), s), ln = fma(alpha_d, dv[ls * ROWS + r], lv[ls * ROWS + r]);
                         // an accepted trial / polish point: the true slack (>= 0 up to rounding; floored so that lam / s stays finite)
-                        const double sw = ((was_trial | was_polish) & row_on(ls, r)) ? fmax(sn, 1e-30) : sn;
+                        const double sw = ((was_trial | was_polish) & row_in(ls, r)) ? fmax(sn, 1e-30) : sn;
                         cx.st_s(ls * ROWS + r, (pnext & (sn < ln)) ? -sw : sw);
                         cx.st_l(ls * ROWS + r, ln);
                     }
+                    }
+                }
             }
             MPCX_UNROLL
             for (int ls = 0; ls < SPL; ls++) {
