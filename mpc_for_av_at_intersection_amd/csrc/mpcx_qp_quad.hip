@@ -72,31 +72,51 @@ struct GroupCx {
 // work queue: group leaders draw problem indices from a global ticket until the batch is exhausted; idle groups are refilled
 // once REFILL_GROUPS of them are waiting (or nobody is running any more)
 constexpr int REFILL_GROUPS = 2;
-template <int LQ, int SPL, bool TUNED>
+template <int LQ, int SPL, bool TUNED, bool JERK>
 struct QueueSrc {
     const QpArgs &a;
+    // The compiler loads every field of the by-value argument once, at the kernel's entry, and keeps it in scalar registers.  A round
+    // reads few of them (the rows' bounds, dt, tol, T); the thirteen base pointers and the queue's words are read only by the draw, the
+    // set-up and the hand-in, yet were held across every round, spilled to and reloaded from VGPR lanes all over the row passes and
+    // sweeps.  With LATE_ARGS, at() and fetch() read them through late(): the kernel-argument segment again (QpArgs is the
+    // kernel's only argument, so it lies at offset 0), behind an empty asm that hides from the compiler that the pointer is the same every
+    // time.  Its loads stay where they are written, scalar loads at the refill.
+    // On for the four-state kernel without tuning rows at SPL = 3 only: that is the instantiation whose time was measured with it (six
+    // alternating pairs against the parent).  The other eleven read `a` as before and compile to the code they had; their static
+    // counts with late reads are in DESIGN 4.1 (ten of them better, <8,4,false,false> with more scratch), none of them timed.
+    static constexpr bool LATE_ARGS = SPL == 3 && !TUNED && !JERK;
+    typedef const __attribute__((address_space(4))) QpArgs *LateArgs;
+    __device__ __forceinline__ auto late() const {
+        if constexpr (LATE_ARGS) {
+            LateArgs pa = (LateArgs)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(pa));
+            return pa;
+        } else return &a;
+    }
     __device__ __forceinline__ mpcx_mpc_params params() const { return a.p; }
     __device__ __forceinline__ bool plain_rounds() const { return a.plain_rounds != 0; }     // mpcx_qp_set_plain_rounds
     __device__ __forceinline__ mpcx_stage::Problem at(int b) const {
+        const auto l = late();
         const int T = a.p.T, W = T + 1;
-        return mpcx_stage::Problem{a.x0 + (size_t)b * 4, a.xref + (size_t)b * 4 * W, a.xbar + (size_t)b * 4 * W,
-                                   a.has_warm ? a.u_warm + (size_t)b * 2 * T : nullptr, a.re + (size_t)b * W,
-                                   a.x_out + (size_t)b * 4 * W, a.u_out + (size_t)b * 2 * T, a.kkt + (size_t)b * 4,
-                                   a.status + b, a.iters + b};
+        return mpcx_stage::Problem{l->x0 + (size_t)b * 4, l->xref + (size_t)b * 4 * W, l->xbar + (size_t)b * 4 * W,
+                                   l->has_warm ? l->u_warm + (size_t)b * 2 * T : nullptr, l->re + (size_t)b * W,
+                                   l->x_out + (size_t)b * 4 * W, l->u_out + (size_t)b * 2 * T, l->kkt + (size_t)b * 4,
+                                   l->status + b, l->iters + b};
     }
     // every round either advances some group's iteration counter or consumes a ticket
     __device__ __forceinline__ int refill_min() const { return REFILL_GROUPS * LQ; }   // in lanes
     __device__ __forceinline__ long max_rounds() const { return ((long)a.B + 2) * (long)(a.p.max_iter + 6) * (MPCX_POLISH_TRIES + 1); }
     template <class Cx>
     __device__ __forceinline__ bool fetch(Cx &cx, mpcx_mpc_params &P, int &pbi) const {
+        const auto l = late();
         int t = 0;
-        if (cx.q == 0) t = atomicAdd(a.ticket, 1);
+        if (cx.q == 0) t = atomicAdd(l->ticket, 1);
         t = (int)cx.gsum((double)t);                  // the other lanes contribute 0: everybody gets the leader's ticket
-        const bool have = t < (a.has_queue_len ? *a.queue_len : a.B);
-        const int b = have ? (a.has_order ? a.order[t] : t) : 0;
+        const bool have = t < (l->has_queue_len ? *l->queue_len : l->B);
+        const int b = have ? (l->has_order ? l->order[t] : t) : 0;
         pbi = b;
         if (TUNED) {
-            const mpcx_qp_tuning &tu = a.tune[b];
+            const mpcx_qp_tuning &tu = l->tune[b];
             P.w_perp = tu.w_perp; P.w_para = tu.w_para;
             P.R[0] = tu.R[0]; P.R[1] = tu.R[1]; P.Rd[0] = tu.Rd[0]; P.Rd[1] = tu.Rd[1];
             P.Q_v_yaw[0] = tu.Q_v_yaw[0]; P.Q_v_yaw[1] = tu.Q_v_yaw[1];
@@ -115,7 +135,7 @@ __global__ __launch_bounds__(64, 1) void qp_quad_kernel(QpArgs a) {
     __shared__ double sh[(3 * SPL * 8 + 2 * SPL) * 64];
     const int lane = threadIdx.x;
     GroupCx<LQ, SPL, JERK> cx{lane & (LQ - 1), lane, (lds_double *)sh};
-    QueueSrc<LQ, SPL, TUNED> src{a};
+    QueueSrc<LQ, SPL, TUNED, JERK> src{a};
     mpcx_stage::solve_queue(cx, src);
 }
 
